@@ -13,11 +13,16 @@ five losses + smoothness term) -> backward -> Adam on decoder + hash table (+ un
 5th iteration).  N > 1: one process per GPU, every rank renders its own 2048-ray shard of a 2048*N batch
 (weak scaling), the loss sums and the flat gradient are all-reduced over RCCL.
 
-Prints ONE JSON line on rank 0 (see the driver contract) with two extra objects:
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times the K steps and prints
+the line (metric, value, unit, ms_per_step, ...).  --full adds what takes runs of its own (each can be left out with
+its --no-* option):
   roofline     -- the dominant kernel's algorithmic rate against the roof that bounds it, from HIP events on
                   the launch stream around K launches of that kernel (the per-kernel table is in "kernels");
+  dropin, mapping_iter, ms_per_step_median_of_5_chunks -- the reference's unchanged loop body, the BA iteration
+                  end to end, the step time as the median over five further chunks;
   cpu_baseline -- the oracle's (CPU PyTorch restatement, oracle/spec_torch.py) identical mapping iteration on
                   this host's cores, on a bounded sample.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 
 from __future__ import annotations
@@ -436,6 +441,54 @@ def bench_rays(cfg, n_rays: int, seed: int = 0):
     return syn.random_rays(n_rays, cfg["mapping"]["bound"], seed=seed, depth_range=(0.15, 0.7) if unit else (0.5, 2.5))
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_SAMPLE = 4 << 20          # elements kept of an array larger than DUMP_SAMPLE_OVER elements
+DUMP_SAMPLE_OVER = 8 << 20
+
+
+def dump_outputs(out_dir: str, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 kept, everything else as float32.  An array of more than
+    DUMP_SAMPLE_OVER elements (the hash table at T = 2^22) is written as <name>_sample.npy: its flattened elements at DUMP_SAMPLE
+    indices drawn with a fixed seed (np.random.default_rng(0), sorted), the same indices in every run of the same workload."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE_OVER:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        a = t.cpu().numpy()
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        total += a.nbytes
+        assert total <= DUMP_BYTES, f"--dump-outputs: more than {DUMP_BYTES >> 20} MB"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def train_state(tr):
+    """The tensors a training step carries into the next one: parameters, the uncertainty grid's accumulated gradient, both
+    optimisers' moments and step counts, the iteration word the kernels key their random numbers by (the set
+    MappingTrainer.capture puts back after its own warm-up iterations)."""
+    ts = tr.parameters() + [tr.model.uncert_grid.grad]
+    opts = [tr.map_optimizer, tr.uncert_optim]
+    if tr.table_shard is not None:
+        ts.append(tr.table_shard["store"])
+        opts.append(tr.table_optimizer)
+    if tr.direct:
+        ts.append(tr.iter_state)
+    for o in opts:
+        if hasattr(o, "step_dev"):
+            ts.append(o.step_dev)
+        ts += [v for st in o.state.values() for v in st.values() if torch.is_tensor(v)]
+    return ts
+
+
+def train_outputs(tr, ret, loss):
+    """What a caller of a training step receives from it: the rendered colour and depth, the loss vector (ops.TrainStep.losses
+    slots), the total loss and the parameters the step's optimisers left."""
+    return dict({"rgb": ret["rgb"], "depth": ret["depth"], "losses": ret["_losses"], "loss": loss.reshape(1)}, **tr.model._params())
+
+
 def run_eval(args, dev):
     """--workload office0_8192x43_eval (BASELINE configs[2], the planner query path): one step = the eval-mode render of 8192
     rays (naruto_render_fwd: sampling + field query + compositing + uncertainty aggregation in one launch, raw kept on chip);
@@ -464,10 +517,12 @@ def run_eval(args, dev):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        ret = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ms = dt / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: v for k, v in ret.items() if torch.is_tensor(v)})
     k_ms = events_ms(step, max(10, min(args.steps, 50)))
     gather = 16 * 8 * 8 + 32
     alg = n_rays * (S_tot * gather + 64)                       # render inference, per ray S x 1056 B + 28 B in + 36 B out
@@ -536,7 +591,7 @@ def ba_scene(mlp: str, active_ray: bool, dev):
 
 
 def mapping_iter_ms(mlp: str, dev, steps: int, warmup: int):
-    """BASELINE's second metric for the default line: one global_BA iteration END TO END (ray assembly -> [active ray selection] ->
+    """BASELINE's second metric, in the --full line: one global_BA iteration END TO END (ray assembly -> [active ray selection] ->
     training iteration, one hipGraph: naruto_amd.ba_loop.FusedBA), shipped sampling (32 + 11), active rays off and on; ms per iteration,
     median of five chunks after >= PREWARM_MS of untimed replays.  `--workload office0_ba_iter` gives the long form."""
     from naruto_amd.ba_loop import FusedBA
@@ -583,9 +638,12 @@ def run_ba_iter(args, dev):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(n_calls):
-            ba.call_iterations()
+            last = ba.call_iterations()
         torch.cuda.synchronize()
         res[mode] = (time.perf_counter() - t0) / (n_calls * iters) * 1e3
+        if mode == "graph" and args.dump_outputs:            # the headline's path; the eager mode below trains the same model further
+            tr.model.check_asserts(block=True)
+            dump_outputs(args.dump_outputs, train_outputs(tr, *last))
         if mode == "graph":
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -644,24 +702,35 @@ def main():
     ap.add_argument("--no-chain", action="store_true", help="one graph launch per iteration instead of one per global_BA call of mapping.iters iterations")
     ap.add_argument("--path", choices=("trainer", "dropin"), default="trainer",
                     help="trainer: MappingTrainer's fused iteration (hipGraph replay), the headline; dropin: the reference's unchanged loop body "
-                         "(coslam.py:361-399) around NarutoFieldHIP is the timed step (its figures ride in the default line too, as `dropin`)")
+                         "(coslam.py:361-399) around NarutoFieldHIP is the timed step (its figures ride in the --full line too, as `dropin`)")
     ap.add_argument("--no-dropin", action="store_true")
-    ap.add_argument("--no-mapping-iter", action="store_true", help="skip the mapping-iter ms (office0_ba_iter) figures of the default line")
+    ap.add_argument("--no-mapping-iter", action="store_true", help="skip the mapping-iter ms (office0_ba_iter) figures of the --full line")
     ap.add_argument("--active-ray", action="store_true", help="office0_ba_iter: mapping.active_ray on (4x oversampled batch -> active ray selection)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: per-kernel table and rooflines, drop-in caller, mapping-iter ms, median-of-chunks step times, "
+                         "CPU and torch-on-GPU baselines (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.path == "dropin":
+        ap.error("--dump-outputs: --path dropin times several variants of the caller's loop, none of which is kept")
 
-    # `python bench.py --gpus N` WITHOUT a launcher (no WORLD_SIZE in the environment): become the documented launch line -- one process per
+    # `python bench.py --gpus N` WITHOUT a launcher (no WORLD_SIZE in the environment): run the documented launch line -- one process per
     # GPU through torch.distributed.run on 127.0.0.1 -- instead of failing on the world-size check (round-3 review: a scaling run issued like
-    # the 1-GPU command would have wasted its 8-GPU lease).  exec: the launcher inherits stdout, rank 0's one JSON line is this command's.
+    # the 1-GPU command would have wasted its 8-GPU lease).  The launcher is a child process that inherits stdout: rank 0's one JSON line
+    # is this command's, and its exit status is this command's.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        print("[bench] --gpus %d without a launcher: exec %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
-        os.execv(sys.executable, cmd)
+        print("[bench] --gpus %d without a launcher: running %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
+        rc = subprocess.run(cmd).returncode
+        sys.exit(rc if rc >= 0 else 128 - rc)              # killed by signal s: the shell's 128 + s
 
     # stdout carries exactly ONE line, the JSON result.  RCCL writes its version banner to the C-level stdout (it lands in
     # libc's buffer and would come out after the result); route file descriptor 1 to stderr for the whole run and give it
@@ -758,22 +827,31 @@ def main():
                                                                                           rays["target_d"])
 
     def step():
-        tr.step(rays["rays_o"], rays["rays_d"], rays["target_rgb"], rays["target_d"], smooth=True, n_rays_total=n_total)
+        return tr.step(rays["rays_o"], rays["rays_d"], rays["target_rgb"], rays["target_d"], smooth=True, n_rays_total=n_total)
 
     chain_n = tr.chain_length() if use_graph and tr._graphs is not None else 0
 
     def steps(k: int):
-        """k iterations: whole calls of chain_n iterations as one graph launch each, the remainder iteration by iteration"""
+        """k iterations: whole calls of chain_n iterations as one graph launch each, the remainder iteration by iteration; returns the
+        last iteration's (ret, loss)"""
+        out = None
         while chain_n and k >= chain_n:
-            tr.step_chain(n_rays_total=n_total)
+            out = tr.step_chain(n_rays_total=n_total)
             k -= chain_n
         for _ in range(k):
-            step()
+            out = step()
+        return out
 
     steps(args.warmup)
     # pre-warm: the timed window of the default run is ~5 ms (20 - 50 steps of ~0.23 ms) -- short enough to be read at ramping clocks right
     # after the captures and copies above.  Untimed steps for >= PREWARM_MS of wall time first (every rank the same count: the collectives
-    # of a data-parallel step must pair up), stated in the line.
+    # of a data-parallel step must pair up), stated in the line.  Their count depends on the speed of the build, so the training state
+    # is put back afterwards: the timed steps start from the state after the warm-up steps, and what they compute depends on the
+    # arguments alone (--dump-outputs).
+    state = train_state(tr)
+    saved = [t.detach().clone() for t in state]
+    saved_iter = tr.iter
+    saved_rng = None if tr.direct else torch.cuda.get_rng_state(dev)          # the autograd iteration's jitter comes from torch's RNG
     torch.cuda.synchronize()
     t_w = time.perf_counter()
     for _ in range(8):
@@ -787,11 +865,18 @@ def main():
         n_prewarm = int(t.item())
     steps(n_prewarm)
     tr.model.check_asserts(block=True)
+    with torch.no_grad():
+        for t, s in zip(state, saved):
+            t.copy_(s)
+    tr.iter = saved_iter
+    if saved_rng is not None:
+        torch.cuda.set_rng_state(saved_rng, dev)
+    del saved
     if group is not None:
         torch.distributed.barrier(group)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    steps(args.steps)
+    last = steps(args.steps)
     torch.cuda.synchronize()
     if group is not None:
         torch.distributed.barrier(group)
@@ -801,10 +886,12 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX, group=group)
         dt = float(t.item())
     tr.model.check_asserts(block=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(tr, *last))
     # beside the contract's figure (exactly K steps between two syncs, above): the MEDIAN over five further chunks of K steps each, which a
     # single disturbed chunk cannot move (single process only: the chunks' syncs would need barriers of their own)
     ms_chunks = ms_single = None
-    if group is None:
+    if args.full and group is None:
         if chain_n:
             per = max(chain_n, args.steps // chain_n * chain_n)
             ms_chunks = timed_chunks(lambda i: steps(per), 5) / per
@@ -824,7 +911,8 @@ def main():
             "value": round(n_total * args.steps / dt, 1), "unit": "rays/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": args.scaling,
             "vs_baseline": None, "dtype": DTYPE_F32 if args.mlp == "fp32" else "bf16 (MLP operands; fp32 accumulate, fp32 elsewhere)", "data": "synthetic",
-            "prewarm": {"untimed_steps_before_the_timed_region": args.warmup + 8 + n_prewarm, "target_ms": PREWARM_MS},
+            "prewarm": {"untimed_steps_before_the_timed_region": args.warmup + 8 + n_prewarm, "target_ms": PREWARM_MS,
+                        "training_state": f"put back to where the {args.warmup} warm-up steps left it"},
             "ms_per_step_median_of_5_chunks": None if ms_chunks is None else round(ms_chunks, 4),
             "graph_launches": (f"one hipGraph per {chain_n} iterations (= one global_BA call, mapping.iters); the remainder of K and --no-chain: one per iteration"
                                if chain_n else ("one hipGraph per iteration" if use_graph and tr._graphs is not None else "eager")),
@@ -848,7 +936,7 @@ def main():
                                 "hbm_frac": round(step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                                 "mfma_util": round(rays_s / world * S_tot * 31104 / (mfma_peak * 1e12), 6),
                                 "mfma_peak": f"{mfma_peak} TFLOP/s " + ("(fp32 MFMA = fp32 vector rate)" if args.mlp == "fp32" else "(bf16 MFMA, dense)")}
-        if not args.no_kernels:
+        if args.full and not args.no_kernels:
             rows = kernel_table(tr, rays, cfg, max(10, min(args.steps, 50)))
             dom = max((r for r in rows if r["bound"] is not None), key=lambda r: r["ms"])
             # the dominant kernel OF THE ITERATION: the table scatter when its launch (iteration shape, timed alone) outlasts the field
@@ -1001,7 +1089,7 @@ def main():
                                              "hbm_frac_active_samples": round(act_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
             out["kernels"] = rows
             out["kernels_ms_sum"] = round(sum(r["ms"] for r in rows if r["bound"] is not None), 4)
-        if not args.no_dropin and world == 1:
+        if args.full and not args.no_dropin and world == 1:
             try:
                 d = dropin_timing(cfg, n_rays, dev, max(10, min(args.steps, 50)), 10)
                 out["dropin"] = d
@@ -1011,8 +1099,8 @@ def main():
                                       "ms_per_step / value above are MappingTrainer's fused iteration under hipGraph replay")
             except Exception as e:                               # informational: never fail the bench line over it
                 out["dropin"] = {"error": repr(e)[:300]}
-        if world == 1 and args.workload.startswith("office0") and not args.no_mapping_iter:
-            # BASELINE's metric is "rays/sec (train step) + mapping-iter ms": the second half, measured by the same default run
+        if args.full and world == 1 and args.workload.startswith("office0") and not args.no_mapping_iter:
+            # BASELINE's metric is "rays/sec (train step) + mapping-iter ms": the second half, measured by the same --full run
             try:
                 mi = mapping_iter_ms(args.mlp, dev, max(10, min(args.steps, 50)), 10)
                 # the shipped setting is active rays ON (configs/default.py:54 enable_active_ray = True, read at coslam.py:100): that is the headline figure
@@ -1023,7 +1111,7 @@ def main():
                                            "32 + 11 samples, one hipGraph (naruto_amd.ba_loop.FusedBA); median of five chunks; long form: --workload office0_ba_iter")
             except Exception as e:                               # informational: never fail the bench line over it
                 out["mapping_iter"] = {"error": repr(e)[:300]}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, n_rays)
             try:
                 out["torch_gpu_baseline"] = dict(cpu_baseline(cfg, n_rays, device=dev),

@@ -3179,6 +3179,35 @@ def test_bench_self_launches_without_a_launcher(gpu):
     assert out["n_gpus"] == 2 and out["config"]["rays_per_step"] == 4096 and "multi_gpu_note" in out
 
 
+def test_bench_plain_run_dumps_the_same_outputs_twice(gpu, tmp_path):
+    """A plain `bench.py --steps K --warmup W` times K steps and measures nothing of --full's; with --dump-outputs two runs write the
+    same last-step outputs, although their time-based pre-warm runs a different number of untimed steps."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "13", "--warmup", "3", "--workload", "office0_2048x43",
+               "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 13 and abs(out["value"] - 2048 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+        for k in ("kernels", "roofline", "dropin", "mapping_iter", "cpu_baseline", "torch_gpu_baseline"):
+            assert k not in out, k
+        assert out["ms_per_step_median_of_5_chunks"] is None
+        outs.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = outs
+    assert sorted(a) == sorted(b) and {"rgb.npy", "depth.npy", "losses.npy", "loss.npy", "table.npy", "sdf_w0.npy"} <= set(a)
+    assert a["rgb.npy"].shape == (2048, 3) and a["rgb.npy"].dtype == np.float32
+    for f in a:
+        assert np.all(np.isfinite(a[f])), f
+        np.testing.assert_allclose(a[f], b[f], rtol=1e-5, atol=1e-7, err_msg=f)
+
+
 def test_fused_adam_is_a_torch_optimizer(gpu):
     """FusedAdam behind the torch.optim.Optimizer surface the reference's driver and checkpointing use: param groups edited in place
     (a scheduler's lr change), a parameter without gradient skipped, add_param_group, state_dict -> load_state_dict into a fresh

@@ -247,6 +247,25 @@ def test_bench_host_helpers():
     assert bench.physical_cores() >= 1
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float64 stays float64, the rest is written as float32, an array past DUMP_SAMPLE_OVER elements as the same
+    seeded sample in every run, and the files together stay within DUMP_BYTES."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(bench.DUMP_SAMPLE_OVER + 1, dtype=torch.float32)
+    arrays = {"a": torch.tensor([[1.5, 2.0]]), "b": torch.tensor([0.25], dtype=torch.float64), "c": torch.tensor([3], dtype=torch.int32), "big": big}
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a, b, c = (np.load(tmp_path / "one" / f"{k}.npy") for k in "abc")
+    assert a.dtype == np.float32 and a.shape == (1, 2) and b.dtype == np.float64 and c.dtype == np.float32 and c[0] == 3.0
+    assert not (tmp_path / "one" / "big.npy").exists()
+    s1, s2 = (np.load(tmp_path / d / "big_sample.npy") for d in ("one", "two"))
+    assert s1.shape == (bench.DUMP_SAMPLE,) and np.array_equal(s1, s2) and np.all(np.diff(s1) >= 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "one").iterdir()) <= bench.DUMP_BYTES
+
+
 def test_no_kernel_spills_to_scratch(built_lib):
     """Every kernel of the built device code object: no vector register spilled, no private (scratch) segment -- read from the code
     object's own metadata notes, so a change that pushes a hot kernel over its register budget fails HERE, before anyone times it.

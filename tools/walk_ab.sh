@@ -4,7 +4,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 for v in 0 2; do
   for wl in ${WLS:-office0_ba_iter office0_2048x43 office0_8192x43 unit1024_131072x43}; do
-    extra="--no-cpu-baseline --no-dropin --no-kernels --no-mapping-iter"; [ $wl = office0_ba_iter ] && extra=""
+    extra="--full --no-cpu-baseline --no-dropin --no-kernels --no-mapping-iter"; [ $wl = office0_ba_iter ] && extra=""
     NARUTO_WALK_PARTIAL=$v timeout 300 python bench.py --workload $wl --steps 20 $extra 2>/dev/null | grep '^{"metric' | python -c "
 import json,sys; d=json.loads(sys.stdin.readline()); print('WALK_PARTIAL=$v $wl', d['ms_per_step'], d.get('ms_per_step_median_of_5_chunks'))"
   done
