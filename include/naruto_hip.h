@@ -206,6 +206,34 @@ int naruto_query_bwd(const NarutoField* f, const NarutoParams* p, uint32_t M, co
                      const NarutoExtraPoints* extra, uint32_t flags,
                      const NarutoGrads* g, void* workspace, void* stream);
 
+/* Gradient of naruto_query_fwd with respect to its POINTS (autograd of the same forward through x, or through rays_o / rays_d
+ * of run_network's p = o + d * z): pose refinement and tracking differentiate the rendering through the rays
+ * (global_BA's pose_optim, coslam.py:264-281, 330-347, 378-407; Co-SLAM tracking_render, coslam.py:595-602).  Terms:
+ *   hash grid     d feat_l / d x = scale_l * sum_corners (d trilinear weight / d w) * value   (tcnn HashGrid, linear
+ *                 interpolation; corner indices are piecewise constant and contribute nothing)   [parity unpinned]
+ *   OneBlob       d quartic_cdf / du = 15/16 (1 - u^2)^2 for |u| <= 1, else 0; u = (b - x) * 16, with the +-1 periodic terms
+ *                 and the wrapped last bin (tcnn OneBlob)                                           [parity unpinned]
+ *   uncertainty   derivative of the trilinear grid_sample in its coordinates, d ix / d x = W etc. (scene_rep.py:58-64:
+ *                 align_corners=False, zero padding, x <-> z transposed); reaches raw[...,4] only
+ *   MLPs          nn.Linear + ReLU, ReLU'(0) = 0 (decoder.py:29-41, 99-116), evaluated in exact fp32 on the fp32 master
+ *                 weights in BOTH MLP modes (in bf16 mode: the gradient of the exact network at the same point)
+ *   ray points    run_network's box normalisation [Co-SLAM; called at scene_rep.py:183-184]: d rays_o[r] = sum_s g[r,s] / ext,
+ *                 d rays_d[r] = sum_s z[r,s] g[r,s] / ext per axis, g = gradient w.r.t. the normalised point; z_vals are
+ *                 constants (scene_rep.py:161-183)
+ * d_raw [M,5] required; d_geo [M,15] or NULL (= 0).  active_idx / n_active: both NULL or both given, as naruto_query_bwd
+ * (naruto_compact_active); points outside the list contribute zero.  Outputs: x points write d_x [M,3] (normalised space);
+ * ray points write d_rays_o and / or d_rays_d [N,3] (N = M / n_samples) and need workspace =
+ * naruto_query_bwd_points_workspace(f, M) bytes (x points: NULL allowed).  flags: NARUTO_BWD_POINTS_ACCUMULATE adds into the
+ * outputs instead of writing them.  No float atomics: each ray's samples are summed in a fixed order, bitwise reproducible.
+ * Parameter gradients are not touched (naruto_query_bwd gives them). */
+#define NARUTO_BWD_POINTS_ACCUMULATE 1u
+size_t naruto_query_bwd_points_workspace(const NarutoField* f, uint32_t M);
+int naruto_query_bwd_points(const NarutoField* f, const NarutoParams* p, uint32_t M, const NarutoPoints* pts,
+                            const float* d_raw, const float* d_geo /* or NULL */,
+                            const uint32_t* active_idx, const uint32_t* n_active /* both or neither */,
+                            float* d_x /* [M,3] or NULL */, float* d_rays_o, float* d_rays_d /* [N,3] or NULL */,
+                            uint32_t flags, void* workspace, void* stream);
+
 /* A1-A7 in ONE launch -- render_rays as an inference call (scene_rep.py:150-225; eval-mode forward, planner-side queries): depth
  * sampling as naruto_sample_z, the field query of naruto_query_fwd and the compositing of naruto_composite_fwd per ray, raw kept
  * in LDS.  Outputs (any may be NULL): rgb [N,3], depth, disp, acc, depth_var, uncert_map [N], weights [N,S], raw [N,S,5],

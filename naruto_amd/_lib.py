@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -53,6 +53,7 @@ class NarutoAdamSeg(C.Structure):
 MLP_FP32, MLP_BF16 = 0, 1
 BWD_OVERWRITE_WEIGHT_GRADS = 1
 BWD_OVERWRITE_TABLE_GRAD = 2
+BWD_POINTS_ACCUMULATE = 1
 TRAIN_BWD_MLP_ONLY, TRAIN_BWD_TABLE_ONLY = 4, 8
 TRAIN_FWD_DEFER_TAIL, TRAIN_BWD_DEFERRED_TAIL, TRAIN_BWD_SUMS_GIVEN = 2, 16, 32
 TRAIN_FWD_SUMS_TV_LATER, TRAIN_BWD_TV_MOVED = 3, 64
@@ -156,6 +157,8 @@ SIGNATURES = {
     "naruto_query_bwd_workspace": (C.c_size_t, [_V, _U32]),
     "naruto_query_bwd": (_I, [_V, C.POINTER(NarutoParams), _U32, C.POINTER(NarutoPoints), _V, _V, _V, _V, _V,
                               C.POINTER(NarutoExtraPoints), _U32, C.POINTER(NarutoGrads), _V, _V]),
+    "naruto_query_bwd_points_workspace": (C.c_size_t, [_V, _U32]),
+    "naruto_query_bwd_points": (_I, [_V, C.POINTER(NarutoParams), _U32, C.POINTER(NarutoPoints), _V, _V, _V, _V, _V, _V, _V, _U32, _V, _V]),
     "naruto_active_ray_workspace": (C.c_size_t, [_U32, _U32]),
     "naruto_active_ray_select_keyed": (_I, [_U32, _U32, _U32, _U32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "naruto_active_ray_select": (_I, [_U32, _U32, _U32, _U32, _V, _V, _V, _V, _V, C.POINTER(_U32), C.POINTER(_F), _F, _V, _V, _V, _V, _V, _V]),

@@ -17,6 +17,7 @@
 #include "naruto_planner.hip"
 #include "naruto_mesh.hip"
 #include "naruto_parts.hip"
+#include "naruto_pointgrad.hip"
 
 using namespace naruto;
 
@@ -813,6 +814,54 @@ int naruto_query_bwd(const NarutoField* f, const NarutoParams* p, uint32_t M, co
                      const float* d_raw, const float* d_geo, const uint32_t* active_idx, const uint32_t* n_active, const NarutoExtraPoints* extra,
                      uint32_t flags, const NarutoGrads* g, void* workspace, void* stream) {
     return query_bwd_impl(f, p, M, pts, feat_save, d_raw, d_geo, active_idx, n_active, extra, flags, g, workspace, stream, 0u, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Gradient of the query with respect to its points (see naruto_pointgrad.hip)
+// ------------------------------------------------------------------------------------------------
+size_t naruto_query_bwd_points_workspace(const NarutoField* f, uint32_t M) {
+    (void)f;
+    return 3u * sizeof(float) * (size_t)M + 256u;
+}
+
+int naruto_query_bwd_points(const NarutoField* f, const NarutoParams* p, uint32_t M, const NarutoPoints* pts, const float* d_raw, const float* d_geo,
+                            const uint32_t* active_idx, const uint32_t* n_active, float* d_x, float* d_rays_o, float* d_rays_d, uint32_t flags,
+                            void* workspace, void* stream) {
+    if (f == nullptr || p == nullptr || pts == nullptr || d_raw == nullptr) return fail(NARUTO_ERR_INVALID, "query_bwd_points: NULL argument");
+    if (p->table == nullptr || p->uncert_grid == nullptr || p->sdf_w0 == nullptr || p->sdf_w1 == nullptr || p->col_w0 == nullptr || p->col_w1 == nullptr)
+        return fail(NARUTO_ERR_INVALID, "query_bwd_points: NULL parameter");
+    if ((active_idx == nullptr) != (n_active == nullptr)) return fail(NARUTO_ERR_INVALID, "query_bwd_points: active_idx and n_active go together");
+    if ((flags & ~NARUTO_BWD_POINTS_ACCUMULATE) != 0u) return fail(NARUTO_ERR_INVALID, "query_bwd_points: unknown flags 0x%x", flags);
+    if (int rc = check_points(pts)) return rc;
+    if (M > (1u << 29)) return fail(NARUTO_ERR_INVALID, "query_bwd_points: at most 2^29 points per call (got %u)", M);
+    const bool rays = pts->x == nullptr;
+    const int acc = (flags & NARUTO_BWD_POINTS_ACCUMULATE) ? 1 : 0;
+    const hipStream_t st = (hipStream_t)stream;
+    const PointSrc ps = make_points(pts);
+    if (!rays) {
+        if (d_rays_o != nullptr || d_rays_d != nullptr) return fail(NARUTO_ERR_INVALID, "query_bwd_points: d_rays_o / d_rays_d belong to ray points, these are x points");
+        if (d_x == nullptr) return fail(NARUTO_ERR_INVALID, "query_bwd_points: no output (x points write d_x)");
+    } else {
+        if (d_x != nullptr) return fail(NARUTO_ERR_INVALID, "query_bwd_points: d_x belongs to x points; ray points write d_rays_o / d_rays_d");
+        if (d_rays_o == nullptr && d_rays_d == nullptr) return fail(NARUTO_ERR_INVALID, "query_bwd_points: no output (ray points write d_rays_o and / or d_rays_d)");
+        if (pts->n_samples > (uint32_t)kMaxSamples) return fail(NARUTO_ERR_INVALID, "query_bwd_points: at most %d samples per ray (got %u)", kMaxSamples, pts->n_samples);
+        if (M % pts->n_samples != 0u) return fail(NARUTO_ERR_INVALID, "query_bwd_points: M = %u is not a whole number of rays of %u samples", M, pts->n_samples);
+        if (workspace == nullptr) return fail(NARUTO_ERR_INVALID, "query_bwd_points: ray points need naruto_query_bwd_points_workspace(f, M) bytes of workspace");
+    }
+    if (M == 0) return NARUTO_OK;
+    float* out = rays ? reinterpret_cast<float*>(workspace) : d_x;
+    // a list leaves the other points' rows alone: they must read as zero where the result is written, not added
+    if (active_idx != nullptr && (rays || !acc)) {
+        if (hipMemsetAsync(out, 0, 3u * sizeof(float) * (size_t)M, st) != hipSuccess) return check_launch("query_bwd_points: zero fill");
+    }
+    const uint32_t blocks = (M + (uint32_t)kPgThreads - 1u) / (uint32_t)kPgThreads;
+    hipLaunchKernelGGL(k_query_bwd_points, dim3(blocks), dim3(kPgThreads), 0, st, f->lt, f->ut, f->bt, ps, M, reinterpret_cast<const float2*>(p->table),
+                       p->uncert_grid, p->sdf_w0, p->sdf_w1, p->col_w0, p->col_w1, d_raw, d_geo, active_idx, n_active, out, rays ? 1 : 0, rays ? 0 : acc);
+    if (int rc = check_launch("query_bwd_points")) return rc;
+    if (!rays) return NARUTO_OK;
+    const uint32_t n_rays = M / pts->n_samples;
+    hipLaunchKernelGGL(k_ray_point_reduce, dim3((n_rays + 3u) / 4u), dim3(256), 0, st, n_rays, pts->n_samples, out, pts->z_vals, d_rays_o, d_rays_d, acc);
+    return check_launch("ray_point_reduce");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -371,7 +371,10 @@ class NarutoFieldHIP(nn.Module):
         if _check and not capturing:
             self.check_asserts()
         cfg = self.config
-        if self.fused_train and _smooth is None and self.process_group is None and rays_o.is_cuda:
+        # ray gradients (pose refinement / tracking: rays built from poses that require grad) come from the modular operators; the
+        # fused training node is parameter-only
+        rays_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+        if self.fused_train and not rays_grad and _smooth is None and self.process_group is None and rays_o.is_cuda:
             # the unchanged caller's route: sampling + field query + loss stage + tail as the fused training launches, the backward
             # as naruto_train_backward with the caller's loss weights read from the cotangents of the scalar losses
             if not cfg['training']['perturb'] > 0.:

@@ -319,8 +319,9 @@ def smoothness(handle: FieldHandle, table: torch.Tensor, sample_points: int, vox
 # A2-A5 fused
 # ---------------------------------------------------------------------------------------------------
 class _FieldQuery(torch.autograd.Function):
-    """raw (or sdf_uncert) [, geo] = field(points).  Gradients flow to the six parameter tensors only
-    (the reference never differentiates w.r.t. the query points: tracking is disabled in every config)."""
+    """raw (or sdf_uncert) [, geo] = field(points).  Gradients flow to the six parameter tensors (naruto_query_bwd) and, when
+    asked for, to the points: x, or rays_o / rays_d (naruto_query_bwd_points; z_vals stay constants).  Pose refinement and
+    tracking differentiate the rendering through the rays (reference coslam.py:264-281, 330-347; tracking_render)."""
 
     @staticmethod
     def forward(ctx, handle, color, want_geo, x, rays_o, rays_d, z_vals, table, uncert_grid, sdf_w0, sdf_w1, col_w0, col_w1):
@@ -336,6 +337,7 @@ class _FieldQuery(torch.autograd.Function):
             dev = z_vals.device
         pts, M = _points_struct(x, rays_o, rays_d, z_vals)
         need_grad = any(ctx.needs_input_grad[7:])
+        need_pts = any(ctx.needs_input_grad[3:6])
         out = torch.empty(M, 5 if color else 2, dtype=torch.float32, device=dev)
         geo = torch.empty(M, 15, dtype=torch.float32, device=dev) if want_geo else None
         feat = torch.empty(16, M, 2, dtype=torch.float32, device=dev) if need_grad else None
@@ -346,7 +348,8 @@ class _FieldQuery(torch.autograd.Function):
         ctx.handle, ctx.color, ctx.want_geo, ctx.M = handle, color, want_geo, M
         ctx.set_materialize_grads(False)
         ctx.has_x = x is not None
-        if need_grad:
+        ctx.need_grad = need_grad
+        if need_grad or need_pts:
             ctx.save_for_backward(feat, *(t for t in (x, rays_o, rays_d, z_vals) if t is not None),
                                   *(params[k] for k in PARAM_NAMES))
         if want_geo:
@@ -367,7 +370,7 @@ class _FieldQuery(torch.autograd.Function):
             rest = saved[4:]
         params = dict(zip(PARAM_NAMES, rest))
         M = ctx.M
-        dev = feat.device
+        dev = params["table"].device
         d_out = _f32c(d_out, "d_out") if d_out is not None else None
         if ctx.color:
             d_raw = d_out if d_out is not None else torch.zeros(M, 5, dtype=torch.float32, device=dev)
@@ -385,12 +388,36 @@ class _FieldQuery(torch.autograd.Function):
             setattr(gs, n, _p(grads[n]))
         ps = _params_struct(params)
         pts, _ = _points_struct(x, rays_o, rays_d, z_vals)
+        d_x = d_o = d_d = None
         with _on_device(dev):
-            ws_bytes = lib.naruto_query_bwd_workspace(ctx.handle.ptr, M)
-            ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
-            check(lib.naruto_query_bwd(ctx.handle.ptr, C.byref(ps), M, C.byref(pts), _p(feat), _p(d_raw), _p(d_geo), None, None,
-                                       None, 0, C.byref(gs), _p(ws), _stream()), "naruto_query_bwd")
-        return (None, None, None, None, None, None, None) + tuple(grads[n] for n in PARAM_NAMES)
+            if ctx.need_grad:
+                ws_bytes = lib.naruto_query_bwd_workspace(ctx.handle.ptr, M)
+                ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+                check(lib.naruto_query_bwd(ctx.handle.ptr, C.byref(ps), M, C.byref(pts), _p(feat), _p(d_raw), _p(d_geo), None, None,
+                                           None, 0, C.byref(gs), _p(ws), _stream()), "naruto_query_bwd")
+            if ctx.has_x and ctx.needs_input_grad[3]:
+                d_x = torch.empty(M, 3, dtype=torch.float32, device=dev)
+                point_grads(ctx.handle, params, pts, M, d_raw, d_geo, d_x=d_x)
+            elif not ctx.has_x and (ctx.needs_input_grad[4] or ctx.needs_input_grad[5]):
+                d_o = torch.empty_like(rays_o) if ctx.needs_input_grad[4] else None
+                d_d = torch.empty_like(rays_d) if ctx.needs_input_grad[5] else None
+                point_grads(ctx.handle, params, pts, M, d_raw, d_geo, d_rays_o=d_o, d_rays_d=d_d)
+        return (None, None, None, d_x, d_o, d_d, None) + tuple(grads[n] for n in PARAM_NAMES)
+
+
+def point_grads(handle: FieldHandle, params: Dict[str, torch.Tensor], pts: NarutoPoints, M: int, d_raw: torch.Tensor,
+                d_geo: Optional[torch.Tensor] = None, *, d_x=None, d_rays_o=None, d_rays_d=None, active=None, n_active=None,
+                accumulate: bool = False) -> None:
+    """naruto_query_bwd_points on the current stream: d_raw [M,5] (+ d_geo [M,15]) -> d_x [M,3] (x points) or d_rays_o /
+    d_rays_d [N,3] (ray points), written (or added, ``accumulate``).  ``active`` / ``n_active``: naruto_compact_active's list."""
+    lib = _lib.load()
+    ps = _params_struct(params)
+    ws = None
+    if d_x is None:
+        ws = torch.empty((lib.naruto_query_bwd_points_workspace(handle.ptr, M) + 3) // 4, dtype=torch.float32, device=d_raw.device)
+    check(lib.naruto_query_bwd_points(handle.ptr, C.byref(ps), M, C.byref(pts), _p(d_raw), _p(d_geo), _p(active), _p(n_active), _p(d_x),
+                                      _p(d_rays_o), _p(d_rays_d), _lib.BWD_POINTS_ACCUMULATE if accumulate else 0, _p(ws), _stream()),
+          "naruto_query_bwd_points")
 
 
 def field_query(handle: FieldHandle, params: Dict[str, torch.Tensor], *, x=None, rays_o=None, rays_d=None, z_vals=None,
@@ -531,6 +558,7 @@ class _RenderTrain(torch.autograd.Function):
         M = N * S
         dev = z_vals.device
         need_grad = any(ctx.needs_input_grad[11:])
+        need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         raw = torch.empty(N, S, 5, dtype=torch.float32, device=dev)
         losses = torch.zeros(10, dtype=torch.float32, device=dev)
         sm_loss = sm_x = sm_d = None
@@ -568,7 +596,8 @@ class _RenderTrain(torch.autograd.Function):
         ctx.handle, ctx.depth_trunc, ctx.rgb_missing, ctx.n_total = handle, depth_trunc, rgb_missing, n_total
         ctx.has_smooth = smooth is not None
         ctx.set_materialize_grads(False)
-        if need_grad:
+        ctx.need_grad = need_grad
+        if need_grad or need_rays:
             extra = (sm_x, sm_d) if smooth is not None else ()
             ctx.save_for_backward(raw, feat, rays_o, rays_d, z_vals, target_rgb, target_d, sums, *(params[k] for k in PARAM_NAMES), *extra)
         ctx.mark_non_differentiable(disp, acc, depth_var, um, raw)
@@ -636,10 +665,16 @@ class _RenderTrain(torch.autograd.Function):
                 ex = _lib.NarutoExtraPoints()
                 ex.x, ex.d_feat, ex.scale, ex.n = _p(sm_x), _p(sm_d), d_smooth.data_ptr(), sm_x.shape[0]
                 n_extra = sm_x.shape[0]
-            ws = torch.empty((lib.naruto_query_bwd_workspace(ctx.handle.ptr, M + n_extra) + 3) // 4, dtype=torch.float32, device=dev)
-            check(lib.naruto_query_bwd(ctx.handle.ptr, C.byref(ps), M, C.byref(pts), _p(feat), _p(d_raw), None, _p(active), _p(n_active),
-                                       None if ex is None else C.byref(ex), flags, C.byref(gs), _p(ws), st), "naruto_query_bwd")
-        return (None,) * 11 + tuple(grads[n] for n in PARAM_NAMES)
+            if ctx.need_grad:
+                ws = torch.empty((lib.naruto_query_bwd_workspace(ctx.handle.ptr, M + n_extra) + 3) // 4, dtype=torch.float32, device=dev)
+                check(lib.naruto_query_bwd(ctx.handle.ptr, C.byref(ps), M, C.byref(pts), _p(feat), _p(d_raw), None, _p(active), _p(n_active),
+                                           None if ex is None else C.byref(ex), flags, C.byref(gs), _p(ws), st), "naruto_query_bwd")
+            # ray gradients (pose refinement / tracking): the same d_raw, over the same active list when there is one
+            d_o = torch.empty_like(rays_o) if ctx.needs_input_grad[1] else None
+            d_d = torch.empty_like(rays_d) if ctx.needs_input_grad[2] else None
+            if d_o is not None or d_d is not None:
+                point_grads(ctx.handle, params, pts, M, d_raw, None, d_rays_o=d_o, d_rays_d=d_d, active=active, n_active=n_active)
+        return (None, d_o, d_d) + (None,) * 8 + tuple(grads[n] for n in PARAM_NAMES)
 
 
 def handle_supports_overwrite(handle: FieldHandle) -> bool:
@@ -961,6 +996,10 @@ class _TrainForward(torch.autograd.Function):
         if d_rgb is not None or d_depth is not None:
             raise NotImplementedError("the fused training node differentiates the losses only; to differentiate the rendered rgb / depth "
                                       "as well set model.fused_train = False (the modular operators)")
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            raise NotImplementedError("the fused training node gives parameter gradients only; ray gradients (pose refinement / tracking) "
+                                      "come from the modular operators (ops.render_train), which NarutoFieldHIP.forward uses whenever "
+                                      "rays_o or rays_d requires grad")
         rays_o, rays_d, target_rgb, target_d = ctx.saved_tensors[:4]
         params = dict(zip(PARAM_NAMES, ctx.saved_tensors[4:10]))
         dev = rays_o.device
