@@ -460,7 +460,7 @@ typedef struct NarutoTrainStep {
                                                          draw their own numbers (splitmix64 keyed by seed, counter,
                                                          index); the counter advances once per forward.        */
     const float *loss_weights;                        /* [10] device: d(total)/d(losses[i]); slots 4,6,7,9 ignored */
-    float *z_vals, *raw, *feat_save;                  /* [N,S] [N,S,5] [16][N*S][2]                           */
+    float *z_vals, *raw, *feat_save;                  /* [N,S] [N,S,5] [16][N*S][2]: all three required        */
                                                       /* feat_save is PRIVATE to the forward / backward pair of one step: level-major as
                                                        * written above, or sample-major [N*S][16][2] where the forward runs in Morton
                                                        * order of the samples (tables > 64 MB, batches >= 4 M samples; round 6).  Same
@@ -511,6 +511,19 @@ int naruto_debug_fwd_timeline(void* device_buffer);
 /* profiling (bench.py's roofline): k_hash_scatter_lds alone, over the point list the preceding naruto_train_backward left in the
  * workspace, in the launch shape of the iteration; writes the scatter's partial tables only (no gradient, no parameter). */
 int naruto_debug_train_scatter(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, void* stream);
+
+/* The launch plans, host only (nothing is launched, no GPU needed; tests/test_launch_plans_host.py, tests/test_gpu_launch_forms.py).
+ * naruto_debug_train_plan: what naruto_train_forward's field-query launch is for this step (only n_rays, n_samples_d and n_range_d of t
+ *   are read; the NARUTO_FWD_* / NARUTO_WALK_* / NARUTO_DEBUG_* knobs as the launcher reads them); with_loss = the loss stage may ride along
+ *   (naruto_train_forward), deferred = forward + backward as one iteration.  out = {form (0 Flat, 1 Walk, 2 Packed, 3 Short, 4 Sorted), fused
+ *   loss stage, two-phase tile, smoothness term moved to the backward, tiles per ray (Walk), rays per loss row, ray workgroups, threads per
+ *   workgroup}.  Packed's fall-back to Flat, where not even one row fits the LDS, is reported as Flat.
+ * naruto_debug_render_plan: naruto_render_fwd's launch for n_rays rays of S samples (bf16 != 0: NARUTO_MLP_BF16 mode); wide = -1 reads
+ *   NARUTO_RENDER_WIDE as the launcher does, 0 / 1 / 2 override it.  out = {form (0 k_render_fwd, 1 k_render_fwd_packed<*, 256>,
+ *   2 k_render_fwd_packed<*, 512>), rays per group, workgroups, rays per pass of the grid-stride loop, dynamic LDS bytes of the launch,
+ *   dynamic LDS bytes reserved for the kernel, the kernel's static LDS bytes, threads per workgroup}. */
+int naruto_debug_train_plan(const NarutoField* f, const NarutoTrainStep* t, int with_loss, int deferred, uint32_t out[8]);
+int naruto_debug_render_plan(const NarutoField* f, uint32_t n_rays, uint32_t S, int bf16, int wide, uint32_t out[8]);
 
 /* Measurement aid (bench.py, workloads whose table fits no cache): one launch that reads RANDOM 64-byte lines out of `table`
  * (table_bytes of it) -- the access pattern of the hash gather on the T = 2^22 levels, without the kernel around it; *n_lines_out

@@ -186,6 +186,8 @@ SIGNATURES = {
     "naruto_debug_train_query_fwd": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), _V]),
     "naruto_debug_fwd_timeline": (_I, [_V]),
     "naruto_debug_train_scatter": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), _V]),
+    "naruto_debug_train_plan": (_I, [_V, C.POINTER(NarutoTrainStep), _I, _I, C.POINTER(_U32)]),
+    "naruto_debug_render_plan": (_I, [_V, _U32, _U32, _I, _I, C.POINTER(_U32)]),
     "naruto_render_fwd": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoRender), _V]),
     "naruto_train_backward": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), C.POINTER(NarutoGrads), _U32,
                                    C.POINTER(NarutoFusedAdam), _V]),

@@ -903,7 +903,7 @@ int train_check(const NarutoField* f, const NarutoParams* p, const NarutoTrainSt
     if (p->table == nullptr || p->uncert_grid == nullptr || p->sdf_w0 == nullptr || p->sdf_w1 == nullptr || p->col_w0 == nullptr || p->col_w1 == nullptr)
         return fail(NARUTO_ERR_INVALID, "%s: NULL parameter", who);
     if (t->rays_o == nullptr || t->rays_d == nullptr || t->target_rgb == nullptr || t->target_d == nullptr || t->z_vals == nullptr || t->raw == nullptr ||
-        t->sums == nullptr || t->losses == nullptr || t->workspace == nullptr)
+        t->feat_save == nullptr || t->sums == nullptr || t->losses == nullptr || t->workspace == nullptr)
         return fail(NARUTO_ERR_INVALID, "%s: NULL buffer in NarutoTrainStep", who);
     const uint32_t S = t->n_samples_d + t->n_range_d;
     if (t->n_rays == 0 || S < 2 || S > (uint32_t)kMaxSamples) return fail(NARUTO_ERR_INVALID, "%s: need rays and 2..%d samples per ray", who, kMaxSamples);
@@ -941,7 +941,13 @@ struct TrainFwdPlan {
     bool tv_moved;      // the walk samples its own depths and encodes the lattice; the term is evaluated in the backward's first launch
     uint32_t tpr;       // Walk: tiles per ray
     uint32_t rays_per_row;      // rays per row of the loss stage's partial sums (kRaysPerBlock, or Short's rays per workgroup)
+    uint32_t blocks;            // workgroups of the field-query launch (ray workgroups: the smoothness tail's are not counted)
+    uint32_t threads;           // threads per workgroup of that launch
+    uint32_t pack_rows;         // Packed: loss rows a workgroup holds at a time
+    uint32_t pack_waves;        // Packed: waves per workgroup
 };
+// what a Packed workgroup of W waves keeps besides its rays: the static LDS of the fp32 form (the larger) + 256 B
+inline size_t packed_fixed_lds(uint32_t W) { return (W == 4u ? packed_static_lds<false, 4>() : packed_static_lds<false, 8>()) + 256u; }
 TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool with_loss, bool deferred) {
     static const bool tv_on = getenv("NARUTO_TV_MOVE") == nullptr || atoi(getenv("NARUTO_TV_MOVE")) != 0;
     static const bool no_fuse = getenv("NARUTO_DEBUG_NO_FUSED_LOSS_STAGE") != nullptr, no_ee = getenv("NARUTO_DEBUG_NO_EARLY_EXIT") != nullptr;
@@ -951,7 +957,15 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
     // 0.171 -> 0.159 ms, the BA batch 0.1875 -> 0.1795 -- and loses beyond (8 192 x 43: 0.391 -> 0.408, 131 072 x 43: 4.86 -> 4.92)
     static const uint32_t partial_max = getenv("NARUTO_WALK_PARTIAL_MAX") ? (uint32_t)atoi(getenv("NARUTO_WALK_PARTIAL_MAX")) : 8u;
     const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d;
-    TrainFwdPlan pl{FwdForm::Flat, false, false, false, 0u, (uint32_t)kRaysPerBlock};
+    static const bool small_wg_on = getenv("NARUTO_DEBUG_FWD_SMALL_WG") == nullptr || atoi(getenv("NARUTO_DEBUG_FWD_SMALL_WG")) != 0;
+    static const int pack_waves = getenv("NARUTO_PACK_WAVES") ? atoi(getenv("NARUTO_PACK_WAVES")) : 8;
+    TrainFwdPlan pl{FwdForm::Flat, false, false, false, 0u, (uint32_t)kRaysPerBlock, 0u, 256u, 0u, 0u};
+    // the flat launch, where every other form falls back to: 64-sample tiles; between one and two four-wave workgroups per CU (2 048 rays
+    // x 43 samples: 1 376 tiles) two-wave workgroups (see k_query_fwd), from two per CU on one eight-wave workgroup per CU
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)N * S + 63u) / 64u);
+    if (small_wg_on && n_tiles > cu_count(f) * 4u && n_tiles < cu_count(f) * 8u) { pl.blocks = (n_tiles + 1u) / 2u; pl.threads = 128u; }
+    else if (kFwdSplit && n_tiles >= cu_count(f) * 8u) { pl.blocks = cu_count(f); pl.threads = 512u; }
+    else pl.blocks = (n_tiles + 3u) / 4u < cu_count(f) * 4u ? (n_tiles + 3u) / 4u : cu_count(f) * 4u;
     const bool exact = S % 64u == 0u && S > 64u;
     const bool can_fuse = with_loss && !no_fuse && ray_scratch_bytes(S) <= kFwdLossMaxRayLds;
     bool packed_on = packed_mode == 2 || ((packed_mode == 1 || packed_mode == 3) && !exact);
@@ -964,11 +978,27 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
     const bool big_batch = (uint64_t)N * S >= 4000000ull && S <= 64u;
     if (with_loss && kFwdSplit && (sorted_mode == 2 || (sorted_mode == 1 && (big_table || big_batch) && packed_mode == 1)) && (uint64_t)N * S < 0x0FFFFFFFull) {
         pl.form = FwdForm::Sorted;
+        pl.blocks = cu_count(f);            // the list queries (k_query_fwd_list)
+        pl.threads = 512u;
         return pl;
     }
     if (packed_on && with_loss && !no_fuse && kFwdSplit && S <= 4095u && N >= 1u) {
-        pl.form = FwdForm::Packed;          // (falls back to the flat launch inside launch_train_query if not even one row fits the LDS)
-        pl.fused = true;
+        // workgroup shape: 8 waves x 1 per CU, or 4 waves x 2 per CU (NARUTO_PACK_WAVES); rows (of four rays) a workgroup holds at a time: as many as
+        // the LDS next to the weights, the feature slabs and the tiles' points takes, at most three
+        const uint32_t W = pack_waves == 4 ? 4u : 8u, per_cu = W == 4u ? 2u : 1u;
+        const size_t lds_free = (size_t)160u * 1024u / per_cu > packed_fixed_lds(W) ? (size_t)160u * 1024u / per_cu - packed_fixed_lds(W) : 0u;
+        uint32_t rows = kPackMaxRows;
+        while (rows > 0u && packed_lds_bytes(rows, S) > lds_free) --rows;
+        if (rows > 0u) {                    // (else not even one row fits the LDS: the flat launch, its loss stage in a launch of its own)
+            const uint32_t n_rows = (N + (uint32_t)kRaysPerBlock - 1u) / (uint32_t)kRaysPerBlock;
+            const uint32_t slots = cu_count(f) * per_cu;
+            pl.form = FwdForm::Packed;
+            pl.fused = true;
+            pl.blocks = n_rows < slots ? n_rows : slots;        // every workgroup resident at once, the rows spread evenly over them
+            pl.threads = 64u * W;
+            pl.pack_rows = rows;
+            pl.pack_waves = W;
+        }
         return pl;
     }
     if (S <= 64u && can_fuse && kFwdSplit && partial_mode != 0) {
@@ -978,6 +1008,8 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
             pl.fused = true;
             pl.split = true;
             pl.rays_per_row = R;
+            pl.blocks = (N + R - 1u) / R < cu_count(f) * 4u ? (N + R - 1u) / R : cu_count(f) * 4u;
+            pl.threads = 256u;
             pl.tv_moved = tv_on && deferred && t->smooth_points != 0;
             return pl;
         }
@@ -989,6 +1021,8 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
     if (!walk) return pl;
     pl.form = FwdForm::Walk;
     pl.tpr = tpr;
+    pl.blocks = (N + 3u) / 4u < cu_count(f) * 4u ? (N + 3u) / 4u : cu_count(f) * 4u;          // one wave per ray
+    pl.threads = 256u;
     pl.fused = can_fuse;
     // (two workgroups per CU: static LDS -- weight images, four slabs, the loss rows -- + the rays' images within half a CU's 160 KB)
     pl.split = pl.fused && kFwdSplit && sizeof(FwdLdsExact) + (size_t)kRaysPerBlock * sizeof(FwdSlab) + ray_scratch_fwd_bytes(S) + 256u <= (size_t)80u * 1024u;
@@ -1020,16 +1054,12 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
     if (wx_on != pl.tv_moved) return fail(NARUTO_ERR_INVALID, "train query: the caller's launch plan (depth sampling in the walk: %d) is not the launcher's (%d)", (int)wx_on, (int)pl.tv_moved);
     PointSrc ps{};
     ps.rays_o = t->rays_o; ps.rays_d = t->rays_d; ps.z_vals = t->z_vals; ps.S = S;
-    const uint32_t n_tiles = (M + 63u) / 64u;
-    uint32_t blocks = (n_tiles + 3u) / 4u;
-    if (blocks > cu_count(f) * 4u) blocks = cu_count(f) * 4u;
+    const uint32_t blocks = pl.blocks;
     EarlyExit ee{};
     if (pl.form == FwdForm::Walk) {      // depth-ordered early termination: one wave per ray, front to back
         ee.target_d = t->target_d;
         ee.trunc_sc = f->desc.trunc * f->desc.sc_factor;
         ee.tiles_per_ray = pl.tpr;
-        blocks = (N + 3u) / 4u;
-        if (blocks > cu_count(f) * 4u) blocks = cu_count(f) * 4u;
     }
     // the packed forward (k_query_fwd_loss_packed: only the samples a consumer can see, packed across rays, loss stage from LDS; any
     // samples-per-ray count).  Its workgroup works in barrier-separated steps -- all gathers of a pass, then all matrix chains -- so what it
@@ -1070,57 +1100,40 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
         return check_launch("sort_more / query_fwd_list");          // (*fused stays false: the caller launches the loss stage)
     }
     if (pl.form == FwdForm::Packed) {
-        // workgroup shape: 8 waves x 1 per CU, or 4 waves x 2 per CU (NARUTO_PACK_WAVES); rows (of four rays) a workgroup holds at a time: as many as
-        // the LDS next to the weights, the feature slabs and the tiles' points takes, at most three
-        static const int pack_waves = getenv("NARUTO_PACK_WAVES") ? atoi(getenv("NARUTO_PACK_WAVES")) : 8;
-        const uint32_t W = pack_waves == 4 ? 4u : 8u, per_cu = W == 4u ? 2u : 1u;
-        static size_t static_lds[2] = {0, 0};                                    // the kernel's own static LDS, fp32 form (the larger), from the code object
-        if (static_lds[W == 4u] == 0u) {
-            hipFuncAttributes fa{};
-            const void* fn = W == 4u ? reinterpret_cast<const void*>(k_query_fwd_loss_packed<false, 4>) : reinterpret_cast<const void*>(k_query_fwd_loss_packed<false, 8>);
-            if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return fail(NARUTO_ERR_LAUNCH, "query_fwd_loss_packed: hipFuncGetAttributes: %s", hipGetErrorString(hipGetLastError()));
-            static_lds[W == 4u] = fa.sharedSizeBytes;
-        }
-        const size_t fixed = static_lds[W == 4u] + 256u;
-        const size_t lds_free = (size_t)160u * 1024u / per_cu > fixed ? (size_t)160u * 1024u / per_cu - fixed : 0u;
-        uint32_t rows = kPackMaxRows;
-        while (rows > 0u && packed_lds_bytes(rows, S) > lds_free) --rows;
-        if (rows > 0u) {
-            static size_t attr_bytes[2] = {0, 0};
-            const size_t need = packed_lds_bytes(rows, S);
-            if (need > attr_bytes[W == 4u]) {
-                hipError_t e1, e2;
-                if (W == 4u) {
-                    e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
-                    e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
-                } else {
-                    e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
-                    e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
-                }
-                if (e1 != hipSuccess || e2 != hipSuccess)
-                    return fail(NARUTO_ERR_LAUNCH, "query_fwd_loss_packed: cannot reserve %zu bytes of LDS: %s", lds_free, hipGetErrorString(hipGetLastError()));
-                attr_bytes[W == 4u] = lds_free;
+        const uint32_t W = pl.pack_waves, per_cu = W == 4u ? 2u : 1u, rows = pl.pack_rows;
+        const size_t lds_free = (size_t)160u * 1024u / per_cu - packed_fixed_lds(W);
+        static size_t attr_bytes[2] = {0, 0};
+        const size_t need = packed_lds_bytes(rows, S);
+        if (need > attr_bytes[W == 4u]) {
+            hipError_t e1, e2;
+            if (W == 4u) {
+                e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
+                e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
+            } else {
+                e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
+                e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
             }
-            const uint32_t n_rows = (N + (uint32_t)kRaysPerBlock - 1u) / (uint32_t)kRaysPerBlock;
-            const uint32_t slots = cu_count(f) * per_cu;
-            const uint32_t pblocks = n_rows < slots ? n_rows : slots;            // every workgroup resident at once, the rows spread evenly over them
-            EarlyExit pe{};
-            pe.target_d = t->target_d;
-            pe.trunc_sc = f->desc.trunc * f->desc.sc_factor;
-            const bool bfm = f->desc.mlp_mode == NARUTO_MLP_BF16;
-            static const int one_pass_env = getenv("NARUTO_PACK_ONE_PASS") ? atoi(getenv("NARUTO_PACK_ONE_PASS")) : -1;
-            const bool one_pass = one_pass_env == 1;
-            uint32_t rays_cap = rows * (uint32_t)kRaysPerBlock;
-            if (one_pass && rays_cap * S > 64u * W && 64u * W / S >= 1u) rays_cap = 64u * W / S;           // one pass: all of a chunk's samples in one group of tiles
-            const uint32_t rows_arg = rays_cap | (one_pass ? 0x100u : 0u);
+            if (e1 != hipSuccess || e2 != hipSuccess)
+                return fail(NARUTO_ERR_LAUNCH, "query_fwd_loss_packed: cannot reserve %zu bytes of LDS: %s", lds_free, hipGetErrorString(hipGetLastError()));
+            attr_bytes[W == 4u] = lds_free;
+        }
+        const uint32_t pblocks = pl.blocks;
+        EarlyExit pe{};
+        pe.target_d = t->target_d;
+        pe.trunc_sc = f->desc.trunc * f->desc.sc_factor;
+        const bool bfm = f->desc.mlp_mode == NARUTO_MLP_BF16;
+        static const int one_pass_env = getenv("NARUTO_PACK_ONE_PASS") ? atoi(getenv("NARUTO_PACK_ONE_PASS")) : -1;
+        const bool one_pass = one_pass_env == 1;
+        uint32_t rays_cap = rows * (uint32_t)kRaysPerBlock;
+        if (one_pass && rays_cap * S > 64u * W && 64u * W / S >= 1u) rays_cap = 64u * W / S;           // one pass: all of a chunk's samples in one group of tiles
+        const uint32_t rows_arg = rays_cap | (one_pass ? 0x100u : 0u);
 #define NARUTO_LAUNCH_PACKED(BFV, WV) hipLaunchKernelGGL((k_query_fwd_loss_packed<BFV, WV>), dim3(pblocks + loss->n_tv_blocks), dim3(64 * WV), need, st, f->lt, f->ut, f->bt, *p, ps, M, \
                                                          t->raw, t->feat_save, pe, *loss, pblocks, rows_arg, g_fwd_timeline)
-            if (W == 4u) { if (bfm) NARUTO_LAUNCH_PACKED(true, 4); else NARUTO_LAUNCH_PACKED(false, 4); }
-            else { if (bfm) NARUTO_LAUNCH_PACKED(true, 8); else NARUTO_LAUNCH_PACKED(false, 8); }
+        if (W == 4u) { if (bfm) NARUTO_LAUNCH_PACKED(true, 4); else NARUTO_LAUNCH_PACKED(false, 4); }
+        else { if (bfm) NARUTO_LAUNCH_PACKED(true, 8); else NARUTO_LAUNCH_PACKED(false, 8); }
 #undef NARUTO_LAUNCH_PACKED
-            if (fused != nullptr) *fused = true;
-            return check_launch("query_fwd_loss_packed");
-        }
+        if (fused != nullptr) *fused = true;
+        return check_launch("query_fwd_loss_packed");
     }
     if (pl.form == FwdForm::Short) {
         if (int rc = ray_lds_attr()) return rc;
@@ -1128,8 +1141,7 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
         const WalkExtra wxa = walk_extra != nullptr ? *walk_extra : WalkExtra{};
         const uint32_t tail_blocks = wxa.on ? tv_encode_blocks(loss->tv.n * loss->tv.n * loss->tv.n, wxa.tv_groups) : loss->n_tv_blocks;
         const uint32_t R = pl.rays_per_row;
-        uint32_t sblocks = (N + R - 1u) / R;
-        if (sblocks > cu_count(f) * 4u) sblocks = cu_count(f) * 4u;
+        const uint32_t sblocks = pl.blocks;
         if (bfm) hipLaunchKernelGGL(k_query_fwd_loss_short<true>, dim3(sblocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, *loss, sblocks, wxa, R, g_fwd_timeline);
         else hipLaunchKernelGGL(k_query_fwd_loss_short<false>, dim3(sblocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, *loss, sblocks, wxa, R, g_fwd_timeline);
         if (fused != nullptr) *fused = true;
@@ -1149,19 +1161,17 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
         if (fused != nullptr) *fused = true;
         return check_launch("query_fwd_loss");
     }
-    // flat tiles, between one and two four-wave workgroups per CU (2 048 rays x 43 samples: 1 376 tiles): two-wave workgroups (see k_query_fwd)
-    static const bool small_wg_on = getenv("NARUTO_DEBUG_FWD_SMALL_WG") == nullptr || atoi(getenv("NARUTO_DEBUG_FWD_SMALL_WG")) != 0;
-    const bool small_wg = small_wg_on && ee.tiles_per_ray == 0u && n_tiles > cu_count(f) * 4u && n_tiles < cu_count(f) * 8u;
+    // flat tiles in the plan's workgroup shape (see train_fwd_plan), or the unfused walk
     const bool walk = ee.tiles_per_ray != 0u;          // the depth-ordered walk has its own instantiation: the flat launches carry none of its code (full tiles only: S = 64 k)
     if (f->desc.mlp_mode == NARUTO_MLP_BF16) {
         if (walk) hipLaunchKernelGGL((k_query_fwd_bf<true, 256, true>), dim3(blocks), dim3(256), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-        else if (small_wg) hipLaunchKernelGGL((k_query_fwd_bf<true, 128>), dim3((n_tiles + 1u) / 2u), dim3(128), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-        else if (kFwdSplit && n_tiles >= cu_count(f) * 8u) hipLaunchKernelGGL((k_query_fwd_bf<true, 512>), dim3(cu_count(f)), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
+        else if (pl.threads == 128u) hipLaunchKernelGGL((k_query_fwd_bf<true, 128>), dim3(blocks), dim3(128), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
+        else if (pl.threads == 512u) hipLaunchKernelGGL((k_query_fwd_bf<true, 512>), dim3(blocks), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
         else hipLaunchKernelGGL((k_query_fwd_bf<true, 256>), dim3(blocks), dim3(256), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
     } else {
         if (walk) hipLaunchKernelGGL((k_query_fwd<true, 256, true>), dim3(blocks), dim3(256), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-        else if (small_wg) hipLaunchKernelGGL((k_query_fwd<true, 128>), dim3((n_tiles + 1u) / 2u), dim3(128), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-        else if (kFwdSplit && n_tiles >= cu_count(f) * 8u) hipLaunchKernelGGL((k_query_fwd<true, 512>), dim3(cu_count(f)), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);      // see naruto_query_fwd
+        else if (pl.threads == 128u) hipLaunchKernelGGL((k_query_fwd<true, 128>), dim3(blocks), dim3(128), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
+        else if (pl.threads == 512u) hipLaunchKernelGGL((k_query_fwd<true, 512>), dim3(blocks), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);      // see naruto_query_fwd
         else hipLaunchKernelGGL((k_query_fwd<true, 256>), dim3(blocks), dim3(256), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
     }
     return check_launch("query_fwd");
@@ -1205,6 +1215,69 @@ LossStageArgs loss_stage_args(const NarutoField* f, const NarutoTrainStep* t, co
     a.n_tv_blocks = t->smooth_points != 0 ? w.n_tv_blocks : 0u;
     if (tail_rides_in_backward(t)) a.ray_count = t->ray_count;      // list lengths for the backward's fused first launch (either flag)
     return a;
+}
+// The eval render's launch (naruto_render_fwd), ONE decision for the launcher and naruto_debug_render_plan:
+//   Ray      S > 64: k_render_fwd, one wave per ray (four per workgroup), the ray's image in dynamic LDS
+//   Packed4  S <= 64: k_render_fwd_packed<*, 256>, kPackRays rays per workgroup, samples packed into full 64-sample tiles
+//   Packed8  S <= 64 from one group per CU upwards (round 6): k_render_fwd_packed<*, 512>, one eight-wave workgroup per CU whose exact-mode
+//            matrix phase is the x3 chain; R8(S) rays per group.  NARUTO_RENDER_WIDE: 0 never, 1 (default) exact mode from one group per
+//            CU upwards (measured, 8 192 x 43: exact mode 0.1213 -> 0.1077 ms; bf16 mode 0.1041 -> 0.1057: its chain is short either way,
+//            the four-wave form stays), 2 at any ray count
+// Every form loops over its ray groups with a grid capped near the CU count: rays_per_pass rays per trip.
+enum class RenderForm { Ray, Packed4, Packed8 };
+struct RenderPlan {
+    RenderForm form;
+    uint32_t rays_per_group, blocks, rays_per_pass, threads;
+    size_t dyn_lds;             // dynamic LDS of the launch
+    size_t reserved;            // what naruto_render_fwd reserves for the kernel (hipFuncAttributeMaxDynamicSharedMemorySize), for any S it may get
+    size_t static_lds;          // the kernel's static LDS (the larger of its two MLP modes' forms is what the reservation has to fit next to)
+};
+// the eight-wave form's reservation: its largest launch over every S it runs at
+inline size_t render_packed8_reserve() {
+    size_t m = 0;
+    for (uint32_t S = 2; S <= 64u; ++S) {
+        const size_t b = render_packed_lds_bytes(S, render_packed8_rays(S));
+        if (b > m) m = b;
+    }
+    return m;
+}
+RenderPlan render_plan(const NarutoField* f, uint32_t n_rays, uint32_t S, bool bf, int wide) {
+    static const int wide_env = getenv("NARUTO_RENDER_WIDE") ? atoi(getenv("NARUTO_RENDER_WIDE")) : 1;
+    if (wide < 0) wide = wide_env;
+    RenderPlan pl{};
+    const uint32_t cap = cu_count(f) * 4u;
+    if (S <= 64u) {
+        const uint32_t R8 = render_packed8_rays(S);
+        if (kFwdSplit && wide != 0 && R8 >= 8u && (wide == 2 || (!bf && (n_rays + R8 - 1u) / R8 >= cu_count(f)))) {
+            pl.form = RenderForm::Packed8;
+            pl.rays_per_group = R8;
+            pl.blocks = (n_rays + R8 - 1u) / R8 < cu_count(f) ? (n_rays + R8 - 1u) / R8 : cu_count(f);
+            pl.rays_per_pass = cu_count(f) * R8;
+            pl.threads = 512u;
+            pl.dyn_lds = render_packed_lds_bytes(S, R8);
+            pl.reserved = render_packed8_reserve();
+            pl.static_lds = (bf ? sizeof(FwdLdsBf) : sizeof(FwdLdsExact)) + (kFwdSplit ? 8u : 1u) * sizeof(FwdSlab);
+            return pl;
+        }
+        pl.form = RenderForm::Packed4;
+        pl.rays_per_group = kPackRays;
+        pl.blocks = (n_rays + kPackRays - 1u) / kPackRays < cap ? (n_rays + kPackRays - 1u) / kPackRays : cap;
+        pl.rays_per_pass = cap * kPackRays;
+        pl.threads = 256u;
+        pl.dyn_lds = render_packed_lds_bytes(S);
+        pl.reserved = render_packed_lds_bytes(64u);
+        pl.static_lds = (bf ? sizeof(FwdLdsBf) : sizeof(FwdLds)) + (kFwdSplit ? 4u : 1u) * sizeof(FwdSlab);
+        return pl;
+    }
+    pl.form = RenderForm::Ray;
+    pl.rays_per_group = 4u;
+    pl.blocks = (n_rays + 3u) / 4u < cap ? (n_rays + 3u) / 4u : cap;
+    pl.rays_per_pass = cap * 4u;
+    pl.threads = 256u;
+    pl.dyn_lds = ray_scratch_bytes(S);
+    pl.reserved = ray_scratch_bytes(kMaxSamples);
+    pl.static_lds = bf ? sizeof(FwdLdsBf) : sizeof(FwdLds);
+    return pl;
 }
 }  // namespace
 
@@ -1511,48 +1584,56 @@ int naruto_render_fwd(const NarutoField* f, const NarutoParams* p, const NarutoR
     a.trunc = f->desc.trunc; a.sc_factor = f->desc.sc_factor; a.white_bkgd = f->desc.white_bkgd;
     a.rgb = r->rgb; a.depth = r->depth; a.disp = r->disp; a.acc = r->acc; a.depth_var = r->depth_var; a.uncert_map = r->uncert_map;
     a.weights = r->weights; a.raw = r->raw; a.z_vals = r->z_vals;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const int bytes = (int)ray_scratch_bytes(kMaxSamples);
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_render_fwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_render_fwd<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-            return fail(NARUTO_ERR_LAUNCH, "render_fwd: cannot reserve %d bytes of LDS: %s", bytes, hipGetErrorString(hipGetLastError()));
-        attr_set = true;
-    }
     const bool bf = f->desc.mlp_mode == NARUTO_MLP_BF16;
-    if (S <= 64u) {              // short rays: 16 rays per workgroup, samples packed into full 64-sample tiles
-        // round 6: from one group per CU upwards, eight-wave workgroups (one per CU) whose exact-mode matrix phase is the x3 chain (k_render_fwd_packed<*, 512>)
-        static const int wide_env = getenv("NARUTO_RENDER_WIDE") ? atoi(getenv("NARUTO_RENDER_WIDE")) : 1;
-        const uint32_t R8 = render_packed8_rays(S);
-        // (measured, 8 192 x 43: exact mode 0.1213 -> 0.1077 ms; bf16 mode 0.1041 -> 0.1057: its chain is short either way, the four-wave form stays)
-        if (kFwdSplit && wide_env != 0 && R8 >= 8u && (wide_env == 2 || (!bf && (r->n_rays + R8 - 1u) / R8 >= cu_count(f)))) {
-            static bool attr8 = false;
-            if (!attr8) {
-                const int bytes = (int)render_packed_lds_bytes(64u, render_packed8_rays(64u));
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_render_fwd_packed<false, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(k_render_fwd_packed<true, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-                    return fail(NARUTO_ERR_LAUNCH, "render_fwd: cannot reserve %d bytes of LDS: %s", bytes, hipGetErrorString(hipGetLastError()));
-                attr8 = true;
-            }
-            uint32_t blocks8 = (r->n_rays + R8 - 1u) / R8;
-            if (blocks8 > cu_count(f)) blocks8 = cu_count(f);
-            if (bf) hipLaunchKernelGGL((k_render_fwd_packed<true, 512>), dim3(blocks8), dim3(512), render_packed_lds_bytes(S, R8), (hipStream_t)stream, f->lt, f->ut, f->bt, *p, a, R8);
-            else hipLaunchKernelGGL((k_render_fwd_packed<false, 512>), dim3(blocks8), dim3(512), render_packed_lds_bytes(S, R8), (hipStream_t)stream, f->lt, f->ut, f->bt, *p, a, R8);
-            return check_launch("render_fwd_packed8");
-        }
-        uint32_t blocks = (r->n_rays + kPackRays - 1u) / kPackRays;
-        if (blocks > cu_count(f) * 4u) blocks = cu_count(f) * 4u;
-        if (bf) hipLaunchKernelGGL((k_render_fwd_packed<true, 256>), dim3(blocks), dim3(256), render_packed_lds_bytes(S), (hipStream_t)stream, f->lt, f->ut, f->bt, *p, a, kPackRays);
-        else hipLaunchKernelGGL((k_render_fwd_packed<false, 256>), dim3(blocks), dim3(256), render_packed_lds_bytes(S), (hipStream_t)stream, f->lt, f->ut, f->bt, *p, a, kPackRays);
+    const RenderPlan pl = render_plan(f, r->n_rays, S, bf, -1);
+    // every kernel reserves, once, the dynamic LDS of the largest launch it may get (render_plan's reserved)
+    static bool attr_set[3] = {false, false, false};
+    const int k = (int)pl.form;
+    if (!attr_set[k]) {
+        const void* fn_fp32 = pl.form == RenderForm::Ray ? reinterpret_cast<const void*>(k_render_fwd<false>)
+                            : pl.form == RenderForm::Packed4 ? reinterpret_cast<const void*>(k_render_fwd_packed<false, 256>) : reinterpret_cast<const void*>(k_render_fwd_packed<false, 512>);
+        const void* fn_bf = pl.form == RenderForm::Ray ? reinterpret_cast<const void*>(k_render_fwd<true>)
+                          : pl.form == RenderForm::Packed4 ? reinterpret_cast<const void*>(k_render_fwd_packed<true, 256>) : reinterpret_cast<const void*>(k_render_fwd_packed<true, 512>);
+        if (hipFuncSetAttribute(fn_fp32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.reserved) != hipSuccess ||
+            hipFuncSetAttribute(fn_bf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.reserved) != hipSuccess)
+            return fail(NARUTO_ERR_LAUNCH, "render_fwd: cannot reserve %zu bytes of LDS: %s", pl.reserved, hipGetErrorString(hipGetLastError()));
+        attr_set[k] = true;
+    }
+    if (pl.dyn_lds > pl.reserved) return fail(NARUTO_ERR_LAUNCH, "render_fwd: %zu bytes of dynamic LDS, %zu reserved", pl.dyn_lds, pl.reserved);
+    const hipStream_t st = (hipStream_t)stream;
+    if (pl.form == RenderForm::Packed8) {
+        if (bf) hipLaunchKernelGGL((k_render_fwd_packed<true, 512>), dim3(pl.blocks), dim3(512), pl.dyn_lds, st, f->lt, f->ut, f->bt, *p, a, pl.rays_per_group);
+        else hipLaunchKernelGGL((k_render_fwd_packed<false, 512>), dim3(pl.blocks), dim3(512), pl.dyn_lds, st, f->lt, f->ut, f->bt, *p, a, pl.rays_per_group);
+        return check_launch("render_fwd_packed8");
+    }
+    if (pl.form == RenderForm::Packed4) {
+        if (bf) hipLaunchKernelGGL((k_render_fwd_packed<true, 256>), dim3(pl.blocks), dim3(256), pl.dyn_lds, st, f->lt, f->ut, f->bt, *p, a, pl.rays_per_group);
+        else hipLaunchKernelGGL((k_render_fwd_packed<false, 256>), dim3(pl.blocks), dim3(256), pl.dyn_lds, st, f->lt, f->ut, f->bt, *p, a, pl.rays_per_group);
         return check_launch("render_fwd_packed");
     }
-    uint32_t blocks = (r->n_rays + 3u) / 4u;
-    if (blocks > cu_count(f) * 4u) blocks = cu_count(f) * 4u;
-    if (bf)
-        hipLaunchKernelGGL(k_render_fwd<true>, dim3(blocks), dim3(256), ray_scratch_bytes(S), (hipStream_t)stream, f->lt, f->ut, f->bt, *p, a);
-    else
-        hipLaunchKernelGGL(k_render_fwd<false>, dim3(blocks), dim3(256), ray_scratch_bytes(S), (hipStream_t)stream, f->lt, f->ut, f->bt, *p, a);
+    if (bf) hipLaunchKernelGGL(k_render_fwd<true>, dim3(pl.blocks), dim3(256), pl.dyn_lds, st, f->lt, f->ut, f->bt, *p, a);
+    else hipLaunchKernelGGL(k_render_fwd<false>, dim3(pl.blocks), dim3(256), pl.dyn_lds, st, f->lt, f->ut, f->bt, *p, a);
     return check_launch("render_fwd");
+}
+
+int naruto_debug_render_plan(const NarutoField* f, uint32_t n_rays, uint32_t S, int bf16, int wide, uint32_t out[8]) {
+    if (f == nullptr || out == nullptr) return fail(NARUTO_ERR_INVALID, "debug_render_plan: NULL argument");
+    if (S < 2 || S > (uint32_t)kMaxSamples) return fail(NARUTO_ERR_INVALID, "debug_render_plan: need 2 <= samples per ray <= %d (got %u)", kMaxSamples, S);
+    if (wide < -1 || wide > 2) return fail(NARUTO_ERR_INVALID, "debug_render_plan: wide must be -1, 0, 1 or 2 (got %d)", wide);
+    const RenderPlan pl = render_plan(f, n_rays, S, bf16 != 0, wide);
+    out[0] = (uint32_t)pl.form; out[1] = pl.rays_per_group; out[2] = pl.blocks; out[3] = pl.rays_per_pass;
+    out[4] = (uint32_t)pl.dyn_lds; out[5] = (uint32_t)pl.reserved; out[6] = (uint32_t)pl.static_lds; out[7] = pl.threads;
+    return NARUTO_OK;
+}
+
+int naruto_debug_train_plan(const NarutoField* f, const NarutoTrainStep* t, int with_loss, int deferred, uint32_t out[8]) {
+    if (f == nullptr || t == nullptr || out == nullptr) return fail(NARUTO_ERR_INVALID, "debug_train_plan: NULL argument");
+    const uint32_t S = t->n_samples_d + t->n_range_d;
+    if (t->n_rays == 0 || S < 2 || S > (uint32_t)kMaxSamples) return fail(NARUTO_ERR_INVALID, "debug_train_plan: need rays and 2..%d samples per ray", kMaxSamples);
+    const TrainFwdPlan pl = train_fwd_plan(f, t, with_loss != 0, deferred != 0);
+    out[0] = (uint32_t)pl.form; out[1] = pl.fused; out[2] = pl.split; out[3] = pl.tv_moved;
+    out[4] = pl.tpr; out[5] = pl.rays_per_row; out[6] = pl.blocks; out[7] = pl.threads;
+    return NARUTO_OK;
 }
 
 int naruto_composite_fwd(const NarutoField* f, uint32_t n_rays, uint32_t S, const float* raw, const float* z_vals, float* rgb, float* disp,

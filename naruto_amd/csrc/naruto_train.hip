@@ -554,6 +554,14 @@ __device__ __forceinline__ void pack_unit_retire(const PackUnit& q, FwdSlab* __r
     slabs[q.tile].feat[q.T][1][lane] = b1;
 }
 
+// k_query_fwd_loss_packed's static LDS: its __shared__ declarations in order (tests/test_launch_plans_host.py holds this equal to the code object's)
+template <bool BF, int WAVES>
+constexpr size_t packed_static_lds() {
+    using Lds = std::conditional_t<BF, FwdLdsBf, FwdLds>;
+    return sizeof(Lds) + WAVES * sizeof(FwdSlab) + sizeof(PackPts<WAVES>) + 4u * sizeof(double) + kPackMaxRays * 10u * sizeof(float) + 10u * sizeof(double) +
+           2u * kPackMaxRays * sizeof(uint32_t);
+}
+
 template <bool BF, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 2) void k_query_fwd_loss_packed(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, float* __restrict__ raw,
                                                                              float* __restrict__ feat_save, EarlyExit ee, LossStageArgs a, uint32_t n_fwd_blocks,

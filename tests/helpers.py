@@ -93,3 +93,27 @@ def device_rng_uniform(seed: int, counter: int, idx):
     """float32 array of the values rng_uniform(rng_key({seed, counter}), i) for i in idx (python ints: exact)."""
     key = _splitmix64((seed & _M64) ^ _splitmix64(counter & _M64))
     return np.array([(_splitmix64((key + int(i)) & _M64) >> 40) * 2.0 ** -24 for i in idx], dtype=np.float32)
+
+
+def grad_close(got, want, what, frac=1e-4):
+    """Gradients: frac of the largest magnitude of the wanted tensor + 1e-3 relative."""
+    want = torch.as_tensor(want).detach().double().cpu()
+    scale = max(want.abs().max().item(), 1e-12)
+    assert_close(got, want, frac * scale, what, rel=1e-3)
+
+
+def relu_kink_distance(ora, cfg, rays_o, rays_d, z_vals, active):
+    """Smallest |pre-activation| of either hidden layer over the samples that carry a cotangent (fp64, oracle weights).  A unit
+    within fp32 rounding of 0 has its ReLU mask decided by rounding noise: the reference itself would flip it."""
+    bb = torch.tensor(cfg["mapping"]["bound"], dtype=torch.float32)
+    pts = (rays_o[:, None, :] + rays_d[:, None, :] * z_vals[..., None]).reshape(-1, 3)
+    xn = ((pts - bb[:, 0]) / (bb[:, 1] - bb[:, 0]))[active.reshape(-1)]
+    if xn.shape[0] == 0:
+        return float("inf"), 0
+    with torch.no_grad():
+        feats, pos = S.hash_encode(xn, ora.table, ora.meta).double(), S.oneblob_encode(xn, 16).double()
+        h = torch.cat([feats, pos], -1) @ ora.sdf_w0.double().T
+        out = torch.relu(h) @ ora.sdf_w1.double().T
+        c = torch.cat([pos, out[:, 1:]], -1) @ ora.col_w0.double().T
+    near = (h.abs() < 2e-6).any(1) | (c.abs() < 2e-6).any(1)
+    return min(float(h.abs().min()), float(c.abs().min())), int(near.sum())

@@ -20,10 +20,7 @@ pytestmark = pytest.mark.gpu
 TOL_OUT = 1e-4
 
 
-def grad_close(got, want, what, frac=1e-4):
-    want = torch.as_tensor(want).detach().double().cpu()
-    scale = max(want.abs().max().item(), 1e-12)
-    H.assert_close(got, want, frac * scale, what, rel=1e-3)
+grad_close = H.grad_close
 
 
 # --------------------------------------------------------------------------------------------- hardware layout probes
@@ -1304,21 +1301,7 @@ def test_train_step_full_size_against_oracle(gpu, workload):
         assert 0 < n_stopped < N, f"early termination: {n_stopped} of {N} rays stopped after the first tile"
 
 
-def _relu_kink_distance(ora, cfg, rays_o, rays_d, z_vals, active):
-    """Smallest |pre-activation| of either hidden layer over the samples that carry a cotangent (fp64, oracle weights).  A unit
-    within fp32 rounding of 0 has its ReLU mask decided by rounding noise: the reference itself would flip it."""
-    bb = torch.tensor(cfg["mapping"]["bound"], dtype=torch.float32)
-    pts = (rays_o[:, None, :] + rays_d[:, None, :] * z_vals[..., None]).reshape(-1, 3)
-    xn = ((pts - bb[:, 0]) / (bb[:, 1] - bb[:, 0]))[active.reshape(-1)]
-    if xn.shape[0] == 0:
-        return float("inf"), 0
-    with torch.no_grad():
-        feats, pos = S.hash_encode(xn, ora.table, ora.meta).double(), S.oneblob_encode(xn, 16).double()
-        h = torch.cat([feats, pos], -1) @ ora.sdf_w0.double().T
-        out = torch.relu(h) @ ora.sdf_w1.double().T
-        c = torch.cat([pos, out[:, 1:]], -1) @ ora.col_w0.double().T
-    near = (h.abs() < 2e-6).any(1) | (c.abs() < 2e-6).any(1)
-    return min(float(h.abs().min()), float(c.abs().min())), int(near.sum())
+_relu_kink_distance = H.relu_kink_distance
 
 
 @pytest.mark.parametrize("case", list(range(24)))
