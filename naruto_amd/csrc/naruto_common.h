@@ -60,8 +60,11 @@ struct PointSrc {
 };
 
 // ---------------------------------------------------------------------------------------------
-// point m -> normalised coordinates.  rays: p = o + d*z (separately rounded mul and add, as the
-// reference's eager torch ops), then (p - bmin) / (bmax - bmin)   [Co-SLAM run_network].
+// point m -> normalised coordinates.  rays: p = fmaf(d, z, o) -- ONE rounding, written out: hipcc contracts by default and the
+// clang HIP headers define __fmul_rn / __fadd_rn as the plain operators, so this is what the separately written multiply and add
+// always compiled to (the reference's eager torch ops round twice: they differ by at most that one rounding of p) -- then
+// (p - bmin) / (bmax - bmin), correctly rounded subtraction and division   [Co-SLAM run_network].  Every copy of this arithmetic
+// (finish_point, the training forwards, the fused render) writes the same fmaf.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void load_point(const PointSrc& ps, const BoxTab& bt, uint32_t m, float& x, float& y, float& z) {
     if (ps.xsoa) {                     // 32-bit element offsets: 3 * M < 2^32 (checked where the list is built)
@@ -75,9 +78,9 @@ __device__ __forceinline__ void load_point(const PointSrc& ps, const BoxTab& bt,
     } else {
         const uint32_t n = m / ps.S;
         const float t = ps.z_vals[m];
-        const float px = __fadd_rn(ps.rays_o[3 * n + 0], __fmul_rn(ps.rays_d[3 * n + 0], t));
-        const float py = __fadd_rn(ps.rays_o[3 * n + 1], __fmul_rn(ps.rays_d[3 * n + 1], t));
-        const float pz = __fadd_rn(ps.rays_o[3 * n + 2], __fmul_rn(ps.rays_d[3 * n + 2], t));
+        const float px = fmaf(ps.rays_d[3 * n + 0], t, ps.rays_o[3 * n + 0]);
+        const float py = fmaf(ps.rays_d[3 * n + 1], t, ps.rays_o[3 * n + 1]);
+        const float pz = fmaf(ps.rays_d[3 * n + 2], t, ps.rays_o[3 * n + 2]);
         x = __fdiv_rn(__fsub_rn(px, bt.bmin[0]), bt.bext[0]);
         y = __fdiv_rn(__fsub_rn(py, bt.bmin[1]), bt.bext[1]);
         z = __fdiv_rn(__fsub_rn(pz, bt.bmin[2]), bt.bext[2]);
@@ -107,9 +110,9 @@ __device__ __forceinline__ void finish_point(const PointSrc& ps, const BoxTab& b
     if (ps.xsoa || ps.x) {
         x = r.v[0]; y = r.v[1]; z = r.v[2];
     } else {                                                    // same arithmetic as load_point
-        const float px = __fadd_rn(r.v[0], __fmul_rn(r.v[3], r.v[6]));
-        const float py = __fadd_rn(r.v[1], __fmul_rn(r.v[4], r.v[6]));
-        const float pz = __fadd_rn(r.v[2], __fmul_rn(r.v[5], r.v[6]));
+        const float px = fmaf(r.v[3], r.v[6], r.v[0]);
+        const float py = fmaf(r.v[4], r.v[6], r.v[1]);
+        const float pz = fmaf(r.v[5], r.v[6], r.v[2]);
         x = __fdiv_rn(__fsub_rn(px, bt.bmin[0]), bt.bext[0]);
         y = __fdiv_rn(__fsub_rn(py, bt.bmin[1]), bt.bext[1]);
         z = __fdiv_rn(__fsub_rn(pz, bt.bmin[2]), bt.bext[2]);

@@ -48,8 +48,8 @@ __global__ __launch_bounds__(256, 2) void k_render_fwd(LevelTab lt, UncertTab ut
             const bool valid = s_raw < S;
             const uint32_t s = valid ? s_raw : S - 1u;
             const float t = rs.z[s];
-            // same arithmetic as load_point: separately rounded multiply and add, then the box normalisation
-            const float px = __fadd_rn(ox, __fmul_rn(dx, t)), py = __fadd_rn(oy, __fmul_rn(dy, t)), pz = __fadd_rn(oz, __fmul_rn(dz, t));
+            // same arithmetic as load_point: one fma, then the box normalisation
+            const float px = fmaf(dx, t, ox), py = fmaf(dy, t, oy), pz = fmaf(dz, t, oz);
             const float x = __fdiv_rn(__fsub_rn(px, bt.bmin[0]), bt.bext[0]);
             const float y = __fdiv_rn(__fsub_rn(py, bt.bmin[1]), bt.bext[1]);
             const float z = __fdiv_rn(__fsub_rn(pz, bt.bmin[2]), bt.bext[2]);
@@ -169,9 +169,9 @@ __global__ __launch_bounds__(NT, NT == 256 ? NARUTO_RENDER_PACKED_MINWAVES : 1) 
             const RayScratch rs = image(r);
             const uint32_t n = n0 + r;
             const float t = rs.z[s];
-            const float px = __fadd_rn(a.rays_o[3 * (size_t)n], __fmul_rn(a.rays_d[3 * (size_t)n], t));
-            const float py = __fadd_rn(a.rays_o[3 * (size_t)n + 1], __fmul_rn(a.rays_d[3 * (size_t)n + 1], t));
-            const float pz = __fadd_rn(a.rays_o[3 * (size_t)n + 2], __fmul_rn(a.rays_d[3 * (size_t)n + 2], t));
+            const float px = fmaf(a.rays_d[3 * (size_t)n], t, a.rays_o[3 * (size_t)n]);
+            const float py = fmaf(a.rays_d[3 * (size_t)n + 1], t, a.rays_o[3 * (size_t)n + 1]);
+            const float pz = fmaf(a.rays_d[3 * (size_t)n + 2], t, a.rays_o[3 * (size_t)n + 2]);
             const float x = __fdiv_rn(__fsub_rn(px, bt.bmin[0]), bt.bext[0]);
             const float y = __fdiv_rn(__fsub_rn(py, bt.bmin[1]), bt.bext[1]);
             const float z = __fdiv_rn(__fsub_rn(pz, bt.bmin[2]), bt.bext[2]);

@@ -276,9 +276,9 @@ __global__ __launch_bounds__(256, 2) void k_query_fwd_loss(LevelTab lt, UncertTa
                 const float* __restrict__ rc = ray_c[wave];
                 const float td_ee = rc[6];
                 // load_point's arithmetic with the depth from the image
-                const float x = __fdiv_rn(__fsub_rn(__fadd_rn(rc[0], __fmul_rn(rc[3], zv)), bt.bmin[0]), bt.bext[0]);
-                const float y = __fdiv_rn(__fsub_rn(__fadd_rn(rc[1], __fmul_rn(rc[4], zv)), bt.bmin[1]), bt.bext[1]);
-                const float z = __fdiv_rn(__fsub_rn(__fadd_rn(rc[2], __fmul_rn(rc[5], zv)), bt.bmin[2]), bt.bext[2]);
+                const float x = __fdiv_rn(__fsub_rn(fmaf(rc[3], zv, rc[0]), bt.bmin[0]), bt.bext[0]);
+                const float y = __fdiv_rn(__fsub_rn(fmaf(rc[4], zv, rc[1]), bt.bmin[1]), bt.bext[1]);
+                const float z = __fdiv_rn(__fsub_rn(fmaf(rc[5], zv, rc[2]), bt.bmin[2]), bt.bext[2]);
                 const bool live = valid && ((tq > 0u && kEeLaneSkip) ? ee_lane_live_r(ees, ee.trunc_sc, td_ee, zv) : true);
                 const float u = live ? uncert_sample(ut, p.uncert_grid, x, y, z) : 0.0f;
                 FwdTileOut to;
@@ -437,9 +437,9 @@ __global__ __launch_bounds__(256, 2) void k_query_fwd_loss_short(LevelTab lt, Un
             const float zv = rs.z[s];
             // load_point's arithmetic with the depth from the image
             const float* __restrict__ rc = rayc[r];
-            const float px = __fadd_rn(rc[0], __fmul_rn(rc[3], zv));
-            const float py = __fadd_rn(rc[1], __fmul_rn(rc[4], zv));
-            const float pz = __fadd_rn(rc[2], __fmul_rn(rc[5], zv));
+            const float px = fmaf(rc[3], zv, rc[0]);
+            const float py = fmaf(rc[4], zv, rc[1]);
+            const float pz = fmaf(rc[5], zv, rc[2]);
             const float x = __fdiv_rn(__fsub_rn(px, bt.bmin[0]), bt.bext[0]);
             const float y = __fdiv_rn(__fsub_rn(py, bt.bmin[1]), bt.bext[1]);
             const float z = __fdiv_rn(__fsub_rn(pz, bt.bmin[2]), bt.bext[2]);
@@ -659,10 +659,10 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_query_fwd_loss_packed(LevelTa
                     const uint32_t code = list[valid ? e_raw : total - 1u];      // padding lanes redo the last entry (their stores repeat its values)
                     const uint32_t r = code >> 12, s2 = code & 4095u, n = n0 + r;
                     const float tz = image(r).z[s2];
-                    // load_point's arithmetic: p = o + d t (separately rounded), then the box normalisation
-                    const float px = __fadd_rn(ps.rays_o[3 * n + 0], __fmul_rn(ps.rays_d[3 * n + 0], tz));
-                    const float py = __fadd_rn(ps.rays_o[3 * n + 1], __fmul_rn(ps.rays_d[3 * n + 1], tz));
-                    const float pz = __fadd_rn(ps.rays_o[3 * n + 2], __fmul_rn(ps.rays_d[3 * n + 2], tz));
+                    // load_point's arithmetic: p = fmaf(d, t, o), then the box normalisation
+                    const float px = fmaf(ps.rays_d[3 * n + 0], tz, ps.rays_o[3 * n + 0]);
+                    const float py = fmaf(ps.rays_d[3 * n + 1], tz, ps.rays_o[3 * n + 1]);
+                    const float pz = fmaf(ps.rays_d[3 * n + 2], tz, ps.rays_o[3 * n + 2]);
                     const float x = __fdiv_rn(__fsub_rn(px, bt.bmin[0]), bt.bext[0]);
                     const float y = __fdiv_rn(__fsub_rn(py, bt.bmin[1]), bt.bext[1]);
                     const float z = __fdiv_rn(__fsub_rn(pz, bt.bmin[2]), bt.bext[2]);

@@ -270,6 +270,12 @@ class _HashEncode(torch.autograd.Function):
 
 
 def hash_encode(handle: FieldHandle, x: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """embed_fn(x), query_sdf(x, embed=True), calc_embedding's features: differentiable w.r.t. the table only.  A point gradient
+    (x requiring grad) is refused here rather than returned as None."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise NotImplementedError("embed_fn / query_sdf(embed=True) / calc_embedding are differentiable w.r.t. the table only, not x "
+                                  "(call them with x detached); gradients w.r.t. x flow through query_sdf / query_color_sdf / "
+                                  "query_color / run_network / render_rays")
     return _HashEncode.apply(handle, x, table)
 
 

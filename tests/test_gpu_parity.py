@@ -168,15 +168,7 @@ def test_random_field_configs(gpu, case):
     """Drawn scene boxes (anisotropic, 1 .. 25 m), finest voxel sizes and table sizes 2^10 .. 2^18 (18: larger than the LDS-tiled
     scatter takes: the binned scatter): level tables, features, outputs and every gradient of the fused query against the oracle, on
     points inside and outside the box."""
-    from naruto_amd import config as C
-    rs = np.random.RandomState(500 + case)
-    ext = rs.uniform(1.0, 25.0, 3)
-    lo = rs.uniform(-10.0, 5.0, 3)
-    cfg = C.office0_config()
-    cfg["mapping"]["bound"] = [[float(lo[i]), float(lo[i] + ext[i])] for i in range(3)]
-    cfg["mapping"]["marching_cubes_bound"] = cfg["mapping"]["bound"]
-    cfg["grid"]["voxel_sdf"] = float(rs.choice([0.02, 0.04, 0.1]))
-    cfg["grid"]["hash_size"] = int(rs.choice([10, 12, 14, 16, 17, 18]))
+    cfg, rs = H.drawn_field_config(case)
     ora = H.make_oracle(cfg, 0.25, 500 + case)
     m = H.make_hip_from_oracle(cfg, ora, gpu)
     sc, res, size, off = m._handle().levels()

@@ -15,27 +15,12 @@ pytestmark = pytest.mark.gpu
 LOSS_KEYS = ("rgb_loss", "depth_loss", "sdf_loss", "fs_loss", "uncert_loss")
 
 
-def _rel(a, b):
-    a, b = torch.as_tensor(a).detach().double().cpu().reshape(-1), torch.as_tensor(b).detach().double().cpu().reshape(-1)
-    return float((a - b).norm() / (b.norm() + 1e-300))
+_rel, _oracle_pair, _bound = H.rel, H.oracle_pair, H.bound
 
 
 def _cos(a, b):
     a, b = torch.as_tensor(a).detach().double().cpu().reshape(-1), torch.as_tensor(b).detach().double().cpu().reshape(-1)
     return float(a @ b / (a.norm() * b.norm() + 1e-300))
-
-
-def _oracle_pair(ora):
-    """The oracle in fp32 and an fp64 copy of it (same parameters)."""
-    o64 = H.make_oracle(ora.config, 0.25, 0)
-    o64.load_state_dict(ora.state_dict())
-    return ora, o64.double()
-
-
-def _bound(o32, o64, factor=4.0, floor=2e-5):
-    """Tolerance of a relative l2 comparison: a multiple of the oracle's own fp32 rounding (its fp32 result against its fp64 one),
-    with a floor for the cases where the oracle happens to be closer than the summation orders allow."""
-    return max(factor * _rel(o32, o64), floor)
 
 
 # --------------------------------------------------------------------------------------------- 1. x gradients
