@@ -539,6 +539,44 @@ int naruto_debug_permlane_swap(const float* v0, const float* v1, float* out, voi
  * A lane l = A[l&31][8*(l>>5) + e], B lane l = B[8*(l>>5) + e][l&31], e = 0..7 (test_mfma_bf16_layout). */
 int naruto_debug_mfma_bf16_layout(const float* a, const float* b, float* out, void* stream);
 
+/* Camera tracking: Co-SLAM tracking_render (reference call site coslam.py:594-602; parity unpinned), one frame's pose optimised with
+ * the network frozen.  Pose = (omega [3], the axis-angle of the camera-to-world rotation; t [3]); R(omega) by Rodrigues' formula.
+ * Per call: naruto_track_draw draws n_rays distinct pixels of the frame's interior [edge_h, H - edge_h) x [edge_w, W - edge_w) with the
+ * keyed permutation of naruto_sample_distinct (key from rng = {seed, counter} with salt 4; flat interior index k maps to
+ * h = edge_h + k % (H - 2 edge_h), w = edge_w + k / (H - 2 edge_h)) and gathers d_cam and the training step's target_rgb / target_d;
+ * naruto_track_rays resets the state from pose_init, writes the training step's rays_o / rays_d of iteration 0 and advances rng[1].
+ * Per iteration: naruto_train_forward with finalize = 1 and no smoothness term, then naruto_track_backward on the same training step:
+ * the loss backward and compaction, the ray gradients of naruto_query_bwd_points, and ONE workgroup that sums the pose gradient in a
+ * fixed order (no atomics), keeps the best pose (the first loss is the best, then loss < best resets thresh, else thresh + 1; thresh >
+ * wait_iters stops the call: later iterations change nothing), takes one torch.optim.Adam step and writes the NEXT iteration's rays. */
+typedef struct NarutoTrackStep {
+    uint32_t n_rays;                                  /* pixels per call (= the training step's n_rays)             */
+    uint32_t H, W, edge_h, edge_w;                    /* frame size and margins (0: no margin)                      */
+    const float *direction, *rgb, *depth;             /* the frame: [H,W,3] camera-frame directions, [H,W,3], [H,W]  */
+    uint64_t *rng;                                    /* {seed, counter}: keys the draw                              */
+    float *d_cam;                                     /* [N,3] directions of the drawn pixels                        */
+    int64_t *pix;                                     /* optional [N]: flat pixel index h * W + w of each ray        */
+    const float *pose_init;                           /* [6] (omega, t) of the initial pose                          */
+    float *pose, *exp_avg, *exp_avg_sq;               /* [6] the pose and its Adam moments                           */
+    int32_t *state;                                   /* [4] {Adam step, thresh, stopped, iteration}                 */
+    float lr_rot, lr_trans, beta1, beta2, eps;        /* Adam (no weight decay): lr_rot for omega, lr_trans for t    */
+    uint32_t wait_iters;
+    int32_t best;                                     /* != 0: c2w is the best pose, else the pose evaluated last    */
+    float *best_pose, *best_loss;                     /* [6] [1]                                                    */
+    float *c2w;                                       /* [16] the result, row-major camera-to-world                 */
+    float *d_rays_o, *d_rays_d;                       /* [N,3] the iteration's ray gradients                         */
+    float *trace_loss, *trace_pose, *trace_d_pose;    /* optional [max_trace] [max_trace,6] [max_trace,6]: per evaluated
+                                                         iteration its total loss, pose and pose gradient              */
+    uint32_t max_trace;
+    void *workspace;                                  /* naruto_track_workspace bytes                                */
+} NarutoTrackStep;
+size_t naruto_track_workspace(const NarutoField* f, uint32_t n_rays, uint32_t n_samples);
+int naruto_track_draw(const NarutoTrackStep* k, const NarutoTrainStep* t, void* stream);
+int naruto_track_rays(const NarutoTrackStep* k, const NarutoTrainStep* t, void* stream);
+int naruto_track_backward(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const NarutoTrackStep* k, void* stream);
+/* host only: R(w) (row-major) and the VJP d_w of sum(G * R(w)), in fp64, by the tracking kernels' own code (R or d_w may be NULL) */
+int naruto_debug_rodrigues(const double* w, const double* G, double* R, double* d_w);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ from . import config, synthetic  # noqa: F401
 
 def __getattr__(name):
     # torch-dependent modules are imported lazily so that `import naruto_amd` stays cheap
-    if name in ("ops", "field", "parallel", "trainer", "_lib", "graphed", "ba_loop", "keyframe_store", "active_ray_sampler", "planner_aggregation", "mesh"):
+    if name in ("ops", "field", "parallel", "trainer", "_lib", "graphed", "ba_loop", "keyframe_store", "active_ray_sampler", "planner_aggregation", "mesh",
+                "tracking"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "NarutoFieldHIP":
@@ -24,4 +25,7 @@ def __getattr__(name):
     if name == "FusedBA":
         from .ba_loop import FusedBA
         return FusedBA
+    if name == "TrackerHIP":
+        from .tracking import TrackerHIP
+        return TrackerHIP
     raise AttributeError(name)

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -90,6 +90,20 @@ class NarutoTrainStep(C.Structure):
         ("sums", C.c_void_p), ("losses", C.c_void_p), ("d_raw", C.c_void_p),
         ("ray_count", C.c_void_p), ("ray_offset", C.c_void_p), ("active_idx", C.c_void_p), ("n_active", C.c_void_p),
         ("workspace", C.c_void_p), ("loss_weight_parts", C.c_void_p * 10), ("min_uncert_running", C.c_void_p),
+    ]
+
+
+class NarutoTrackStep(C.Structure):
+    _fields_ = [
+        ("n_rays", C.c_uint32), ("H", C.c_uint32), ("W", C.c_uint32), ("edge_h", C.c_uint32), ("edge_w", C.c_uint32),
+        ("direction", C.c_void_p), ("rgb", C.c_void_p), ("depth", C.c_void_p), ("rng", C.c_void_p),
+        ("d_cam", C.c_void_p), ("pix", C.c_void_p), ("pose_init", C.c_void_p),
+        ("pose", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("state", C.c_void_p),
+        ("lr_rot", C.c_float), ("lr_trans", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("wait_iters", C.c_uint32), ("best", C.c_int32),
+        ("best_pose", C.c_void_p), ("best_loss", C.c_void_p), ("c2w", C.c_void_p), ("d_rays_o", C.c_void_p), ("d_rays_d", C.c_void_p),
+        ("trace_loss", C.c_void_p), ("trace_pose", C.c_void_p), ("trace_d_pose", C.c_void_p), ("max_trace", C.c_uint32),
+        ("workspace", C.c_void_p),
     ]
 
 
@@ -191,6 +205,11 @@ SIGNATURES = {
     "naruto_render_fwd": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoRender), _V]),
     "naruto_train_backward": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), C.POINTER(NarutoGrads), _U32,
                                    C.POINTER(NarutoFusedAdam), _V]),
+    "naruto_track_workspace": (C.c_size_t, [_V, _U32, _U32]),
+    "naruto_track_draw": (_I, [C.POINTER(NarutoTrackStep), C.POINTER(NarutoTrainStep), _V]),
+    "naruto_track_rays": (_I, [C.POINTER(NarutoTrackStep), C.POINTER(NarutoTrainStep), _V]),
+    "naruto_track_backward": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), C.POINTER(NarutoTrackStep), _V]),
+    "naruto_debug_rodrigues": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "naruto_compact_active": (_I, [_U32, _U32, _V, _V, _V, _V, _V]),
     "naruto_composite_fwd": (_I, [_V, _U32, _U32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "naruto_composite_bwd": (_I, [_V, _U32, _U32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _I, _V]),

@@ -18,6 +18,7 @@
 #include "naruto_mesh.hip"
 #include "naruto_parts.hip"
 #include "naruto_pointgrad.hip"
+#include "naruto_track.hip"
 
 using namespace naruto;
 
@@ -1426,7 +1427,34 @@ int naruto_debug_train_scatter(const NarutoField* f, const NarutoParams* p, cons
                           nullptr, unc_g, unc_g != nullptr ? const_cast<float*>(p->uncert_grid) : nullptr, n_front);
 }
 
-namespace { int assemble_args(const NarutoRayBatch* b, bool need_out, AssembleArgs& a, const char* who); }
+namespace {
+int assemble_args(const NarutoRayBatch* b, bool need_out, AssembleArgs& a, const char* who);
+
+LossArgs train_loss_args(const NarutoField* f, const NarutoTrainStep* t) {
+    return LossArgs{t->target_rgb, t->target_d, t->sums, t->loss_weights, t->n_rays_total ? t->n_rays_total : t->n_rays, t->depth_trunc, t->rgb_missing,
+                    f->desc.trunc * f->desc.sc_factor};
+}
+
+// The loss block's backward (k_composite_bwd: d_raw and the per-ray sample counts) and the compaction of the samples whose cotangent
+// is not zero into the active list (k_count_blocks for large batches, then k_compact), after a forward that finalised its losses: the
+// sequence naruto_train_backward runs where the tail was not deferred, and naruto_track_backward in front of the point gradients.
+int loss_bwd_compact(const NarutoField* f, const NarutoTrainStep* t, const TrainWs& w, const LossArgs& la, uint32_t n_front, uint32_t* n_total, hipStream_t st) {
+    const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d;
+    CompositeCot cot{};
+    hipLaunchKernelGGL(k_composite_bwd<true>, dim3((N + kRaysPerBlock - 1) / kRaysPerBlock), dim3(64 * kRaysPerBlock), ray_scratch_bytes(S), st, N, S, f->desc.trunc,
+                       f->desc.sc_factor, f->desc.white_bkgd, t->raw, t->z_vals, cot, la, t->d_raw, 0, t->ray_count);
+    if (int rc = check_launch("loss_bwd")) return rc;
+    const uint32_t* block_sums = nullptr;
+    if (N > 4u * kCompactBlock) {     // large batch: two-level prefix of the per-ray counts
+        hipLaunchKernelGGL(k_count_blocks, dim3((N + kCompactBlock - 1u) / kCompactBlock), dim3(256), 0, st, N, t->ray_count, w.block_sums);
+        if (int rc = check_launch("count_blocks")) return rc;
+        block_sums = w.block_sums;
+    }
+    hipLaunchKernelGGL(k_compact, dim3((N + 3u) / 4u), dim3(256), 0, st, N, S, t->ray_count, t->ray_offset, t->active_idx, t->n_active, n_front, n_total,
+                       block_sums);
+    return check_launch("compact");
+}
+}  // namespace
 
 int naruto_train_backward(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t_in, const NarutoGrads* g, uint32_t flags,
                           const NarutoFusedAdam* opt, void* stream) {
@@ -1470,9 +1498,7 @@ int naruto_train_backward(const NarutoField* f, const NarutoParams* p, const Nar
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d, M = N * S;
     const TrainWs w = train_ws(f, t);
-    CompositeCot cot{};
-    LossArgs la{t->target_rgb, t->target_d, t->sums, t->loss_weights, t->n_rays_total ? t->n_rays_total : N, t->depth_trunc, t->rgb_missing,
-                f->desc.trunc * f->desc.sc_factor};
+    const LossArgs la = train_loss_args(f, t);
     if ((flags & NARUTO_TRAIN_BWD_MLP_ONLY) && (flags & NARUTO_TRAIN_BWD_TABLE_ONLY)) return fail(NARUTO_ERR_INVALID, "train_backward: pick one phase");
     const bool table_only = (flags & NARUTO_TRAIN_BWD_TABLE_ONLY) != 0u;
     if ((flags & NARUTO_TRAIN_BWD_DEFERRED_TAIL) && (flags & (NARUTO_TRAIN_BWD_MLP_ONLY | NARUTO_TRAIN_BWD_TABLE_ONLY | NARUTO_TRAIN_BWD_SUMS_GIVEN)))
@@ -1519,24 +1545,11 @@ int naruto_train_backward(const NarutoField* f, const NarutoParams* p, const Nar
         hipLaunchKernelGGL(k_loss_bwd_fused, dim3(fa.n_ray_blocks + 2u + fa.tv_n_blocks), dim3(64 * kRaysPerBlock), ray_scratch_bytes(S), st, fa);
         if (int rc = check_launch("loss_bwd_fused")) return rc;
     }
-    if (!table_only && !deferred) {
-        hipLaunchKernelGGL(k_composite_bwd<true>, dim3((N + kRaysPerBlock - 1) / kRaysPerBlock), dim3(64 * kRaysPerBlock), ray_scratch_bytes(S), st, N, S, f->desc.trunc,
-                           f->desc.sc_factor, f->desc.white_bkgd, t->raw, t->z_vals, cot, la, t->d_raw, 0, t->ray_count);
-        if (int rc = check_launch("loss_bwd")) return rc;
-    }
     const bool smooth = t->smooth_points != 0 && (g->table != nullptr || opt != nullptr);
     const uint32_t n_front = smooth ? w.n3 : 0u;
     const BwdWs bw = bwd_ws(f, w.bwd, list_cap(M + w.n3));
-    const uint32_t* block_sums = nullptr;
-    if (!table_only && !deferred && N > 4u * kCompactBlock) {     // large batch: two-level prefix of the per-ray counts
-        hipLaunchKernelGGL(k_count_blocks, dim3((N + kCompactBlock - 1u) / kCompactBlock), dim3(256), 0, st, N, t->ray_count, w.block_sums);
-        if (int rc = check_launch("count_blocks")) return rc;
-        block_sums = w.block_sums;
-    }
     if (!table_only && !deferred) {
-        hipLaunchKernelGGL(k_compact, dim3((N + 3u) / 4u), dim3(256), 0, st, N, S, t->ray_count, t->ray_offset, t->active_idx, t->n_active, n_front, bw.n_total,
-                           block_sums);
-        if (int rc = check_launch("compact")) return rc;
+        if (int rc = loss_bwd_compact(f, t, w, la, n_front, bw.n_total, st)) return rc;
     }
     NarutoPoints pts{};
     pts.rays_o = t->rays_o; pts.rays_d = t->rays_d; pts.z_vals = t->z_vals; pts.n_samples = S;
@@ -2065,6 +2078,109 @@ int naruto_debug_permlane_swap(const float* v0, const float* v1, float* out, voi
     if (v0 == nullptr || v1 == nullptr || out == nullptr) return fail(NARUTO_ERR_INVALID, "debug_permlane_swap: NULL argument");
     hipLaunchKernelGGL(k_debug_swap, dim3(1), dim3(64), 0, (hipStream_t)stream, v0, v1, out);
     return check_launch("debug_permlane_swap");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Camera tracking (see naruto_track.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+int track_check(const NarutoTrackStep* k, const NarutoTrainStep* t, bool frame, const char* who) {
+    if (k == nullptr || t == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL argument", who);
+    if (k->n_rays == 0 || k->n_rays != t->n_rays)
+        return fail(NARUTO_ERR_INVALID, "%s: NarutoTrackStep.n_rays (%u) must be the training step's n_rays (%u), not 0", who, k->n_rays, t->n_rays);
+    if (t->rays_o == nullptr || t->rays_d == nullptr || t->target_rgb == nullptr || t->target_d == nullptr)
+        return fail(NARUTO_ERR_INVALID, "%s: NULL ray / target buffer in NarutoTrainStep", who);
+    if (k->rng == nullptr || k->d_cam == nullptr || k->pose_init == nullptr || k->pose == nullptr || k->exp_avg == nullptr || k->exp_avg_sq == nullptr ||
+        k->state == nullptr || k->best_pose == nullptr || k->best_loss == nullptr || k->c2w == nullptr || k->d_rays_o == nullptr || k->d_rays_d == nullptr ||
+        k->workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "%s: NULL buffer in NarutoTrackStep", who);
+    const bool any_trace = k->trace_loss != nullptr || k->trace_pose != nullptr || k->trace_d_pose != nullptr || k->max_trace != 0;
+    const bool all_trace = k->trace_loss != nullptr && k->trace_pose != nullptr && k->trace_d_pose != nullptr && k->max_trace != 0;
+    if (any_trace && !all_trace) return fail(NARUTO_ERR_INVALID, "%s: the trace needs trace_loss, trace_pose, trace_d_pose and max_trace together", who);
+    if (!(k->lr_rot >= 0.0f) || !(k->lr_trans >= 0.0f) || !(k->beta1 >= 0.0f && k->beta1 < 1.0f) || !(k->beta2 >= 0.0f && k->beta2 < 1.0f) || !(k->eps >= 0.0f))
+        return fail(NARUTO_ERR_INVALID, "%s: Adam needs lr >= 0, 0 <= betas < 1 and eps >= 0", who);
+    if (frame) {
+        if (k->direction == nullptr || k->rgb == nullptr || k->depth == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL frame", who);
+        if (k->H == 0 || k->W == 0 || 2ull * k->edge_h >= k->H || 2ull * k->edge_w >= k->W)
+            return fail(NARUTO_ERR_INVALID, "%s: the edges %u / %u leave no interior of a %u x %u frame", who, k->edge_h, k->edge_w, k->H, k->W);
+        const uint64_t n_int = (uint64_t)(k->H - 2u * k->edge_h) * (k->W - 2u * k->edge_w);
+        if (k->n_rays > n_int) return fail(NARUTO_ERR_INVALID, "%s: %u distinct pixels out of %llu interior pixels", who, k->n_rays, (unsigned long long)n_int);
+    }
+    return NARUTO_OK;
+}
+
+TrackArgs track_args(const NarutoTrackStep* k, const NarutoTrainStep* t) {
+    TrackArgs a{};
+    a.n_rays = k->n_rays; a.H = k->H; a.W = k->W; a.edge_h = k->edge_h; a.edge_w = k->edge_w;
+    a.direction = k->direction; a.rgb = k->rgb; a.depth = k->depth; a.rng = k->rng;
+    a.d_cam = k->d_cam; a.pix = k->pix;
+    // the training step's ray and target buffers are the tracker's own: written by the draw, the ray launch and the pose step
+    a.target_rgb = const_cast<float*>(t->target_rgb); a.target_d = const_cast<float*>(t->target_d);
+    a.rays_o = const_cast<float*>(t->rays_o); a.rays_d = const_cast<float*>(t->rays_d);
+    a.pose_init = k->pose_init; a.pose = k->pose; a.exp_avg = k->exp_avg; a.exp_avg_sq = k->exp_avg_sq; a.state = k->state;
+    a.lr_rot = k->lr_rot; a.lr_trans = k->lr_trans; a.beta1 = k->beta1; a.beta2 = k->beta2; a.eps = k->eps;
+    a.wait_iters = k->wait_iters; a.best = k->best;
+    a.best_pose = k->best_pose; a.best_loss = k->best_loss; a.c2w = k->c2w;
+    a.d_rays_o = k->d_rays_o; a.d_rays_d = k->d_rays_d; a.losses = t->losses;
+    a.trace_loss = k->trace_loss; a.trace_pose = k->trace_pose; a.trace_d_pose = k->trace_d_pose; a.max_trace = k->max_trace;
+    return a;
+}
+}  // namespace
+
+size_t naruto_track_workspace(const NarutoField* f, uint32_t n_rays, uint32_t n_samples) {
+    const uint64_t M = (uint64_t)n_rays * n_samples;
+    return M > (1ull << 29) ? 0u : naruto_query_bwd_points_workspace(f, (uint32_t)M);
+}
+
+int naruto_track_draw(const NarutoTrackStep* k, const NarutoTrainStep* t, void* stream) {
+    if (int rc = track_check(k, t, true, "track_draw")) return rc;
+    const uint64_t n_int = (uint64_t)(k->H - 2u * k->edge_h) * (k->W - 2u * k->edge_w);
+    hipLaunchKernelGGL(k_track_draw, dim3((k->n_rays + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, track_args(k, t), n_int, half_bits_for(n_int));
+    return check_launch("track_draw");
+}
+
+int naruto_track_rays(const NarutoTrackStep* k, const NarutoTrainStep* t, void* stream) {
+    if (int rc = track_check(k, t, false, "track_rays")) return rc;
+    hipLaunchKernelGGL(k_track_rays, dim3((k->n_rays + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, track_args(k, t));
+    return check_launch("track_rays");
+}
+
+int naruto_track_backward(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const NarutoTrackStep* k, void* stream) {
+    if (int rc = train_check(f, p, t, "track_backward")) return rc;
+    if (int rc = track_check(k, t, false, "track_backward")) return rc;
+    if (t->smooth_points != 0) return fail(NARUTO_ERR_INVALID, "track_backward: tracking has no smoothness term (smooth_points must be 0)");
+    if (t->loss_weights == nullptr || t->d_raw == nullptr || t->ray_count == nullptr || t->ray_offset == nullptr || t->active_idx == nullptr || t->n_active == nullptr)
+        return fail(NARUTO_ERR_INVALID, "track_backward: NULL buffer in NarutoTrainStep");
+    const hipStream_t st = (hipStream_t)stream;
+    const uint32_t S = t->n_samples_d + t->n_range_d, M = t->n_rays * S;
+    if (M > (1u << 29)) return fail(NARUTO_ERR_INVALID, "track_backward: at most 2^29 samples per iteration (got %u)", M);
+    const TrainWs w = train_ws(f, t);
+    const BwdWs bw = bwd_ws(f, w.bwd, list_cap(M + w.n3));
+    if (int rc = ray_lds_attr()) return rc;
+    if (int rc = loss_bwd_compact(f, t, w, train_loss_args(f, t), 0u, bw.n_total, st)) return rc;
+    // naruto_query_bwd_points' launches for ray points over the active list (its zero fill as a kernel)
+    NarutoPoints pts{};
+    pts.rays_o = t->rays_o; pts.rays_d = t->rays_d; pts.z_vals = t->z_vals; pts.n_samples = S;
+    if (int rc = check_points(&pts)) return rc;
+    float* gp = reinterpret_cast<float*>(k->workspace);
+    const uint64_t n_gp = 3u * (uint64_t)M;
+    hipLaunchKernelGGL(k_track_zero, dim3((uint32_t)((n_gp + 255u) / 256u)), dim3(256), 0, st, gp, n_gp);
+    if (int rc = check_launch("track_zero")) return rc;
+    hipLaunchKernelGGL(k_query_bwd_points, dim3((M + (uint32_t)kPgThreads - 1u) / (uint32_t)kPgThreads), dim3(kPgThreads), 0, st, f->lt, f->ut, f->bt, make_points(&pts), M,
+                       reinterpret_cast<const float2*>(p->table), p->uncert_grid, p->sdf_w0, p->sdf_w1, p->col_w0, p->col_w1, t->d_raw, nullptr, t->active_idx,
+                       t->n_active, gp, 1, 0);
+    if (int rc = check_launch("query_bwd_points")) return rc;
+    hipLaunchKernelGGL(k_ray_point_reduce, dim3((t->n_rays + 3u) / 4u), dim3(256), 0, st, t->n_rays, S, gp, t->z_vals, k->d_rays_o, k->d_rays_d, 0);
+    if (int rc = check_launch("ray_point_reduce")) return rc;
+    hipLaunchKernelGGL(k_track_step, dim3(1), dim3(kTrackStepThreads), 0, st, track_args(k, t));
+    return check_launch("track_step");
+}
+
+int naruto_debug_rodrigues(const double* w, const double* G, double* R, double* d_w) {
+    if (w == nullptr || (d_w != nullptr && G == nullptr)) return fail(NARUTO_ERR_INVALID, "debug_rodrigues: NULL argument");
+    if (R != nullptr) rodrigues(w, R);
+    if (d_w != nullptr) rodrigues_vjp(w, G, d_w);
+    return NARUTO_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,282 @@
+// Camera tracking (Co-SLAM tracking_render, called at coslam.py:594-602; parity unpinned -- the function is not in the reference tree):
+// the pose of ONE frame is optimised with the network frozen.  Per call:
+//   k_track_draw   tracking.sample distinct interior pixels (keyed Feistel permutation, naruto_rays.hip) -> d_cam, target_rgb, target_d
+//   k_track_rays   state reset + iteration 0's rays from the initial pose
+// and per iteration, after the training forward, the loss backward + compaction and the point gradients (k_query_bwd_points,
+// k_ray_point_reduce):
+//   k_track_step   ONE workgroup: d_t = sum_r d_rays_o[r], G = sum_r d_rays_d[r] (x) d_cam[r] in a fixed order (no atomics), d_omega as the
+//                  VJP of Rodrigues' formula, the best-pose / wait_iters bookkeeping, one torch.optim.Adam step, and the NEXT iteration's rays.
+// The pose is an absolute axis-angle omega of the camera-to-world rotation plus the translation t; R(omega) = exp([omega]x).
+#pragma once
+
+#include "naruto_common.h"
+
+namespace naruto {
+
+constexpr int kTrackStepThreads = 256;
+
+// A = sin(th)/th, B = (1 - cos(th))/th^2 and a = A'(th)/th, b = B'(th)/th; series below th = 1e-2 (fp64: the closed forms lose
+// ~1e-16 / th^2 there; the truncated series' error is below th^8 / 1e6)
+__host__ __device__ inline void rodrigues_coeffs(double th2, double& A, double& B, double& a, double& b) {
+    if (th2 < 1e-4) {
+        A = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0 * (1.0 - th2 / 42.0));
+        B = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0 * (1.0 - th2 / 56.0));
+        a = -1.0 / 3.0 + th2 / 30.0 - th2 * th2 / 840.0 + th2 * th2 * th2 / 45360.0;
+        b = -1.0 / 12.0 + th2 / 180.0 - th2 * th2 / 6720.0 + th2 * th2 * th2 / 453600.0;
+        return;
+    }
+    const double th = sqrt(th2), s = sin(th), c = cos(th);
+    A = s / th;
+    B = (1.0 - c) / th2;
+    a = (th * c - s) / (th2 * th);
+    b = (th * s - 2.0 * (1.0 - c)) / (th2 * th2);
+}
+
+// R = I + A K + B K^2, K = [w]x (row-major)
+__host__ __device__ inline void rodrigues(const double w[3], double R[9]) {
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    double A, B, a, b;
+    rodrigues_coeffs(th2, A, B, a, b);
+    const double K[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double k2 = 0.0;
+            for (int m = 0; m < 3; ++m) k2 += K[3 * i + m] * K[3 * m + j];
+            R[3 * i + j] = (i == j ? 1.0 : 0.0) + A * K[3 * i + j] + B * k2;
+        }
+}
+
+// d_w = VJP of rodrigues at w with cotangent G (dL/dR, row-major):
+//   dR/dw_k = a w_k K + A K_k + b w_k K^2 + B (K_k K + K K_k),  K_k = [e_k]x
+__host__ __device__ inline void rodrigues_vjp(const double w[3], const double G[9], double d_w[3]) {
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    double A, B, a, b;
+    rodrigues_coeffs(th2, A, B, a, b);
+    const double K[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+    double gK = 0.0, gK2 = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double k2 = 0.0;
+            for (int m = 0; m < 3; ++m) k2 += K[3 * i + m] * K[3 * m + j];
+            gK += G[3 * i + j] * K[3 * i + j];
+            gK2 += G[3 * i + j] * k2;
+        }
+    for (int k = 0; k < 3; ++k) {
+        double Kk[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        const int p = (k + 1) % 3, q = (k + 2) % 3;        // [e_k]x: +1 at (q, p), -1 at (p, q)
+        Kk[3 * q + p] = 1.0;
+        Kk[3 * p + q] = -1.0;
+        double gKk = 0.0, gS = 0.0;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                double s = 0.0;
+                for (int m = 0; m < 3; ++m) s += Kk[3 * i + m] * K[3 * m + j] + K[3 * i + m] * Kk[3 * m + j];
+                gKk += G[3 * i + j] * Kk[3 * i + j];
+                gS += G[3 * i + j] * s;
+            }
+        d_w[k] = a * w[k] * gK + A * gKk + b * w[k] * gK2 + B * gS;
+    }
+}
+
+struct TrackArgs {
+    uint32_t n_rays;
+    uint32_t H, W, edge_h, edge_w;
+    const float* direction; const float* rgb; const float* depth;      // the frame [H,W,3] [H,W,3] [H,W]
+    uint64_t* rng;                                                      // {seed, counter}
+    float* d_cam; int64_t* pix;
+    float* target_rgb; float* target_d;
+    float* rays_o; float* rays_d;
+    const float* pose_init;
+    float* pose; float* exp_avg; float* exp_avg_sq;
+    int32_t* state;                                                     // {step, thresh, stopped, iteration}
+    float lr_rot, lr_trans, beta1, beta2, eps;
+    uint32_t wait_iters; int32_t best;
+    float* best_pose; float* best_loss; float* c2w;
+    const float* d_rays_o; const float* d_rays_d;
+    const float* losses;
+    float* trace_loss; float* trace_pose; float* trace_d_pose; uint32_t max_trace;
+};
+
+// rays_o[r] = t, rays_d[r] = R d_cam[r] in fp32, in the order of coslam.py:343 (torch.sum(d[..., None, :] * R, -1))
+__device__ __forceinline__ void track_write_ray(const TrackArgs& a, uint32_t r, const float Rf[9], const float t[3]) {
+    const float dx = a.d_cam[3 * (size_t)r], dy = a.d_cam[3 * (size_t)r + 1], dz = a.d_cam[3 * (size_t)r + 2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        a.rays_d[3 * (size_t)r + i] = __fadd_rn(__fadd_rn(__fmul_rn(dx, Rf[3 * i]), __fmul_rn(dy, Rf[3 * i + 1])), __fmul_rn(dz, Rf[3 * i + 2]));
+        a.rays_o[3 * (size_t)r + i] = t[i];
+    }
+}
+
+__device__ __forceinline__ void track_pose_matrix(const float p[6], float Rf[9]) {
+    const double w[3] = {(double)p[0], (double)p[1], (double)p[2]};
+    double R[9];
+    rodrigues(w, R);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Rf[i] = (float)R[i];
+}
+
+__device__ __forceinline__ void track_write_c2w(float* c2w, const float p[6]) {
+    float Rf[9];
+    track_pose_matrix(p, Rf);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        c2w[4 * i] = Rf[3 * i]; c2w[4 * i + 1] = Rf[3 * i + 1]; c2w[4 * i + 2] = Rf[3 * i + 2]; c2w[4 * i + 3] = p[3 + i];
+    }
+    c2w[12] = 0.0f; c2w[13] = 0.0f; c2w[14] = 0.0f; c2w[15] = 1.0f;
+}
+
+// row i of the draw: flat interior index k = perm(i) -> h = edge_h + k % Hi (h fastest, Co-SLAM's order), w = edge_w + k / Hi
+__global__ __launch_bounds__(256) void k_track_draw(TrackArgs a, uint64_t n_int, uint32_t half_bits) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_rays) return;
+    const uint64_t key = mix_key(a.rng[0], a.rng[1], 4);
+    const uint64_t k = perm_index(i, n_int, half_bits, key);
+    const uint32_t Hi = a.H - 2u * a.edge_h;
+    const uint64_t h = a.edge_h + k % Hi, w = a.edge_w + k / Hi;
+    const uint64_t px = h * a.W + w;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        a.d_cam[3 * (size_t)i + d] = a.direction[3 * px + d];
+        a.target_rgb[3 * (size_t)i + d] = a.rgb[3 * px + d];
+    }
+    a.target_d[i] = a.depth[px];
+    if (a.pix != nullptr) a.pix[i] = (int64_t)px;
+}
+
+// zero fill of the per-point gradient rows k_query_bwd_points leaves alone (the samples off the active list) -- a kernel, not a memset
+// node, so that a captured call is one chain of kernel nodes
+__global__ __launch_bounds__(256) void k_track_zero(float* __restrict__ out, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = 0.0f;
+}
+
+// the call's state from the initial pose (one thread) + iteration 0's rays; advances the draw's counter for the next call
+__global__ __launch_bounds__(256) void k_track_rays(TrackArgs a) {
+    float p[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) p[k] = a.pose_init[k];
+    float Rf[9];
+    track_pose_matrix(p, Rf);
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < a.n_rays) track_write_ray(a, r, Rf, p + 3);
+    if (r == 0) {
+        for (int k = 0; k < 6; ++k) {
+            a.pose[k] = p[k]; a.best_pose[k] = p[k]; a.exp_avg[k] = 0.0f; a.exp_avg_sq[k] = 0.0f;
+        }
+        a.state[0] = 0; a.state[1] = 0; a.state[2] = 0; a.state[3] = 0;
+        a.best_loss[0] = __int_as_float(0x7F800000);
+        track_write_c2w(a.c2w, p);
+        a.rng[1] += 1ull;
+    }
+}
+
+// after the point gradients of iteration i = state[3]: see the file header
+__global__ __launch_bounds__(kTrackStepThreads) void k_track_step(TrackArgs a) {
+    __shared__ double red[kTrackStepThreads][12];
+    __shared__ float s_next[16];            // Rf[9] | t[3] of the next pose | go on
+    const uint32_t tid = threadIdx.x;
+    double acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] = 0.0;
+    for (uint32_t r = tid; r < a.n_rays; r += kTrackStepThreads) {
+        float dc[3], dro[3], drd[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            dc[d] = a.d_cam[3 * (size_t)r + d]; dro[d] = a.d_rays_o[3 * (size_t)r + d]; drd[d] = a.d_rays_d[3 * (size_t)r + d];
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            acc[d] += (double)dro[d];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) acc[3 + 3 * d + j] += (double)drd[d] * (double)dc[j];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) red[tid][k] = acc[k];
+    __syncthreads();
+    for (uint32_t h = kTrackStepThreads / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) red[tid][k] += red[tid + h][k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int32_t it = a.state[3];
+        a.state[3] = it + 1;
+        s_next[15] = 0.0f;
+        if (a.state[2] == 0) {
+            float p[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) p[k] = a.pose[k];
+            const double w[3] = {(double)p[0], (double)p[1], (double)p[2]};
+            double G[9], dw[3];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) G[k] = red[0][3 + k];
+            rodrigues_vjp(w, G, dw);
+            const float g[6] = {(float)dw[0], (float)dw[1], (float)dw[2], (float)red[0][0], (float)red[0][1], (float)red[0][2]};
+            const float L = a.losses[9];
+            if (a.trace_loss != nullptr && (uint32_t)it < a.max_trace) {
+                a.trace_loss[it] = L;
+                for (int k = 0; k < 6; ++k) { a.trace_pose[6 * it + k] = p[k]; a.trace_d_pose[6 * it + k] = g[k]; }
+            }
+            // Co-SLAM's order: the first loss is the best so far, then the comparison (which the first loss fails: thresh = 1)
+            float best = it == 0 ? L : a.best_loss[0];
+            if (it == 0)
+                for (int k = 0; k < 6; ++k) a.best_pose[k] = p[k];
+            int32_t thresh = a.state[1];
+            if (L < best) {
+                best = L;
+                for (int k = 0; k < 6; ++k) a.best_pose[k] = p[k];
+                thresh = 0;
+            } else {
+                thresh += 1;
+            }
+            a.best_loss[0] = best;
+            a.state[1] = thresh;
+            if (a.best) {
+                float bp[6];
+                for (int k = 0; k < 6; ++k) bp[k] = a.best_pose[k];
+                track_write_c2w(a.c2w, bp);
+            } else {
+                track_write_c2w(a.c2w, p);          // the pose evaluated last: Co-SLAM recomputes c2w_est before the step
+            }
+            if ((uint32_t)thresh > a.wait_iters) {
+                a.state[2] = 1;
+            } else {
+                // torch.optim.Adam (single tensor, no weight decay, amsgrad off): moments in fp32, bias corrections in fp64
+                const int32_t step = a.state[0] + 1;
+                a.state[0] = step;
+                const double bc1 = 1.0 - pow((double)a.beta1, (double)step), bc2 = 1.0 - pow((double)a.beta2, (double)step);
+                const float bc2_sqrt = (float)sqrt(bc2);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const float lr = k < 3 ? a.lr_rot : a.lr_trans;
+                    const float step_size = (float)((double)lr / bc1);
+                    float m = a.exp_avg[k], v = a.exp_avg_sq[k];
+                    m = fmaf(1.0f - a.beta1, g[k] - m, m);
+                    v = fmaf((1.0f - a.beta2) * g[k], g[k], v * a.beta2);
+                    a.exp_avg[k] = m; a.exp_avg_sq[k] = v;
+                    const float denom = sqrtf(v) / bc2_sqrt + a.eps;
+                    p[k] = p[k] - step_size * (m / denom);
+                    a.pose[k] = p[k];
+                }
+                float Rf[9];
+                track_pose_matrix(p, Rf);
+                for (int k = 0; k < 9; ++k) s_next[k] = Rf[k];
+                for (int k = 0; k < 3; ++k) s_next[9 + k] = p[3 + k];
+                s_next[15] = 1.0f;
+            }
+        }
+    }
+    __syncthreads();
+    if (s_next[15] == 0.0f) return;
+    float Rf[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rf[k] = s_next[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = s_next[9 + k];
+    for (uint32_t r = tid; r < a.n_rays; r += kTrackStepThreads) track_write_ray(a, r, Rf, t);
+}
+
+}  // namespace naruto
