@@ -329,6 +329,18 @@ int naruto_active_ray_select_keyed(uint32_t n_total, uint32_t base, uint32_t K, 
                                    const float* rays_d, const float* target_s, const float* target_d, const uint32_t* keys,
                                    float* out_o, float* out_d, float* out_s, float* out_t, void* stream);
 
+/* The two selections with one more, optional output: src_rows [base + n_tail] = the input row each output row was taken from (NULL: the
+ * calls above).  The selection permutes rows; whatever is known per assembled row (NarutoRayBatch.ids_out: the pose of a ray) follows the
+ * rays through it: id of output row r = ids[src_rows[r]]. */
+int naruto_active_ray_select_rows(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o,
+                                  const float* rays_d, const float* target_s, const float* target_d,
+                                  const float* uncert_vol, const uint32_t* vol_dims, const float* bbox_min,
+                                  float voxel_scale, float* out_o, float* out_d, float* out_s, float* out_t,
+                                  uint32_t* src_rows, void* workspace, void* stream);
+int naruto_active_ray_select_keyed_rows(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o,
+                                        const float* rays_d, const float* target_s, const float* target_d, const uint32_t* keys,
+                                        float* out_o, float* out_d, float* out_s, float* out_t, uint32_t* src_rows, void* stream);
+
 /* N2 ("next" row) -- camera-frame directions to world rays (coslam.py:342-344): rays_d[r] = R[pose_id[r]] . d_cam[r],
  * rays_o[r] = t[pose_id[r]]; poses [P,4,4] row-major camera-to-world, pose_id int64 [n]. */
 int naruto_rays_to_world(uint32_t n, const float* d_cam, const int64_t* pose_id, const float* poses, float* rays_o,
@@ -576,6 +588,60 @@ int naruto_track_rays(const NarutoTrackStep* k, const NarutoTrainStep* t, void* 
 int naruto_track_backward(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const NarutoTrackStep* k, void* stream);
 /* host only: R(w) (row-major) and the VJP d_w of sum(G * R(w)), in fp64, by the tracking kernels' own code (R or d_w may be NULL) */
 int naruto_debug_rodrigues(const double* w, const double* G, double* R, double* d_w);
+
+
+/* Pose refinement inside global_BA: the pose optimiser of the reference's loop (coslam.py:256-281, 342-344, 378-407; parity unpinned --
+ * get_pose_param_optim and matrix_from_tensor are Co-SLAM functions that are not in the reference tree, the loop around them is the
+ * contract).  Per call with P = dyn[1] poses (the current frame's last): pose 0 is fixed, poses 1 .. P-2 are parameters, pose P-1 is one
+ * iff optim_cur.  A parameter pose is (omega [3], the absolute axis-angle of the camera-to-world rotation; t [3]), R(omega) by Rodrigues'
+ * formula, stepped by torch.optim.Adam with lr_rot / lr_trans and ONE step count shared by all poses.
+ *   naruto_ba_poses_init         once per call, before its first batch is assembled: pose6 <- pose_init (the caller's (omega, t), P rows), moments,
+ *                                sums and state zeroed, the parameter poses' [4,4] rows of `poses` rewritten from R(omega) (fixed poses keep their bits)
+ *   naruto_train_backward_poses  naruto_train_backward with, between its loss backward and the launches that scatter and step the network,
+ *                                the iteration's ray gradients (naruto_query_bwd_points' kernels over the active list), their sums per pose
+ *                                -- d_t[p] = sum d_rays_o[r], H[p] = sum d_rays_d[r] (x) rays_d[r] over the rays of pose p, fp64, fixed order, no
+ *                                atomics -- added to `accum`, and ONE workgroup that counts the iteration (state[1]) and, when
+ *                                (iteration + 1) % pose_accum_step == 0, steps every parameter pose: d_omega = VJP of Rodrigues with cotangent
+ *                                H R(omega), d_t, one Adam step, sums zeroed, the new [4,4] rows written to `poses` -- before the launch that
+ *                                assembles the next batch (NarutoFusedAdam.next_batch).  bap NULL: naruto_train_backward, launch for launch.
+ * The pose of training ray r is ids[src_rows ? src_rows[r] : r] (-1 = the current frame = pose P-1): ids as NarutoRayBatch.ids_out leaves
+ * them, src_rows as naruto_active_ray_select_rows does.  All pointers are device memory; a captured launch stays valid while P grows. */
+typedef struct NarutoBAPoses {
+    uint32_t max_poses;                               /* rows of poses, pose_init, pose6, the moments, accum and of a trace slice */
+    uint32_t optim_cur;                               /* != 0: the current frame's pose (the last) is a parameter too (mapping.optim_cur) */
+    uint32_t pose_accum_step;                         /* mapping.pose_accum_step (> 0)                               */
+    const uint64_t *dyn;                              /* {n_kf, n_poses, n_cur_pop} as NarutoRayBatch.dyn            */
+    float *poses;                                     /* [max_poses,4,4] camera-to-world: what the ray assembly reads */
+    const float *pose_init;                           /* [max_poses,6] the caller's poses as (omega, t)              */
+    float *pose6, *exp_avg, *exp_avg_sq;              /* [max_poses,6] the parameters and their Adam moments         */
+    double *accum;                                    /* [max_poses,12] the window's sums: d_t[3] | H[9]             */
+    int32_t *state;                                   /* [4] {pose steps, iterations} of this call, 0, 0             */
+    const int64_t *ids;                               /* [n_ids] pose id per assembled row                           */
+    uint32_t n_ids;
+    const uint32_t *src_rows;                         /* optional [n_rays]: assembled row of each training ray       */
+    float *d_rays_o, *d_rays_d;                       /* [n_rays,3] the iteration's ray gradients                    */
+    float lr_rot, lr_trans, beta1, beta2, eps;        /* Adam (no weight decay): lr_rot for omega, lr_trans for t    */
+    float *trace_pose, *trace_grad;                   /* optional [max_trace,max_poses,6] x2: per pose step the (omega, t) before the
+                                                         step and the accumulated gradient (fixed poses: their (omega, t), 0)   */
+    uint32_t max_trace;
+    void *workspace;                                  /* naruto_ba_poses_workspace bytes                             */
+} NarutoBAPoses;
+size_t naruto_ba_poses_workspace(const NarutoField* f, uint32_t n_rays, uint32_t n_samples);
+int naruto_ba_poses_init(const NarutoBAPoses* b, void* stream);
+int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const NarutoGrads* g,
+                                uint32_t flags, const NarutoFusedAdam* opt, const NarutoBAPoses* bap /* NULL: off */, void* stream);
+/* host only (nothing is launched, no GPU needed; tests/test_ba_poses_host.py):
+ * naruto_debug_ba_poses_check: the argument checks naruto_train_backward_poses applies to bap for a batch of n_rays rays.
+ * naruto_debug_ba_poses_fields: the struct as the library reads it, field by field in declaration order (floats as their bits).
+ * naruto_debug_pose_adam: one step (number `step`, 1-based) of the kernels' own Adam on a pose [6], its gradient and moments, in place.
+ * naruto_debug_ba_pose_sums: pose `pose`'s sums of one batch in the accumulation kernel's order, ADDED to sums [12] (host arrays
+ *   throughout); grad [6] (optional, needs pose6 [6]): (d_omega, d_t) from the sums as the pose step forms it. */
+int naruto_debug_ba_poses_check(const NarutoBAPoses* b, uint32_t n_rays);
+int naruto_debug_ba_poses_fields(const NarutoBAPoses* b, uint64_t out[25]);
+int naruto_debug_pose_adam(float* pose, const float* grad, float* exp_avg, float* exp_avg_sq, int32_t step, float lr_rot, float lr_trans,
+                           float beta1, float beta2, float eps);
+int naruto_debug_ba_pose_sums(uint32_t n_rays, const int64_t* ids, uint32_t n_ids, const uint32_t* src_rows, uint32_t n_poses, uint32_t pose,
+                              const float* rays_d, const float* d_rays_o, const float* d_rays_d, const float* pose6, double* sums, float* grad);
 
 #ifdef __cplusplus
 }

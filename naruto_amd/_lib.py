@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -107,6 +107,17 @@ class NarutoTrackStep(C.Structure):
     ]
 
 
+class NarutoBAPoses(C.Structure):
+    _fields_ = [
+        ("max_poses", C.c_uint32), ("optim_cur", C.c_uint32), ("pose_accum_step", C.c_uint32), ("dyn", C.c_void_p),
+        ("poses", C.c_void_p), ("pose_init", C.c_void_p), ("pose6", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("accum", C.c_void_p), ("state", C.c_void_p), ("ids", C.c_void_p), ("n_ids", C.c_uint32), ("src_rows", C.c_void_p),
+        ("d_rays_o", C.c_void_p), ("d_rays_d", C.c_void_p),
+        ("lr_rot", C.c_float), ("lr_trans", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("trace_pose", C.c_void_p), ("trace_grad", C.c_void_p), ("max_trace", C.c_uint32), ("workspace", C.c_void_p),
+    ]
+
+
 class NarutoRender(C.Structure):
     _fields_ = [("n_rays", C.c_uint32), ("rays_o", C.c_void_p), ("rays_d", C.c_void_p), ("target_d", C.c_void_p),
                 ("near_", C.c_float), ("far_", C.c_float), ("n_samples_d", C.c_uint32), ("n_range_d", C.c_uint32), ("range_d", C.c_float),
@@ -176,6 +187,8 @@ SIGNATURES = {
     "naruto_active_ray_workspace": (C.c_size_t, [_U32, _U32]),
     "naruto_active_ray_select_keyed": (_I, [_U32, _U32, _U32, _U32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "naruto_active_ray_select": (_I, [_U32, _U32, _U32, _U32, _V, _V, _V, _V, _V, C.POINTER(_U32), C.POINTER(_F), _F, _V, _V, _V, _V, _V, _V]),
+    "naruto_active_ray_select_keyed_rows": (_I, [_U32, _U32, _U32, _U32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "naruto_active_ray_select_rows": (_I, [_U32, _U32, _U32, _U32, _V, _V, _V, _V, _V, C.POINTER(_U32), C.POINTER(_F), _F, _V, _V, _V, _V, _V, _V, _V]),
     "naruto_rays_to_world": (_I, [_U32, _V, _V, _V, _V, _V, _V]),
     "naruto_map_volumes": (_I, [_U32, _V, _V, _V]),
     "naruto_assemble_rays": (_I, [C.POINTER(NarutoRayBatch), _V]),
@@ -209,6 +222,14 @@ SIGNATURES = {
     "naruto_track_draw": (_I, [C.POINTER(NarutoTrackStep), C.POINTER(NarutoTrainStep), _V]),
     "naruto_track_rays": (_I, [C.POINTER(NarutoTrackStep), C.POINTER(NarutoTrainStep), _V]),
     "naruto_track_backward": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), C.POINTER(NarutoTrackStep), _V]),
+    "naruto_ba_poses_workspace": (C.c_size_t, [_V, _U32, _U32]),
+    "naruto_ba_poses_init": (_I, [C.POINTER(NarutoBAPoses), _V]),
+    "naruto_train_backward_poses": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), C.POINTER(NarutoGrads), _U32,
+                                         C.POINTER(NarutoFusedAdam), C.POINTER(NarutoBAPoses), _V]),
+    "naruto_debug_ba_poses_check": (_I, [C.POINTER(NarutoBAPoses), _U32]),
+    "naruto_debug_ba_poses_fields": (_I, [C.POINTER(NarutoBAPoses), C.POINTER(_U64)]),
+    "naruto_debug_pose_adam": (_I, [C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), C.c_int32, _F, _F, _F, _F, _F]),
+    "naruto_debug_ba_pose_sums": (_I, [_U32, _V, _U32, _V, _U32, _U32, _V, _V, _V, _V, _V, _V]),
     "naruto_debug_rodrigues": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "naruto_compact_active": (_I, [_U32, _U32, _V, _V, _V, _V, _V]),
     "naruto_composite_fwd": (_I, [_V, _U32, _U32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),

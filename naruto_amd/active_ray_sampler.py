@@ -88,11 +88,13 @@ class ActiveRaySamplerHIP:
         assert keys.is_cuda and keys.dtype == torch.int32 and keys.numel() >= n_total - n_tail - self.base_sample_num
         return keys, self.base_sample_num, n_tail, vol, tuple(float(b[0]) for b in bbox)
 
-    def sample_rays(self, rays_o, rays_d, target_s, target_d, idx_cur, uncert_vol, bbox: List, out=None, workspace=None, keys=None):
+    def sample_rays(self, rays_o, rays_d, target_s, target_d, idx_cur, uncert_vol, bbox: List, out=None, workspace=None, keys=None, src_rows=None):
         """active_ray_sampler.py:77-149.  ``idx_cur``: the current-frame indices (only their NUMBER is used, as in the reference) or
         that number.  ``out`` = (rays_o, rays_d, target_s, target_d) to write into (e.g. a captured trainer's ``ray_buffers()``) and
         ``workspace`` (int32, ``workspace_elems`` long) make the call allocation-free.  ``keys`` (int32 [candidates]): the candidates' keys as
-        the batch's assembly left them (``key_lookup``): the lookup is skipped (``uncert_vol`` is then not read)."""
+        the batch's assembly left them (``key_lookup``): the lookup is skipped (``uncert_vol`` is then not read).  ``src_rows`` (int32
+        [n_out]): the input row every output row was taken from is written there -- what is known per input row (its pose id) follows
+        the rays through the selection."""
         lib = _lib.load()
         rays_o, rays_d, target_s = _f32c(rays_o, "rays_o"), _f32c(rays_d, "rays_d"), _f32c(target_s, "target_s")
         td = _f32c(target_d, "target_d").reshape(-1)
@@ -110,17 +112,27 @@ class ActiveRaySamplerHIP:
         else:
             o_out, d_out, s_out = (torch.empty(n_out, 3, device=dev) for _ in range(3))
             t_out = torch.empty(n_out, 1, device=dev)
+        if src_rows is not None:
+            assert src_rows.is_cuda and src_rows.dtype == torch.int32 and src_rows.is_contiguous() and src_rows.numel() >= n_out, "src_rows: int32 [n_out] on the device"
         if keys is not None:
             assert keys.is_cuda and keys.dtype == torch.int32 and keys.numel() >= n_total - n_tail - base
             with torch.cuda.device(dev):
-                _lib.check(lib.naruto_active_ray_select_keyed(n_total, base, K, n_tail, _p(rays_o), _p(rays_d), _p(target_s), _p(td), _p(keys),
-                                                              _p(o_out), _p(d_out), _p(s_out), _p(t_out), _stream()), "naruto_active_ray_select_keyed")
+                if src_rows is not None:
+                    _lib.check(lib.naruto_active_ray_select_keyed_rows(n_total, base, K, n_tail, _p(rays_o), _p(rays_d), _p(target_s), _p(td), _p(keys), _p(o_out),
+                                                                       _p(d_out), _p(s_out), _p(t_out), _p(src_rows), _stream()), "naruto_active_ray_select_keyed_rows")
+                else:
+                    _lib.check(lib.naruto_active_ray_select_keyed(n_total, base, K, n_tail, _p(rays_o), _p(rays_d), _p(target_s), _p(td), _p(keys),
+                                                                  _p(o_out), _p(d_out), _p(s_out), _p(t_out), _stream()), "naruto_active_ray_select_keyed")
             return o_out, d_out, s_out, t_out
         dims = (C.c_uint32 * 3)(*vol.shape)
         bmin = (C.c_float * 3)(*(float(b[0]) for b in bbox))
         with torch.cuda.device(dev):
             ws = workspace if workspace is not None else torch.empty(self.workspace_elems(n_total), dtype=torch.int32, device=dev)
             assert ws.dtype == torch.int32 and ws.numel() >= self.workspace_elems(n_total)
-            _lib.check(lib.naruto_active_ray_select(n_total, base, K, n_tail, _p(rays_o), _p(rays_d), _p(target_s), _p(td), _p(vol), dims, bmin, 10.0,
-                                                    _p(o_out), _p(d_out), _p(s_out), _p(t_out), _p(ws), _stream()), "naruto_active_ray_select")
+            if src_rows is not None:
+                _lib.check(lib.naruto_active_ray_select_rows(n_total, base, K, n_tail, _p(rays_o), _p(rays_d), _p(target_s), _p(td), _p(vol), dims, bmin, 10.0,
+                                                             _p(o_out), _p(d_out), _p(s_out), _p(t_out), _p(src_rows), _p(ws), _stream()), "naruto_active_ray_select_rows")
+            else:
+                _lib.check(lib.naruto_active_ray_select(n_total, base, K, n_tail, _p(rays_o), _p(rays_d), _p(target_s), _p(td), _p(vol), dims, bmin, 10.0,
+                                                        _p(o_out), _p(d_out), _p(s_out), _p(t_out), _p(ws), _stream()), "naruto_active_ray_select")
         return o_out, d_out, s_out, t_out

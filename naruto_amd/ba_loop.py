@@ -15,23 +15,70 @@ planner's uncertainty volume is refreshed in place.  The graph is re-captured on
 // n_kf, min_pixels_cur): constant once n_kf exceeds sample_num / min_pixels_cur, i.e. for all but the first ~20 keyframes).
 
 The reference draws with Python's ``random`` on the host and round-trips through numpy for the active rays; the drawn sets differ by
-construction (tests: same distribution properties, and the chained launches equal the three operators run one by one)."""
+construction (tests: same distribution properties, and the chained launches equal the three operators run one by one).
+
+POSE REFINEMENT (``optimize_poses``; the reference turns it on with ``tracking.disable: False``).  ``get_pose_param_optim`` and
+``matrix_from_tensor`` are Co-SLAM functions that are not in the reference tree: what follows restates the loop around them
+(coslam.py:256-281, 342-344, 378-407) with the pose parametrisation of ``naruto_amd.tracking`` -- parity unpinned.  Per ``global_BA``
+call with P poses (``poses_all``, the current frame's last; ray id -1 means the last):
+
+1. Pose optimisation is OFF for the call when fewer than 2 keyframes are stored or the caller does not ask for it (coslam.py:264): the
+   call is then the plain call, launch for launch and bit for bit.
+2. Otherwise pose 0 is fixed, poses 1 .. P-2 are parameters, pose P-1 (the current frame) is one iff ``mapping.optim_cur``
+   (coslam.py:273-281).  A parameter pose starts from ``(matrix_to_axis_angle(R), t)`` of the caller's matrix -- converted on the host
+   in fp64, rounded to fp32 -- and from the first iteration on its rays are formed from ``R(omega)`` (Rodrigues, evaluated on the
+   device for the initial matrices and after every step alike), not from the caller's matrix.  Fixed poses keep the caller's bits.
+3. Every iteration is the ordinary mapping iteration (forward, losses incl. smoothness, backward, Adam on the network, uncertainty grid
+   every 5th) AND the gradient of the same total loss w.r.t. every parameter pose, taken at the parameters the forward used,
+   accumulated over the iterations since the last pose step (``naruto_train_backward_poses``).
+4. After the iterations with ``(i + 1) % mapping.pose_accum_step == 0``: one ``torch.optim.Adam`` step (betas 0.9 / 0.999, eps 1e-8,
+   ``mapping.lr_rot`` / ``mapping.lr_trans``) on all parameter poses with one shared step count (a pose that drew no ray has gradient
+   0 and is still stepped), the accumulated gradient is zeroed, and all later batches of the call -- the prefetched one included -- are
+   formed from the new poses (coslam.py:378-395).  Fresh moments and step count at every call.
+5. ``refined_poses()`` returns the P poses [P,4,4] float32 on the device; the caller writes them to ``est_c2w_data`` (coslam.py:401-407).
+
+Whether a pose step is due is decided ON THE DEVICE from the call's iteration count, so the per-iteration graphs and the call graph are
+the plain ones plus five launches per iteration; ``prepare`` adds one launch per call (the reset, outside the graphs).  The graphs are
+re-captured when the switch changes, not when P grows."""
 
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 from typing import Dict, Optional
 
 import torch
 
+from . import _lib
 from .active_ray_sampler import ActiveRaySamplerHIP
 from .keyframe_store import KeyFrameStoreHIP
 from .trainer import MappingTrainer
 
 
+# graphs a FusedBA had to drop while somebody's stream capture was under way (its finaliser ran inside the capture: destroying a graph
+# there ends the capture with an error); released by the next prepare() outside a capture
+_PARKED_GRAPHS = []
+
+
+@contextlib.contextmanager
+def _no_collection():
+    """Around a stream capture: the garbage there is is collected first, and the cyclic collector rests until the capture has ended --
+    a finaliser that frees graphs or device memory (a dropped FusedBA / MappingTrainer) must not run inside it."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
 class FusedBA:
     def __init__(self, trainer: MappingTrainer, store: KeyFrameStoreHIP, sampler: Optional[ActiveRaySamplerHIP] = None,
-                 max_poses: int = 4096, use_graph: bool = True, one_launch_prologue: Optional[bool] = None, prefetch: Optional[bool] = None):
+                 max_poses: int = 4096, use_graph: bool = True, one_launch_prologue: Optional[bool] = None, prefetch: Optional[bool] = None,
+                 optimize_poses: Optional[bool] = None):
         assert trainer.direct and trainer.group is None, "FusedBA drives the single-process fused trainer (MappingTrainer(fused_adam=True))"
         self.trainer, self.store, self.sampler = trainer, store, sampler
         self.config = trainer.config
@@ -76,6 +123,15 @@ class FusedBA:
         self._stage = None            # the oversampled batch between assembly and selection (active ray only)
         self._ws = None
         self.bbox = [[float(v) for v in row] for row in self.config['mapping']['bound']]
+        # pose refinement (see the module docstring): the default follows the reference's switch, tracking.disable
+        tk = self.config.get('tracking') or {}
+        self.optimize_poses = (not bool(tk.get('disable', True))) if optimize_poses is None else bool(optimize_poses)
+        self._pose = None             # the per-pose device buffers (allocated on first use)
+        self._bap = None              # the NarutoBAPoses of the current shape
+        self._pose_on = False         # this call refines poses
+        self._pose_ts = None          # the TrainStep whose backward carries self._bap
+        self._n_poses = 0
+        self._init_c2w = None
 
     # ---------------------------------------------------------------------------------------------
     def sizes(self, n_kf: int, n_valid_cur: int):
@@ -95,7 +151,7 @@ class FusedBA:
         def prologue(rays_o, rays_d, target_rgb, target_d):
             # (the candidates' keys were looked up by the assembly that rode in the previous iteration's finishing launch)
             sampler.sample_rays(*self._stage, n_cur, None, self.bbox, out=(rays_o, rays_d, target_rgb, target_d), workspace=self._ws,
-                                keys=self._keys if self._keyed(n_cur) else None)
+                                keys=self._keys if self._keyed(n_cur) else None, src_rows=self._src_rows())
         return prologue
 
     def _keyed(self, n_cur: int) -> bool:
@@ -107,7 +163,8 @@ class FusedBA:
         out = self._stage if self.active else bufs
         keys = self.sampler.key_lookup(self.sample_num + n_cur, n_cur, self.bbox, self._keys) if (self.active and self._keyed(n_cur)) else None
         b, keep = self.store.next_batch_struct(self.sample_num, self.current, self.poses, self.min_pixels_cur, out, filter_depth=self.filter_depth,
-                                               rng=self.trainer.iter_state, dyn=self.dyn, n_cur=n_cur, n_cur_pop=self._n_cur_pop, keys=keys)
+                                               rng=self.trainer.iter_state, dyn=self.dyn, n_cur=n_cur, n_cur_pop=self._n_cur_pop, keys=keys,
+                                               ids_out=self._ids())
         assert train_step.opt is not None, "prefetch needs the optimiser in the backward (MappingTrainer(fused_adam=True))"
         import ctypes as C
         self._disarm_prefetch()
@@ -130,11 +187,21 @@ class FusedBA:
         """Detach from the trainer: the TrainStep this object armed keeps working as a plain training step (trainer.step, first_frame_mapping).
         A graph captured with the prefetch inside is dropped (its finishing launch would go on drawing batches)."""
         armed = getattr(self, "_armed", None)
+        pose_ts = getattr(self, "_pose_ts", None)
         st = getattr(self.trainer, "_static", None)
-        if armed is not None and self.use_graph and st is not None and st.get('ts') is armed:
-            self.trainer._graphs = None
+        if self.use_graph and st is not None and ((armed is not None and st.get('ts') is armed) or (pose_ts is not None and st.get('ts') is pose_ts)):
+            self._drop_graphs()
         self._disarm_prefetch()
+        self._detach_poses()
         self._shape = None
+
+    def _drop_graphs(self):
+        """Forget the trainer's graphs (they hold this object's prefetch / pose launches).  Inside a stream capture -- this object's
+        finaliser can run in somebody else's -- the graph objects are parked instead of destroyed."""
+        tr = self.trainer
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            _PARKED_GRAPHS.append((tr._graphs, getattr(tr, "_static", None)))
+        tr._graphs = None
 
     def __del__(self):
         try:
@@ -148,28 +215,132 @@ class FusedBA:
 
         def prologue(rays_o, rays_d, target_rgb, target_d):
             kw = dict(filter_depth=self.filter_depth, rng=rng, dyn=self.dyn, n_cur=n_cur, n_cur_pop=self._n_cur_pop)
+            if self._pose_on:
+                kw["ids_out"] = self._ids()
             if not self.active:
                 store.assemble_batch(self.sample_num, self.current, self.poses, self.min_pixels_cur, out=(rays_o, rays_d, target_rgb, target_d), **kw)
                 return
             if self.one_launch_prologue and self.sample_num + n_cur - sampler.n_out(n_cur) <= 8192:
                 # assembly + selection in one launch (naruto_assemble_select): the oversampled batch is never written
+                assert not self._pose_on
                 store.assemble_select(sampler, self.sample_num, self.current, self.poses, self.min_pixels_cur, self.bbox,
                                       out=(rays_o, rays_d, target_rgb, target_d), **kw)
                 return
             if self._keyed(n_cur):         # the assembly looks the candidates' keys up while the rows are in registers (NarutoRayBatch.keys_out)
                 store.assemble_batch(self.sample_num, self.current, self.poses, self.min_pixels_cur, out=self._stage,
                                      keys=sampler.key_lookup(self.sample_num + n_cur, n_cur, self.bbox, self._keys), **kw)
-                sampler.sample_rays(*self._stage, n_cur, None, self.bbox, out=(rays_o, rays_d, target_rgb, target_d), workspace=self._ws, keys=self._keys)
+                sampler.sample_rays(*self._stage, n_cur, None, self.bbox, out=(rays_o, rays_d, target_rgb, target_d), workspace=self._ws, keys=self._keys,
+                                    src_rows=self._src_rows())
                 return
             store.assemble_batch(self.sample_num, self.current, self.poses, self.min_pixels_cur, out=self._stage, **kw)
-            sampler.sample_rays(*self._stage, n_cur, None, self.bbox, out=(rays_o, rays_d, target_rgb, target_d), workspace=self._ws)
+            sampler.sample_rays(*self._stage, n_cur, None, self.bbox, out=(rays_o, rays_d, target_rgb, target_d), workspace=self._ws, src_rows=self._src_rows())
         return prologue
 
-    def prepare(self, current_rays: torch.Tensor, poses_all: torch.Tensor, uncert_vol=None, smooth: bool = True):
+    # --------------------------------------------------------------------------------------------- pose refinement
+    def _ids(self):
+        return self._pose["ids"] if self._pose_on else None
+
+    def _src_rows(self):
+        return self._pose["src_rows"] if (self._pose_on and self.active) else None
+
+    def _check_pose_refinement(self):
+        """The refusals, before anything is launched."""
+        mp, tr = self.config['mapping'], self.config['training']
+        rot_rep = tr.get('rot_rep', 'axis_angle')
+        if rot_rep != 'axis_angle':
+            raise NotImplementedError(f"FusedBA refines axis-angle poses: training.rot_rep = {rot_rep!r} is not implemented")
+        if self.trainer.group is not None:
+            raise NotImplementedError("FusedBA(optimize_poses=True): pose gradients are not all-reduced across data-parallel ranks")
+        if self.active and self.one_launch_prologue:
+            raise NotImplementedError("FusedBA(optimize_poses=True) with one_launch_prologue=True: naruto_assemble_select never writes the oversampled "
+                                      "batch the pose ids follow; use the two-launch prologue (the default)")
+        if int(mp.get('map_accum_step', 1)) != 1 or int(mp.get('map_wait_step', 0)) != 0:
+            raise NotImplementedError("FusedBA(optimize_poses=True): mapping.map_accum_step must be 1 and mapping.map_wait_step 0")
+        if int(mp.get('pose_accum_step', 5)) <= 0:
+            raise ValueError("mapping.pose_accum_step must be positive")
+
+    def _pose_buffers(self):
+        if self._pose is None:
+            dev, n = self.device, self.poses.shape[0]
+            f32 = dict(dtype=torch.float32, device=dev)
+            mp = self.config['mapping']
+            accum = max(int(mp.get('pose_accum_step', 5)), 1)
+            max_trace = max(-(-int(mp['iters']) // accum), 1)
+            self._pose = {"pose_init": torch.zeros(n, 6, **f32), "pose6": torch.zeros(n, 6, **f32), "exp_avg": torch.zeros(n, 6, **f32),
+                          "exp_avg_sq": torch.zeros(n, 6, **f32), "accum": torch.zeros(n, 12, dtype=torch.float64, device=dev),
+                          "state": torch.zeros(4, dtype=torch.int32, device=dev), "trace_pose": torch.zeros(max_trace, n, 6, **f32),
+                          "trace_grad": torch.zeros(max_trace, n, 6, **f32), "max_trace": max_trace}
+        return self._pose
+
+    def _build_bap(self, n_cur: int, n_train: int):
+        """The NarutoBAPoses of this shape (ids / source rows / ray-gradient buffers are per shape, the per-pose buffers are not)."""
+        pb = self._pose_buffers()
+        dev = self.device
+        mp, tr = self.config['mapping'], self.config['training']
+        n_stage = self.sample_num + n_cur
+        S = int(tr['n_samples_d']) + int(tr['n_range_d'])
+        lib = _lib.load()
+        pb["ids"] = torch.zeros(n_stage, dtype=torch.int64, device=dev)
+        pb["src_rows"] = torch.zeros(n_train, dtype=torch.int32, device=dev) if self.active else None
+        pb["d_rays_o"], pb["d_rays_d"] = torch.zeros(n_train, 3, device=dev), torch.zeros(n_train, 3, device=dev)
+        pb["ws"] = torch.zeros((lib.naruto_ba_poses_workspace(self.trainer.model._handle().ptr, n_train, S) + 3) // 4, device=dev)
+        b = _lib.NarutoBAPoses()
+        b.max_poses, b.optim_cur, b.pose_accum_step = self.poses.shape[0], 1 if mp.get('optim_cur', True) else 0, int(mp.get('pose_accum_step', 5))
+        b.dyn, b.poses = self.dyn.data_ptr(), self.poses.data_ptr()
+        b.pose_init, b.pose6, b.exp_avg, b.exp_avg_sq = (pb[k].data_ptr() for k in ("pose_init", "pose6", "exp_avg", "exp_avg_sq"))
+        b.accum, b.state = pb["accum"].data_ptr(), pb["state"].data_ptr()
+        b.ids, b.n_ids = pb["ids"].data_ptr(), n_stage
+        b.src_rows = pb["src_rows"].data_ptr() if self.active else None
+        b.d_rays_o, b.d_rays_d = pb["d_rays_o"].data_ptr(), pb["d_rays_d"].data_ptr()
+        b.lr_rot, b.lr_trans, b.beta1, b.beta2, b.eps = float(mp['lr_rot']), float(mp['lr_trans']), 0.9, 0.999, 1e-8
+        b.trace_pose, b.trace_grad, b.max_trace = pb["trace_pose"].data_ptr(), pb["trace_grad"].data_ptr(), pb["max_trace"]
+        b.workspace = pb["ws"].data_ptr()
+        self._bap = b
+
+    def _attach_poses(self, train_step):
+        """Hang the pose refinement on the TrainStep this object's iterations run on (or take it off: a plain call)."""
+        old = self._pose_ts
+        if old is not None and old is not train_step:
+            old.ba_poses = None
+        want = self._bap if self._pose_on else None
+        if train_step.ba_poses is not want:
+            train_step.ba_poses = want
+        self._pose_ts = train_step if want is not None else None
+
+    def _detach_poses(self):
+        ts = getattr(self, "_pose_ts", None)
+        self._pose_ts = None
+        if ts is not None:
+            ts.ba_poses = None
+
+    def refined_poses(self) -> torch.Tensor:
+        """The P poses of the last ``prepare`` / ``global_BA`` as they stand now, [P,4,4] float32 on the device: refined where the call
+        optimised them, the caller's bits otherwise.  The caller writes them back to ``est_c2w_data`` (coslam.py:401-407)."""
+        return self.poses[:self._n_poses].clone()
+
+    def last_pose_trace(self) -> Dict:
+        """The last refining call, read when asked: ``n_steps`` pose steps taken; per step ``pose`` [n_steps,P,6] the (omega, t) BEFORE the
+        step and ``grad`` [n_steps,P,6] the accumulated gradient (fixed poses: their (omega, t) and zeros); ``init_c2w`` [P,4,4] the
+        matrices the call started from (R(omega) for the parameter poses); ``iterations`` of the call so far."""
+        if not self._pose_on or self._pose is None:
+            raise RuntimeError("last_pose_trace: the last call did not optimise poses")
+        pb, P = self._pose, self._n_poses
+        state = pb["state"].cpu()
+        n = min(int(state[0]), pb["max_trace"])
+        return {"n_steps": int(state[0]), "iterations": int(state[1]), "pose": pb["trace_pose"][:n, :P].cpu().clone(),
+                "grad": pb["trace_grad"][:n, :P].cpu().clone(), "init_c2w": self._init_c2w.clone(), "pose6": pb["pose6"][:P].cpu().clone()}
+
+    def prepare(self, current_rays: torch.Tensor, poses_all: torch.Tensor, uncert_vol=None, smooth: bool = True, optimize_poses: Optional[bool] = None):
         """Per ``global_BA`` call: the current frame's rays [H*W,7], all poses [P,4,4] (the current frame's LAST), optionally the
         planner's refreshed uncertainty volume.  One count of the valid-depth pixels is read back (the reference does the same
-        filtering on the host, coslam.py:332-337); everything else is asynchronous."""
+        filtering on the host, coslam.py:332-337); everything else is asynchronous.  ``optimize_poses`` (default: the constructor's):
+        refine the keyframe poses during the call (module docstring); the matrices are converted to (omega, t) on the host."""
         dev = self.device
+        if _PARKED_GRAPHS and not torch.cuda.is_current_stream_capturing():
+            del _PARKED_GRAPHS[:]
+        want_poses = self.optimize_poses if optimize_poses is None else bool(optimize_poses)
+        if want_poses:
+            self._check_pose_refinement()
         cur = current_rays.to(dev, torch.float32).reshape(-1, 7)
         assert cur.shape[0] == self.current.shape[0], "current_rays: one row per pixel of the frame the store was built for"
         self.current.copy_(cur, non_blocking=True)
@@ -178,6 +349,13 @@ class FusedBA:
         self.poses[:P].copy_(poses_all.to(dev, torch.float32), non_blocking=True)
         n_kf = len(self.store)
         assert n_kf > 0, "no keyframe stored yet"
+        self._n_poses = P
+        pose_on = bool(want_poses and n_kf >= 2 and P >= 2)            # coslam.py:264
+        if pose_on:
+            # (omega, t) of every pose, fp64 on the host, through pinned memory (the caching host allocator keeps the block until the copy ran)
+            from .tracking import matrices_to_pose6
+            host6 = matrices_to_pose6(poses_all).float().pin_memory()
+            self._pose_buffers()["pose_init"][:P].copy_(host6, non_blocking=True)
         n_valid = cur.shape[0]
         if self.filter_depth:
             n_valid = int(((cur[:, -1] > 0.0) & (cur[:, -1] <= self.config["cam"]["depth_trunc"])).sum().item())
@@ -198,7 +376,11 @@ class FusedBA:
             vol_moved = self._vol_ptr is not None and vol.data_ptr() != self._vol_ptr      # a new tensor (other shape): the captured launch reads the old one
             self._vol_ptr = vol.data_ptr()
         n_cur, n_train = self.sizes(n_kf, n_valid)
-        if self._shape != (n_cur, n_train, smooth) or (vol_moved and (self.use_graph or self.keyed)):
+        if self._shape != (n_cur, n_train, smooth, pose_on) or (vol_moved and (self.use_graph or self.keyed)):
+            self._detach_poses()
+            self._pose_on = pose_on
+            if pose_on:
+                self._build_bap(n_cur, n_train)
             f32 = dict(dtype=torch.float32, device=dev)
             n_stage = self.sample_num + n_cur
             if self.active:
@@ -209,21 +391,33 @@ class FusedBA:
             self._pro_later = self._later_prologue(n_cur) if self.prefetch else self._pro
             if self.use_graph:
                 chain = [(i + 1) % 5 == 0 for i in range(int(self.config['mapping']['iters']))] if self.call_graph else None
-                if self.prefetch:
-                    self.trainer.capture(n_train, smooth=smooth, prologue=self._pro_later, first_prologue=self._pro, chain=chain,
-                                         on_buffers=lambda ro, rd, tc, td, ts: self._arm_prefetch(n_cur, (ro, rd, tc, td), ts))
-                else:
-                    self.trainer.capture(n_train, smooth=smooth, prologue=self._pro, chain=chain)
+                with _no_collection():
+                    if self.prefetch:
+                        self.trainer.capture(n_train, smooth=smooth, prologue=self._pro_later, first_prologue=self._pro, chain=chain,
+                                             on_buffers=lambda ro, rd, tc, td, ts: (self._arm_prefetch(n_cur, (ro, rd, tc, td), ts), self._attach_poses(ts)))
+                    else:
+                        self.trainer.capture(n_train, smooth=smooth, prologue=self._pro, chain=chain,
+                                             on_buffers=lambda ro, rd, tc, td, ts: self._attach_poses(ts))
             else:
                 f = torch.zeros(n_train * 10, **f32)
                 from .trainer import unpack_rays
                 self._eager_bufs = unpack_rays(f, n_train)
                 self.trainer._graphs = None
                 self._disarm_prefetch()
+                tr_cfg = self.config['training']
+                ts0 = self.trainer._train_step(n_train, bool(smooth and tr_cfg['smooth_weight'] > 0))
                 if self.prefetch:
-                    tr_cfg = self.config['training']
-                    self._arm_prefetch(n_cur, self._eager_bufs, self.trainer._train_step(n_train, bool(smooth and tr_cfg['smooth_weight'] > 0)))
-            self._shape = (n_cur, n_train, smooth)
+                    self._arm_prefetch(n_cur, self._eager_bufs, ts0)
+                self._attach_poses(ts0)
+            self._shape = (n_cur, n_train, smooth, pose_on)
+        if pose_on:
+            # the call's reset: (omega, t) <- the upload, moments / sums / counts zeroed, the parameter poses' matrices from R(omega) -- after
+            # a capture's warm-up iterations (they step the poses like any other iteration) and in front of the call's first assembly
+            import ctypes as C
+            from .ops import _on_device, _stream
+            with _on_device(dev):
+                _lib.check(_lib.load().naruto_ba_poses_init(C.byref(self._bap), _stream()), "naruto_ba_poses_init")
+            self._init_c2w = self.poses[:P].clone()
         return n_cur, n_train
 
     def iteration(self, i: int, smooth: bool = True):
@@ -235,6 +429,9 @@ class FusedBA:
             return tr.step(*bufs, smooth=smooth, uncert_step=(i + 1) % 5 == 0, first=(i == 0))           # the replay starts with the prologue's launches
         bufs = self._eager_bufs
         full = i == 0 or not self.prefetch
+        if self._pose_on or self._pose_ts is not None:
+            tr_cfg = self.config['training']
+            self._attach_poses(tr._train_step(bufs[0].shape[0], bool(smooth and tr_cfg['smooth_weight'] > 0)))
         if self.prefetch:
             # the TrainStep this iteration WILL run on (the trainer's cache is keyed on (n_rays, smooth, n_rays_total) and evicts): if it is not
             # the one whose finishing launch draws the batches, nothing drew this iteration's batch and nothing would draw the next one --
@@ -249,10 +446,12 @@ class FusedBA:
             pro(*bufs)
         return tr.step(*bufs, smooth=smooth, uncert_step=(i + 1) % 5 == 0)
 
-    def global_BA(self, current_rays: torch.Tensor, poses_all: torch.Tensor, n_iters: Optional[int] = None, uncert_vol=None, smooth: bool = True):
-        """The optimisation loop of one ``global_BA`` call (coslam.py:293-399 without pose optimisation: tracking is off in every
-        shipped config)."""
-        self.prepare(current_rays, poses_all, uncert_vol, smooth)
+    def global_BA(self, current_rays: torch.Tensor, poses_all: torch.Tensor, n_iters: Optional[int] = None, uncert_vol=None, smooth: bool = True,
+                  optimize_poses: Optional[bool] = None):
+        """The optimisation loop of one ``global_BA`` call (coslam.py:293-399).  ``optimize_poses`` (default: the constructor's, which
+        follows ``tracking.disable``; off in every shipped config): refine the keyframe poses during the call as the reference's pose
+        optimiser does (module docstring); read them with ``refined_poses()`` afterwards."""
+        self.prepare(current_rays, poses_all, uncert_vol, smooth, optimize_poses)
         return self.call_iterations(n_iters, smooth)
 
     def call_iterations(self, n_iters: Optional[int] = None, smooth: bool = True):

@@ -19,6 +19,7 @@
 #include "naruto_parts.hip"
 #include "naruto_pointgrad.hip"
 #include "naruto_track.hip"
+#include "naruto_bapose.hip"
 
 using namespace naruto;
 
@@ -1456,9 +1457,26 @@ int loss_bwd_compact(const NarutoField* f, const NarutoTrainStep* t, const Train
 }
 }  // namespace
 
+namespace {
+int ba_poses_check(const NarutoBAPoses* b, const NarutoTrainStep* t, bool backward, const char* who);
+int ba_poses_launch(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const NarutoBAPoses* b, hipStream_t st);
+}  // namespace
+
 int naruto_train_backward(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t_in, const NarutoGrads* g, uint32_t flags,
                           const NarutoFusedAdam* opt, void* stream) {
+    return naruto_train_backward_poses(f, p, t_in, g, flags, opt, nullptr, stream);
+}
+
+// naruto_train_backward's body; bap != NULL: the iteration's pose gradients and the pose step ride between the loss backward and the
+// launches that scatter and step the network (see naruto_bapose.hip)
+int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t_in, const NarutoGrads* g, uint32_t flags,
+                                const NarutoFusedAdam* opt, const NarutoBAPoses* bap, void* stream) {
     if (int rc = train_check(f, p, t_in, "train_backward")) return rc;
+    if (bap != nullptr) {
+        if (flags & (NARUTO_TRAIN_BWD_MLP_ONLY | NARUTO_TRAIN_BWD_TABLE_ONLY | NARUTO_TRAIN_BWD_SUMS_GIVEN))
+            return fail(NARUTO_ERR_INVALID, "train_backward_poses: pose refinement belongs to the one-piece single-process backward");
+        if (int rc = ba_poses_check(bap, t_in, true, "train_backward_poses")) return rc;
+    }
     // loss weights given as separate device scalars: gather them (+ the vector, if any) into the workspace first
     NarutoTrainStep t_local;
     const NarutoTrainStep* t = t_in;
@@ -1550,6 +1568,11 @@ int naruto_train_backward(const NarutoField* f, const NarutoParams* p, const Nar
     const BwdWs bw = bwd_ws(f, w.bwd, list_cap(M + w.n3));
     if (!table_only && !deferred) {
         if (int rc = loss_bwd_compact(f, t, w, la, n_front, bw.n_total, st)) return rc;
+    }
+    // pose refinement: d_raw and the active list are there, the parameters are still the ones the forward used, and the launch that
+    // assembles the next batch (below) comes after the pose step
+    if (bap != nullptr) {
+        if (int rc = ba_poses_launch(f, p, t, bap, st)) return rc;
     }
     NarutoPoints pts{};
     pts.rays_o = t->rays_o; pts.rays_d = t->rays_d; pts.z_vals = t->z_vals; pts.n_samples = S;
@@ -1743,6 +1766,13 @@ size_t naruto_active_ray_workspace(uint32_t n_total, uint32_t K) { return ((size
 int naruto_active_ray_select(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o, const float* rays_d, const float* target_s,
                              const float* target_d, const float* uncert_vol, const uint32_t* vol_dims, const float* bbox_min, float voxel_scale,
                              float* out_o, float* out_d, float* out_s, float* out_t, void* workspace, void* stream) {
+    return naruto_active_ray_select_rows(n_total, base, K, n_tail, rays_o, rays_d, target_s, target_d, uncert_vol, vol_dims, bbox_min, voxel_scale, out_o, out_d,
+                                         out_s, out_t, nullptr, workspace, stream);
+}
+
+int naruto_active_ray_select_rows(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o, const float* rays_d, const float* target_s,
+                                  const float* target_d, const float* uncert_vol, const uint32_t* vol_dims, const float* bbox_min, float voxel_scale,
+                                  float* out_o, float* out_d, float* out_s, float* out_t, uint32_t* src_rows, void* workspace, void* stream) {
     if (rays_o == nullptr || rays_d == nullptr || target_s == nullptr || target_d == nullptr || uncert_vol == nullptr || vol_dims == nullptr ||
         bbox_min == nullptr || out_o == nullptr || out_d == nullptr || out_s == nullptr || out_t == nullptr || workspace == nullptr)
         return fail(NARUTO_ERR_INVALID, "active_ray_select: NULL argument");
@@ -1758,7 +1788,7 @@ int naruto_active_ray_select(uint32_t n_total, uint32_t base, uint32_t K, uint32
         a.rays_o = rays_o; a.rays_d = rays_d; a.target_s = target_s; a.target_d = target_d; a.vol = uncert_vol;
         a.X = (int)vol_dims[0]; a.Y = (int)vol_dims[1]; a.Z = (int)vol_dims[2];
         a.bx = bbox_min[0]; a.by = bbox_min[1]; a.bz = bbox_min[2]; a.voxel_scale = voxel_scale;
-        a.o_out = out_o; a.d_out = out_d; a.s_out = out_s; a.t_out = out_t;
+        a.o_out = out_o; a.d_out = out_d; a.s_out = out_s; a.t_out = out_t; a.src_out = src_rows;
         const uint32_t n_copy = base + n_tail - K;
         hipLaunchKernelGGL(k_ars_fused<false>, dim3(1u + (n_copy + kArsFusedThreads - 1u) / kArsFusedThreads), dim3(kArsFusedThreads), 0, (hipStream_t)stream, a, AssembleArgs{});
         return check_launch("ars_fused");
@@ -1773,12 +1803,18 @@ int naruto_active_ray_select(uint32_t n_total, uint32_t base, uint32_t K, uint32
     if (int rc = check_launch("ars_select")) return rc;
     const uint32_t n_out = base + n_tail;
     hipLaunchKernelGGL(k_ars_gather, dim3((n_out + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, n_out, K, base, n_total, n_tail, sel, rays_o, rays_d,
-                       target_s, target_d, out_o, out_d, out_s, out_t);
+                       target_s, target_d, out_o, out_d, out_s, out_t, src_rows);
     return check_launch("ars_gather");
 }
 
 int naruto_active_ray_select_keyed(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o, const float* rays_d, const float* target_s,
                                    const float* target_d, const uint32_t* keys, float* out_o, float* out_d, float* out_s, float* out_t, void* stream) {
+    return naruto_active_ray_select_keyed_rows(n_total, base, K, n_tail, rays_o, rays_d, target_s, target_d, keys, out_o, out_d, out_s, out_t, nullptr, stream);
+}
+
+int naruto_active_ray_select_keyed_rows(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o, const float* rays_d,
+                                        const float* target_s, const float* target_d, const uint32_t* keys, float* out_o, float* out_d, float* out_s,
+                                        float* out_t, uint32_t* src_rows, void* stream) {
     if (rays_o == nullptr || rays_d == nullptr || target_s == nullptr || target_d == nullptr || keys == nullptr || out_o == nullptr || out_d == nullptr ||
         out_s == nullptr || out_t == nullptr)
         return fail(NARUTO_ERR_INVALID, "active_ray_select_keyed: NULL argument");
@@ -1790,7 +1826,7 @@ int naruto_active_ray_select_keyed(uint32_t n_total, uint32_t base, uint32_t K, 
     ArsArgs a{};
     a.n_total = n_total; a.base = base; a.K = K; a.n_tail = n_tail; a.n_cand = n_cand;
     a.rays_o = rays_o; a.rays_d = rays_d; a.target_s = target_s; a.target_d = target_d; a.keys = keys;
-    a.o_out = out_o; a.d_out = out_d; a.s_out = out_s; a.t_out = out_t;
+    a.o_out = out_o; a.d_out = out_d; a.s_out = out_s; a.t_out = out_t; a.src_out = src_rows;
     const uint32_t n_copy = base + n_tail - K;
     hipLaunchKernelGGL(k_ars_fused<false>, dim3(1u + (n_copy + kArsFusedThreads - 1u) / kArsFusedThreads), dim3(kArsFusedThreads), 0, (hipStream_t)stream, a, AssembleArgs{});
     return check_launch("ars_fused (keyed)");
@@ -2174,6 +2210,127 @@ int naruto_track_backward(const NarutoField* f, const NarutoParams* p, const Nar
     if (int rc = check_launch("ray_point_reduce")) return rc;
     hipLaunchKernelGGL(k_track_step, dim3(1), dim3(kTrackStepThreads), 0, st, track_args(k, t));
     return check_launch("track_step");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pose refinement inside global_BA (see naruto_bapose.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+int ba_poses_check(const NarutoBAPoses* b, const NarutoTrainStep* t, bool backward, const char* who) {
+    if (b == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL NarutoBAPoses", who);
+    if (b->max_poses < 2u) return fail(NARUTO_ERR_INVALID, "%s: NarutoBAPoses.max_poses = %u (pose refinement needs at least 2 poses)", who, b->max_poses);
+    if (b->pose_accum_step == 0u) return fail(NARUTO_ERR_INVALID, "%s: NarutoBAPoses.pose_accum_step must be positive", who);
+    if (b->dyn == nullptr || b->poses == nullptr || b->pose_init == nullptr || b->pose6 == nullptr || b->exp_avg == nullptr || b->exp_avg_sq == nullptr ||
+        b->accum == nullptr || b->state == nullptr)
+        return fail(NARUTO_ERR_INVALID, "%s: NULL buffer in NarutoBAPoses", who);
+    const bool any_trace = b->trace_pose != nullptr || b->trace_grad != nullptr || b->max_trace != 0;
+    const bool all_trace = b->trace_pose != nullptr && b->trace_grad != nullptr && b->max_trace != 0;
+    if (any_trace && !all_trace) return fail(NARUTO_ERR_INVALID, "%s: the trace needs trace_pose, trace_grad and max_trace together", who);
+    if (!(b->lr_rot >= 0.0f) || !(b->lr_trans >= 0.0f) || !(b->beta1 >= 0.0f && b->beta1 < 1.0f) || !(b->beta2 >= 0.0f && b->beta2 < 1.0f) || !(b->eps >= 0.0f))
+        return fail(NARUTO_ERR_INVALID, "%s: Adam needs lr >= 0, 0 <= betas < 1 and eps >= 0", who);
+    if (!backward) return NARUTO_OK;
+    if (b->ids == nullptr || b->d_rays_o == nullptr || b->d_rays_d == nullptr || b->workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "%s: NULL ids / d_rays_o / d_rays_d / workspace in NarutoBAPoses", who);
+    // without src_rows row r of the training batch IS assembled row r
+    if (b->n_ids == 0u || (b->src_rows == nullptr && b->n_ids < t->n_rays))
+        return fail(NARUTO_ERR_INVALID, "%s: NarutoBAPoses.n_ids = %u pose ids for %u rays", who, b->n_ids, t->n_rays);
+    const uint64_t M = (uint64_t)t->n_rays * (t->n_samples_d + t->n_range_d);
+    if (M > (1ull << 29)) return fail(NARUTO_ERR_INVALID, "%s: at most 2^29 samples per iteration (got %llu)", who, (unsigned long long)M);
+    return NARUTO_OK;
+}
+
+BAPoseArgs ba_pose_args(const NarutoBAPoses* b, const NarutoTrainStep* t) {
+    BAPoseArgs a{};
+    a.max_poses = b->max_poses; a.optim_cur = b->optim_cur != 0u ? 1 : 0; a.accum_step = b->pose_accum_step; a.dyn = b->dyn;
+    a.poses = b->poses; a.pose_init = b->pose_init; a.pose6 = b->pose6; a.exp_avg = b->exp_avg; a.exp_avg_sq = b->exp_avg_sq; a.accum = b->accum; a.state = b->state;
+    a.ids = b->ids; a.n_ids = b->n_ids; a.src_rows = b->src_rows;
+    if (t != nullptr) { a.n_rays = t->n_rays; a.rays_d = t->rays_d; }
+    a.d_rays_o = b->d_rays_o; a.d_rays_d = b->d_rays_d;
+    a.lr_rot = b->lr_rot; a.lr_trans = b->lr_trans; a.beta1 = b->beta1; a.beta2 = b->beta2; a.eps = b->eps;
+    a.trace_pose = b->trace_pose; a.trace_grad = b->trace_grad; a.max_trace = b->max_trace;
+    return a;
+}
+
+// after the loss backward and the compaction: naruto_query_bwd_points' launches for ray points over the active list (its zero fill as a
+// kernel: a captured call stays one chain of kernel nodes), the per-pose sums and the pose step
+int ba_poses_launch(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const NarutoBAPoses* b, hipStream_t st) {
+    const uint32_t S = t->n_samples_d + t->n_range_d, M = t->n_rays * S;
+    NarutoPoints pts{};
+    pts.rays_o = t->rays_o; pts.rays_d = t->rays_d; pts.z_vals = t->z_vals; pts.n_samples = S;
+    if (int rc = check_points(&pts)) return rc;
+    float* gp = reinterpret_cast<float*>(b->workspace);
+    const uint64_t n_gp = 3u * (uint64_t)M;
+    hipLaunchKernelGGL(k_track_zero, dim3((uint32_t)((n_gp + 255u) / 256u)), dim3(256), 0, st, gp, n_gp);
+    if (int rc = check_launch("ba_poses: zero")) return rc;
+    hipLaunchKernelGGL(k_query_bwd_points, dim3((M + (uint32_t)kPgThreads - 1u) / (uint32_t)kPgThreads), dim3(kPgThreads), 0, st, f->lt, f->ut, f->bt, make_points(&pts), M,
+                       reinterpret_cast<const float2*>(p->table), p->uncert_grid, p->sdf_w0, p->sdf_w1, p->col_w0, p->col_w1, t->d_raw, nullptr, t->active_idx,
+                       t->n_active, gp, 1, 0);
+    if (int rc = check_launch("ba_poses: query_bwd_points")) return rc;
+    hipLaunchKernelGGL(k_ray_point_reduce, dim3((t->n_rays + 3u) / 4u), dim3(256), 0, st, t->n_rays, S, gp, t->z_vals, b->d_rays_o, b->d_rays_d, 0);
+    if (int rc = check_launch("ba_poses: ray_point_reduce")) return rc;
+    const BAPoseArgs a = ba_pose_args(b, t);
+    hipLaunchKernelGGL(k_ba_pose_accum, dim3(b->max_poses), dim3(kBaPoseThreads), 0, st, a);
+    if (int rc = check_launch("ba_pose_accum")) return rc;
+    hipLaunchKernelGGL(k_ba_pose_step, dim3(1), dim3(kBaPoseThreads), 0, st, a);
+    return check_launch("ba_pose_step");
+}
+}  // namespace
+
+size_t naruto_ba_poses_workspace(const NarutoField* f, uint32_t n_rays, uint32_t n_samples) {
+    const uint64_t M = (uint64_t)n_rays * n_samples;
+    return M > (1ull << 29) ? 0u : naruto_query_bwd_points_workspace(f, (uint32_t)M);
+}
+
+int naruto_ba_poses_init(const NarutoBAPoses* b, void* stream) {
+    if (int rc = ba_poses_check(b, nullptr, false, "ba_poses_init")) return rc;
+    hipLaunchKernelGGL(k_ba_pose_init, dim3((b->max_poses + (uint32_t)kBaPoseThreads - 1u) / (uint32_t)kBaPoseThreads), dim3(kBaPoseThreads), 0, (hipStream_t)stream,
+                       ba_pose_args(b, nullptr));
+    return check_launch("ba_pose_init");
+}
+
+int naruto_debug_ba_poses_check(const NarutoBAPoses* b, uint32_t n_rays) {
+    NarutoTrainStep t{};
+    t.n_rays = n_rays; t.n_samples_d = 1; t.n_range_d = 1;
+    return ba_poses_check(b, &t, true, "debug_ba_poses_check");
+}
+
+int naruto_debug_ba_poses_fields(const NarutoBAPoses* b, uint64_t out[25]) {
+    if (b == nullptr || out == nullptr) return fail(NARUTO_ERR_INVALID, "debug_ba_poses_fields: NULL argument");
+    auto fbits = [](float v) { uint32_t u; memcpy(&u, &v, 4); return (uint64_t)u; };
+    const uint64_t v[25] = {b->max_poses, b->optim_cur, b->pose_accum_step, (uint64_t)(uintptr_t)b->dyn, (uint64_t)(uintptr_t)b->poses, (uint64_t)(uintptr_t)b->pose_init,
+                            (uint64_t)(uintptr_t)b->pose6, (uint64_t)(uintptr_t)b->exp_avg, (uint64_t)(uintptr_t)b->exp_avg_sq, (uint64_t)(uintptr_t)b->accum,
+                            (uint64_t)(uintptr_t)b->state, (uint64_t)(uintptr_t)b->ids, b->n_ids, (uint64_t)(uintptr_t)b->src_rows, (uint64_t)(uintptr_t)b->d_rays_o,
+                            (uint64_t)(uintptr_t)b->d_rays_d, fbits(b->lr_rot), fbits(b->lr_trans), fbits(b->beta1), fbits(b->beta2), fbits(b->eps),
+                            (uint64_t)(uintptr_t)b->trace_pose, (uint64_t)(uintptr_t)b->trace_grad, b->max_trace, (uint64_t)(uintptr_t)b->workspace};
+    for (int i = 0; i < 25; ++i) out[i] = v[i];
+    return NARUTO_OK;
+}
+
+int naruto_debug_pose_adam(float* pose, const float* grad, float* exp_avg, float* exp_avg_sq, int32_t step, float lr_rot, float lr_trans, float beta1, float beta2,
+                           float eps) {
+    if (pose == nullptr || grad == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || step < 1) return fail(NARUTO_ERR_INVALID, "debug_pose_adam: NULL argument or step < 1");
+    pose_adam_step(pose, grad, exp_avg, exp_avg_sq, step, lr_rot, lr_trans, beta1, beta2, eps);
+    return NARUTO_OK;
+}
+
+int naruto_debug_ba_pose_sums(uint32_t n_rays, const int64_t* ids, uint32_t n_ids, const uint32_t* src_rows, uint32_t n_poses, uint32_t pose, const float* rays_d,
+                              const float* d_rays_o, const float* d_rays_d, const float* pose6, double* sums, float* grad) {
+    if (ids == nullptr || rays_d == nullptr || d_rays_o == nullptr || d_rays_d == nullptr || sums == nullptr)
+        return fail(NARUTO_ERR_INVALID, "debug_ba_pose_sums: NULL argument");
+    if (pose >= n_poses) return fail(NARUTO_ERR_INVALID, "debug_ba_pose_sums: pose %u of %u", pose, n_poses);
+    if (grad != nullptr && pose6 == nullptr) return fail(NARUTO_ERR_INVALID, "debug_ba_pose_sums: the gradient needs the pose");
+    // k_ba_pose_accum's order: thread t takes rays t, t + 256, ...; then the tree
+    double red[kBaPoseThreads][12];
+    for (uint32_t tid = 0; tid < (uint32_t)kBaPoseThreads; ++tid) {
+        for (int k = 0; k < 12; ++k) red[tid][k] = 0.0;
+        for (uint32_t r = tid; r < n_rays; r += kBaPoseThreads) ba_row_add(red[tid], pose, n_poses, r, ids, n_ids, src_rows, rays_d, d_rays_o, d_rays_d);
+    }
+    for (uint32_t h = kBaPoseThreads / 2; h > 0; h >>= 1)
+        for (uint32_t tid = 0; tid < h; ++tid)
+            for (int k = 0; k < 12; ++k) red[tid][k] += red[tid + h][k];
+    for (int k = 0; k < 12; ++k) sums[k] += red[0][k];
+    if (grad != nullptr) ba_pose_grad(pose6, sums, grad);
+    return NARUTO_OK;
 }
 
 int naruto_debug_rodrigues(const double* w, const double* G, double* R, double* d_w) {

@@ -350,6 +350,7 @@ struct ArsArgs {
     float bx, by, bz, voxel_scale;
     float *o_out, *d_out, *s_out, *t_out;
     const uint32_t* keys;         // optional [n_cand]: the candidates' keys, already looked up (AssembleArgs.keys_out)
+    uint32_t* src_out;            // optional [base + n_tail]: the input row each output row was taken from (what follows the rays: pose ids)
 };
 constexpr uint32_t kArsFusedThreads = 1024, kArsSelThreads = 256, kArsFusedPer = 32, kArsFusedMax = kArsSelThreads * kArsFusedPer;
 
@@ -381,6 +382,7 @@ __device__ __forceinline__ void ars_copy_row(const ArsArgs& a, const AssembleArg
 #pragma unroll
     for (int c = 0; c < 3; ++c) { a.o_out[3 * r + c] = v[c]; a.d_out[3 * r + c] = v[3 + c]; a.s_out[3 * r + c] = v[6 + c]; }
     a.t_out[r] = v[9];
+    if (a.src_out != nullptr) a.src_out[r] = (uint32_t)src;
 }
 // exclusive scan over the values of the selecting waves (0 .. 3); called by ALL waves of the workgroup (the barriers are the workgroup's),
 // the others pass 0; every thread gets the total too
@@ -566,13 +568,15 @@ template __global__ void k_ars_fused<true>(ArsArgs, AssembleArgs);
 __global__ __launch_bounds__(256) void k_ars_gather(uint32_t n_out, uint32_t K, uint32_t base, uint32_t n_total, uint32_t n_tail,
                                                     const uint32_t* __restrict__ sel, const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                     const float* __restrict__ target_s, const float* __restrict__ target_d, float* __restrict__ o_out,
-                                                    float* __restrict__ d_out, float* __restrict__ s_out, float* __restrict__ t_out) {
+                                                    float* __restrict__ d_out, float* __restrict__ s_out, float* __restrict__ t_out,
+                                                    uint32_t* __restrict__ src_out = nullptr) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_out) return;
     size_t src;
     if (r < K) src = (size_t)sel[r] + base;
     else if (r < base) src = r - K;
     else src = (size_t)n_total - n_tail + (r - base);
+    if (src_out != nullptr) src_out[r] = (uint32_t)src;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         o_out[3 * (size_t)r + c] = rays_o[3 * src + c];

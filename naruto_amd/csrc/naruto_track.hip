@@ -6,77 +6,16 @@
 // k_ray_point_reduce):
 //   k_track_step   ONE workgroup: d_t = sum_r d_rays_o[r], G = sum_r d_rays_d[r] (x) d_cam[r] in a fixed order (no atomics), d_omega as the
 //                  VJP of Rodrigues' formula, the best-pose / wait_iters bookkeeping, one torch.optim.Adam step, and the NEXT iteration's rays.
-// The pose is an absolute axis-angle omega of the camera-to-world rotation plus the translation t; R(omega) = exp([omega]x).
+// The pose is an absolute axis-angle omega of the camera-to-world rotation plus the translation t; R(omega) = exp([omega]x): the pose
+// arithmetic (Rodrigues, its VJP, the Adam step) lives in naruto_pose.h, shared with naruto_bapose.hip.
 #pragma once
 
 #include "naruto_common.h"
+#include "naruto_pose.h"
 
 namespace naruto {
 
 constexpr int kTrackStepThreads = 256;
-
-// A = sin(th)/th, B = (1 - cos(th))/th^2 and a = A'(th)/th, b = B'(th)/th; series below th = 1e-2 (fp64: the closed forms lose
-// ~1e-16 / th^2 there; the truncated series' error is below th^8 / 1e6)
-__host__ __device__ inline void rodrigues_coeffs(double th2, double& A, double& B, double& a, double& b) {
-    if (th2 < 1e-4) {
-        A = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0 * (1.0 - th2 / 42.0));
-        B = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0 * (1.0 - th2 / 56.0));
-        a = -1.0 / 3.0 + th2 / 30.0 - th2 * th2 / 840.0 + th2 * th2 * th2 / 45360.0;
-        b = -1.0 / 12.0 + th2 / 180.0 - th2 * th2 / 6720.0 + th2 * th2 * th2 / 453600.0;
-        return;
-    }
-    const double th = sqrt(th2), s = sin(th), c = cos(th);
-    A = s / th;
-    B = (1.0 - c) / th2;
-    a = (th * c - s) / (th2 * th);
-    b = (th * s - 2.0 * (1.0 - c)) / (th2 * th2);
-}
-
-// R = I + A K + B K^2, K = [w]x (row-major)
-__host__ __device__ inline void rodrigues(const double w[3], double R[9]) {
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    double A, B, a, b;
-    rodrigues_coeffs(th2, A, B, a, b);
-    const double K[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double k2 = 0.0;
-            for (int m = 0; m < 3; ++m) k2 += K[3 * i + m] * K[3 * m + j];
-            R[3 * i + j] = (i == j ? 1.0 : 0.0) + A * K[3 * i + j] + B * k2;
-        }
-}
-
-// d_w = VJP of rodrigues at w with cotangent G (dL/dR, row-major):
-//   dR/dw_k = a w_k K + A K_k + b w_k K^2 + B (K_k K + K K_k),  K_k = [e_k]x
-__host__ __device__ inline void rodrigues_vjp(const double w[3], const double G[9], double d_w[3]) {
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    double A, B, a, b;
-    rodrigues_coeffs(th2, A, B, a, b);
-    const double K[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-    double gK = 0.0, gK2 = 0.0;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double k2 = 0.0;
-            for (int m = 0; m < 3; ++m) k2 += K[3 * i + m] * K[3 * m + j];
-            gK += G[3 * i + j] * K[3 * i + j];
-            gK2 += G[3 * i + j] * k2;
-        }
-    for (int k = 0; k < 3; ++k) {
-        double Kk[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        const int p = (k + 1) % 3, q = (k + 2) % 3;        // [e_k]x: +1 at (q, p), -1 at (p, q)
-        Kk[3 * q + p] = 1.0;
-        Kk[3 * p + q] = -1.0;
-        double gKk = 0.0, gS = 0.0;
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double s = 0.0;
-                for (int m = 0; m < 3; ++m) s += Kk[3 * i + m] * K[3 * m + j] + K[3 * i + m] * Kk[3 * m + j];
-                gKk += G[3 * i + j] * Kk[3 * i + j];
-                gS += G[3 * i + j] * s;
-            }
-        d_w[k] = a * w[k] * gK + A * gKk + b * w[k] * gK2 + B * gS;
-    }
-}
 
 struct TrackArgs {
     uint32_t n_rays;
@@ -105,24 +44,6 @@ __device__ __forceinline__ void track_write_ray(const TrackArgs& a, uint32_t r, 
         a.rays_d[3 * (size_t)r + i] = __fadd_rn(__fadd_rn(__fmul_rn(dx, Rf[3 * i]), __fmul_rn(dy, Rf[3 * i + 1])), __fmul_rn(dz, Rf[3 * i + 2]));
         a.rays_o[3 * (size_t)r + i] = t[i];
     }
-}
-
-__device__ __forceinline__ void track_pose_matrix(const float p[6], float Rf[9]) {
-    const double w[3] = {(double)p[0], (double)p[1], (double)p[2]};
-    double R[9];
-    rodrigues(w, R);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rf[i] = (float)R[i];
-}
-
-__device__ __forceinline__ void track_write_c2w(float* c2w, const float p[6]) {
-    float Rf[9];
-    track_pose_matrix(p, Rf);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        c2w[4 * i] = Rf[3 * i]; c2w[4 * i + 1] = Rf[3 * i + 1]; c2w[4 * i + 2] = Rf[3 * i + 2]; c2w[4 * i + 3] = p[3 + i];
-    }
-    c2w[12] = 0.0f; c2w[13] = 0.0f; c2w[14] = 0.0f; c2w[15] = 1.0f;
 }
 
 // row i of the draw: flat interior index k = perm(i) -> h = edge_h + k % Hi (h fastest, Co-SLAM's order), w = edge_w + k / Hi
@@ -244,23 +165,15 @@ __global__ __launch_bounds__(kTrackStepThreads) void k_track_step(TrackArgs a) {
             if ((uint32_t)thresh > a.wait_iters) {
                 a.state[2] = 1;
             } else {
-                // torch.optim.Adam (single tensor, no weight decay, amsgrad off): moments in fp32, bias corrections in fp64
+                // torch.optim.Adam (pose_adam_step, naruto_pose.h)
                 const int32_t step = a.state[0] + 1;
                 a.state[0] = step;
-                const double bc1 = 1.0 - pow((double)a.beta1, (double)step), bc2 = 1.0 - pow((double)a.beta2, (double)step);
-                const float bc2_sqrt = (float)sqrt(bc2);
+                float m[6], v[6];
 #pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const float lr = k < 3 ? a.lr_rot : a.lr_trans;
-                    const float step_size = (float)((double)lr / bc1);
-                    float m = a.exp_avg[k], v = a.exp_avg_sq[k];
-                    m = fmaf(1.0f - a.beta1, g[k] - m, m);
-                    v = fmaf((1.0f - a.beta2) * g[k], g[k], v * a.beta2);
-                    a.exp_avg[k] = m; a.exp_avg_sq[k] = v;
-                    const float denom = sqrtf(v) / bc2_sqrt + a.eps;
-                    p[k] = p[k] - step_size * (m / denom);
-                    a.pose[k] = p[k];
-                }
+                for (int k = 0; k < 6; ++k) { m[k] = a.exp_avg[k]; v[k] = a.exp_avg_sq[k]; }
+                pose_adam_step(p, g, m, v, step, a.lr_rot, a.lr_trans, a.beta1, a.beta2, a.eps);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) { a.exp_avg[k] = m[k]; a.exp_avg_sq[k] = v[k]; a.pose[k] = p[k]; }
                 float Rf[9];
                 track_pose_matrix(p, Rf);
                 for (int k = 0; k < 9; ++k) s_next[k] = Rf[k];

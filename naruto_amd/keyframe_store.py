@@ -159,7 +159,8 @@ class KeyFrameStoreHIP:
 
     def assemble_batch(self, sample_num: int, current_rays: torch.Tensor, poses_all: torch.Tensor, min_pixels_cur: int,
                        filter_depth: bool = False, return_ids: bool = False, out=None, rng: Optional[torch.Tensor] = None,
-                       dyn: Optional[torch.Tensor] = None, n_cur: Optional[int] = None, n_cur_pop: Optional[int] = None, keys=None):
+                       dyn: Optional[torch.Tensor] = None, n_cur: Optional[int] = None, n_cur_pop: Optional[int] = None, keys=None,
+                       ids_out: Optional[torch.Tensor] = None):
         """coslam.py:310-344 fused: -> rays_o [N,3], rays_d [N,3], target_s [N,3], target_d [N,1], n_cur (and ids_all).
         N = sample_num + n_cur, n_cur = max(sample_num // n_kf, min_pixels_cur) (capped by the valid pixels).
         current_rays [H*W,7]; poses_all [P,4,4] camera-to-world with the current frame's pose LAST (index -1).
@@ -170,7 +171,8 @@ class KeyFrameStoreHIP:
         time; ``n_cur`` / ``n_cur_pop`` then fix the current-frame draw's size and population up front (no device read-back; with
         ``filter_depth`` in the reference's mode the population is the number of valid-depth pixels, counted by the caller).
         ``keys``: ``ActiveRaySamplerHIP.key_lookup(...)`` -- the active ray sampler's candidate keys are looked up here, while the rows are
-        in registers, for ``sample_rays(..., keys=...)``."""
+        in registers, for ``sample_rays(..., keys=...)``.  ``ids_out`` (int64 [N], device): the pose index of every row is written there
+        (-1 for current-frame rows), as ``return_ids`` returns it, without an allocation."""
         lib = _lib.load()
         b, n_cur, keep = self._draw(sample_num, current_rays, poses_all, min_pixels_cur, filter_depth, rng, dyn, n_cur, n_cur_pop)
         n = sample_num + n_cur
@@ -183,7 +185,9 @@ class KeyFrameStoreHIP:
         else:
             rays_o, rays_d, target_s = torch.empty(n, 3, **f32), torch.empty(n, 3, **f32), torch.empty(n, 3, **f32)
             target_d = torch.empty(n, 1, **f32)
-        ids = torch.empty(n, dtype=torch.int64, device=self.device) if return_ids else None
+        if ids_out is not None:
+            assert ids_out.is_cuda and ids_out.dtype == torch.int64 and ids_out.is_contiguous() and ids_out.numel() >= n, "ids_out: int64 [N] on the device"
+        ids = ids_out if ids_out is not None else (torch.empty(n, dtype=torch.int64, device=self.device) if return_ids else None)
         b.rays_o, b.rays_d, b.target_s, b.target_d = rays_o.data_ptr(), rays_d.data_ptr(), target_s.data_ptr(), target_d.data_ptr()
         b.ids_out = ids.data_ptr() if ids is not None else None
         self._set_keys(b, keys)
@@ -194,7 +198,7 @@ class KeyFrameStoreHIP:
 
     def next_batch_struct(self, sample_num: int, current_rays: torch.Tensor, poses_all: torch.Tensor, min_pixels_cur: int, out, filter_depth: bool = False,
                           rng: Optional[torch.Tensor] = None, dyn: Optional[torch.Tensor] = None, n_cur: Optional[int] = None, n_cur_pop: Optional[int] = None,
-                          keys=None):
+                          keys=None, ids_out: Optional[torch.Tensor] = None):
         """The ``NarutoRayBatch`` of ``assemble_batch(..., out=out)`` WITHOUT launching anything: for ``NarutoFusedAdam.next_batch`` (the next
         iteration's batch assembled by the launch that finishes this iteration's gradients).  Device-keyed draws only (``rng``).  Returns the
         struct and the tensors it points into (keep both alive as long as the struct is in use)."""
@@ -206,9 +210,11 @@ class KeyFrameStoreHIP:
             if not (a.is_cuda and a.dtype == torch.float32 and a.is_contiguous() and a.numel() == n * c):
                 raise RuntimeError(f"next_batch_struct: out tensors must be contiguous fp32 device tensors of {n} rows")
         b.rays_o, b.rays_d, b.target_s, b.target_d = rays_o.data_ptr(), rays_d.data_ptr(), target_s.data_ptr(), target_d.data_ptr()
-        b.ids_out = None
+        if ids_out is not None:
+            assert ids_out.is_cuda and ids_out.dtype == torch.int64 and ids_out.is_contiguous() and ids_out.numel() >= n, "ids_out: int64 [N] on the device"
+        b.ids_out = ids_out.data_ptr() if ids_out is not None else None
         self._set_keys(b, keys)
-        return b, (keep, out, rng, dyn, keys)
+        return b, (keep, out, rng, dyn, keys, ids_out)
 
     def assemble_select(self, sampler, sample_num: int, current_rays: torch.Tensor, poses_all: torch.Tensor, min_pixels_cur: int, bbox,
                         uncert_vol=None, filter_depth: bool = False, out=None, rng: Optional[torch.Tensor] = None,

@@ -829,6 +829,7 @@ class TrainStep:
         self._zero_table = not handle_supports_overwrite(handle)
         self.opt = None                      # NarutoFusedAdam: set by fuse_adam()
         self._gs_nograd = None
+        self.ba_poses = None                 # NarutoBAPoses: set by naruto_amd.ba_loop.FusedBA while it refines poses (naruto_train_backward_poses)
 
     def fuse_adam(self, entries: Dict[str, tuple], betas, step_dev: torch.Tensor, write_grads: bool = False):
         """Optimiser in the backward (single process): ``entries[name] = (exp_avg, exp_avg_sq, lr, eps, weight_decay)`` for the
@@ -867,6 +868,13 @@ class TrainStep:
             t.rand = self.rand.data_ptr() if self.perturb else None
             t.rand6 = self.rand[M:].data_ptr() if t.smooth_points else None
             t.rng = None
+
+    def explicit_jitter(self, on: bool):
+        """Depth jitter from ``self.rand[:N*S]`` (the caller writes it before every forward) while the device-side {seed, counter} word
+        keeps keying everything else and keeps advancing: what a test needs to hand the same jitter to a reference.  ``False``: back
+        to the kernels' own draw."""
+        assert self.device_rng, "explicit_jitter belongs to TrainStep(device_rng=True)"
+        self.t.rand = self.rand.data_ptr() if (on and self.perturb) else None
 
     def run(self, rays_o, rays_d, target_rgb, target_d, rand: Optional[torch.Tensor] = None):
         """One forward + backward.  Afterwards: self.losses[10], self.rgb / depth / uncert_map, gradients in self.grads.
@@ -930,7 +938,11 @@ class TrainStep:
             if self.group is not None and not given:
                 check(lib.naruto_train_finalize(self.handle.ptr, C.byref(t), st), "naruto_train_finalize")
             fl = self.flags | (_lib.TRAIN_BWD_DEFERRED_TAIL if _deferred_tail else 0) | given
-            if self.opt is not None:
+            if self.ba_poses is not None:
+                assert self.opt is not None, "pose refinement rides in the backward of the fused optimiser"
+                check(lib.naruto_train_backward_poses(self.handle.ptr, C.byref(self.ps), C.byref(t), C.byref(self._gs_nograd), fl, C.byref(self.opt),
+                                                      C.byref(self.ba_poses), st), "naruto_train_backward_poses")
+            elif self.opt is not None:
                 check(lib.naruto_train_backward(self.handle.ptr, C.byref(self.ps), C.byref(t), C.byref(self._gs_nograd), fl, C.byref(self.opt), st),
                       "naruto_train_backward")
             else:

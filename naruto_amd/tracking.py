@@ -95,6 +95,28 @@ def matrix_to_axis_angle(R: torch.Tensor) -> torch.Tensor:
     return q[1:] * (2.0 * torch.atan2(n, q[0]) / n)
 
 
+def matrices_to_pose6(c2w: torch.Tensor) -> torch.Tensor:
+    """``(matrix_to_axis_angle(R), t)`` of P camera-to-world matrices [P,4,4] at once -> [P,6] fp64 on the CPU: the same branches
+    and formulas as ``matrix_to_axis_angle``, batched (a ``global_BA`` call converts every keyframe pose)."""
+    a = torch.as_tensor(c2w).detach().double().cpu().reshape(-1, 4, 4)
+    R = a[:, :3, :3]
+    d0, d1, d2 = R[:, 0, 0], R[:, 1, 1], R[:, 2, 2]
+    cand = torch.stack([1 + d0 + d1 + d2, 1 + d0 - d1 - d2, 1 - d0 + d1 - d2, 1 - d0 - d1 + d2], 1)
+    k = cand.argmax(1)
+    s = 2.0 * torch.sqrt(cand.gather(1, k[:, None])[:, 0].clamp_min(1e-300))
+    x, y, z = R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]
+    xy, xz, yz = R[:, 0, 1] + R[:, 1, 0], R[:, 0, 2] + R[:, 2, 0], R[:, 1, 2] + R[:, 2, 1]
+    q4 = s / 4
+    branches = torch.stack([torch.stack([q4, x / s, y / s, z / s], 1), torch.stack([x / s, q4, xy / s, xz / s], 1),
+                            torch.stack([y / s, xy / s, q4, yz / s], 1), torch.stack([z / s, xz / s, yz / s, q4], 1)], 1)      # [P,4 branches,4]
+    q = branches[torch.arange(a.shape[0]), k]
+    q = torch.where(q[:, :1] < 0, -q, q)                       # w >= 0: angle in [0, pi]
+    n = q[:, 1:].norm(dim=1)
+    small = n < 1e-12
+    scale = torch.where(small, 2.0 / q[:, 0], 2.0 * torch.atan2(n, q[:, 0]) / torch.where(small, torch.ones_like(n), n))
+    return torch.cat([q[:, 1:] * scale[:, None], a[:, :3, 3]], 1)
+
+
 def axis_angle_to_matrix(w: torch.Tensor) -> torch.Tensor:
     """Rodrigues' formula for w [3]: R = I + sin(th)/th K + (1 - cos(th))/th^2 K^2, K = [w]x (the kernels' R(omega)); differentiable."""
     th2 = (w * w).sum()
