@@ -433,6 +433,82 @@ int naruto_mesh_emit(const uint32_t* dims, const float* sdf_vol, double isolevel
                      uint64_t cap_vertices, uint64_t cap_triangles, double* vertices, int32_t* triangles,
                      void* stream);
 
+/* The planner's local RRT (reference src/planner/rrt.py and src/planner/rrt_naruto.py: class RRTNaruto, the
+ * local_planner_method of every shipped config), on the volumes of naruto_map_volumes.  Unit: voxel.
+ *
+ * NarutoRrtPlan (HOST struct) describes one planner and its caller-owned device buffers:
+ *   dims            {X,Y,Z} of sdf_vol
+ *   range           x/y/z_range of RRT.__init__ (rrt.py:205-208), full_range full_x/y/z_range (:209-211): the box the rows
+ *                   handed to naruto_rrt_grow are drawn from in mode RUN / FULL.  The library draws nothing; it checks lo <= hi.
+ *   step_size, step_amplifier, collision_thre, enable_direct_line: the constructor arguments (rrt_naruto.py:37-50)
+ *   sdf_vol         DEVICE float32 [X,Y,Z], z fastest
+ *   workspace       DEVICE, naruto_rrt_workspace bytes, 16-byte aligned.  It opens with the state block int32[16] (indices
+ *                   NARUTO_RRT_STATE_*) the caller reads back after a launch, then the goal and the per-voxel cell lists' heads.
+ *   nodes_xyz       DEVICE float64 [capacity,3]  the reference's Node._xyz_arr
+ *   nodes_xyz32     DEVICE float32 [capacity,3]  its nodes_tensor (rrt.py:144: the float64 coordinates rounded)
+ *   parent, next    DEVICE int32 [capacity]      parent node (-1: the start) / next node of the same cell list (-1: end)
+ *   capacity        entries of the four tree buffers; cell_threshold: node count from which the nearest-node search walks the
+ *                   cell lists instead of scanning nodes_xyz32 (0: NARUTO_RRT_CELL_THRESHOLD).  Both give the same tree.
+ * The tree lives in the caller's buffers, so a second naruto_rrt_grow continues it, as a second RRTNaruto.run() does.
+ *
+ * naruto_rrt_start (rrt.py:248-277 start_new_plan): tree = {start}, goal stored, counters zero.  start, goal: HOST fp64[3].
+ * naruto_rrt_grow: mode NARUTO_RRT_MODE_RUN = RRTNaruto.run() (rrt_naruto.py:189-234): per iteration the direct line
+ *   goal -> last node first (:92-133, if enable_direct_line), else / then the random extension (:135-187), early exit
+ *   when a new node is within step_size of the goal in float32, and afterwards goal.parent = nearest node, reachable iff its
+ *   fp64 distance <= step_size.  NARUTO_RRT_MODE_FULL = RRT.run_full() (rrt.py:350-355): max_iter random extensions, no goal
+ *   test.  rows: DEVICE fp64 [n_rows,3], one row per random extension, in order.  max_iter counts from the call with
+ *   restart != 0; a call with restart == 0 resumes the same run()/run_full() where the last launch stopped.  One persistent
+ *   launch of one workgroup; it ends with state[NARUTO_RRT_STATE_STATUS] =
+ *     NARUTO_RRT_DONE       finished (RUN: state GOAL_PARENT / REACHABLE are set),
+ *     NARUTO_RRT_NEED_ROWS  every row used: call again (restart = 0) with fresh rows; state ROWS_USED rows were consumed,
+ *     NARUTO_RRT_NEED_ROOM  the next append would exceed capacity: nothing of that step was consumed; grow the four tree
+ *                           buffers (copy the first state NODES entries) and call again (restart = 0) with the unused rows.
+ *   The tree does not depend on where such a stop fell.
+ * naruto_rrt_path (rrt.py:376-387 find_path) as node indices: path DEVICE int32 [capacity+1], path[0] = count, then
+ *   goal.parent, its parent, ..., the start, so that only the path has to be copied back.
+ * naruto_segments_free (rrt.py:77-117 is_collision_free, imported at naruto_planner.py:34, called at :556) for n segments:
+ *   pa, pb DEVICE fp64 [n,3]; num_collision_free DEVICE int32 [n], complete_free DEVICE uint8 [n].
+ * naruto_reachable_mask (rrt.py:389-431 get_reachable_mask): mask DEVICE float32 [X,Y,Z] = 1 where some node of the plan's
+ *   tree lies within step_size of the voxel (float32 arithmetic), else 0.
+ * Differences to the reference: a sample outside [0, dim-1] counts as blocked (the reference raises on `None > thre`); at a
+ * coordinate of exactly dim-1 the upper corner has weight 0 and its index is clamped (the reference indexes out of bounds);
+ * a direct line of length 0 (start == goal, where the reference divides by zero) ends the run as reached. */
+#define NARUTO_RRT_MODE_RUN 0
+#define NARUTO_RRT_MODE_FULL 1
+#define NARUTO_RRT_DONE 0
+#define NARUTO_RRT_NEED_ROWS 1
+#define NARUTO_RRT_NEED_ROOM 2
+#define NARUTO_RRT_CELL_THRESHOLD 2048u
+#define NARUTO_RRT_STATE_NODES 0        /* node count */
+#define NARUTO_RRT_STATE_ITER 1         /* iterations of the current run()/run_full() completed */
+#define NARUTO_RRT_STATE_RRT_ITER 2     /* the reference's rrt_iter (advanced by RUN only) */
+#define NARUTO_RRT_STATE_STATUS 3
+#define NARUTO_RRT_STATE_ROWS_USED 4    /* rows consumed by the last launch */
+#define NARUTO_RRT_STATE_GOAL_PARENT 5  /* goal.parent as a node index, -1 before the first finished RUN */
+#define NARUTO_RRT_STATE_REACHABLE 6
+#define NARUTO_RRT_STATE_MID_ITER 7     /* the direct-line half of iteration ITER is already in the tree (a stop fell after it) */
+#define NARUTO_RRT_STATE_USE_CELLS 9    /* the cell lists are valid (the start lay inside the grid): nearest search and mask may use them;
+                                           clearing it sends naruto_reachable_mask through node tiles instead */
+typedef struct NarutoRrtPlan {
+    uint32_t dims[3];
+    double range[3][2], full_range[3][2];
+    double step_size, step_amplifier, collision_thre;
+    int32_t enable_direct_line;
+    const float* sdf_vol;
+    void* workspace;
+    double* nodes_xyz; float* nodes_xyz32; int32_t* parent; int32_t* next;
+    uint32_t capacity, cell_threshold;
+} NarutoRrtPlan;
+size_t naruto_rrt_workspace(const uint32_t* dims /* HOST {X,Y,Z} */);
+int naruto_rrt_start(const NarutoRrtPlan* plan, const double* start, const double* goal, void* stream);
+int naruto_rrt_grow(const NarutoRrtPlan* plan, int mode, const double* rows, uint32_t n_rows, uint32_t max_iter,
+                    int restart, void* stream);
+int naruto_rrt_path(const NarutoRrtPlan* plan, int32_t* path, void* stream);
+int naruto_segments_free(const uint32_t* dims /* HOST */, const float* sdf_vol, uint32_t n, const double* pa,
+                         const double* pb, double step_size, double collision_thre, int32_t* num_collision_free,
+                         uint8_t* complete_free, void* stream);
+int naruto_reachable_mask(const NarutoRrtPlan* plan, float* mask, void* stream);
+
 /* All parameter tensors of one optimiser in a single launch (<= 8 segments, per-segment lr / eps / weight_decay,
  * shared betas and step). */
 typedef struct NarutoAdamSeg {

@@ -13,7 +13,7 @@ from . import config, synthetic  # noqa: F401
 def __getattr__(name):
     # torch-dependent modules are imported lazily so that `import naruto_amd` stays cheap
     if name in ("ops", "field", "parallel", "trainer", "_lib", "graphed", "ba_loop", "keyframe_store", "active_ray_sampler", "planner_aggregation", "mesh",
-                "tracking"):
+                "tracking", "rrt"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "NarutoFieldHIP":
@@ -28,4 +28,7 @@ def __getattr__(name):
     if name == "TrackerHIP":
         from .tracking import TrackerHIP
         return TrackerHIP
+    if name == "RRTNarutoHIP":
+        from .rrt import RRTNarutoHIP
+        return RRTNarutoHIP
     raise AttributeError(name)

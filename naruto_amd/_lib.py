@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -118,6 +118,21 @@ class NarutoBAPoses(C.Structure):
     ]
 
 
+class NarutoRrtPlan(C.Structure):
+    _fields_ = [("dims", C.c_uint32 * 3), ("range", (C.c_double * 2) * 3), ("full_range", (C.c_double * 2) * 3),
+                ("step_size", C.c_double), ("step_amplifier", C.c_double), ("collision_thre", C.c_double), ("enable_direct_line", C.c_int32),
+                ("sdf_vol", C.c_void_p), ("workspace", C.c_void_p), ("nodes_xyz", C.c_void_p), ("nodes_xyz32", C.c_void_p),
+                ("parent", C.c_void_p), ("next", C.c_void_p), ("capacity", C.c_uint32), ("cell_threshold", C.c_uint32)]
+
+
+RRT_MODE_RUN, RRT_MODE_FULL = 0, 1
+RRT_DONE, RRT_NEED_ROWS, RRT_NEED_ROOM = 0, 1, 2
+RRT_CELL_THRESHOLD = 2048
+RRT_STATE_NODES, RRT_STATE_ITER, RRT_STATE_RRT_ITER, RRT_STATE_STATUS, RRT_STATE_ROWS_USED, RRT_STATE_GOAL_PARENT, RRT_STATE_REACHABLE = range(7)
+RRT_STATE_MID_ITER, RRT_STATE_USE_CELLS = 7, 9
+RRT_STATE_INTS = 16
+
+
 class NarutoRender(C.Structure):
     _fields_ = [("n_rays", C.c_uint32), ("rays_o", C.c_void_p), ("rays_d", C.c_void_p), ("target_d", C.c_void_p),
                 ("near_", C.c_float), ("far_", C.c_float), ("n_samples_d", C.c_uint32), ("n_range_d", C.c_uint32), ("range_d", C.c_float),
@@ -198,6 +213,12 @@ SIGNATURES = {
     "naruto_goal_targets_workspace": (C.c_size_t, [_U32, _U32]),
     "naruto_goal_targets": (_I, [C.POINTER(_U32), _V, _U32, _U32, _V, _V, _V]),
     "naruto_goal_aggregate": (_I, [C.POINTER(_U32), _V, _V, _U32, _V, _U32, _V, _F, _F, _F, _V, _V, _V]),
+    "naruto_rrt_workspace": (C.c_size_t, [C.POINTER(_U32)]),
+    "naruto_rrt_start": (_I, [C.POINTER(NarutoRrtPlan), C.POINTER(C.c_double), C.POINTER(C.c_double), _V]),
+    "naruto_rrt_grow": (_I, [C.POINTER(NarutoRrtPlan), _I, _V, _U32, _U32, _I, _V]),
+    "naruto_rrt_path": (_I, [C.POINTER(NarutoRrtPlan), _V, _V]),
+    "naruto_segments_free": (_I, [C.POINTER(_U32), _V, _U32, _V, _V, C.c_double, C.c_double, _V, _V, _V]),
+    "naruto_reachable_mask": (_I, [C.POINTER(NarutoRrtPlan), _V, _V]),
     "naruto_lattice_points": (_I, [C.POINTER(_U32), _V, _V, _V, _V, _V]),
     "naruto_mesh_workspace": (C.c_size_t, [C.POINTER(_U32)]),
     "naruto_mesh_count": (_I, [C.POINTER(_U32), _V, C.c_double, C.c_double, _V, _V, _V]),

@@ -20,6 +20,7 @@
 #include "naruto_pointgrad.hip"
 #include "naruto_track.hip"
 #include "naruto_bapose.hip"
+#include "naruto_rrt.hip"
 
 using namespace naruto;
 
@@ -1871,6 +1872,107 @@ int naruto_goal_aggregate(const uint32_t* dims, const float* uncert_vol, const f
     hipLaunchKernelGGL(k_goal_aggregate, dim3((n_goals + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d, uncert_vol, sdf_vol, n_goals, goal_idx, n_targets,
                        targets, min_dist, max_dist, safe_sdf, collections, aggregated);
     return check_launch("goal_aggregate");
+}
+
+// ---- the planner's local RRT (naruto_rrt.hip) --------------------------------------------------------------------------
+namespace {
+int rrt_dims(const uint32_t* dims, const char* who, RrtVol* vol, const float* sdf) {
+    if (dims == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL dims", who);
+    const uint64_t n64 = (uint64_t)dims[0] * dims[1] * dims[2];
+    if (n64 == 0 || n64 > (1ull << 28) || dims[0] > (1u << 28) || dims[1] > (1u << 28) || dims[2] > (1u << 28))
+        return fail(NARUTO_ERR_INVALID, "%s: volume must have 1 .. 2^28 voxels", who);
+    *vol = RrtVol{sdf, (int)dims[0], (int)dims[1], (int)dims[2]};
+    return NARUTO_OK;
+}
+int rrt_plan(const NarutoRrtPlan* p, const char* who, RrtVol* vol) {
+    if (p == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL plan", who);
+    if (int rc = rrt_dims(p->dims, who, vol, p->sdf_vol)) return rc;
+    if (p->sdf_vol == nullptr || p->workspace == nullptr || p->nodes_xyz == nullptr || p->nodes_xyz32 == nullptr || p->parent == nullptr || p->next == nullptr)
+        return fail(NARUTO_ERR_INVALID, "%s: NULL buffer in the plan", who);
+    if (p->capacity == 0 || p->capacity > 0x7FFFFFFFu / 3u) return fail(NARUTO_ERR_INVALID, "%s: capacity must be 1 .. %u nodes", who, 0x7FFFFFFFu / 3u);
+    if (!(p->step_size > 0.0) || !(p->step_amplifier > 0.0) || !(p->step_size < 1.0e9) || !(p->step_amplifier < 1.0e9) || !(p->collision_thre == p->collision_thre))
+        return fail(NARUTO_ERR_INVALID, "%s: step_size and step_amplifier must be positive and finite, collision_thre a number", who);
+    for (int a = 0; a < 3; ++a)
+        if (!(p->range[a][0] <= p->range[a][1]) || !(p->full_range[a][0] <= p->full_range[a][1]))
+            return fail(NARUTO_ERR_INVALID, "%s: a sampling range has lo > hi", who);
+    return NARUTO_OK;
+}
+int32_t* rrt_state(const NarutoRrtPlan* p) { return reinterpret_cast<int32_t*>(p->workspace); }
+double* rrt_goal(const NarutoRrtPlan* p) { return reinterpret_cast<double*>(reinterpret_cast<char*>(p->workspace) + kRrtGoalOffset); }
+int32_t* rrt_head(const NarutoRrtPlan* p) { return reinterpret_cast<int32_t*>(reinterpret_cast<char*>(p->workspace) + kRrtHeadOffset); }
+}  // namespace
+
+size_t naruto_rrt_workspace(const uint32_t* dims) {
+    RrtVol vol;
+    if (rrt_dims(dims, "rrt_workspace", &vol, nullptr)) return 0;
+    return (size_t)kRrtHeadOffset + (size_t)vol.X * vol.Y * vol.Z * sizeof(int32_t);
+}
+
+int naruto_rrt_start(const NarutoRrtPlan* plan, const double* start, const double* goal, void* stream) {
+    RrtVol vol;
+    if (int rc = rrt_plan(plan, "rrt_start", &vol)) return rc;
+    if (start == nullptr || goal == nullptr) return fail(NARUTO_ERR_INVALID, "rrt_start: NULL start or goal");
+    bool inside = true;
+    for (int a = 0; a < 3; ++a) {
+        if (!(start[a] == start[a]) || !(goal[a] == goal[a])) return fail(NARUTO_ERR_INVALID, "rrt_start: start or goal is not a number");
+        inside = inside && start[a] >= 0.0 && start[a] <= (double)(plan->dims[a] - 1u);
+    }
+    // the shell search's bound needs every node inside the grid; the nodes lie on segments between the start and in-grid points
+    const uint32_t n = (uint32_t)(vol.X * vol.Y * vol.Z);
+    hipLaunchKernelGGL(k_rrt_start, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, vol, D3{start[0], start[1], start[2]}, D3{goal[0], goal[1], goal[2]},
+                       inside ? 1 : 0, plan->nodes_xyz, plan->nodes_xyz32, plan->parent, plan->next, rrt_head(plan), rrt_state(plan), rrt_goal(plan));
+    return check_launch("rrt_start");
+}
+
+int naruto_rrt_grow(const NarutoRrtPlan* plan, int mode, const double* rows, uint32_t n_rows, uint32_t max_iter, int restart, void* stream) {
+    RrtVol vol;
+    if (int rc = rrt_plan(plan, "rrt_grow", &vol)) return rc;
+    if (mode != NARUTO_RRT_MODE_RUN && mode != NARUTO_RRT_MODE_FULL) return fail(NARUTO_ERR_INVALID, "rrt_grow: unknown mode %d", mode);
+    if (n_rows != 0 && rows == nullptr) return fail(NARUTO_ERR_INVALID, "rrt_grow: NULL rows");
+    if (n_rows > 0x7FFFFFFFu || max_iter > 0x7FFFFFFFu) return fail(NARUTO_ERR_INVALID, "rrt_grow: n_rows and max_iter must fit int32");
+    RrtArgs a;
+    a.vol = vol;
+    a.step = plan->step_size; a.amp = plan->step_amplifier; a.thre = plan->collision_thre;
+    a.direct = plan->enable_direct_line != 0; a.mode = mode; a.restart = restart != 0;
+    a.xyz64 = plan->nodes_xyz; a.xyz32 = plan->nodes_xyz32; a.parent = plan->parent; a.next = plan->next;
+    a.head = rrt_head(plan); a.state = rrt_state(plan); a.goal = rrt_goal(plan);
+    a.rows = rows; a.n_rows = (int)n_rows; a.max_iter = (int)max_iter; a.cap = (int)plan->capacity;
+    a.cell_threshold = (int)(plan->cell_threshold ? std::min(plan->cell_threshold, 0x7FFFFFFFu) : NARUTO_RRT_CELL_THRESHOLD);
+    hipLaunchKernelGGL(k_rrt_grow, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    return check_launch("rrt_grow");
+}
+
+int naruto_segments_free(const uint32_t* dims, const float* sdf_vol, uint32_t n, const double* pa, const double* pb, double step_size, double collision_thre,
+                         int32_t* num_collision_free, uint8_t* complete_free, void* stream) {
+    RrtVol vol;
+    if (int rc = rrt_dims(dims, "segments_free", &vol, sdf_vol)) return rc;
+    if (sdf_vol == nullptr || pa == nullptr || pb == nullptr || num_collision_free == nullptr || complete_free == nullptr)
+        return fail(NARUTO_ERR_INVALID, "segments_free: NULL argument");
+    if (!(step_size > 0.0) || !(step_size < 1.0e9) || !(collision_thre == collision_thre))
+        return fail(NARUTO_ERR_INVALID, "segments_free: step_size must be positive and finite, collision_thre a number");
+    if (n > 0x40000000u) return fail(NARUTO_ERR_INVALID, "segments_free: at most 2^30 segments");
+    if (n == 0) return NARUTO_OK;
+    hipLaunchKernelGGL(k_segments_free, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, vol, n, pa, pb, step_size, collision_thre, num_collision_free,
+                       complete_free);
+    return check_launch("segments_free");
+}
+
+int naruto_rrt_path(const NarutoRrtPlan* plan, int32_t* path, void* stream) {
+    RrtVol vol;
+    if (int rc = rrt_plan(plan, "rrt_path", &vol)) return rc;
+    if (path == nullptr) return fail(NARUTO_ERR_INVALID, "rrt_path: NULL path");
+    hipLaunchKernelGGL(k_rrt_path, dim3(1), dim3(64), 0, (hipStream_t)stream, plan->parent, rrt_state(plan), (int)plan->capacity, path);
+    return check_launch("rrt_path");
+}
+
+int naruto_reachable_mask(const NarutoRrtPlan* plan, float* mask, void* stream) {
+    RrtVol vol;
+    if (int rc = rrt_plan(plan, "reachable_mask", &vol)) return rc;
+    if (mask == nullptr) return fail(NARUTO_ERR_INVALID, "reachable_mask: NULL mask");
+    const uint32_t n = (uint32_t)(vol.X * vol.Y * vol.Z);
+    hipLaunchKernelGGL(k_reachable_mask, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, vol, (float)plan->step_size, plan->nodes_xyz32, rrt_head(plan),
+                       plan->next, rrt_state(plan), mask);
+    return check_launch("reachable_mask");
 }
 
 // ---- N4: dense volume -> mesh (naruto_mesh.hip) ----------------------------------------------------------------------
