@@ -433,6 +433,58 @@ int naruto_mesh_emit(const uint32_t* dims, const float* sdf_vol, double isolevel
                      uint64_t cap_vertices, uint64_t cap_triangles, double* vertices, int32_t* triangles,
                      void* stream);
 
+/* Reconstruction metrics (the reference's evaluation protocol, README "Evaluation": scripts/evaluation/eval_replica.sh:56-83 ->
+ * src/evaluation/eval_recon.py -> third-party calc_3d_mesh_metric, which is not in its tree: 200 000 area-weighted surface samples
+ * per mesh, nearest neighbour each way through scipy's cKDTree, Accuracy = mean rec->gt, Completion = mean gt->rec, Completion
+ * ratio = share of gt->rec below 5 cm).  The chain stays on the device; the contract is restated in the evaluation module of the
+ * Python package.  Counts are uint64 so that a count beyond int32 is an error code instead of a wrapped launch.
+ *
+ * naruto_surface_areas: areas[f] = 0.5 * |e1 x e2| in float64, e1 = v1 - v0, e2 = v2 - v0, cross product component by component
+ *   with every product rounded (no fused multiply-add), norm as sqrt((cx*cx + cy*cy) + cz*cz).  vertices [V,3] float32, or float64
+ *   when vertices_f64 != 0; faces int32 [F,3].  The data is on the device, so a face index outside [0, V) cannot be refused here: it
+ *   is the caller's contract; such a face gets area 0 and is never read through.
+ * naruto_surface_sample: sample s draws three float64 uniforms in [0,1) = (splitmix64(splitmix64(seed) + 3*s + draw) >> 11) * 2^-53;
+ *   face = first index with cum_area[face] >= u0 * cum_area[F-1] (searchsorted, left side; cum_area: the caller's inclusive prefix
+ *   sums of the areas, float64 [F]); (u1, u2) become (|u1 - 1|, |u2 - 1|) when u1 + u2 > 1; point = v0 + (e1*u1 + e2*u2) in float64,
+ *   stored as float32 [count,3]; face_index int32 [count].  A zero-area face is picked only as searchsorted's boundary case: it leads
+ *   the mesh and u0 is exactly 0.
+ * naruto_nn_grid_plan (HOST only, launches nothing): fills grid->n_points, dims, lo, cell for a cloud with bounding box lo .. hi
+ *   (host float64 [3] each).  cell = 0 derives the edge from the cloud: 2 * sqrt(box surface / n_points), or extent / cbrt(n_points)
+ *   for a box without surface, or 1 for a single position.  dims[a] = floor(extent[a] / cell) + 1; while their product exceeds
+ *   max_cells (0 = 2^21) the cell grows by a quarter.
+ * naruto_nn_grid_build: the points (float32 [n,3]) counting-sorted by cell into grid->cell_start (uint32 [cells + 1]) and
+ *   grid->points (16 bytes per point: x, y, z, original index), both caller-owned; workspace: naruto_nn_grid_workspace(grid) bytes,
+ *   free afterwards.  Also used on a QUERY cloud with the target's geometry (cells clamped) to put queries in cell order.
+ * naruto_nn_grid_query: per query the nearest target, dist float64 [n_queries] (Euclidean, d2 = (dx*dx + dy*dy) + dz*dz on float64-
+ *   promoted coordinates, sqrt at the end: bit for bit what scipy's cKDTree.query returns) and index int32 [n_queries] (the original
+ *   index; among equal distances the lowest).  queries float32 [n,3], or queries_sorted = the `points` array of a grid built over the
+ *   queries (results still land at the original query index).  Rings of cells around the query's cell, `ring_budget` of them at
+ *   most; what has not closed by then is served by the scan.  fallback: uint32 [1 + n_queries], [0] = number of such queries afterwards.
+ * naruto_nn_scan: the same result by brute force over targets float32 [m,3], tiled through LDS.
+ * naruto_dist_reduce: out[0] = mean of dist [n], out[1] = number of entries < threshold (device float64 [2]), fixed summation order
+ *   (per-workgroup partials, one finishing pass), no atomics: bitwise reproducible.  workspace: naruto_dist_reduce_workspace(n) bytes. */
+typedef struct NarutoNnGrid {
+    uint64_t n_points;
+    uint32_t dims[3];             /* cells per axis                                              */
+    double   lo[3];               /* lower corner of the cloud's bounding box                    */
+    double   cell;                /* cell edge                                                   */
+    void*    cell_start;          /* DEVICE uint32 [dims[0]*dims[1]*dims[2] + 1]                 */
+    void*    points;              /* DEVICE 16 bytes x n_points                                  */
+} NarutoNnGrid;
+int naruto_surface_areas(uint64_t n_faces, uint64_t n_vertices, const void* vertices, int vertices_f64, const int32_t* faces,
+                         double* areas, void* stream);
+int naruto_surface_sample(uint64_t n_faces, uint64_t n_vertices, const void* vertices, int vertices_f64, const int32_t* faces,
+                          const double* cum_area, uint64_t count, uint64_t seed, float* points, int32_t* face_index, void* stream);
+int naruto_nn_grid_plan(uint64_t n_points, const double* lo, const double* hi, double cell, uint64_t max_cells, NarutoNnGrid* grid);
+size_t naruto_nn_grid_workspace(const NarutoNnGrid* grid);
+int naruto_nn_grid_build(const NarutoNnGrid* grid, const float* points, void* workspace, void* stream);
+int naruto_nn_grid_query(const NarutoNnGrid* grid, uint64_t n_queries, const float* queries, const void* queries_sorted,
+                         uint32_t ring_budget, double* dist, int32_t* index, uint32_t* fallback, void* stream);
+int naruto_nn_scan(uint64_t n_targets, const float* targets, uint64_t n_queries, const float* queries, double* dist, int32_t* index,
+                   void* stream);
+size_t naruto_dist_reduce_workspace(uint64_t n);
+int naruto_dist_reduce(uint64_t n, const double* dist, double threshold, void* workspace, double* out, void* stream);
+
 /* The planner's local RRT (reference src/planner/rrt.py and src/planner/rrt_naruto.py: class RRTNaruto, the
  * local_planner_method of every shipped config), on the volumes of naruto_map_volumes.  Unit: voxel.
  *

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -125,6 +125,11 @@ class NarutoRrtPlan(C.Structure):
                 ("parent", C.c_void_p), ("next", C.c_void_p), ("capacity", C.c_uint32), ("cell_threshold", C.c_uint32)]
 
 
+class NarutoNnGrid(C.Structure):
+    _fields_ = [("n_points", C.c_uint64), ("dims", C.c_uint32 * 3), ("lo", C.c_double * 3), ("cell", C.c_double),
+                ("cell_start", C.c_void_p), ("points", C.c_void_p)]
+
+
 RRT_MODE_RUN, RRT_MODE_FULL = 0, 1
 RRT_DONE, RRT_NEED_ROWS, RRT_NEED_ROOM = 0, 1, 2
 RRT_CELL_THRESHOLD = 2048
@@ -223,6 +228,15 @@ SIGNATURES = {
     "naruto_mesh_workspace": (C.c_size_t, [C.POINTER(_U32)]),
     "naruto_mesh_count": (_I, [C.POINTER(_U32), _V, C.c_double, C.c_double, _V, _V, _V]),
     "naruto_mesh_emit": (_I, [C.POINTER(_U32), _V, C.c_double, _V, _U64, _U64, _V, _V, _V]),
+    "naruto_surface_areas": (_I, [_U64, _U64, _V, _I, _V, _V, _V]),
+    "naruto_surface_sample": (_I, [_U64, _U64, _V, _I, _V, _V, _U64, _U64, _V, _V, _V]),
+    "naruto_nn_grid_plan": (_I, [_U64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, _U64, C.POINTER(NarutoNnGrid)]),
+    "naruto_nn_grid_workspace": (C.c_size_t, [C.POINTER(NarutoNnGrid)]),
+    "naruto_nn_grid_build": (_I, [C.POINTER(NarutoNnGrid), _V, _V, _V]),
+    "naruto_nn_grid_query": (_I, [C.POINTER(NarutoNnGrid), _U64, _V, _V, _U32, _V, _V, _V, _V]),
+    "naruto_nn_scan": (_I, [_U64, _V, _U64, _V, _V, _V, _V]),
+    "naruto_dist_reduce_workspace": (C.c_size_t, [_U64]),
+    "naruto_dist_reduce": (_I, [_U64, _V, C.c_double, _V, _V, _V]),
     "naruto_adam_multi": (_I, [C.POINTER(NarutoAdamSeg), _U32, _F, _F, _U32, _V, _U32, _V]),
     "naruto_train_workspace": (C.c_size_t, [_V, C.POINTER(NarutoTrainStep)]),
     "naruto_train_forward": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), _I, _V]),

@@ -21,6 +21,7 @@
 #include "naruto_track.hip"
 #include "naruto_bapose.hip"
 #include "naruto_rrt.hip"
+#include "naruto_recon.hip"
 
 using namespace naruto;
 
@@ -2048,6 +2049,194 @@ int naruto_mesh_emit(const uint32_t* dims, const float* sdf_vol, double isolevel
     hipLaunchKernelGGL(k_mc_emit, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, d, sdf_vol, w.cases, w.flags, w.prefix, w.block_total, isolevel,
                        cap_vertices, cap_triangles, vertices, triangles);
     return check_launch("mc_emit");
+}
+
+// ---- reconstruction metrics (naruto_recon.hip) ------------------------------------------------------------------------
+namespace {
+constexpr uint64_t kReconMaxCount = 0x7FFFFFFFull;
+constexpr uint64_t kNnGridDefaultCap = 1ull << 21;          // cells: 8 MB of starts; above it the cell edge grows
+size_t recon_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
+uint64_t nn_grid_cells(const NarutoNnGrid* g) { return (uint64_t)g->dims[0] * g->dims[1] * g->dims[2]; }
+int nn_grid_check(const NarutoNnGrid* g, const char* who) {
+    if (g == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL grid", who);
+    if (g->n_points == 0 || g->n_points > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "%s: grid over 1 .. 2^31-1 points", who);
+    const uint64_t cells = nn_grid_cells(g);
+    if (cells == 0 || cells > (1ull << 26) || g->dims[0] > (1u << 26) || g->dims[1] > (1u << 26) || g->dims[2] > (1u << 26))
+        return fail(NARUTO_ERR_INVALID, "%s: grid must have 1 .. 2^26 cells", who);
+    if (!(g->cell > 0.0) || !std::isfinite(g->cell)) return fail(NARUTO_ERR_INVALID, "%s: cell edge must be finite and positive", who);
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(g->lo[a])) return fail(NARUTO_ERR_INVALID, "%s: non-finite box", who);
+    return NARUTO_OK;
+}
+NnGrid nn_grid_args(const NarutoNnGrid* g) {
+    NnGrid a{};
+    a.nx = g->dims[0]; a.ny = g->dims[1]; a.nz = g->dims[2]; a.n = (uint32_t)g->n_points;
+    for (int k = 0; k < 3; ++k) a.lo[k] = g->lo[k];
+    a.h = g->cell;
+    a.inv_h = 1.0 / g->cell;
+    const double ext = g->cell * (double)std::max(g->dims[0], std::max(g->dims[1], g->dims[2]));
+    a.slack = ext * 0x1p-40;
+    a.start = reinterpret_cast<const uint32_t*>(g->cell_start);
+    a.pts = reinterpret_cast<const float4*>(g->points);
+    return a;
+}
+struct NnGridWs { uint32_t* cells; uint32_t* count; uint32_t* block_total; uint32_t n_blocks; };
+NnGridWs nn_grid_ws(const NarutoNnGrid* g, void* workspace) {
+    NnGridWs w;
+    char* p = reinterpret_cast<char*>(workspace);
+    const uint64_t cells = nn_grid_cells(g);
+    w.n_blocks = (uint32_t)((cells + kGridScanItems - 1u) / kGridScanItems);
+    w.cells = reinterpret_cast<uint32_t*>(p); p += recon_align((size_t)g->n_points * 4u);
+    w.count = reinterpret_cast<uint32_t*>(p); p += recon_align((size_t)cells * 4u);
+    w.block_total = reinterpret_cast<uint32_t*>(p);
+    return w;
+}
+int mesh_args_check(uint64_t n_faces, uint64_t n_vertices, const void* vertices, const int32_t* faces, const char* who) {
+    if (n_faces == 0) return fail(NARUTO_ERR_INVALID, "%s: a mesh without faces has no surface to sample", who);
+    if (n_vertices == 0) return fail(NARUTO_ERR_INVALID, "%s: zero vertices", who);
+    if (n_faces > kReconMaxCount || n_vertices > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "%s: counts beyond int32", who);
+    if (vertices == nullptr || faces == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL argument", who);
+    return NARUTO_OK;
+}
+}  // namespace
+
+int naruto_surface_areas(uint64_t n_faces, uint64_t n_vertices, const void* vertices, int vertices_f64, const int32_t* faces, double* areas, void* stream) {
+    if (int rc = mesh_args_check(n_faces, n_vertices, vertices, faces, "surface_areas")) return rc;
+    if (areas == nullptr) return fail(NARUTO_ERR_INVALID, "surface_areas: NULL output");
+    const dim3 grid((uint32_t)((n_faces + kReconThreads - 1u) / kReconThreads)), block(kReconThreads);
+    if (vertices_f64) hipLaunchKernelGGL(k_face_areas<true>, grid, block, 0, (hipStream_t)stream, (uint32_t)n_faces, (uint32_t)n_vertices, vertices, faces, areas);
+    else hipLaunchKernelGGL(k_face_areas<false>, grid, block, 0, (hipStream_t)stream, (uint32_t)n_faces, (uint32_t)n_vertices, vertices, faces, areas);
+    return check_launch("face_areas");
+}
+
+int naruto_surface_sample(uint64_t n_faces, uint64_t n_vertices, const void* vertices, int vertices_f64, const int32_t* faces, const double* cum_area,
+                          uint64_t count, uint64_t seed, float* points, int32_t* face_index, void* stream) {
+    if (int rc = mesh_args_check(n_faces, n_vertices, vertices, faces, "surface_sample")) return rc;
+    if (count > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "surface_sample: counts beyond int32");
+    if (count == 0) return NARUTO_OK;
+    if (cum_area == nullptr || points == nullptr || face_index == nullptr) return fail(NARUTO_ERR_INVALID, "surface_sample: NULL argument");
+    const dim3 grid((uint32_t)((count + kReconThreads - 1u) / kReconThreads)), block(kReconThreads);
+    if (vertices_f64) hipLaunchKernelGGL(k_surface_sample<true>, grid, block, 0, (hipStream_t)stream, (uint32_t)n_faces, (uint32_t)n_vertices, vertices, faces, cum_area, (uint32_t)count, seed, points, face_index);
+    else hipLaunchKernelGGL(k_surface_sample<false>, grid, block, 0, (hipStream_t)stream, (uint32_t)n_faces, (uint32_t)n_vertices, vertices, faces, cum_area, (uint32_t)count, seed, points, face_index);
+    return check_launch("surface_sample");
+}
+
+int naruto_nn_grid_plan(uint64_t n_points, const double* lo, const double* hi, double cell, uint64_t max_cells, NarutoNnGrid* grid) {
+    if (grid == nullptr || lo == nullptr || hi == nullptr) return fail(NARUTO_ERR_INVALID, "nn_grid_plan: NULL argument");
+    if (n_points == 0) return fail(NARUTO_ERR_INVALID, "nn_grid_plan: zero points");
+    if (n_points > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "nn_grid_plan: counts beyond int32");
+    if (!std::isfinite(cell) || cell < 0.0) return fail(NARUTO_ERR_INVALID, "nn_grid_plan: cell edge must be finite and not negative (0 = derive it from the cloud)");
+    if (max_cells == 0) max_cells = kNnGridDefaultCap;
+    if (max_cells > (1ull << 26)) return fail(NARUTO_ERR_INVALID, "nn_grid_plan: at most 2^26 cells");
+    double ext[3], top = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a]) || hi[a] < lo[a]) return fail(NARUTO_ERR_INVALID, "nn_grid_plan: the box must be finite with lo <= hi");
+        ext[a] = hi[a] - lo[a];
+        if (!std::isfinite(ext[a])) return fail(NARUTO_ERR_INVALID, "nn_grid_plan: the box must be finite with lo <= hi");
+        top = std::max(top, ext[a]);
+    }
+    double h = cell;
+    if (h == 0.0) {
+        // the clouds of this path are surface samples: n points spread over an area of the order of the box's own surface, so a cell of edge
+        // 2 * sqrt(box surface / n) holds a handful of them; a box without surface (a line, a point) falls back to extent / cbrt(n), then to 1
+        const double area = 2.0 * (ext[0] * ext[1] + ext[1] * ext[2] + ext[2] * ext[0]);
+        if (area > 0.0) h = 2.0 * std::sqrt(area / (double)n_points);
+        else if (top > 0.0) h = top / std::cbrt((double)n_points);
+        else h = 1.0;
+    }
+    if (!(h > 0.0) || !std::isfinite(h)) h = top > 0.0 ? top : 1.0;
+    double dims[3];
+    for (;;) {
+        double cells = 1.0;
+        for (int a = 0; a < 3; ++a) { dims[a] = std::floor(ext[a] / h) + 1.0; cells *= dims[a]; }
+        if (cells <= (double)max_cells) break;
+        h *= 1.25;                                          // the cap enlarges the cell
+    }
+    grid->n_points = n_points;
+    for (int a = 0; a < 3; ++a) { grid->dims[a] = (uint32_t)dims[a]; grid->lo[a] = lo[a]; }
+    grid->cell = h;
+    return NARUTO_OK;
+}
+
+size_t naruto_nn_grid_workspace(const NarutoNnGrid* grid) {
+    if (nn_grid_check(grid, "nn_grid_workspace")) return 0;
+    const uint64_t cells = nn_grid_cells(grid);
+    const size_t n_blocks = (size_t)((cells + kGridScanItems - 1u) / kGridScanItems);
+    return recon_align((size_t)grid->n_points * 4u) + recon_align((size_t)cells * 4u) + recon_align(n_blocks * 4u);
+}
+
+int naruto_nn_grid_build(const NarutoNnGrid* grid, const float* points, void* workspace, void* stream) {
+    if (int rc = nn_grid_check(grid, "nn_grid_build")) return rc;
+    if (points == nullptr || workspace == nullptr || grid->cell_start == nullptr || grid->points == nullptr) return fail(NARUTO_ERR_INVALID, "nn_grid_build: NULL argument");
+    const NnGrid g = nn_grid_args(grid);
+    const NnGridWs w = nn_grid_ws(grid, workspace);
+    const uint32_t cells = (uint32_t)nn_grid_cells(grid);
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* start = reinterpret_cast<uint32_t*>(grid->cell_start);
+    if (hipMemsetAsync(w.count, 0, (size_t)cells * 4u, st) != hipSuccess) return check_launch("nn_grid_build: memset");
+    const dim3 block(kReconThreads), per_point((g.n + kReconThreads - 1u) / kReconThreads);
+    hipLaunchKernelGGL(k_grid_count, per_point, block, 0, st, g, points, w.cells, w.count);
+    if (int rc = check_launch("grid_count")) return rc;
+    hipLaunchKernelGGL(k_grid_scan_local, dim3(w.n_blocks), block, 0, st, cells, w.count, start, w.block_total);
+    if (int rc = check_launch("grid_scan_local")) return rc;
+    hipLaunchKernelGGL(k_grid_scan_totals, dim3(1), dim3(1024), 0, st, w.n_blocks, w.block_total);
+    if (int rc = check_launch("grid_scan_totals")) return rc;
+    hipLaunchKernelGGL(k_grid_scan_add, dim3(cells / kReconThreads + 1u), block, 0, st, cells, g.n, w.block_total, start, w.count);
+    if (int rc = check_launch("grid_scan_add")) return rc;
+    hipLaunchKernelGGL(k_grid_fill, per_point, block, 0, st, g, points, w.cells, start, w.count, reinterpret_cast<float4*>(grid->points));
+    return check_launch("grid_fill");
+}
+
+int naruto_nn_grid_query(const NarutoNnGrid* grid, uint64_t n_queries, const float* queries, const void* queries_sorted, uint32_t ring_budget,
+                         double* dist, int32_t* index, uint32_t* fallback, void* stream) {
+    if (int rc = nn_grid_check(grid, "nn_grid_query")) return rc;
+    if (n_queries > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "nn_grid_query: counts beyond int32");
+    if (n_queries == 0) return NARUTO_OK;
+    if ((queries == nullptr && queries_sorted == nullptr) || dist == nullptr || index == nullptr || fallback == nullptr || grid->cell_start == nullptr || grid->points == nullptr)
+        return fail(NARUTO_ERR_INVALID, "nn_grid_query: NULL argument");
+    const NnGrid g = nn_grid_args(grid);
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nq = (uint32_t)n_queries;
+    const float4* q4 = reinterpret_cast<const float4*>(queries_sorted);
+    if (hipMemsetAsync(fallback, 0, 4u, st) != hipSuccess) return check_launch("nn_grid_query: memset");
+    hipLaunchKernelGGL(k_nn_grid, dim3((nq + kReconThreads - 1u) / kReconThreads), dim3(kReconThreads), 0, st, g, nq, queries, q4, ring_budget, dist, index,
+                       fallback + 1, fallback);
+    if (int rc = check_launch("nn_grid")) return rc;
+    // the queries whose rings did not close: their number is on the device, so the launch covers the worst case and empty workgroups leave at once
+    const uint32_t per = (uint32_t)(kReconThreads * kScanQ);
+    hipLaunchKernelGGL(k_nn_scan, dim3((nq + per - 1u) / per), dim3(kReconThreads), 0, st, g.n, (const float*)nullptr, g.pts, nq, queries, q4, fallback + 1, fallback, dist, index);
+    return check_launch("nn_scan (fallback)");
+}
+
+int naruto_nn_scan(uint64_t n_targets, const float* targets, uint64_t n_queries, const float* queries, double* dist, int32_t* index, void* stream) {
+    if (n_targets == 0) return fail(NARUTO_ERR_INVALID, "nn_scan: zero points");
+    if (n_targets > kReconMaxCount || n_queries > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "nn_scan: counts beyond int32");
+    if (n_queries == 0) return NARUTO_OK;
+    if (targets == nullptr || queries == nullptr || dist == nullptr || index == nullptr) return fail(NARUTO_ERR_INVALID, "nn_scan: NULL argument");
+    const uint32_t nq = (uint32_t)n_queries, per = (uint32_t)(kReconThreads * kScanQ);
+    hipLaunchKernelGGL(k_nn_scan, dim3((nq + per - 1u) / per), dim3(kReconThreads), 0, (hipStream_t)stream, (uint32_t)n_targets, targets, (const float4*)nullptr, nq, queries,
+                       (const float4*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, dist, index);
+    return check_launch("nn_scan");
+}
+
+size_t naruto_dist_reduce_workspace(uint64_t n) {
+    if (n == 0 || n > kReconMaxCount) return 0;
+    const size_t parts = (size_t)((n + kReconThreads * kDistPer - 1u) / (kReconThreads * kDistPer));
+    return 2u * recon_align(parts * 8u);
+}
+
+int naruto_dist_reduce(uint64_t n, const double* dist, double threshold, void* workspace, double* out, void* stream) {
+    if (n == 0) return fail(NARUTO_ERR_INVALID, "dist_reduce: zero points");
+    if (n > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "dist_reduce: counts beyond int32");
+    if (std::isnan(threshold)) return fail(NARUTO_ERR_INVALID, "dist_reduce: the threshold is not a number");
+    if (dist == nullptr || workspace == nullptr || out == nullptr) return fail(NARUTO_ERR_INVALID, "dist_reduce: NULL argument");
+    const uint32_t parts = (uint32_t)((n + kReconThreads * kDistPer - 1u) / (kReconThreads * kDistPer));
+    double* part_sum = reinterpret_cast<double*>(workspace);
+    unsigned long long* part_cnt = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + recon_align((size_t)parts * 8u));
+    hipLaunchKernelGGL(k_dist_partial, dim3(parts), dim3(kReconThreads), 0, (hipStream_t)stream, (uint32_t)n, dist, threshold, part_sum, part_cnt);
+    if (int rc = check_launch("dist_partial")) return rc;
+    hipLaunchKernelGGL(k_dist_finish, dim3(1), dim3(kReconThreads), 0, (hipStream_t)stream, (uint32_t)n, parts, part_sum, part_cnt, out);
+    return check_launch("dist_finish");
 }
 
 int naruto_sample_distinct(uint64_t n, uint32_t count, uint64_t seed, uint64_t counter, int64_t* out, void* stream) {

@@ -92,6 +92,114 @@ class Mesh:
             f.write(vert.tobytes())
             f.write(face.tobytes())
 
+    @staticmethod
+    def load(path: str) -> "Mesh":
+        return load_ply(path)
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def load_ply(path: str) -> Mesh:
+    """ASCII or binary little-endian PLY -> :class:`Mesh`.  Vertices may carry any scalar properties (x, y, z are taken as float64;
+    red / green / blue [/ alpha] uchar are kept as ``vertex_colors``); faces are lists of three or four indices, a quad a-b-c-d
+    becoming a-b-c and a-c-d; other face sizes and other elements are refused.  Reads back what :meth:`Mesh.export` writes, exactly."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    body = data.index(b"\n", end) + 1
+    fmt, elements = None, []                                   # elements: [name, count, [(kind, name, types...)]]
+    for line in data[:end].decode("ascii").splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[0] == "property":
+            if tok[1] == "list":
+                elements[-1][2].append(("list", tok[4], _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
+            else:
+                elements[-1][2].append(("scalar", tok[2], _PLY_TYPES[tok[1]]))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: PLY format {fmt!r} is not read (ascii and binary_little_endian are)")
+    vert, faces = None, np.zeros((0, 3), dtype=np.int64)
+    words = data[body:].split() if fmt == "ascii" else None
+    pos = 0 if fmt == "ascii" else body
+    for name, count, props in elements:
+        lists = [p for p in props if p[0] == "list"]
+        if name == "vertex":
+            if lists:
+                raise ValueError(f"{path}: list property on the vertex element")
+            if fmt == "ascii":
+                k = len(props)
+                table = np.array(words[pos:pos + count * k], dtype=np.float64).reshape(count, k)
+                pos += count * k
+                vert = {p[1]: table[:, i] for i, p in enumerate(props)}
+            else:
+                dt = np.dtype([(p[1], "<" + p[2]) for p in props])
+                rec = np.frombuffer(data, dtype=dt, count=count, offset=pos)
+                pos += dt.itemsize * count
+                vert = {p[1]: rec[p[1]] for p in props}
+        elif name == "face":
+            if len(lists) != 1 or props[0][0] != "list":
+                raise ValueError(f"{path}: the face element must start with one index list")
+            tris = []
+            if fmt == "ascii":
+                extra = len(props) - 1
+                for _ in range(count):
+                    n = int(words[pos])
+                    tris.append([int(w) for w in words[pos + 1:pos + 1 + n]])
+                    pos += 1 + n + extra
+            else:
+                _, _, ct, it = props[0]
+                rest = sum(np.dtype(p[2]).itemsize for p in props[1:])
+                if count:                                       # uniform lists (the usual case) are read as one record array
+                    n0 = int(np.frombuffer(data, dtype="<" + ct, count=1, offset=pos)[0])
+                    dt = np.dtype([("n", "<" + ct), ("i", "<" + it, (n0,)), ("rest", "u1", (rest,))])
+                    if pos + dt.itemsize * count <= len(data):
+                        rec = np.frombuffer(data, dtype=dt, count=count, offset=pos)
+                        if (rec["n"] == n0).all():
+                            tris = rec["i"].astype(np.int64)
+                            pos += dt.itemsize * count
+                if count and len(tris) == 0:
+                    cs, isz = np.dtype(ct).itemsize, np.dtype(it).itemsize
+                    for _ in range(count):
+                        n = int(np.frombuffer(data, dtype="<" + ct, count=1, offset=pos)[0])
+                        tris.append(np.frombuffer(data, dtype="<" + it, count=n, offset=pos + cs).astype(np.int64).tolist())
+                        pos += cs + n * isz + rest
+            if isinstance(tris, np.ndarray):
+                sizes = {tris.shape[1]}
+                rows = tris
+            else:
+                sizes = {len(t) for t in tris}
+                rows = None
+            if not sizes <= {3, 4}:
+                raise ValueError(f"{path}: faces of {sorted(sizes)} vertices; triangles and quads are read")
+            if rows is not None and rows.shape[1] == 3:
+                faces = rows
+            else:
+                out = []
+                for t in (rows.tolist() if rows is not None else tris):
+                    out.append(t[:3])
+                    if len(t) == 4:
+                        out.append([t[0], t[2], t[3]])
+                faces = np.array(out, dtype=np.int64).reshape(-1, 3)
+        else:
+            raise ValueError(f"{path}: element {name!r} is not read")
+    if vert is None or not all(k in vert for k in "xyz"):
+        raise ValueError(f"{path}: no vertex element with x, y, z")
+    vertices = np.stack([np.asarray(vert[k], dtype=np.float64) for k in "xyz"], -1).reshape(-1, 3)
+    colors = None
+    if all(k in vert for k in ("red", "green", "blue")):
+        alpha = vert["alpha"] if "alpha" in vert else np.full(len(vertices), 255)
+        colors = np.stack([vert["red"], vert["green"], vert["blue"], alpha], -1).astype(np.uint8).reshape(-1, 4)
+    return Mesh(vertices, np.ascontiguousarray(faces, dtype=np.int64), colors)
+
 
 def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     """trimesh's ``Trimesh.vertex_normals`` (third-party, unpinned; used by the reference at coslam_utils.py:180-181) restated:
@@ -164,9 +272,10 @@ def marching_cubes(sdf_vol: torch.Tensor, isolevel: float = 0.0, truncation: flo
 
 
 @torch.no_grad()
-def extract_mesh(query_fn: Callable, config, bounding_box: torch.Tensor, marching_cube_bound=None, color_func: Optional[Callable] = None, voxel_size=None,
-                 resolution=None, isolevel: float = 0.0, scene_name: str = "", mesh_savepath: str = "", render_uncert: bool = True) -> Mesh:
-    """coslam_utils.py:100-226.  ``query_fn`` = ``model.query_sdf``, ``color_func`` = ``model.query_color`` or None."""
+def extract_surface(query_fn: Callable, config, bounding_box: torch.Tensor, marching_cube_bound=None, voxel_size=None, resolution=None,
+                    isolevel: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The geometry half of :func:`extract_mesh` (coslam_utils.py:100-162), left on the device: (vertices float64 [V,3] in metric
+    world coordinates, triangles int32 [F,3])."""
     device = bounding_box.device
     if marching_cube_bound is None:
         marching_cube_bound = bounding_box
@@ -195,6 +304,16 @@ def extract_mesh(query_fn: Callable, config, bounding_box: torch.Tensor, marchin
     vertices = verts_idx / n_axis
     vertices = scale[None, :] * vertices + offset
     vertices = vertices / config["data"]["sc_factor"] - config["data"]["translation"]
+
+    return vertices, triangles
+
+
+@torch.no_grad()
+def extract_mesh(query_fn: Callable, config, bounding_box: torch.Tensor, marching_cube_bound=None, color_func: Optional[Callable] = None, voxel_size=None,
+                 resolution=None, isolevel: float = 0.0, scene_name: str = "", mesh_savepath: str = "", render_uncert: bool = True) -> Mesh:
+    """coslam_utils.py:100-226.  ``query_fn`` = ``model.query_sdf``, ``color_func`` = ``model.query_color`` or None."""
+    device = bounding_box.device
+    vertices, triangles = extract_surface(query_fn, config, bounding_box, marching_cube_bound, voxel_size, resolution, isolevel)
 
     colors = None
     if color_func is not None or render_uncert:

@@ -168,3 +168,31 @@ class AnalyticRoom:
         depth = np.where(t <= self.max_depth, t, 0.0)
         return {"rays_o": o.astype(np.float32), "rays_d": dw.astype(np.float32), "target_rgb": self.colour(hit, kind).astype(np.float32),
                 "target_d": depth[:, None].astype(np.float32), "hit": hit.astype(np.float32)}
+
+
+def room_sphere_mesh(shift: float = 0.0, radius: float = 0.8, lo=(0.0, 0.0, 0.0), hi=(6.0, 5.0, 3.0), centre=(3.0, 2.5, 1.4), n_lat: int = 48, n_lon: int = 96,
+                     zero_area_face: bool = True):
+    """A triangle mesh for the reconstruction-metric tests and timings: the six walls of a box (12 triangles, faces 0..11; every wall
+    vertex moved by ``shift`` along all three axes) and a UV sphere (2 * n_lon * (n_lat - 1) triangles) inside it, plus -- last -- one
+    zero-area face.  Returns (vertices float32 [V,3], faces int32 [F,3])."""
+    lo, hi, centre = (np.asarray(a, dtype=np.float64) for a in (lo, hi, centre))
+    corners = np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])]) + shift
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    faces = [t for a, b, c, d in quads for t in ((a, b, c), (a, c, d))]
+    lat = np.pi * np.arange(1, n_lat) / n_lat
+    lon = 2.0 * np.pi * np.arange(n_lon) / n_lon
+    ring = np.stack([np.sin(lat)[:, None] * np.cos(lon)[None], np.sin(lat)[:, None] * np.sin(lon)[None], np.cos(lat)[:, None] * np.ones_like(lon)[None]], -1)
+    sphere = np.concatenate([[[0.0, 0.0, 1.0]], ring.reshape(-1, 3), [[0.0, 0.0, -1.0]]]) * radius + centre
+    base, north, first = len(corners), len(corners), len(corners) + 1
+    south = first + (n_lat - 1) * n_lon
+    for j in range(n_lon):
+        j1 = (j + 1) % n_lon
+        faces.append((north, first + j, first + j1))
+        faces.append((south, first + (n_lat - 2) * n_lon + j1, first + (n_lat - 2) * n_lon + j))
+        for i in range(n_lat - 2):
+            a, b = first + i * n_lon + j, first + i * n_lon + j1
+            c, d = a + n_lon, b + n_lon
+            faces += [(a, c, b), (b, c, d)]
+    if zero_area_face:
+        faces.append((base, base, first))
+    return np.concatenate([corners, sphere]).astype(np.float32), np.array(faces, dtype=np.int32)
