@@ -771,6 +771,38 @@ int naruto_debug_pose_adam(float* pose, const float* grad, float* exp_avg, float
 int naruto_debug_ba_pose_sums(uint32_t n_rays, const int64_t* ids, uint32_t n_ids, const uint32_t* src_rows, uint32_t n_poses, uint32_t pose,
                               const float* rays_d, const float* d_rays_o, const float* d_rays_d, const float* pose6, double* sums, float* grad);
 
+/* Mesh culling: the step between save_mesh and eval_recon.py of the reference's evaluation protocol (scripts/evaluation/eval_replica.sh:55-72;
+ * cull_mesh.py --remove_occlusion is third-party code outside the reference tree: parity unpinned, the contract is restated in
+ * naruto_amd/culling.py and csrc/naruto_cull.hip).  Camera: x right, y up, looking along -z; pixel (i, j) has the ray
+ * ((i - cx)/fx, -(j - cy)/fy, -1).  Poses are row-major float32 camera-to-world [4,4].  All pointers are device memory.
+ *   render depth        float32 [n_poses,H,W] depth maps (z along the viewing axis) of a double-sided mesh, one per pose; +inf where nothing is
+ *                       hit inside (near, far).  face_mask (optional uint8 [F]): faces with 0 are not drawn.  A triangle whose candidate pixel
+ *                       box has more than large_threshold pixels is spread over workgroups in 2048-pixel chunks (a second launch); the result
+ *                       does not depend on the threshold, nor on anything else about the launch: every bit is fixed by the arithmetic.
+ *   observed vertices   mask[v] |= 1 where vertex v is in the frustum of one of the poses and (depth given) zc < depth[pose, j, i] + eps
+ *   cull faces          face_keep[f] = (inside NULL or any vertex of f inside) and (observed NULL or any vertex of f observed);
+ *                       vertex_used (optional, zeroed first) = 1 on the vertices of kept faces
+ *   cull compact        kept faces and used vertices to their rows (face_pos / vertex_pos: INCLUSIVE prefix sums of the flags, int32),
+ *                       original order, faces re-indexed; vertices float32 or float64 [V,3], colors optional RGBA8 [V,4] */
+typedef struct NarutoCullCam {
+    uint32_t H, W;
+    float fx, fy, cx, cy;
+    float near_, far_;                                /* the depth render only                                       */
+} NarutoCullCam;
+size_t naruto_render_depth_workspace(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses);
+int naruto_render_depth(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const uint8_t* face_mask,
+                        uint32_t n_poses, const float* poses, uint32_t large_threshold, void* workspace, float* depth, void* stream);
+int naruto_observed_vertices(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint32_t n_poses, const float* poses, const float* depth, float eps,
+                             uint8_t* mask, void* stream);
+int naruto_cull_faces(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const uint8_t* observed, const uint8_t* inside, uint8_t* face_keep,
+                      uint8_t* vertex_used, void* stream);
+int naruto_cull_compact(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const uint8_t* face_keep, const int32_t* face_pos, const uint8_t* vertex_used,
+                        const int32_t* vertex_pos, const void* vertices, int vertices_f64, const uint8_t* colors, uint64_t n_out_faces, uint64_t n_out_vertices,
+                        int32_t* out_faces, void* out_vertices, uint8_t* out_colors, void* stream);
+/* Measurement aid (tools/time_cull.py): n_lanes lanes (rounded up to workgroups of 256) each issue `iters` integer atomicMin at hashed
+ * addresses of buf [n_words] with values that fall per iteration: the rate of scattered 4-byte integer atomics, without a rasteriser. */
+int naruto_debug_atomic_min_rate(uint64_t n_words, uint32_t n_lanes, uint32_t iters, uint32_t* buf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 #include "naruto_bapose.hip"
 #include "naruto_rrt.hip"
 #include "naruto_recon.hip"
+#include "naruto_cull.hip"
 
 using namespace naruto;
 
@@ -2237,6 +2238,122 @@ int naruto_dist_reduce(uint64_t n, const double* dist, double threshold, void* w
     if (int rc = check_launch("dist_partial")) return rc;
     hipLaunchKernelGGL(k_dist_finish, dim3(1), dim3(kReconThreads), 0, (hipStream_t)stream, (uint32_t)n, parts, part_sum, part_cnt, out);
     return check_launch("dist_finish");
+}
+
+// ---- mesh culling (naruto_cull.hip) -------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kCullLargeGrid = 2048;                     // workgroups of the large route: 8 per CU, grid-stride over the chunks
+int cull_cam_check(const NarutoCullCam* cam, const char* who) {
+    if (cam == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL camera", who);
+    if (cam->H == 0 || cam->W == 0 || cam->H >= (1u << 24) || cam->W >= (1u << 24) || (uint64_t)cam->H * cam->W > (1ull << 30))
+        return fail(NARUTO_ERR_INVALID, "%s: image of %u x %u pixels (1 .. 2^30 pixels)", who, cam->W, cam->H);
+    if (!std::isfinite(cam->fx) || !std::isfinite(cam->fy) || cam->fx == 0.0f || cam->fy == 0.0f || !std::isfinite(cam->cx) || !std::isfinite(cam->cy))
+        return fail(NARUTO_ERR_INVALID, "%s: intrinsics must be finite with fx, fy != 0", who);
+    return NARUTO_OK;
+}
+CullCam cull_cam_args(const NarutoCullCam* cam) {
+    CullCam c{};
+    c.H = cam->H; c.W = cam->W; c.fx = cam->fx; c.fy = cam->fy; c.cx = cam->cx; c.cy = cam->cy; c.near_ = cam->near_; c.far_ = cam->far_;
+    return c;
+}
+int cull_raster_sizes_check(const NarutoCullCam* cam, uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses, const char* who) {
+    if (n_faces == 0 || n_vertices == 0 || n_poses == 0) return fail(NARUTO_ERR_INVALID, "%s: zero faces, vertices or poses", who);
+    if (n_faces > kReconMaxCount || n_vertices > kReconMaxCount || n_poses > 65535u) return fail(NARUTO_ERR_INVALID, "%s: counts beyond int32 (poses: 65535 per call)", who);
+    const uint64_t chunks_per_box = ((uint64_t)cam->H * cam->W + kCullChunk - 1u) / kCullChunk;
+    if (n_faces * n_poses >= (1ull << 28) || n_faces * n_poses * chunks_per_box >= (1ull << kCullSlotShift))
+        return fail(NARUTO_ERR_INVALID, "%s: faces x poses per call must stay below 2^28 (and x 2048-pixel chunks of the image below 2^36): use fewer poses per call", who);
+    return NARUTO_OK;
+}
+struct CullWs { unsigned long long* counter; float4* camv; unsigned long long* ent_start; uint32_t* ent_id; };
+CullWs cull_ws(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses, void* workspace) {
+    CullWs w;
+    char* p = reinterpret_cast<char*>(workspace);
+    w.counter = reinterpret_cast<unsigned long long*>(p); p += 256;
+    w.camv = reinterpret_cast<float4*>(p); p += recon_align((size_t)n_vertices * n_poses * 16u);
+    w.ent_start = reinterpret_cast<unsigned long long*>(p); p += recon_align((size_t)n_faces * n_poses * 8u);
+    w.ent_id = reinterpret_cast<uint32_t*>(p);
+    return w;
+}
+}  // namespace
+
+size_t naruto_render_depth_workspace(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses) {
+    if (n_faces == 0 || n_vertices == 0 || n_poses == 0 || n_faces > kReconMaxCount || n_vertices > kReconMaxCount || n_poses > 65535u || n_faces * n_poses >= (1ull << 28)) return 0;
+    return 256u + recon_align((size_t)n_vertices * n_poses * 16u) + recon_align((size_t)n_faces * n_poses * 8u) + recon_align((size_t)n_faces * n_poses * 4u);
+}
+
+int naruto_render_depth(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const uint8_t* face_mask,
+                        uint32_t n_poses, const float* poses, uint32_t large_threshold, void* workspace, float* depth, void* stream) {
+    if (int rc = cull_cam_check(cam, "render_depth")) return rc;
+    if (!(cam->near_ > 0.0f) || !(cam->near_ < cam->far_)) return fail(NARUTO_ERR_INVALID, "render_depth: need 0 < near < far");
+    if (int rc = cull_raster_sizes_check(cam, n_vertices, n_faces, n_poses, "render_depth")) return rc;
+    if (vertices == nullptr || faces == nullptr || poses == nullptr || workspace == nullptr || depth == nullptr) return fail(NARUTO_ERR_INVALID, "render_depth: NULL argument");
+    const CullCam c = cull_cam_args(cam);
+    const CullWs w = cull_ws(n_vertices, n_faces, n_poses, workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nv = (uint32_t)n_vertices, nf = (uint32_t)n_faces, cap = (uint32_t)(n_faces * n_poses);
+    uint32_t* bits = reinterpret_cast<uint32_t*>(depth);
+    if (hipMemsetAsync(w.counter, 0, 8u, st) != hipSuccess) return check_launch("render_depth: memset");
+    if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bits), (int)kCullInfBits, (size_t)n_poses * cam->H * cam->W, st) != hipSuccess) return check_launch("render_depth: fill");
+    const dim3 block(kCullThreads);
+    hipLaunchKernelGGL(k_cull_transform, dim3((nv + kCullThreads - 1u) / kCullThreads, n_poses), block, 0, st, nv, vertices, poses, w.camv);
+    if (int rc = check_launch("cull_transform")) return rc;
+    hipLaunchKernelGGL(k_cull_raster_small, dim3((nf + kCullThreads - 1u) / kCullThreads, n_poses), block, 0, st, c, nf, nv, faces, face_mask, w.camv, large_threshold, bits,
+                       w.counter, w.ent_id, w.ent_start, cap);
+    if (int rc = check_launch("cull_raster_small")) return rc;
+    // the large boxes: their number is on the device, so the launch is a fixed grid and a workgroup without a chunk leaves at once
+    hipLaunchKernelGGL(k_cull_raster_large, dim3(kCullLargeGrid), block, 0, st, c, nf, nv, faces, w.camv, bits, w.counter, w.ent_id, w.ent_start, cap);
+    return check_launch("cull_raster_large");
+}
+
+int naruto_observed_vertices(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint32_t n_poses, const float* poses, const float* depth, float eps,
+                             uint8_t* mask, void* stream) {
+    if (int rc = cull_cam_check(cam, "observed_vertices")) return rc;
+    if (n_vertices > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "observed_vertices: counts beyond int32");
+    if (std::isnan(eps)) return fail(NARUTO_ERR_INVALID, "observed_vertices: eps is not a number");
+    if (n_vertices == 0 || n_poses == 0) return NARUTO_OK;
+    if (vertices == nullptr || poses == nullptr || mask == nullptr) return fail(NARUTO_ERR_INVALID, "observed_vertices: NULL argument");
+    const uint32_t nv = (uint32_t)n_vertices;
+    hipLaunchKernelGGL(k_cull_observed, dim3((nv + kCullThreads - 1u) / kCullThreads), dim3(kCullThreads), 0, (hipStream_t)stream, cull_cam_args(cam), nv, vertices, n_poses, poses,
+                       reinterpret_cast<const uint32_t*>(depth), eps, mask);
+    return check_launch("cull_observed");
+}
+
+int naruto_cull_faces(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const uint8_t* observed, const uint8_t* inside, uint8_t* face_keep, uint8_t* vertex_used,
+                      void* stream) {
+    if (n_faces > kReconMaxCount || n_vertices > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "cull_faces: counts beyond int32");
+    hipStream_t st = (hipStream_t)stream;
+    if (vertex_used != nullptr && n_vertices > 0 && hipMemsetAsync(vertex_used, 0, (size_t)n_vertices, st) != hipSuccess) return check_launch("cull_faces: memset");
+    if (n_faces == 0) return NARUTO_OK;
+    if (faces == nullptr || face_keep == nullptr) return fail(NARUTO_ERR_INVALID, "cull_faces: NULL argument");
+    const uint32_t nf = (uint32_t)n_faces;
+    hipLaunchKernelGGL(k_cull_faces, dim3((nf + kCullThreads - 1u) / kCullThreads), dim3(kCullThreads), 0, st, nf, (uint32_t)n_vertices, faces, observed, inside, face_keep, vertex_used);
+    return check_launch("cull_faces");
+}
+
+int naruto_cull_compact(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const uint8_t* face_keep, const int32_t* face_pos, const uint8_t* vertex_used,
+                        const int32_t* vertex_pos, const void* vertices, int vertices_f64, const uint8_t* colors, uint64_t n_out_faces, uint64_t n_out_vertices,
+                        int32_t* out_faces, void* out_vertices, uint8_t* out_colors, void* stream) {
+    if (n_faces > kReconMaxCount || n_vertices > kReconMaxCount || n_out_faces > n_faces || n_out_vertices > n_vertices) return fail(NARUTO_ERR_INVALID, "cull_compact: counts out of range");
+    if (n_out_faces == 0 || n_out_vertices == 0) return NARUTO_OK;
+    if (faces == nullptr || face_keep == nullptr || face_pos == nullptr || vertex_used == nullptr || vertex_pos == nullptr || vertices == nullptr || out_faces == nullptr ||
+        out_vertices == nullptr || (colors != nullptr && out_colors == nullptr))
+        return fail(NARUTO_ERR_INVALID, "cull_compact: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nf = (uint32_t)n_faces, nv = (uint32_t)n_vertices;
+    hipLaunchKernelGGL(k_cull_compact_faces, dim3((nf + kCullThreads - 1u) / kCullThreads), dim3(kCullThreads), 0, st, nf, nv, faces, face_keep, face_pos, vertex_pos,
+                       (uint32_t)n_out_faces, out_faces);
+    if (int rc = check_launch("cull_compact_faces")) return rc;
+    hipLaunchKernelGGL(k_cull_compact_vertices, dim3((nv + kCullThreads - 1u) / kCullThreads), dim3(kCullThreads), 0, st, nv, vertex_used, vertex_pos,
+                       reinterpret_cast<const uint32_t*>(vertices), vertices_f64 ? 6u : 3u, reinterpret_cast<const uint32_t*>(colors), (uint32_t)n_out_vertices,
+                       reinterpret_cast<uint32_t*>(out_vertices), reinterpret_cast<uint32_t*>(out_colors));
+    return check_launch("cull_compact_vertices");
+}
+
+int naruto_debug_atomic_min_rate(uint64_t n_words, uint32_t n_lanes, uint32_t iters, uint32_t* buf, void* stream) {
+    if (n_words == 0 || n_words > 0xFFFFFFFFull || n_lanes == 0 || iters == 0 || iters > (1u << 20)) return fail(NARUTO_ERR_INVALID, "debug_atomic_min_rate: sizes out of range");
+    if (buf == nullptr) return fail(NARUTO_ERR_INVALID, "debug_atomic_min_rate: NULL argument");
+    hipLaunchKernelGGL(k_cull_atomic_probe, dim3((n_lanes + kCullThreads - 1u) / kCullThreads), dim3(kCullThreads), 0, (hipStream_t)stream, (uint32_t)n_words, iters, buf);
+    return check_launch("cull_atomic_probe");
 }
 
 int naruto_sample_distinct(uint64_t n, uint32_t count, uint64_t seed, uint64_t counter, int64_t* out, void* stream) {

@@ -23,7 +23,9 @@ splitmix64 stream: seed for the ground truth, seed + 1 for the reconstruction, s
 units of the truncation distance, so the metric value is mean * training.trunc * 100; the reference hard-codes ``* 10`` there, which is
 the same number for its trunc of 0.1 m and a quirk for any other (tests/accuracy_study.py uses the same conversion).
 
-Mesh culling (cull_mesh.py, which needs rendered ground-truth depth) and mesh alignment stay with the caller.
+Mesh culling, the step the protocol runs before these metrics (cull_mesh.py --remove_occlusion from the estimated poses), is
+``naruto_amd.culling``; ``evaluate_field(cull_poses=..., cull_cam=...)`` runs it on the device between extraction and sampling.  Mesh
+alignment stays with the caller.
 
 Command line, with the arguments of the reference's eval_recon.py::
 
@@ -263,10 +265,18 @@ class ReconEvaluatorHIP:
         return {"accuracy_cm": acc, "completion_cm": comp, "completion_ratio_pct": ratio}
 
     @torch.no_grad()
-    def evaluate_field(self, model, config, bounding_box: torch.Tensor, voxel_size: float, marching_cube_bound=None) -> Dict[str, float]:
+    def evaluate_field(self, model, config, bounding_box: torch.Tensor, voxel_size: float, marching_cube_bound=None, cull_poses=None, cull_cam=None,
+                       **cull_args) -> Dict[str, float]:
         """field -> SDF lattice -> marching cubes -> metric vertices (as ``mesh.extract_mesh``) -> samples -> both queries, plus ``mad_cm``;
-        no mesh or cloud goes to the host, one copy of four numbers ends the call."""
+        no mesh or cloud goes to the host, one copy of four numbers ends the call.  With ``cull_poses`` ([P,4,4], metric frame) and
+        ``cull_cam`` (config["cam"]) the extracted mesh is culled on the device first (``culling.cull_mesh``; ``cull_args`` are its keyword
+        arguments), at the price of one more copy of two numbers; without them the launches are unchanged."""
         vertices, triangles = M.extract_surface(model.query_sdf, config, bounding_box, marching_cube_bound, voxel_size=voxel_size)
+        if cull_poses is not None and len(triangles) > 0:
+            if cull_cam is None:
+                raise ValueError("evaluate_field: cull_poses needs cull_cam (the intrinsics H, W, fx, fy, cx, cy)")
+            from . import culling
+            vertices, triangles = culling.cull_mesh((vertices, triangles), cull_poses, cull_cam, **cull_args)
         # MAD: the ground-truth samples (metric) into field coordinates (the inverse of extract_mesh's last vertex transform), then into the unit box
         bb = bounding_box.to(self.device)
         pts = (self.gt_points.to(bb.dtype) + config["data"]["translation"]) * config["data"]["sc_factor"]
