@@ -803,6 +803,33 @@ int naruto_cull_compact(uint64_t n_faces, uint64_t n_vertices, const int32_t* fa
  * addresses of buf [n_words] with values that fall per iteration: the rate of scattered 4-byte integer atomics, without a rasteriser. */
 int naruto_debug_atomic_min_rate(uint64_t n_words, uint32_t n_lanes, uint32_t iters, uint32_t* buf, void* stream);
 
+/* Mesh simulator: a mesh in the place of the reference's HabitatSim (src/simulator/habitat_simulator.py; an external renderer that is not
+ * on this stack: parity unpinned; the contract is restated in naruto_amd/simulator.py and csrc/naruto_sim.hip).  Camera and poses as for
+ * the culling above.  All pointers are device memory.
+ *   render rgbd     the depth render with the winning face per pixel (among the faces whose depth equals the minimum in every bit, the
+ *                   lowest index) and its vertex colours interpolated perspective-correctly: depth float32 [n_poses,H,W], color float32
+ *                   [n_poses,H,W,3], face_id int32 [n_poses,H,W]; any of the three may be NULL.  colors: RGBA8 words [V] (c = byte/255) or,
+ *                   with colors_f32, float32 [V,3]; needed iff color is asked for.  Nothing hit: depth 0 (+inf with NARUTO_SIM_KEEP_INF),
+ *                   colour 0, id -1.  Independent of large_threshold and of the launch, as render depth is.
+ *   cube to erp     erp[c][k] = cube[c][table[k]]: a nearest gather of [C,6,s,s] 32-bit words to [C,n_erp] through an index table
+ *                   (naruto_amd.simulator.cube_table restates the reference's C2E, src/layers/c2e.py); entries must lie in [0, 6 s^2)
+ *   depth to dist   dist = depth * sqrt(dx^2 + dy^2 + 1), dx = (i - cx)/fx, dy = (j - cy)/fy (erp_conversions.depth2dist), [n_images,H,W]
+ *   sim erp         per panorama: six cube planes of depth [6,s,s] (rendered with fx = fy = cx = cy = (s-1)/2; 0 or +inf = nothing hit) and
+ *                   optionally colour [6,s,s,3] -> radial distance [n_erp] (1e8 * ray norm where nothing is hit), colour [n_erp,3], and
+ *                   stats uint32 [2]: the bit pattern of the minimum distance and the number of pixels with distance > invalid_thre.
+ *                   erp_dist, erp_color and stats may each be NULL. */
+#define NARUTO_SIM_KEEP_INF 1u
+size_t naruto_render_rgbd_workspace(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses, uint32_t H, uint32_t W);
+int naruto_render_rgbd(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const void* colors, int colors_f32,
+                       uint32_t n_poses, const float* poses, uint32_t large_threshold, uint32_t flags, void* workspace, float* depth, float* color, int32_t* face_id,
+                       void* stream);
+int naruto_cube_to_erp(uint32_t n_channels, uint32_t face_w, uint64_t n_erp, const int32_t* table, const void* cube, void* erp, void* stream);
+int naruto_depth_to_dist(uint32_t n_images, uint32_t H, uint32_t W, float fx, float fy, float cx, float cy, const float* depth, float* dist, void* stream);
+int naruto_sim_erp(uint32_t n_panoramas, uint32_t face_w, uint64_t n_erp, const int32_t* table, const float* cube_depth, const float* cube_color, float invalid_thre,
+                   float* erp_dist, float* erp_color, uint32_t* stats, void* stream);
+/* Measurement aid (tools/time_sim.py): naruto_debug_atomic_min_rate on 8-byte cells, the winner raster's access pattern. */
+int naruto_debug_atomic_min64_rate(uint64_t n_cells, uint32_t n_lanes, uint32_t iters, uint64_t* buf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_sim.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -135,6 +135,8 @@ class NarutoCullCam(C.Structure):
                 ("near_", C.c_float), ("far_", C.c_float)]
 
 
+SIM_KEEP_INF = 1
+
 RRT_MODE_RUN, RRT_MODE_FULL = 0, 1
 RRT_DONE, RRT_NEED_ROWS, RRT_NEED_ROOM = 0, 1, 2
 RRT_CELL_THRESHOLD = 2048
@@ -248,6 +250,12 @@ SIGNATURES = {
     "naruto_cull_faces": (_I, [_U64, _U64, _V, _V, _V, _V, _V, _V]),
     "naruto_cull_compact": (_I, [_U64, _U64, _V, _V, _V, _V, _V, _V, _I, _V, _U64, _U64, _V, _V, _V, _V]),
     "naruto_debug_atomic_min_rate": (_I, [_U64, _U32, _U32, _V, _V]),
+    "naruto_render_rgbd_workspace": (C.c_size_t, [_U64, _U64, _U32, _U32, _U32]),
+    "naruto_render_rgbd": (_I, [C.POINTER(NarutoCullCam), _U64, _V, _U64, _V, _V, _I, _U32, _V, _U32, _U32, _V, _V, _V, _V, _V]),
+    "naruto_cube_to_erp": (_I, [_U32, _U32, _U64, _V, _V, _V, _V]),
+    "naruto_depth_to_dist": (_I, [_U32, _U32, _U32, _F, _F, _F, _F, _V, _V, _V]),
+    "naruto_sim_erp": (_I, [_U32, _U32, _U64, _V, _V, _V, _F, _V, _V, _V, _V]),
+    "naruto_debug_atomic_min64_rate": (_I, [_U64, _U32, _U32, _V, _V]),
     "naruto_adam_multi": (_I, [C.POINTER(NarutoAdamSeg), _U32, _F, _F, _U32, _V, _U32, _V]),
     "naruto_train_workspace": (C.c_size_t, [_V, C.POINTER(NarutoTrainStep)]),
     "naruto_train_forward": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), _I, _V]),

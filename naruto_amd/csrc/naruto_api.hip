@@ -23,6 +23,7 @@
 #include "naruto_rrt.hip"
 #include "naruto_recon.hip"
 #include "naruto_cull.hip"
+#include "naruto_sim.hip"
 
 using namespace naruto;
 
@@ -2297,11 +2298,11 @@ int naruto_render_depth(const NarutoCullCam* cam, uint64_t n_vertices, const flo
     const dim3 block(kCullThreads);
     hipLaunchKernelGGL(k_cull_transform, dim3((nv + kCullThreads - 1u) / kCullThreads, n_poses), block, 0, st, nv, vertices, poses, w.camv);
     if (int rc = check_launch("cull_transform")) return rc;
-    hipLaunchKernelGGL(k_cull_raster_small, dim3((nf + kCullThreads - 1u) / kCullThreads, n_poses), block, 0, st, c, nf, nv, faces, face_mask, w.camv, large_threshold, bits,
+    hipLaunchKernelGGL(k_cull_raster_small<uint32_t>, dim3((nf + kCullThreads - 1u) / kCullThreads, n_poses), block, 0, st, c, nf, nv, faces, face_mask, w.camv, large_threshold, bits,
                        w.counter, w.ent_id, w.ent_start, cap);
     if (int rc = check_launch("cull_raster_small")) return rc;
     // the large boxes: their number is on the device, so the launch is a fixed grid and a workgroup without a chunk leaves at once
-    hipLaunchKernelGGL(k_cull_raster_large, dim3(kCullLargeGrid), block, 0, st, c, nf, nv, faces, w.camv, bits, w.counter, w.ent_id, w.ent_start, cap);
+    hipLaunchKernelGGL(k_cull_raster_large<uint32_t>, dim3(kCullLargeGrid), block, 0, st, c, nf, nv, faces, w.camv, bits, w.counter, w.ent_id, w.ent_start, cap);
     return check_launch("cull_raster_large");
 }
 
@@ -2354,6 +2355,94 @@ int naruto_debug_atomic_min_rate(uint64_t n_words, uint32_t n_lanes, uint32_t it
     if (buf == nullptr) return fail(NARUTO_ERR_INVALID, "debug_atomic_min_rate: NULL argument");
     hipLaunchKernelGGL(k_cull_atomic_probe, dim3((n_lanes + kCullThreads - 1u) / kCullThreads), dim3(kCullThreads), 0, (hipStream_t)stream, (uint32_t)n_words, iters, buf);
     return check_launch("cull_atomic_probe");
+}
+
+// ---- mesh simulator (naruto_sim.hip) --------------------------------------------------------------------------------------
+namespace {
+size_t sim_raster_ws(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses) { return naruto_render_depth_workspace(n_vertices, n_faces, n_poses); }
+int sim_fill2(uint64_t n_pairs, uint32_t w0, uint32_t w1, void* p, hipStream_t st, const char* who) {
+    hipLaunchKernelGGL(k_sim_fill2, dim3((uint32_t)((n_pairs + kSimThreads - 1u) / kSimThreads)), dim3(kSimThreads), 0, st, n_pairs, w0, w1, reinterpret_cast<uint2*>(p));
+    return check_launch(who);
+}
+}  // namespace
+
+size_t naruto_render_rgbd_workspace(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses, uint32_t H, uint32_t W) {
+    const size_t raster = sim_raster_ws(n_vertices, n_faces, n_poses);
+    if (raster == 0 || H == 0 || W == 0 || (uint64_t)H * W > (1ull << 30)) return 0;
+    return raster + recon_align((size_t)n_poses * H * W * 8u);
+}
+
+int naruto_render_rgbd(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const void* colors, int colors_f32,
+                       uint32_t n_poses, const float* poses, uint32_t large_threshold, uint32_t flags, void* workspace, float* depth, float* color, int32_t* face_id,
+                       void* stream) {
+    if (int rc = cull_cam_check(cam, "render_rgbd")) return rc;
+    if (!(cam->near_ > 0.0f) || !(cam->near_ < cam->far_)) return fail(NARUTO_ERR_INVALID, "render_rgbd: need 0 < near < far");
+    if (int rc = cull_raster_sizes_check(cam, n_vertices, n_faces, n_poses, "render_rgbd")) return rc;
+    if ((uint64_t)n_poses * cam->H * cam->W >= (1ull << 32)) return fail(NARUTO_ERR_INVALID, "render_rgbd: poses x pixels per call must stay below 2^32: use fewer poses per call");
+    if (flags & ~(uint32_t)NARUTO_SIM_KEEP_INF) return fail(NARUTO_ERR_INVALID, "render_rgbd: unknown flag");
+    if (vertices == nullptr || faces == nullptr || poses == nullptr || workspace == nullptr) return fail(NARUTO_ERR_INVALID, "render_rgbd: NULL argument");
+    if (depth == nullptr && color == nullptr && face_id == nullptr) return fail(NARUTO_ERR_INVALID, "render_rgbd: no output");
+    if (color != nullptr && colors == nullptr) return fail(NARUTO_ERR_INVALID, "render_rgbd: a colour image needs vertex colours");
+    const CullCam c = cull_cam_args(cam);
+    const CullWs w = cull_ws(n_vertices, n_faces, n_poses, workspace);
+    unsigned long long* cells = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + sim_raster_ws(n_vertices, n_faces, n_poses));
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nv = (uint32_t)n_vertices, nf = (uint32_t)n_faces, cap = (uint32_t)(n_faces * n_poses), n_px = cam->H * cam->W;
+    if (hipMemsetAsync(w.counter, 0, 8u, st) != hipSuccess) return check_launch("render_rgbd: memset");
+    if (int rc = sim_fill2((uint64_t)n_poses * n_px, kSimNoFace, kCullInfBits, cells, st, "render_rgbd: fill")) return rc;
+    const dim3 block(kCullThreads);
+    hipLaunchKernelGGL(k_cull_transform, dim3((nv + kCullThreads - 1u) / kCullThreads, n_poses), block, 0, st, nv, vertices, poses, w.camv);
+    if (int rc = check_launch("cull_transform")) return rc;
+    hipLaunchKernelGGL(k_cull_raster_small<unsigned long long>, dim3((nf + kCullThreads - 1u) / kCullThreads, n_poses), block, 0, st, c, nf, nv, faces,
+                       (const uint8_t*)nullptr, w.camv, large_threshold, cells, w.counter, w.ent_id, w.ent_start, cap);
+    if (int rc = check_launch("sim_raster_small")) return rc;
+    hipLaunchKernelGGL(k_cull_raster_large<unsigned long long>, dim3(kCullLargeGrid), block, 0, st, c, nf, nv, faces, w.camv, cells, w.counter, w.ent_id, w.ent_start, cap);
+    if (int rc = check_launch("sim_raster_large")) return rc;
+    hipLaunchKernelGGL(k_sim_shade, dim3((n_px + kSimThreads - 1u) / kSimThreads, n_poses), dim3(kSimThreads), 0, st, c, nf, nv, faces, colors, colors_f32, w.camv, cells,
+                       (int)(flags & NARUTO_SIM_KEEP_INF), depth, color, face_id);
+    return check_launch("sim_shade");
+}
+
+int naruto_cube_to_erp(uint32_t n_channels, uint32_t face_w, uint64_t n_erp, const int32_t* table, const void* cube, void* erp, void* stream) {
+    if (n_channels == 0 || n_erp == 0) return NARUTO_OK;
+    if (face_w == 0 || face_w > 8192u || n_erp > (1ull << 30) || n_channels > 65535u) return fail(NARUTO_ERR_INVALID, "cube_to_erp: sizes out of range");
+    if (table == nullptr || cube == nullptr || erp == nullptr) return fail(NARUTO_ERR_INVALID, "cube_to_erp: NULL argument");
+    hipLaunchKernelGGL(k_sim_gather, dim3((uint32_t)((n_erp + kSimThreads - 1u) / kSimThreads), n_channels), dim3(kSimThreads), 0, (hipStream_t)stream, 6u * face_w * face_w,
+                       (uint32_t)n_erp, table, reinterpret_cast<const uint32_t*>(cube), reinterpret_cast<uint32_t*>(erp));
+    return check_launch("sim_gather");
+}
+
+int naruto_depth_to_dist(uint32_t n_images, uint32_t H, uint32_t W, float fx, float fy, float cx, float cy, const float* depth, float* dist, void* stream) {
+    if (n_images == 0) return NARUTO_OK;
+    if (H == 0 || W == 0 || (uint64_t)H * W > (1ull << 30) || n_images > 65535u) return fail(NARUTO_ERR_INVALID, "depth_to_dist: sizes out of range");
+    if (!std::isfinite(fx) || !std::isfinite(fy) || fx == 0.0f || fy == 0.0f || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail(NARUTO_ERR_INVALID, "depth_to_dist: intrinsics must be finite with fx, fy != 0");
+    if (depth == nullptr || dist == nullptr) return fail(NARUTO_ERR_INVALID, "depth_to_dist: NULL argument");
+    hipLaunchKernelGGL(k_sim_dist, dim3((H * W + kSimThreads - 1u) / kSimThreads, n_images), dim3(kSimThreads), 0, (hipStream_t)stream, H, W, fx, fy, cx, cy, depth, dist);
+    return check_launch("sim_dist");
+}
+
+int naruto_sim_erp(uint32_t n_panoramas, uint32_t face_w, uint64_t n_erp, const int32_t* table, const float* cube_depth, const float* cube_color, float invalid_thre,
+                   float* erp_dist, float* erp_color, uint32_t* stats, void* stream) {
+    if (n_panoramas == 0 || n_erp == 0) return NARUTO_OK;
+    if (face_w < 2 || face_w > 8192u || n_erp > (1ull << 30) || n_panoramas > 65535u) return fail(NARUTO_ERR_INVALID, "sim_erp: sizes out of range (face_w 2 .. 8192)");
+    if (std::isnan(invalid_thre)) return fail(NARUTO_ERR_INVALID, "sim_erp: the threshold is not a number");
+    if (table == nullptr || cube_depth == nullptr || (erp_color != nullptr && cube_color == nullptr)) return fail(NARUTO_ERR_INVALID, "sim_erp: NULL argument");
+    if (erp_dist == nullptr && erp_color == nullptr && stats == nullptr) return fail(NARUTO_ERR_INVALID, "sim_erp: no output");
+    hipStream_t st = (hipStream_t)stream;
+    if (stats != nullptr)
+        if (int rc = sim_fill2(n_panoramas, kCullInfBits, 0u, stats, st, "sim_erp: fill")) return rc;
+    hipLaunchKernelGGL(k_sim_erp, dim3((uint32_t)((n_erp + kSimThreads - 1u) / kSimThreads), n_panoramas), dim3(kSimThreads), 0, st, face_w, (uint32_t)n_erp, table, cube_depth,
+                       cube_color, invalid_thre, erp_dist, erp_color, stats);
+    return check_launch("sim_erp");
+}
+
+int naruto_debug_atomic_min64_rate(uint64_t n_cells, uint32_t n_lanes, uint32_t iters, uint64_t* buf, void* stream) {
+    if (n_cells == 0 || n_cells > 0xFFFFFFFFull || n_lanes == 0 || iters == 0 || iters > (1u << 20)) return fail(NARUTO_ERR_INVALID, "debug_atomic_min64_rate: sizes out of range");
+    if (buf == nullptr) return fail(NARUTO_ERR_INVALID, "debug_atomic_min64_rate: NULL argument");
+    hipLaunchKernelGGL(k_sim_atomic_probe, dim3((n_lanes + kSimThreads - 1u) / kSimThreads), dim3(kSimThreads), 0, (hipStream_t)stream, (uint32_t)n_cells, iters,
+                       reinterpret_cast<unsigned long long*>(buf));
+    return check_launch("sim_atomic_probe");
 }
 
 int naruto_sample_distinct(uint64_t n, uint32_t count, uint64_t seed, uint64_t counter, int64_t* out, void* stream) {

@@ -95,8 +95,11 @@ __device__ __forceinline__ void cull_setup(const float4 a4, const float4 b4, con
     t.num = (a[0] * t.n[0] + a[1] * t.n[1]) + a[2] * t.n[2];
 }
 
-// pixel (i, j) of one pose's depth plane (bit patterns, H*W words)
-__device__ __forceinline__ void cull_pixel(const CullCam& c, const CullTri& t, int i, int j, uint32_t* __restrict__ plane) {
+// pixel (i, j) of one pose's depth plane (H*W cells).  Cell uint32_t: the depth's bit pattern (the cull).  Cell unsigned long long: depth
+// bits in the high word, the face index in the low one (the simulator, naruto_sim.hip): the minimum is the nearest depth and, among the
+// faces whose depth equals it in every bit, the lowest index -- whatever the order of arrival.
+template <typename Cell>
+__device__ __forceinline__ void cull_pixel(const CullCam& c, const CullTri& t, int i, int j, Cell* __restrict__ plane, uint32_t face) {
 #pragma clang fp contract(off)
     const float dx = ((float)i - c.cx) / c.fx;
     const float dy = -(((float)j - c.cy) / c.fy);
@@ -110,9 +113,10 @@ __device__ __forceinline__ void cull_pixel(const CullCam& c, const CullTri& t, i
     if (den == 0.0f) return;
     const float depth = t.num / den;
     if (!(depth > c.near_ && depth < c.far_)) return;
-    const uint32_t bits = __float_as_uint(depth);
-    uint32_t* cell = plane + (size_t)j * c.W + (uint32_t)i;
-    if (bits < *cell) atomicMin(cell, bits);                // (a stale read is only ever too large: the atomic decides)
+    Cell key = (Cell)__float_as_uint(depth);
+    if constexpr (sizeof(Cell) == 8) key = (key << 32) | face;
+    Cell* cell = plane + (size_t)j * c.W + (uint32_t)i;
+    if (key < *cell) atomicMin(cell, key);                  // (a stale read is only ever too large: the atomic decides)
 }
 
 __device__ __forceinline__ bool cull_load_triangle(const int32_t* __restrict__ faces, uint32_t f, uint32_t n_vertices, const float4* __restrict__ camv,
@@ -134,9 +138,10 @@ __global__ __launch_bounds__(kCullThreads) void k_cull_transform(uint32_t n_vert
 
 // grid (faces / 256, poses).  No lane leaves before the list allocation: a wave's large boxes take their slots and chunk ranges with ONE
 // atomic (inclusive scans of the flags and the chunk counts over the wave; lane order = slot order, so the slots stay sorted by chunk range).
+template <typename Cell>
 __global__ __launch_bounds__(kCullThreads) void k_cull_raster_small(CullCam cam, uint32_t n_faces, uint32_t n_vertices, const int32_t* __restrict__ faces,
                                                                      const uint8_t* __restrict__ face_mask, const float4* __restrict__ camv, uint32_t threshold,
-                                                                     uint32_t* __restrict__ depth, unsigned long long* __restrict__ counter,
+                                                                     Cell* __restrict__ depth, unsigned long long* __restrict__ counter,
                                                                      uint32_t* __restrict__ ent_id, unsigned long long* __restrict__ ent_start, uint32_t cap) {
     const uint32_t f = blockIdx.x * kCullThreads + threadIdx.x, pose = blockIdx.y;
     float4 a, b, c;
@@ -170,15 +175,16 @@ __global__ __launch_bounds__(kCullThreads) void k_cull_raster_small(CullCam cam,
     if (!valid || large) return;
     CullTri t;
     cull_setup(a, b, c, t);
-    uint32_t* plane = depth + (size_t)pose * cam.H * cam.W;
+    Cell* plane = depth + (size_t)pose * cam.H * cam.W;
 #pragma unroll 1
     for (int j = box.y0; j <= box.y1; ++j)
 #pragma unroll 1
-        for (int i = box.x0; i <= box.x1; ++i) cull_pixel(cam, t, i, j, plane);
+        for (int i = box.x0; i <= box.x1; ++i) cull_pixel(cam, t, i, j, plane, f);
 }
 
+template <typename Cell>
 __global__ __launch_bounds__(kCullThreads) void k_cull_raster_large(CullCam cam, uint32_t n_faces, uint32_t n_vertices, const int32_t* __restrict__ faces,
-                                                                     const float4* __restrict__ camv, uint32_t* __restrict__ depth,
+                                                                     const float4* __restrict__ camv, Cell* __restrict__ depth,
                                                                      const unsigned long long* __restrict__ counter, const uint32_t* __restrict__ ent_id,
                                                                      const unsigned long long* __restrict__ ent_start, uint32_t cap) {
     const unsigned long long word = *counter;
@@ -201,13 +207,13 @@ __global__ __launch_bounds__(kCullThreads) void k_cull_raster_large(CullCam cam,
         const uint32_t bw = (uint32_t)(box.x1 - box.x0 + 1), bh = (uint32_t)(box.y1 - box.y0 + 1), px = bw * bh;
         CullTri t;
         cull_setup(a, b, c, t);
-        uint32_t* plane = depth + (size_t)pose * cam.H * cam.W;
+        Cell* plane = depth + (size_t)pose * cam.H * cam.W;
 #pragma unroll 1
         for (uint32_t r = 0; r < kCullLargePer; ++r) {
             const uint32_t k = first + r * kCullThreads + threadIdx.x;
             if (k < px) {
                 const uint32_t row = k / bw;
-                cull_pixel(cam, t, box.x0 + (int)(k - row * bw), box.y0 + (int)row, plane);
+                cull_pixel(cam, t, box.x0 + (int)(k - row * bw), box.y0 + (int)row, plane, f);
             }
         }
     }

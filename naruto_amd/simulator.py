@@ -1,0 +1,318 @@
+"""Mesh simulator on the device: a triangle mesh in the place of the reference's HabitatSim.
+
+The reference's run loop (src/naruto/main.py) starts every step with ``sim.simulate(c2w)``: an RGB-D frame from Habitat-Sim at the
+planned pose, and -- with ``return_erp`` -- an equirectangular (ERP) colour image and radial-distance map, which the planner's movement
+check reads (``NarutoPlanner.detect_collision_v2``, naruto_planner.py:544-547: ``erp_depth.min()`` and the share of pixels above 1e6).
+Habitat-Sim is an external renderer that is not on this stack.  :class:`MeshSimHIP` renders a mesh instead -- a ground-truth ``.ply``,
+the room-plus-sphere of ``naruto_amd.synthetic``, or a mesh this library extracted -- with the call surface of ``HabitatSim.simulate``.
+
+PARITY UNPINNED against Habitat.  Pinned, by the reference's recorded results (tests/golden/g13_c2e.npz): the cube-to-panorama gather
+(``C2E``, src/layers/c2e.py, through :func:`cube_table`) and ``erp_conversions.depth2dist`` (:func:`depth_to_dist`).  Differences from
+Habitat:
+
+  * colours are the vertex colours interpolated in float32, not 8-bit images; a mesh without colours renders white;
+  * no lighting, no textures, no physics, no objects;
+  * the reference's ``depth2dist`` call uses ``K = face_w / 2``, half a pixel off the grid ``C2E`` samples; the simulator uses the
+    consistent ``(face_w - 1) / 2``.  :func:`depth_to_dist` takes any intrinsics;
+  * the front half of ``ERPDepth2Dist`` -- six bilinear ``E2P`` resamplings of a Habitat ERP image into cube faces -- is NOT built:
+    a mesh renders its cube faces directly.
+
+Contract (float32 in the operation order at the top of csrc/naruto_sim.hip; tests/sim_spec.py restates it in numpy and the kernels equal
+it in every bit):
+
+  Camera: this repository's convention -- x right, y up, looking along -z; pixel (i, j) has the ray ((i - cx)/fx, -(j - cy)/fy, -1);
+  ``depth`` is z along the viewing axis.  The rasteriser is the culling's (naruto_amd/culling.py): homogeneous, double sided, no
+  clipping.  Per pixel the nearest hit inside (near, far) wins; among the faces whose depth equals the minimum in every bit, the lowest
+  face index.  Colour: perspective-correct barycentrics from the rasteriser's own edge values.  A pixel nothing covers has depth 0
+  (Habitat's invalid value; Co-SLAM masks ``depth > 0``), colour 0 and face id -1.
+
+  Cube faces, in the reference's order F R B L U D, each a ``face_w`` x ``face_w`` pinhole image with fx = fy = cx = cy = (face_w-1)/2
+  (pixel i at tangent -1 + 2i/(face_w-1), as C2E assumes) and pose ``c2w @ R_face``; right, up and view vectors in the camera frame:
+  F identity; R, B, L yawed right by 90, 180, 270 degrees about +y; U right +x, up +z, view +y; D right +x, up -z, view -y.
+
+  Panorama [h, w]: pixel (row, col) reads the cube pixel ``cube_table(face_w, h, w)[row, col]``.  Its centre column looks along the
+  camera's -z, u grows toward +x and v toward +y: the direction is (cos v sin u, sin v, -cos v cos u).  ``erp_depth`` is the radial
+  distance t * sqrt(dx^2 + dy^2 + 1) along the chosen cube pixel's ray; nothing hit: 1e8 * that norm (the reference sets invalid depth to
+  1e8 before its conversion and tests > 1e6).
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+from . import culling as CU
+
+FACE_ORDER = "FRBLUD"
+
+
+def face_rotations() -> np.ndarray:
+    """float64 [6,3,3]: R_face with columns (right, up, -view) in the camera frame, order F R B L U D."""
+    x, y, z = np.eye(3)
+    frames = [(x, y, -z), (z, y, x), (-x, y, z), (-z, y, -x), (x, z, y), (x, -z, -y)]               # (right, up, view)
+    return np.stack([np.stack([r, u, -v], 1) for r, u, v in frames])
+
+
+def cube_grid(face_w: int, h: int, w: int) -> np.ndarray:
+    """The normalised sampling grid of the reference's C2E(face_w, h, w), float32 [h,w,3] = (x, y, face) in [-1, 1], restated from its
+    mathematics: float32 linspace angles (numpy keeps their trigonometry in float32), the face-type map with its rolled ceiling mask,
+    the tangent formulas accumulated in float64 -- clip to +-0.5, (. + 0.5) * (face_w - 1), normalise to [-1, 1] -- cast to float32."""
+    face_w, h, w = int(face_w), int(h), int(w)
+    if face_w < 2:
+        raise ValueError("simulator: face_w >= 2")
+    if h < 2 or w < 8 or w % 8:
+        raise ValueError(f"simulator: a panorama of {w} x {h}: need h >= 2 and w a multiple of 8")
+    u = np.linspace(-np.pi, np.pi, num=w, dtype=np.float32)
+    v = np.linspace(np.pi, -np.pi, num=h, dtype=np.float32) / 2
+    u, v = np.meshgrid(u, v)
+    # face type: four vertical bands F R B L (F centred), then the ceiling and the floor where |v| is beyond the band's upper edge
+    q, roll = w // 4, 3 * w // 8
+    tp = np.roll(np.repeat(np.arange(4), q)[None].repeat(h, 0), roll, 1)
+    edge = h // 2 - np.round(np.arctan(np.cos(np.linspace(-np.pi, np.pi, q) / 4)) * h / np.pi).astype(int)
+    ceil = np.roll(np.tile(np.arange(h)[:, None] < edge[None], (1, 4)), roll, 1)
+    tp[ceil] = 4
+    tp[ceil[::-1]] = 5
+    x, y = np.zeros((h, w)), np.zeros((h, w))
+    for k in range(4):
+        m = tp == k
+        yaw = u[m] - np.pi * k / 2
+        x[m] = 0.5 * np.tan(yaw)
+        y[m] = -0.5 * np.tan(v[m]) / np.cos(yaw)
+    for k, sign in ((4, 1.0), (5, -1.0)):
+        m = tp == k
+        c = 0.5 * np.tan(np.pi / 2 - np.abs(v[m]))
+        x[m] = c * np.sin(u[m])
+        y[m] = sign * c * np.cos(u[m])
+    x = (np.clip(x, -0.5, 0.5) + 0.5) * (face_w - 1)
+    y = (np.clip(y, -0.5, 0.5) + 0.5) * (face_w - 1)
+    return np.stack([x / (face_w - 1) * 2 - 1, y / (face_w - 1) * 2 - 1, tp.astype(np.float64) / 5 * 2 - 1], -1).astype(np.float32)
+
+
+def cube_table(face_w: int, h: int, w: int) -> np.ndarray:
+    """int32 [h,w]: the word of a cube map [6, face_w, face_w] that panorama pixel (row, col) reads -- C2E.forward(mode='nearest'), i.e.
+    grid_sample's own rule on :func:`cube_grid`: ((g + 1)/2) * (size - 1) in float32, rounded half to even."""
+    g = cube_grid(face_w, h, w)
+
+    def nearest(c, size):
+        return np.rint(((c + np.float32(1)) / np.float32(2)) * np.float32(size - 1)).astype(np.int64)
+
+    return ((nearest(g[..., 2], 6) * face_w + nearest(g[..., 1], face_w)) * face_w + nearest(g[..., 0], face_w)).astype(np.int32)
+
+
+def _device(device) -> torch.device:
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _table_on(table, n_cube: int, device) -> torch.Tensor:
+    t = torch.as_tensor(table)
+    if t.dtype not in (torch.int32, torch.int64) or t.numel() == 0:
+        raise ValueError("simulator: the table is a non-empty int32 array of cube indices")
+    lo, hi = (int(x) for x in torch.stack([t.min(), t.max()]).cpu())
+    if lo < 0 or hi >= n_cube:
+        raise ValueError(f"simulator: table entry out of range ({lo} .. {hi} for a cube of {n_cube} words)")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def cube_to_erp(cube, table) -> torch.Tensor:
+    """Nearest gather of a cube map [C,6,s,s] (any 4-byte dtype) to the panorama [C,h,w] through ``table`` [h,w] (:func:`cube_table`)."""
+    c = torch.as_tensor(cube)
+    if c.dim() != 4 or c.shape[1] != 6 or c.shape[2] != c.shape[3] or c.element_size() != 4:
+        raise ValueError(f"simulator: a cube map is [C,6,s,s] of a 4-byte dtype, got {tuple(c.shape)} {c.dtype}")
+    device = c.device if c.is_cuda else _device(None)
+    t = torch.as_tensor(table)
+    if t.dim() != 2:
+        raise ValueError("simulator: the table is [h,w]")
+    s = int(c.shape[2])
+    td = _table_on(t, 6 * s * s, device)
+    c = c.to(device).contiguous()
+    out = torch.empty(c.shape[0], *t.shape, dtype=c.dtype, device=device)
+    with torch.cuda.device(device):
+        check(_lib.load().naruto_cube_to_erp(c.shape[0], s, td.numel(), td.data_ptr(), c.data_ptr(), out.data_ptr(), CU._stream()), "naruto_cube_to_erp")
+    return out
+
+
+def depth_to_dist(depth, fx: float, fy: float, cx: float, cy: float) -> torch.Tensor:
+    """Perspective depth [N,H,W] (or [H,W]) to the distance along the pixel ray: depth * sqrt(((i-cx)/fx)^2 + ((j-cy)/fy)^2 + 1)
+    (reference erp_conversions.depth2dist with K = [[fx,0,cx],[0,fy,cy],[0,0,1]])."""
+    d = torch.as_tensor(depth)
+    one = d.dim() == 2
+    if one:
+        d = d[None]
+    if d.dim() != 3 or d.numel() == 0:
+        raise ValueError(f"simulator: depth is [N,H,W], got {tuple(d.shape)}")
+    fx, fy, cx, cy = float(fx), float(fy), float(cx), float(cy)
+    if not all(math.isfinite(x) for x in (fx, fy, cx, cy)) or fx == 0.0 or fy == 0.0:
+        raise ValueError("simulator: intrinsics must be finite with fx, fy != 0")
+    device = d.device if d.is_cuda else _device(None)
+    d = d.to(device=device, dtype=torch.float32).contiguous()
+    out = torch.empty_like(d)
+    with torch.cuda.device(device):
+        check(_lib.load().naruto_depth_to_dist(d.shape[0], d.shape[1], d.shape[2], fx, fy, cx, cy, d.data_ptr(), out.data_ptr(), CU._stream()), "naruto_depth_to_dist")
+    return out[0] if one else out
+
+
+def _colors(colors, n_vertices: int):
+    """None | RGBA8 [V,4] | float [V,3] -> (host tensor uint8 [V,4] or float32 [V,3], is_float)."""
+    if colors is None:
+        return torch.full((n_vertices, 4), 255, dtype=torch.uint8), False
+    c = torch.as_tensor(colors)
+    if c.dtype == torch.uint8:
+        if c.numel() != 4 * n_vertices:
+            raise ValueError(f"simulator: one RGBA8 colour per vertex ({c.numel()} bytes for {n_vertices} vertices)")
+        return c.reshape(-1, 4), False
+    if not c.dtype.is_floating_point:
+        raise ValueError("simulator: vertex colours are RGBA8 [V,4] or float [V,3]")
+    if c.numel() != 3 * n_vertices:
+        raise ValueError(f"simulator: one float RGB colour per vertex ({c.numel()} values for {n_vertices} vertices)")
+    if not bool(torch.isfinite(c).all()):
+        raise ValueError("simulator: non-finite vertex colour")
+    return c.reshape(-1, 3).to(torch.float32), True
+
+
+class _RasterRGBD:
+    """Workspace and arguments of the RGB-D render of one camera, reused over the calls."""
+
+    def __init__(self, sim: "MeshSimHIP", cam: _lib.NarutoCullCam, chunk: int):
+        self.sim, self.cam = sim, cam
+        n_v, n_f = len(sim.v), len(sim.f)
+        self.chunk = max(1, min(int(chunk), (2 ** 28 - 1) // max(n_f, 1), (2 ** 32 - 1) // (cam.H * cam.W), 65535))
+        n = _lib.load().naruto_render_rgbd_workspace(n_v, n_f, self.chunk, cam.H, cam.W)
+        if n == 0:
+            raise ValueError(f"simulator: a mesh of {n_v} vertices and {n_f} faces at {cam.W} x {cam.H} is beyond the render's sizes")
+        self.ws = torch.empty((n + 7) // 8, dtype=torch.int64, device=sim.device)
+
+    def render(self, poses: torch.Tensor, depth=None, color=None, face_id=None, keep_inf: bool = False) -> None:
+        """poses [B,4,4] float32 on the device, B <= chunk -> depth [B,H,W], color [B,H,W,3], face_id [B,H,W] (each optional)."""
+        s = self.sim
+        ptr = lambda t: t.data_ptr() if t is not None else None                                                   # noqa: E731
+        check(_lib.load().naruto_render_rgbd(C.byref(self.cam), len(s.v), s.v.data_ptr(), len(s.f), s.f.data_ptr(), s.col.data_ptr(), int(s.col_f32), len(poses),
+                                             poses.data_ptr(), s.threshold, _lib.SIM_KEEP_INF if keep_inf else 0, self.ws.data_ptr(), ptr(depth), ptr(color), ptr(face_id),
+                                             CU._stream()), "naruto_render_rgbd")
+
+    def render_depth(self, poses: torch.Tensor, depth: torch.Tensor) -> None:
+        """The culling's depth-only render (32-bit cells, +inf where nothing is hit) in the same workspace: the same depth bits."""
+        s = self.sim
+        check(_lib.load().naruto_render_depth(C.byref(self.cam), len(s.v), s.v.data_ptr(), len(s.f), s.f.data_ptr(), None, len(poses), poses.data_ptr(), s.threshold,
+                                              self.ws.data_ptr(), depth.data_ptr(), CU._stream()), "naruto_render_depth")
+
+
+class MeshSimHIP:
+    """``HabitatSim`` over a mesh (module docstring).  ``mesh``: a :class:`naruto_amd.mesh.Mesh`, the path of a ``.ply`` or a tuple
+    (vertices, faces[, colors]) with colours RGBA8 [V,4] or float [V,3]; uploaded once.  ``cam``: H, W, fx, fy, cx, cy of the pinhole
+    sensor (``config["cam"]``).  ``erp_hw``, ``face_w``: the panorama and the cube faces it is gathered from.  ``plan``: a
+    :class:`naruto_amd.culling.RasterPlan`; no bit of any result depends on it."""
+
+    def __init__(self, mesh, cam: Dict, erp_hw: Tuple[int, int] = (1024, 2048), face_w: int = 512, near: float = 0.01, far: float = 100.0, device=None, plan=None):
+        self.cam_dict = dict(cam)
+        self.cam = CU._camera(cam, near, far)
+        self.h, self.w = (int(x) for x in erp_hw)
+        self.face_w = int(face_w)
+        table = cube_table(self.face_w, self.h, self.w)                                     # (validates face_w, h, w)
+        k = (self.face_w - 1) / 2.0
+        self.cube_cam = CU._camera({"H": self.face_w, "W": self.face_w, "fx": k, "fy": k, "cx": k, "cy": k}, near, far)
+        self.threshold = CU._threshold(plan)
+        vertices, faces, colors, _ = CU._as_mesh(mesh)
+        col, self.col_f32 = _colors(colors, torch.as_tensor(vertices).numel() // 3)
+        v, self.f = CU._geometry(vertices, faces, device)
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError("simulator: non-finite vertex")
+        self.device = v.device
+        self.v = v.to(torch.float32)
+        self.col = col.to(self.device).contiguous()
+        self.table = torch.from_numpy(table).to(self.device).reshape(-1).contiguous()
+        self.face_rot = torch.from_numpy(face_rotations()).to(torch.float32)                # (host: face poses are made before the upload)
+        self._rasters: Dict[Tuple[str, int], _RasterRGBD] = {}
+
+    # ---- plumbing ----------------------------------------------------------------------------------------------------
+    def _raster(self, kind: str, chunk: int) -> _RasterRGBD:
+        key = (kind, int(chunk))
+        if key not in self._rasters:
+            self._rasters[key] = _RasterRGBD(self, self.cam if kind == "pinhole" else self.cube_cam, chunk)
+        return self._rasters[key]
+
+    def _cube_poses(self, p: torch.Tensor) -> torch.Tensor:
+        """host [P,4,4] -> host [P*6,4,4]: c2w @ R_face, the translation kept."""
+        out = p[:, None].repeat(1, 6, 1, 1)
+        out[:, :, :3, :3] = p[:, None, :3, :3] @ self.face_rot[None]
+        return out.reshape(-1, 4, 4).contiguous()
+
+    def _erp(self, p: torch.Tensor, pano_chunk: int, want_images: bool, invalid_thre: float):
+        """-> (erp_color [P,h,w,3] or None, erp_dist [P,h,w] or None, stats uint32-as-int32 [P,2]); no host synchronisation."""
+        n, s, dev = len(p), self.face_w, self.device
+        r = self._raster("cube", 6 * max(1, int(pano_chunk)))
+        per = max(1, r.chunk // 6)
+        if r.chunk < 6:
+            raise ValueError("simulator: the mesh is too large for six cube faces per launch")
+        poses = self._cube_poses(p).to(dev)
+        stats = torch.empty(n, 2, dtype=torch.int32, device=dev)
+        dist = torch.empty(n, self.h, self.w, dtype=torch.float32, device=dev) if want_images else None
+        color = torch.empty(n, self.h, self.w, 3, dtype=torch.float32, device=dev) if want_images else None
+        cube_d = torch.empty(per * 6, s, s, dtype=torch.float32, device=dev)
+        cube_c = torch.empty(per * 6, s, s, 3, dtype=torch.float32, device=dev) if want_images else None
+        lib = _lib.load()
+        for a in range(0, n, per):                                                          # (no host synchronisation in here)
+            b = min(a + per, n)
+            part = poses[6 * a:6 * b]
+            if want_images:
+                r.render(part, depth=cube_d[:len(part)], color=cube_c[:len(part)])
+            else:
+                r.render_depth(part, cube_d[:len(part)])
+            check(lib.naruto_sim_erp(b - a, s, self.h * self.w, self.table.data_ptr(), cube_d.data_ptr(), cube_c.data_ptr() if want_images else None, float(invalid_thre),
+                                     dist[a:b].data_ptr() if want_images else None, color[a:b].data_ptr() if want_images else None, stats[a:b].data_ptr(), CU._stream()),
+                  "naruto_sim_erp")
+        return color, dist, stats
+
+    # ---- the simulator's surface -------------------------------------------------------------------------------------
+    def simulate_batch(self, c2ws, return_erp: bool = False, pose_chunk: int = 8, return_face_id: bool = False):
+        """(color [P,H,W,3], depth [P,H,W]) float32 on the device [+ (erp_color [P,h,w,3], erp_depth [P,h,w])] [+ face_id int32 [P,H,W]];
+        the loop over the pose chunks has no host synchronisation.  No bit depends on ``pose_chunk``."""
+        p = CU._poses(c2ws)
+        if int(pose_chunk) < 1:
+            raise ValueError("simulator: pose_chunk >= 1")
+        with torch.cuda.device(self.device):
+            r = self._raster("pinhole", pose_chunk)
+            pd = p.to(self.device)
+            H, W = self.cam.H, self.cam.W
+            depth = torch.empty(len(p), H, W, dtype=torch.float32, device=self.device)
+            color = torch.empty(len(p), H, W, 3, dtype=torch.float32, device=self.device)
+            fid = torch.empty(len(p), H, W, dtype=torch.int32, device=self.device) if return_face_id else None
+            for a in range(0, len(p), r.chunk):
+                b = a + r.chunk
+                r.render(pd[a:b], depth[a:b], color[a:b], fid[a:b] if fid is not None else None)
+            out = (color, depth)
+            if return_erp:
+                ec, ed, _ = self._erp(p, max(1, int(pose_chunk) // 6), True, 1e6)
+                out += (ec, ed)
+            if return_face_id:
+                out += (fid,)
+        return out
+
+    def simulate(self, c2w, return_erp: bool = False, no_print: bool = False):
+        """``HabitatSim.simulate``: (color [H,W,3] in 0..1, depth [H,W]) or, with ``return_erp``, (color, depth, erp_color [h,w,3],
+        erp_depth [h,w] -- the radial distance map), float32 tensors on the device."""
+        p = CU._poses(c2w)
+        if len(p) != 1:
+            raise ValueError("simulator: simulate takes one [4,4] pose (simulate_batch takes [P,4,4])")
+        if not no_print:
+            print(f"MeshSimHIP: simulating at position [{float(p[0, 0, 3]):.3f}, {float(p[0, 1, 3]):.3f}, {float(p[0, 2, 3]):.3f}]")
+        return tuple(x[0] for x in self.simulate_batch(p, return_erp=return_erp, pose_chunk=1))
+
+    def collision_probe(self, c2w, invalid_thre: float = 1e6) -> Tuple[float, float]:
+        """(dist_closest, invalid_region_ratio) of detect_collision_v2 (naruto_planner.py:544-547) at the pose: the minimum of the
+        ERP distance map and the share of its pixels above ``invalid_thre``, reduced on the device (depth-only cube faces, no images);
+        two scalars come to the host."""
+        p = CU._poses(c2w)
+        if len(p) != 1:
+            raise ValueError("simulator: collision_probe takes one [4,4] pose")
+        if math.isnan(float(invalid_thre)):
+            raise ValueError("simulator: the threshold is not a number")
+        with torch.cuda.device(self.device):
+            _, _, stats = self._erp(p, 1, False, invalid_thre)
+            bits, count = (int(x) for x in stats[0].cpu())
+        return float(np.array([bits], dtype=np.int32).view(np.float32)[0]), count / (self.h * self.w)
