@@ -331,6 +331,13 @@ def check(rc: int, what: str = "") -> None:
         raise NarutoError(f"{what or 'libnaruto_hip'} failed ({rc}): {msg}")
 
 
+def workspace(n_bytes: int, device, dtype=None, zero: bool = False):
+    """The one place a ``naruto_*_workspace()`` byte count becomes a tensor: ``ceil(n_bytes / itemsize)`` elements of ``dtype`` (float32 unless given)."""
+    import torch
+    dtype = dtype or torch.float32
+    return (torch.zeros if zero else torch.empty)(-(-int(n_bytes) // dtype.itemsize), dtype=dtype, device=device)
+
+
 def kernel_resources(lib_path: str = None):
     """Per kernel of the device code object embedded in the built library: the AMDGPU metadata notes the loader reads
     (``.vgpr_count``, ``.agpr_count``, ``.vgpr_spill_count``, ``.sgpr_spill_count``, ``.private_segment_fixed_size`` = scratch bytes per

@@ -127,7 +127,7 @@ class ActiveRaySamplerHIP:
         dims = (C.c_uint32 * 3)(*vol.shape)
         bmin = (C.c_float * 3)(*(float(b[0]) for b in bbox))
         with torch.cuda.device(dev):
-            ws = workspace if workspace is not None else torch.empty(self.workspace_elems(n_total), dtype=torch.int32, device=dev)
+            ws = workspace if workspace is not None else _lib.workspace(4 * self.workspace_elems(n_total), dev, torch.int32)
             assert ws.dtype == torch.int32 and ws.numel() >= self.workspace_elems(n_total)
             if src_rows is not None:
                 _lib.check(lib.naruto_active_ray_select_rows(n_total, base, K, n_tail, _p(rays_o), _p(rays_d), _p(target_s), _p(td), _p(vol), dims, bmin, 10.0,

@@ -279,11 +279,10 @@ class FusedBA:
         mp, tr = self.config['mapping'], self.config['training']
         n_stage = self.sample_num + n_cur
         S = int(tr['n_samples_d']) + int(tr['n_range_d'])
-        lib = _lib.load()
         pb["ids"] = torch.zeros(n_stage, dtype=torch.int64, device=dev)
         pb["src_rows"] = torch.zeros(n_train, dtype=torch.int32, device=dev) if self.active else None
         pb["d_rays_o"], pb["d_rays_d"] = torch.zeros(n_train, 3, device=dev), torch.zeros(n_train, 3, device=dev)
-        pb["ws"] = torch.zeros((lib.naruto_ba_poses_workspace(self.trainer.model._handle().ptr, n_train, S) + 3) // 4, device=dev)
+        pb["ws"] = _lib.workspace(_lib.load().naruto_ba_poses_workspace(self.trainer.model._handle().ptr, n_train, S), dev, zero=True)
         b = _lib.NarutoBAPoses()
         b.max_poses, b.optim_cur, b.pose_accum_step = self.poses.shape[0], 1 if mp.get('optim_cur', True) else 0, int(mp.get('pose_accum_step', 5))
         b.dyn, b.poses = self.dyn.data_ptr(), self.poses.data_ptr()
@@ -385,7 +384,7 @@ class FusedBA:
             n_stage = self.sample_num + n_cur
             if self.active:
                 self._stage = (torch.empty(n_stage, 3, **f32), torch.empty(n_stage, 3, **f32), torch.empty(n_stage, 3, **f32), torch.empty(n_stage, 1, **f32))
-                self._ws = torch.empty(self.sampler.workspace_elems(n_stage), dtype=torch.int32, device=dev)
+                self._ws = _lib.workspace(4 * self.sampler.workspace_elems(n_stage), dev, torch.int32)
                 self._keys = torch.zeros(n_stage, dtype=torch.int32, device=dev)
             self._pro = self._prologue(n_cur)
             self._pro_later = self._later_prologue(n_cur) if self.prefetch else self._pro

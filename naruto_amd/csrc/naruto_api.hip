@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 #include "naruto_field.hip"
@@ -78,6 +79,71 @@ int check_points(const NarutoPoints* pts) {
 
 uint32_t cu_count(const NarutoField* f) { return f->n_cu > 0 ? (uint32_t)f->n_cu : 256u; }
 
+// a profiling / forcing knob of the environment; the sites keep it in a `static const`, so it is read once per process
+int env_int(const char* name, int dflt) { const char* e = getenv(name); return e != nullptr ? atoi(e) : dflt; }
+
+inline size_t align_up(size_t b, size_t a = 256u) { return (b + a - 1u) / a * a; }
+
+// The cursor every workspace layout is written with.  A layout function carves its sections from `base` in order and returns them with the
+// total; over a NULL base the same walk only measures, which is what the naruto_*_workspace() function reports -- a layout is stated once.
+// A section starts where the last one ended; `align` rounds its LENGTH up (1: the next section follows unpadded).
+struct Carve {
+    char* base;
+    size_t off = 0;
+    explicit Carve(void* b) : base(reinterpret_cast<char*>(b)) {}
+    template <typename T> T* take(size_t bytes, size_t align = 256u) {
+        T* p = base != nullptr ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += align_up(bytes, align);
+        return p;
+    }
+    size_t size() const { return off; }
+};
+
+// Dynamic LDS beyond the default limit is reserved per kernel, once per process: `latch` is set only after every kernel of the list has
+// its bytes, so a failed reservation is tried again by the next call.  `what` heads the failure message and may print `told` (%zu).
+struct LdsUse { const void* kernel; size_t bytes; };
+template <typename K> LdsUse lds_use(K* kernel, size_t bytes) { return LdsUse{reinterpret_cast<const void*>(kernel), bytes}; }
+int reserve_lds(bool& latch, std::initializer_list<LdsUse> uses, const char* what, size_t told = 0) {
+    if (latch) return NARUTO_OK;
+    for (const LdsUse& u : uses) {
+        if (hipFuncSetAttribute(u.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)u.bytes) == hipSuccess) continue;
+        char head[128];
+        snprintf(head, sizeof(head), what, told);
+        return fail(NARUTO_ERR_LAUNCH, "%s: %s", head, hipGetErrorString(hipGetLastError()));
+    }
+    latch = true;
+    return NARUTO_OK;
+}
+
+// the stand-alone smoothness term over a lattice of n^3 cells: | features [n3][32] | one partial sum per 256 of them | pad |
+struct TvWs { float* feat; double* partial; char* pad; size_t total; };
+TvWs tv_ws(void* base, size_t n) {
+    static_assert(kFeat * sizeof(float) % 64u == 0u, "the partial sums follow the features 64-byte aligned without a gap");
+    const size_t n3 = n * n * n;
+    Carve c(base);
+    return {c.take<float>(n3 * kFeat * sizeof(float), 64u), c.take<double>((n3 * kFeat + 255u) / 256u * sizeof(double), 1u), c.take<char>(64u, 1u), c.size()};
+}
+// the point gradients of M ray samples (naruto_query_bwd_points, tracking, the BA pose step): | d_x [M][3] | pad |
+struct PointGradWs { float* d_x; char* pad; size_t total; };
+PointGradWs point_grad_ws(void* base, size_t M) {
+    Carve c(base);
+    return {c.take<float>(3u * sizeof(float) * M, 1u), c.take<char>(256u, 1u), c.size()};
+}
+// naruto_loss_sums: | per-ray terms [n_rays][16] |
+struct LossWs { float* terms; size_t total; };
+LossWs loss_ws(void* base, size_t n_rays) {
+    Carve c(base);
+    return {c.take<float>(n_rays * 16u * sizeof(float), 1u), c.size()};
+}
+// a top-K selection (k_ars_select) over n_keys keys: | keys [n_keys] | selected [K] | pad |.  A launch over fewer keys than the workspace
+// was sized for packs its selection right behind them.
+struct SelectWs { uint32_t* keys; uint32_t* sel; uint32_t* pad; size_t total; };
+SelectWs select_ws(void* base, size_t n_keys, size_t K, size_t pad_words) {
+    Carve c(base);
+    return {c.take<uint32_t>(n_keys * sizeof(uint32_t), 1u), c.take<uint32_t>(K * sizeof(uint32_t), 1u), c.take<uint32_t>(pad_words * sizeof(uint32_t), 1u), c.size()};
+}
+constexpr size_t kArsPadWords = 16, kGoalPadWords = 64;
+
 // leading dimension of the scatter's point list: a multiple of 4 so that every row (x [3][cap], d_feat [16][cap][2]) starts
 // 16-byte aligned and the scatter can stream it with 16-byte loads
 inline uint32_t list_cap(uint32_t n) { return (n + 3u) & ~3u; }
@@ -88,34 +154,24 @@ constexpr size_t kFwdLossMaxRayLds = 48u * 1024u;       // S <= 384 samples per 
 // the per-ray kernels keep one ray per wave in dynamic LDS (kRayFields x S floats): allow the kMaxSamples case (128 KB)
 int ray_lds_attr() {
     static bool done = false;
-    if (done) return NARUTO_OK;
-    const int bytes = (int)ray_scratch_bytes(kMaxSamples);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_composite_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_composite_bwd<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_composite_bwd<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_loss_stage), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_loss_bwd_fused), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFwdLossMaxRayLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFwdLossMaxRayLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFwdLossMaxRayLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFwdLossMaxRayLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_short<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_short<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1024) != hipSuccess)
-        return fail(NARUTO_ERR_LAUNCH, "per-ray kernels: cannot reserve %d bytes of LDS: %s", bytes, hipGetErrorString(hipGetLastError()));
-    done = true;
-    return NARUTO_OK;
+    const size_t bytes = ray_scratch_bytes(kMaxSamples);
+    return reserve_lds(done,
+                       {lds_use(k_composite_fwd, bytes), lds_use(k_composite_bwd<true>, bytes), lds_use(k_composite_bwd<false>, bytes), lds_use(k_loss_stage, bytes),
+                        lds_use(k_loss_bwd_fused, bytes), lds_use(k_query_fwd_loss<false, false>, kFwdLossMaxRayLds), lds_use(k_query_fwd_loss<true, false>, kFwdLossMaxRayLds),
+                        lds_use(k_query_fwd_loss<false, true>, kFwdLossMaxRayLds), lds_use(k_query_fwd_loss<true, true>, kFwdLossMaxRayLds),
+                        lds_use(k_query_fwd_loss_short<false>, 16u * 1024u), lds_use(k_query_fwd_loss_short<true>, 16u * 1024u)},
+                       "per-ray kernels: cannot reserve %zu bytes of LDS", bytes);
 }
 
 constexpr uint32_t kBwdMaxBlocks = 512;     // fp32: one 145 KB-LDS block per CU; bf16 mode: NARUTO_BWD_BF_MINWAVES 53 KB blocks per CU
 
-inline size_t al256(size_t b) { return (b + 255u) / 256u * 256u; }
 // Point splits per level for a launch over a list of up to M points.  The plan's own counts (field_create) are an integer partition of
 // the CUs for lists of a few hundred thousand points, where every workgroup is one round.  A long list is cut finer, so that the
 // hardware's workgroup scheduler evens out the unit types over several rounds -- at 3.4 M points the hashed units (2 splits) took
 // 3.4 ms while the dense units (4 splits) were done after 0.85 ms and their CUs idled.  Hashed levels only.  More splits cost partial tables (read
 // once more each by the reduce), nothing else: the sums are fixed point.
 inline uint32_t split_multiplier(uint32_t M) {
-    static const int dbg = getenv("NARUTO_DEBUG_SCATTER_SPLIT_MULT") ? atoi(getenv("NARUTO_DEBUG_SCATTER_SPLIT_MULT")) : 0;      // profiling knob
+    static const int dbg = env_int("NARUTO_DEBUG_SCATTER_SPLIT_MULT", 0);      // profiling knob
     if (dbg > 0) return (uint32_t)dbg;
     return M > 1500000u ? 4u : 1u;            // measured (131 072 x 43 rays, T = 2^16): x2 no gain, x4 6.42 -> 5.70 ms; at 352 k / 554 k points x2 and x4 lose
 }
@@ -154,9 +210,9 @@ inline ScatterPlan scatter_plan(const NarutoField* f, uint32_t M) {
     }
     plan.n_level_blocks = (uint16_t)nb;
     // a level's slice of the list (16 B per point and feature) stays in an XCD's 4 MB L2 up to ~300 k points
-    static const int dbg_xcd = getenv("NARUTO_DEBUG_SCATTER_XCD_AWARE") ? atoi(getenv("NARUTO_DEBUG_SCATTER_XCD_AWARE")) : -1;       // profiling knob
+    static const int dbg_xcd = env_int("NARUTO_DEBUG_SCATTER_XCD_AWARE", -1);       // profiling knob
     plan.xcd_aware = (uint8_t)(dbg_xcd >= 0 ? (dbg_xcd != 0) : (M <= 300000u));
-    static const int dbg_cyc = getenv("NARUTO_DEBUG_SCATTER_CYCLIC") ? atoi(getenv("NARUTO_DEBUG_SCATTER_CYCLIC")) : -1;             // profiling knob
+    static const int dbg_cyc = env_int("NARUTO_DEBUG_SCATTER_CYCLIC", -1);             // profiling knob
     plan.cyclic = (uint8_t)(dbg_cyc >= 0 ? (dbg_cyc != 0) : (M <= 300000u));
     return plan;
 }
@@ -193,22 +249,19 @@ inline uint32_t uncert_pad(const NarutoField* f) { return (f->plan.uncert_voxels
 
 ScatterWs scatter_ws(const NarutoField* f, void* base, uint32_t M) {
     ScatterWs w{};
-    char* b = reinterpret_cast<char*>(base);
-    size_t off = 0;
+    Carve c(base);
     uint32_t smax = 1;
     const LevelSplits ls_ = level_splits(f, M);
     for (int l = 0; l < kLevels; ++l) smax = ls_.s[l] > smax ? ls_.s[l] : smax;
-    w.partial = reinterpret_cast<float*>(b + off);
-    off += al256((f->plan.n_dense + f->plan.n_hashed) ? (size_t)smax * partial_plane(f) * 2u * sizeof(float) : 16u);
-    w.unc_partial = reinterpret_cast<float*>(b + off);
-    off += al256(f->plan.n_uncert ? (size_t)uncert_splits(f, M) * uncert_pad(f) * sizeof(float) : 16u);
+    w.partial = c.take<float>((f->plan.n_dense + f->plan.n_hashed) ? (size_t)smax * partial_plane(f) * 2u * sizeof(float) : 16u);
+    w.unc_partial = c.take<float>(f->plan.n_uncert ? (size_t)uncert_splits(f, M) * uncert_pad(f) * sizeof(float) : 16u);
     if (f->bplan.n_levels != 0) {
-        w.counts = reinterpret_cast<uint32_t*>(b + off); off += al256((size_t)bin_rows(M) * f->bplan.n_bins * sizeof(uint32_t));
-        w.totals = reinterpret_cast<uint32_t*>(b + off); off += al256((size_t)f->bplan.n_bins * sizeof(uint32_t));
-        w.starts = reinterpret_cast<uint32_t*>(b + off); off += al256(((size_t)f->bplan.n_bins + 1u) * sizeof(uint32_t));
-        w.items = reinterpret_cast<BinItem*>(b + off);   off += al256((size_t)M * f->bplan.n_levels * kBinItemsPerPoint * sizeof(BinItem));
+        w.counts = c.take<uint32_t>((size_t)bin_rows(M) * f->bplan.n_bins * sizeof(uint32_t));
+        w.totals = c.take<uint32_t>((size_t)f->bplan.n_bins * sizeof(uint32_t));
+        w.starts = c.take<uint32_t>(((size_t)f->bplan.n_bins + 1u) * sizeof(uint32_t));
+        w.items = c.take<BinItem>((size_t)M * f->bplan.n_levels * kBinItemsPerPoint * sizeof(BinItem));
     }
-    w.total = off;
+    w.total = c.size();
     return w;
 }
 
@@ -237,11 +290,7 @@ int launch_scatter(const NarutoField* f, const PointSrc& ps, uint32_t M, const f
     if (f->plan.n_dense + f->plan.n_hashed > 0) {
         static bool attr_set = false;
         const size_t lds = kScatterLdsBytes;
-        if (!attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_hash_scatter_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return fail(NARUTO_ERR_LAUNCH, "hash_scatter: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(hipGetLastError()));
-            attr_set = true;
-        }
+        if (int rc = reserve_lds(attr_set, {lds_use(k_hash_scatter_lds, lds)}, "hash_scatter: cannot reserve %zu bytes of LDS", lds)) return rc;
         const uint32_t blocks = ((uint32_t)plan.n_level_blocks + (us.g != nullptr ? plan.n_uncert * us.n_splits : 0u) + 7u) / 8u * 8u;      // XCD-aware order: multiple of 8
         hipLaunchKernelGGL(k_hash_scatter_lds, dim3(blocks), dim3(kScatterThreads), lds, st, f->lt, f->bt, ps, M, d_feat, stride_m, stride_l, plan,
                            w.partial, 2u * n_plane, m_dev, scale_dev, us, g_fwd_timeline);
@@ -262,18 +311,14 @@ int launch_scatter(const NarutoField* f, const PointSrc& ps, uint32_t M, const f
             return fail(NARUTO_ERR_INVALID, "scatter: %u list points x %u binned levels x 8 items overflow the 32-bit item offsets (split the batch)", M, f->bplan.n_levels);
         uint32_t nb_max = 0;
         for (uint32_t k = 0; k < f->bplan.n_levels; ++k) nb_max = f->bplan.bin0[k + 1] - f->bplan.bin0[k] > nb_max ? f->bplan.bin0[k + 1] - f->bplan.bin0[k] : nb_max;
-        static const bool force_512 = getenv("NARUTO_DEBUG_BIN_ROUND") != nullptr && atoi(getenv("NARUTO_DEBUG_BIN_ROUND")) == 512;      // same bits: fixed-point sums
+        static const bool force_512 = env_int("NARUTO_DEBUG_BIN_ROUND", 0) == 512;      // same bits: fixed-point sums
         const bool round_1024 = !force_512 && bin_fill_lds_bytes(1024u, nb_max) <= (size_t)160u * 1024u;            // else 512-point rounds (T = 2^24)
         static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_bin_fill<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(k_bin_fill<512>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)bin_fill_lds_bytes(512u, (uint32_t)kMaxBinsPerLevel)) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(k_bin_apply), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(2u * kBinEntries * sizeof(unsigned long long))) != hipSuccess)
-                return fail(NARUTO_ERR_LAUNCH, "binned scatter: cannot reserve LDS: %s", hipGetErrorString(hipGetLastError()));
-            attr_set = true;
-        }
+        if (int rc = reserve_lds(attr_set,
+                                 {lds_use(k_bin_fill<1024>, 160u * 1024u), lds_use(k_bin_fill<512>, bin_fill_lds_bytes(512u, (uint32_t)kMaxBinsPerLevel)),
+                                  lds_use(k_bin_apply, 2u * kBinEntries * sizeof(unsigned long long))},
+                                 "binned scatter: cannot reserve LDS"))
+            return rc;
         const BinPlan& bp = f->bplan;
         const uint32_t rows = bin_rows(M);
         hipLaunchKernelGGL(k_bin_count, dim3(rows, bp.n_levels), dim3(kBinThreads), 0, st, f->lt, f->bt, ps, M, d_feat, stride_m, stride_l, bp, w.counts, m_dev);
@@ -587,11 +632,7 @@ int naruto_hash_encode_bwd(const NarutoField* f, uint32_t M, const float* x, con
     return launch_scatter(f, ps, M, d_feat, (size_t)kFeat, (size_t)2, d_table, workspace, (hipStream_t)stream, nullptr, d_feat_scale);
 }
 
-size_t naruto_smoothness_workspace(uint32_t sample_points) {
-    const size_t n = sample_points > 1 ? sample_points - 1 : 1;
-    const size_t n3 = n * n * n;
-    return n3 * kFeat * sizeof(float) + ((n3 * kFeat + 255) / 256) * sizeof(double) + 64;
-}
+size_t naruto_smoothness_workspace(uint32_t sample_points) { return tv_ws(nullptr, sample_points > 1 ? sample_points - 1 : 1).total; }
 
 int naruto_smoothness_fwd(const NarutoField* f, const float* table, uint32_t sample_points, float voxel_size, float margin, const float* rand6,
                           float* x_out, float* d_feat, float* loss, void* workspace, void* stream) {
@@ -605,15 +646,14 @@ int naruto_smoothness_fwd(const NarutoField* f, const float* table, uint32_t sam
     a.grid_size = (float)(sample_points - 1) * voxel_size;
     a.inv_p3 = 1.0f / ((float)sample_points * (float)sample_points * (float)sample_points);
     const uint32_t n3 = a.n * a.n * a.n;
-    float* feat = reinterpret_cast<float*>(workspace);
-    double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (((size_t)n3 * kFeat * sizeof(float) + 63) / 64) * 64);
+    const TvWs w = tv_ws(workspace, a.n);
     const uint32_t nb = (n3 * kFeat + 255u) / 256u;
     hipLaunchKernelGGL(k_tv_encode, dim3(tv_encode_blocks(n3)), dim3(256), 0, (hipStream_t)stream, f->lt, f->bt, a, rand6,
-                       static_cast<const uint64_t*>(nullptr), reinterpret_cast<const float2*>(table), x_out, feat);
+                       static_cast<const uint64_t*>(nullptr), reinterpret_cast<const float2*>(table), x_out, w.feat);
     if (int rc = check_launch("tv_encode")) return rc;
-    hipLaunchKernelGGL(k_tv_loss, dim3(nb), dim3(256), 0, (hipStream_t)stream, a, feat, d_feat, partial);
+    hipLaunchKernelGGL(k_tv_loss, dim3(nb), dim3(256), 0, (hipStream_t)stream, a, w.feat, d_feat, w.partial);
     if (int rc = check_launch("tv_loss")) return rc;
-    hipLaunchKernelGGL(k_tv_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nb, a.inv_p3, loss);
+    hipLaunchKernelGGL(k_tv_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, w.partial, nb, a.inv_p3, loss);
     return check_launch("tv_finalize");
 }
 
@@ -639,13 +679,13 @@ int naruto_query_fwd(const NarutoField* f, const NarutoParams* p, uint32_t M, co
     const bool bf = f->desc.mlp_mode == NARUTO_MLP_BF16;
     // between one and two four-wave workgroups per CU: two-wave workgroups instead, so that no CU holds more tiles than it must
     // (see k_query_fwd).  NARUTO_DEBUG_FWD_SMALL_WG=0: the four-wave form everywhere (A/B timing).
-    static const bool small_wg_on = getenv("NARUTO_DEBUG_FWD_SMALL_WG") == nullptr || atoi(getenv("NARUTO_DEBUG_FWD_SMALL_WG")) != 0;
+    static const bool small_wg_on = env_int("NARUTO_DEBUG_FWD_SMALL_WG", 1) != 0;
     const bool small_wg = small_wg_on && n_tiles > cu_count(f) * 4u && n_tiles < cu_count(f) * 8u;
     const hipStream_t st = (hipStream_t)stream;
     // launch shape (fp32, phase-split tiles; measured in tools/fwd_lab.hip / profiles/r04_fwd_lab.txt): from 8 tiles per CU on, ONE persistent 8-wave
     // workgroup per CU (one weight image, the waves walk their tiles: 76.5 -> 69.0 us at 4 096 tiles); below that the smaller forms spread the tiles better
     // (1 376 tiles: 42.2 us as 2-wave workgroups, 45.6 as 8-wave ones).  NARUTO_DEBUG_FWD_SHAPE=0: the old shapes everywhere (A/B timing).
-    static const bool big_wg_on = getenv("NARUTO_DEBUG_FWD_SHAPE") == nullptr || atoi(getenv("NARUTO_DEBUG_FWD_SHAPE")) != 0;
+    static const bool big_wg_on = env_int("NARUTO_DEBUG_FWD_SHAPE", 1) != 0;
     const bool big_wg = big_wg_on && kFwdSplit && n_tiles >= cu_count(f) * 8u;
 #define NARUTO_LAUNCH_FWD(KERNEL, COLOR)                                                                                                                      \
     do {                                                                                                                                                        \
@@ -661,28 +701,16 @@ int naruto_query_fwd(const NarutoField* f, const NarutoParams* p, uint32_t M, co
     return check_launch("query_fwd");
 }
 
-size_t naruto_query_bwd_workspace(const NarutoField* f, uint32_t M) {
-    // M here = points + extra points.  d_feat [16][cap][2] | x [4][cap] (x, y, z, d raw[...,4]) | wgrad partials | scatter partials | count word
-    M = list_cap(M);
-    return ((size_t)kLevels * 2u + 4u) * sizeof(float) * (size_t)M + (size_t)kBwdMaxBlocks * kAccFloats * sizeof(float) + naruto_scatter_workspace(f, M) + 64;
-}
-
 }  // extern "C"
 
 namespace {
-struct BwdWs {
-    float* d_feat; float* x_soa; float* partials; float* scatter_ws; uint32_t* n_total;
-};
-// layout of naruto_query_bwd_workspace(): the scatter's point list (d_feat [16][cap][2], x [4][cap]), wgrad partials,
-// scatter partial tables, one count word
+// workspace of the query backward for a list of `cap` = list_cap(points + extra points) points; the float runs follow each other unpadded:
+// | d_feat [16][cap][2] | x [4][cap] (x, y, z, cotangent of raw[...,4]) | wgrad partials | the scatter's workspace | count word + pad |
+struct BwdWs { float* d_feat; float* x_soa; float* partials; float* scatter_ws; uint32_t* n_total; size_t total; };
 BwdWs bwd_ws(const NarutoField* f, void* workspace, uint32_t cap) {
-    BwdWs w;
-    w.d_feat = reinterpret_cast<float*>(workspace);
-    w.x_soa = w.d_feat + (size_t)kLevels * 2u * (size_t)cap;
-    w.partials = w.x_soa + 4u * (size_t)cap;          // x, y, z, cotangent of raw[...,4]
-    w.scatter_ws = w.partials + (size_t)kBwdMaxBlocks * kAccFloats;
-    w.n_total = reinterpret_cast<uint32_t*>(w.scatter_ws + naruto_scatter_workspace(f, cap) / sizeof(float));
-    return w;
+    Carve c(workspace);
+    return {c.take<float>((size_t)kLevels * 2u * (size_t)cap * sizeof(float), 1u), c.take<float>(4u * (size_t)cap * sizeof(float), 1u),
+            c.take<float>((size_t)kBwdMaxBlocks * kAccFloats * sizeof(float), 1u), c.take<float>(naruto_scatter_workspace(f, cap), 1u), c.take<uint32_t>(64u, 1u), c.size()};
 }
 
 // n_front > 0 (fused training path): list positions [0, n_front) were filled by the caller (smoothness lattice: points
@@ -715,17 +743,13 @@ int query_bwd_impl(const NarutoField* f, const NarutoParams* p, uint32_t M, cons
     uint32_t blocks = (n_tiles + waves - 1u) / waves;
     uint32_t max_blocks = cu_count(f) * (bf ? (uint32_t)NARUTO_BWD_BF_MINWAVES : 1u);
     if (max_blocks > kBwdMaxBlocks) max_blocks = kBwdMaxBlocks;
-    static const int dbg_blocks = getenv("NARUTO_DEBUG_BWD_BLOCKS") ? atoi(getenv("NARUTO_DEBUG_BWD_BLOCKS")) : 0;       // profiling knob
+    static const int dbg_blocks = env_int("NARUTO_DEBUG_BWD_BLOCKS", 0);       // profiling knob
     if (dbg_blocks > 0 && (uint32_t)dbg_blocks < max_blocks) max_blocks = (uint32_t)dbg_blocks;
     if (blocks > max_blocks) blocks = max_blocks;
     const PointSrc ps = make_points(pts);
     static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BwdLds)) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_bwd_bf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBwdBfLdsBytes) != hipSuccess)
-            return fail(NARUTO_ERR_LAUNCH, "query_bwd: cannot reserve %zu bytes of LDS: %s", sizeof(BwdLds), hipGetErrorString(hipGetLastError()));
-        attr_set = true;
-    }
+    if (int rc = reserve_lds(attr_set, {lds_use(k_query_bwd, sizeof(BwdLds)), lds_use(k_query_bwd_bf, kBwdBfLdsBytes)}, "query_bwd: cannot reserve %zu bytes of LDS", sizeof(BwdLds)))
+        return rc;
     // the uncertainty grid's gradient: through the scatter (row 3 of the point list) unless the grid is too large for that
     const bool unc_scatter = g->uncert_grid != nullptr && f->plan.n_uncert != 0;
     const int unc_atomic = (g->uncert_grid != nullptr && f->plan.n_uncert == 0) ? 1 : 0;
@@ -816,6 +840,8 @@ int query_bwd_impl(const NarutoField* f, const NarutoParams* p, uint32_t M, cons
 
 extern "C" {
 
+size_t naruto_query_bwd_workspace(const NarutoField* f, uint32_t M) { return bwd_ws(f, nullptr, list_cap(M)).total; }
+
 int naruto_query_bwd(const NarutoField* f, const NarutoParams* p, uint32_t M, const NarutoPoints* pts, const float* feat_save,
                      const float* d_raw, const float* d_geo, const uint32_t* active_idx, const uint32_t* n_active, const NarutoExtraPoints* extra,
                      uint32_t flags, const NarutoGrads* g, void* workspace, void* stream) {
@@ -825,10 +851,7 @@ int naruto_query_bwd(const NarutoField* f, const NarutoParams* p, uint32_t M, co
 // ------------------------------------------------------------------------------------------------
 // Gradient of the query with respect to its points (see naruto_pointgrad.hip)
 // ------------------------------------------------------------------------------------------------
-size_t naruto_query_bwd_points_workspace(const NarutoField* f, uint32_t M) {
-    (void)f;
-    return 3u * sizeof(float) * (size_t)M + 256u;
-}
+size_t naruto_query_bwd_points_workspace(const NarutoField*, uint32_t M) { return point_grad_ws(nullptr, M).total; }
 
 int naruto_query_bwd_points(const NarutoField* f, const NarutoParams* p, uint32_t M, const NarutoPoints* pts, const float* d_raw, const float* d_geo,
                             const uint32_t* active_idx, const uint32_t* n_active, float* d_x, float* d_rays_o, float* d_rays_d, uint32_t flags,
@@ -855,7 +878,7 @@ int naruto_query_bwd_points(const NarutoField* f, const NarutoParams* p, uint32_
         if (workspace == nullptr) return fail(NARUTO_ERR_INVALID, "query_bwd_points: ray points need naruto_query_bwd_points_workspace(f, M) bytes of workspace");
     }
     if (M == 0) return NARUTO_OK;
-    float* out = rays ? reinterpret_cast<float*>(workspace) : d_x;
+    float* out = rays ? point_grad_ws(workspace, M).d_x : d_x;
     // a list leaves the other points' rows alone: they must read as zero where the result is written, not added
     if (active_idx != nullptr && (rays || !acc)) {
         if (hipMemsetAsync(out, 0, 3u * sizeof(float) * (size_t)M, st) != hipSuccess) return check_launch("query_bwd_points: zero fill");
@@ -889,19 +912,17 @@ TrainWs train_ws(const NarutoField* f, const NarutoTrainStep* t) {
     w.n3 = n * n * n;
     w.n_tv_blocks = (w.n3 * (uint32_t)kFeat + 255u) / 256u;        // smoothness role blocks of the loss stage (grid-stride beyond 512: more
     if (w.n_tv_blocks > 512u) w.n_tv_blocks = 512u;                // blocks only move the time into the one-workgroup tail)
-    auto al = [](size_t b) { return (b + 255u) / 256u * 256u; };
-    size_t off = 0;
-    char* base = reinterpret_cast<char*>(t->workspace);
-    w.terms = reinterpret_cast<float*>(base + off);       off += al((size_t)t->n_rays * 16u * sizeof(float));
-    w.tv_feat = reinterpret_cast<float*>(base + off);     off += al((size_t)w.n3 * kFeat * sizeof(float));
-    w.tv_partial = reinterpret_cast<double*>(base + off); off += al((size_t)w.n_tv_blocks * sizeof(double));
-    w.fold = reinterpret_cast<double*>(base + off);       off += al((size_t)kTailRows * 16u * sizeof(double));
-    w.block_sums = reinterpret_cast<uint32_t*>(base + off); off += al(((size_t)t->n_rays / kCompactBlock + 2u) * sizeof(uint32_t));
-    w.w_img = base + off;                                 off += al(bwd_weight_image_bytes());
-    w.w10 = reinterpret_cast<float*>(base + off);         off += al(16u * sizeof(float));          // gathered loss_weight_parts
-    w.bwd = base + off;                                   off += al(naruto_query_bwd_workspace(f, (uint32_t)(M + w.n3)));
-    w.sort = reinterpret_cast<uint32_t*>(base + off);     off += al(sort_ws_words(M) * sizeof(uint32_t));     // (every plan: the plan is not known here, and it is 12 B per sample)
-    w.total = off;
+    Carve c(t->workspace);
+    w.terms = c.take<float>((size_t)t->n_rays * 16u * sizeof(float));
+    w.tv_feat = c.take<float>((size_t)w.n3 * kFeat * sizeof(float));
+    w.tv_partial = c.take<double>((size_t)w.n_tv_blocks * sizeof(double));
+    w.fold = c.take<double>((size_t)kTailRows * 16u * sizeof(double));
+    w.block_sums = c.take<uint32_t>(((size_t)t->n_rays / kCompactBlock + 2u) * sizeof(uint32_t));
+    w.w_img = c.take<void>(bwd_weight_image_bytes());
+    w.w10 = c.take<float>(16u * sizeof(float));          // gathered loss_weight_parts
+    w.bwd = c.take<void>(bwd_ws(f, nullptr, list_cap((uint32_t)(M + w.n3))).total);
+    w.sort = c.take<uint32_t>(sort_ws_words(M) * sizeof(uint32_t));     // (every plan: the plan is not known here, and it is 12 B per sample)
+    w.total = c.size();
     return w;
 }
 int train_check(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const char* who) {
@@ -955,16 +976,16 @@ struct TrainFwdPlan {
 // what a Packed workgroup of W waves keeps besides its rays: the static LDS of the fp32 form (the larger) + 256 B
 inline size_t packed_fixed_lds(uint32_t W) { return (W == 4u ? packed_static_lds<false, 4>() : packed_static_lds<false, 8>()) + 256u; }
 TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool with_loss, bool deferred) {
-    static const bool tv_on = getenv("NARUTO_TV_MOVE") == nullptr || atoi(getenv("NARUTO_TV_MOVE")) != 0;
+    static const bool tv_on = env_int("NARUTO_TV_MOVE", 1) != 0;
     static const bool no_fuse = getenv("NARUTO_DEBUG_NO_FUSED_LOSS_STAGE") != nullptr, no_ee = getenv("NARUTO_DEBUG_NO_EARLY_EXIT") != nullptr;
-    static const int packed_mode = getenv("NARUTO_FWD_PACKED") == nullptr ? 1 : atoi(getenv("NARUTO_FWD_PACKED"));
-    static const int partial_mode = getenv("NARUTO_WALK_PARTIAL") == nullptr ? 1 : atoi(getenv("NARUTO_WALK_PARTIAL"));
+    static const int packed_mode = env_int("NARUTO_FWD_PACKED", 1);
+    static const int partial_mode = env_int("NARUTO_WALK_PARTIAL", 1);
     // measured (tools/walk_ab.sh, profiles/r05_walk_ab.txt): Short wins while its workgroups are ONE round (two per CU: 8 tiles) -- 2 048 x 43
     // 0.171 -> 0.159 ms, the BA batch 0.1875 -> 0.1795 -- and loses beyond (8 192 x 43: 0.391 -> 0.408, 131 072 x 43: 4.86 -> 4.92)
-    static const uint32_t partial_max = getenv("NARUTO_WALK_PARTIAL_MAX") ? (uint32_t)atoi(getenv("NARUTO_WALK_PARTIAL_MAX")) : 8u;
+    static const uint32_t partial_max = (uint32_t)env_int("NARUTO_WALK_PARTIAL_MAX", 8);
     const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d;
-    static const bool small_wg_on = getenv("NARUTO_DEBUG_FWD_SMALL_WG") == nullptr || atoi(getenv("NARUTO_DEBUG_FWD_SMALL_WG")) != 0;
-    static const int pack_waves = getenv("NARUTO_PACK_WAVES") ? atoi(getenv("NARUTO_PACK_WAVES")) : 8;
+    static const bool small_wg_on = env_int("NARUTO_DEBUG_FWD_SMALL_WG", 1) != 0;
+    static const int pack_waves = env_int("NARUTO_PACK_WAVES", 8);
     TrainFwdPlan pl{FwdForm::Flat, false, false, false, 0u, (uint32_t)kRaysPerBlock, 0u, 256u, 0u, 0u};
     // the flat launch, where every other form falls back to: 64-sample tiles; between one and two four-wave workgroups per CU (2 048 rays
     // x 43 samples: 1 376 tiles) two-wave workgroups (see k_query_fwd), from two per CU on one eight-wave workgroup per CU
@@ -978,7 +999,7 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
     if (packed_on && packed_mode == 1) packed_on = (size_t)f->n_entries * 2u * sizeof(float) > ((size_t)64u << 20);
     // NARUTO_FWD_SORTED: 1 (default) the Morton-ordered forward for tables of more than 64 MB -- where every gather is an HBM line --, 2 for
     // every table (tests), 0 never (the packed forward as in round 4 / 5)
-    static const int sorted_mode = getenv("NARUTO_FWD_SORTED") == nullptr ? 1 : atoi(getenv("NARUTO_FWD_SORTED"));
+    static const int sorted_mode = env_int("NARUTO_FWD_SORTED", 1);
     const bool big_table = (size_t)f->n_entries * 2u * sizeof(float) > ((size_t)64u << 20);
     // (cache-resident tables too once the batch is millions of samples -- 131 072 x 43 at T = 2^16: 5.05 -> 4.71 ms -- but not below: 8 192 x 43 0.349 -> 0.380)
     const bool big_batch = (uint64_t)N * S >= 4000000ull && S <= 64u;
@@ -1041,7 +1062,7 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
 // losses with the backward's last launch -- k_sample_encode has no launch of its own.  NARUTO_TV_MOVE=0: the six-launch form (same bits).
 // level groups per lattice-encode workgroup where the encode rides as tail role of the training forward (NARUTO_TV_TAIL_GROUPS: 1, 2, 4)
 inline uint32_t tv_tail_groups() {
-    static const uint32_t g = getenv("NARUTO_TV_TAIL_GROUPS") ? (uint32_t)atoi(getenv("NARUTO_TV_TAIL_GROUPS")) : 1u;
+    static const uint32_t g = (uint32_t)env_int("NARUTO_TV_TAIL_GROUPS", 1);
     return g;
 }
 inline bool tv_moved(const NarutoField* f, const NarutoTrainStep* t, bool deferred) { return train_fwd_plan(f, t, true, deferred).tv_moved; }
@@ -1108,27 +1129,19 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
     if (pl.form == FwdForm::Packed) {
         const uint32_t W = pl.pack_waves, per_cu = W == 4u ? 2u : 1u, rows = pl.pack_rows;
         const size_t lds_free = (size_t)160u * 1024u / per_cu - packed_fixed_lds(W);
-        static size_t attr_bytes[2] = {0, 0};
+        // (each shape reserves all its workgroup can have, once: the plan's rows never need more)
+        static bool attr_set[2] = {false, false};
         const size_t need = packed_lds_bytes(rows, S);
-        if (need > attr_bytes[W == 4u]) {
-            hipError_t e1, e2;
-            if (W == 4u) {
-                e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
-                e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
-            } else {
-                e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
-                e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_query_fwd_loss_packed<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_free);
-            }
-            if (e1 != hipSuccess || e2 != hipSuccess)
-                return fail(NARUTO_ERR_LAUNCH, "query_fwd_loss_packed: cannot reserve %zu bytes of LDS: %s", lds_free, hipGetErrorString(hipGetLastError()));
-            attr_bytes[W == 4u] = lds_free;
-        }
+        const char* const cannot = "query_fwd_loss_packed: cannot reserve %zu bytes of LDS";
+        if (int rc = W == 4u ? reserve_lds(attr_set[1], {lds_use(k_query_fwd_loss_packed<false, 4>, lds_free), lds_use(k_query_fwd_loss_packed<true, 4>, lds_free)}, cannot, lds_free)
+                             : reserve_lds(attr_set[0], {lds_use(k_query_fwd_loss_packed<false, 8>, lds_free), lds_use(k_query_fwd_loss_packed<true, 8>, lds_free)}, cannot, lds_free))
+            return rc;
         const uint32_t pblocks = pl.blocks;
         EarlyExit pe{};
         pe.target_d = t->target_d;
         pe.trunc_sc = f->desc.trunc * f->desc.sc_factor;
         const bool bfm = f->desc.mlp_mode == NARUTO_MLP_BF16;
-        static const int one_pass_env = getenv("NARUTO_PACK_ONE_PASS") ? atoi(getenv("NARUTO_PACK_ONE_PASS")) : -1;
+        static const int one_pass_env = env_int("NARUTO_PACK_ONE_PASS", -1);
         const bool one_pass = one_pass_env == 1;
         uint32_t rays_cap = rows * (uint32_t)kRaysPerBlock;
         if (one_pass && rays_cap * S > 64u * W && 64u * W / S >= 1u) rays_cap = 64u * W / S;           // one pass: all of a chunk's samples in one group of tiles
@@ -1248,7 +1261,7 @@ inline size_t render_packed8_reserve() {
     return m;
 }
 RenderPlan render_plan(const NarutoField* f, uint32_t n_rays, uint32_t S, bool bf, int wide) {
-    static const int wide_env = getenv("NARUTO_RENDER_WIDE") ? atoi(getenv("NARUTO_RENDER_WIDE")) : 1;
+    static const int wide_env = env_int("NARUTO_RENDER_WIDE", 1);
     if (wide < 0) wide = wide_env;
     RenderPlan pl{};
     const uint32_t cap = cu_count(f) * 4u;
@@ -1335,7 +1348,7 @@ int naruto_train_forward(const NarutoField* f, const NarutoParams* p, const Naru
         wx.rand6 = t->rand6; wx.rng = t->rng; wx.x_out = bw.x_soa;
     } else if (t->smooth_points != 0) {
         SampleArgs sa{N, t->target_d, t->near_, t->far_, t->n_samples_d, t->n_range_d, t->range_d, jitter, jitter_rng, t->z_vals, (N + 3u) / 4u};
-        static const int dbg_roles = getenv("NARUTO_DEBUG_SAMPLE_ROLES") ? atoi(getenv("NARUTO_DEBUG_SAMPLE_ROLES")) : 3;   // profiling knob: 1 rays, 2 lattice
+        static const int dbg_roles = env_int("NARUTO_DEBUG_SAMPLE_ROLES", 3);   // profiling knob: 1 rays, 2 lattice
         if (dbg_roles == 2) sa.n_rays = 0;
         hipLaunchKernelGGL(k_sample_encode, dim3(sa.n_ray_blocks + (dbg_roles == 1 ? 0u : tv_encode_blocks(w.n3))), dim3(256), (size_t)4u * 2u * S * sizeof(float), st, sa, f->lt,
                            f->bt, tva, t->rand6, t->rng, reinterpret_cast<const float2*>(p->table), bw.x_soa, w.tv_feat);
@@ -1352,7 +1365,7 @@ int naruto_train_forward(const NarutoField* f, const NarutoParams* p, const Naru
     bool loss_done = false;
     if (int rc = launch_train_query(f, p, t, st, &a, &loss_done, &wx, deferred_)) return rc;
     if (!loss_done) {
-        static const int dbg_ls_roles = getenv("NARUTO_DEBUG_LOSS_STAGE_ROLES") ? atoi(getenv("NARUTO_DEBUG_LOSS_STAGE_ROLES")) : 3;     // profiling knob: 1 rays, 2 lattice
+        static const int dbg_ls_roles = env_int("NARUTO_DEBUG_LOSS_STAGE_ROLES", 3);     // profiling knob: 1 rays, 2 lattice
         if (dbg_ls_roles == 1) a.n_tv_blocks = 0;
         if (dbg_ls_roles == 2) a.n_rays = 0;
         hipLaunchKernelGGL(k_loss_stage, dim3(a.n_ray_blocks + a.n_tv_blocks), dim3(64 * kRaysPerBlock), ray_scratch_bytes(S), st, a);
@@ -1628,17 +1641,11 @@ int naruto_render_fwd(const NarutoField* f, const NarutoParams* p, const NarutoR
     const RenderPlan pl = render_plan(f, r->n_rays, S, bf, -1);
     // every kernel reserves, once, the dynamic LDS of the largest launch it may get (render_plan's reserved)
     static bool attr_set[3] = {false, false, false};
-    const int k = (int)pl.form;
-    if (!attr_set[k]) {
-        const void* fn_fp32 = pl.form == RenderForm::Ray ? reinterpret_cast<const void*>(k_render_fwd<false>)
-                            : pl.form == RenderForm::Packed4 ? reinterpret_cast<const void*>(k_render_fwd_packed<false, 256>) : reinterpret_cast<const void*>(k_render_fwd_packed<false, 512>);
-        const void* fn_bf = pl.form == RenderForm::Ray ? reinterpret_cast<const void*>(k_render_fwd<true>)
-                          : pl.form == RenderForm::Packed4 ? reinterpret_cast<const void*>(k_render_fwd_packed<true, 256>) : reinterpret_cast<const void*>(k_render_fwd_packed<true, 512>);
-        if (hipFuncSetAttribute(fn_fp32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.reserved) != hipSuccess ||
-            hipFuncSetAttribute(fn_bf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.reserved) != hipSuccess)
-            return fail(NARUTO_ERR_LAUNCH, "render_fwd: cannot reserve %zu bytes of LDS: %s", pl.reserved, hipGetErrorString(hipGetLastError()));
-        attr_set[k] = true;
-    }
+    const void* fn_fp32 = pl.form == RenderForm::Ray ? reinterpret_cast<const void*>(k_render_fwd<false>)
+                        : pl.form == RenderForm::Packed4 ? reinterpret_cast<const void*>(k_render_fwd_packed<false, 256>) : reinterpret_cast<const void*>(k_render_fwd_packed<false, 512>);
+    const void* fn_bf = pl.form == RenderForm::Ray ? reinterpret_cast<const void*>(k_render_fwd<true>)
+                      : pl.form == RenderForm::Packed4 ? reinterpret_cast<const void*>(k_render_fwd_packed<true, 256>) : reinterpret_cast<const void*>(k_render_fwd_packed<true, 512>);
+    if (int rc = reserve_lds(attr_set[(int)pl.form], {LdsUse{fn_fp32, pl.reserved}, LdsUse{fn_bf, pl.reserved}}, "render_fwd: cannot reserve %zu bytes of LDS", pl.reserved)) return rc;
     if (pl.dyn_lds > pl.reserved) return fail(NARUTO_ERR_LAUNCH, "render_fwd: %zu bytes of dynamic LDS, %zu reserved", pl.dyn_lds, pl.reserved);
     const hipStream_t st = (hipStream_t)stream;
     if (pl.form == RenderForm::Packed8) {
@@ -1701,7 +1708,7 @@ int naruto_composite_bwd(const NarutoField* f, uint32_t n_rays, uint32_t S, cons
     return check_launch("composite_bwd");
 }
 
-size_t naruto_loss_workspace(uint32_t n_rays) { return (size_t)n_rays * 16u * sizeof(float); }
+size_t naruto_loss_workspace(uint32_t n_rays) { return loss_ws(nullptr, n_rays).total; }
 
 int naruto_loss_sums(const NarutoField* f, uint32_t n_rays, uint32_t S, const float* raw, const float* z_vals, const float* rgb, const float* depth,
                      const float* uncert_map, const float* target_rgb, const float* target_d, float depth_trunc, float rgb_missing, double* sums,
@@ -1710,7 +1717,7 @@ int naruto_loss_sums(const NarutoField* f, uint32_t n_rays, uint32_t S, const fl
         target_d == nullptr || sums == nullptr || workspace == nullptr)
         return fail(NARUTO_ERR_INVALID, "loss_sums: NULL argument");
     if (n_rays == 0) return fail(NARUTO_ERR_INVALID, "loss_sums: no rays");
-    float* terms = reinterpret_cast<float*>(workspace);
+    float* terms = loss_ws(workspace, n_rays).terms;
     hipLaunchKernelGGL(k_loss_terms, dim3((n_rays + kRaysPerBlock - 1) / kRaysPerBlock), dim3(64 * kRaysPerBlock), 0, (hipStream_t)stream, n_rays, S,
                        f->desc.trunc * f->desc.sc_factor, raw, z_vals, rgb, depth, uncert_map, target_rgb, target_d, depth_trunc, rgb_missing, terms);
     if (int rc = check_launch("loss_terms")) return rc;
@@ -1765,7 +1772,7 @@ int naruto_adam_step(float* param, const float* grad, float* exp_avg, float* exp
     return check_launch("adam_step");
 }
 
-size_t naruto_active_ray_workspace(uint32_t n_total, uint32_t K) { return ((size_t)n_total + K + 16) * sizeof(uint32_t); }
+size_t naruto_active_ray_workspace(uint32_t n_total, uint32_t K) { return select_ws(nullptr, n_total, K, kArsPadWords).total; }
 
 int naruto_active_ray_select(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o, const float* rays_d, const float* target_s,
                              const float* target_d, const float* uncert_vol, const uint32_t* vol_dims, const float* bbox_min, float voxel_scale,
@@ -1784,7 +1791,7 @@ int naruto_active_ray_select_rows(uint32_t n_total, uint32_t base, uint32_t K, u
         return fail(NARUTO_ERR_INVALID, "active_ray_select: need 0 < K <= base, n_tail > 0, base + n_tail < n_total");
     const uint32_t n_cand = n_total - n_tail - base;
     if (n_cand <= K) return fail(NARUTO_ERR_INVALID, "active_ray_select: %u candidates for K = %u (numpy argpartition needs K < n)", n_cand, K);
-    static const bool fused_on = getenv("NARUTO_DEBUG_ARS_FUSED") == nullptr || atoi(getenv("NARUTO_DEBUG_ARS_FUSED")) != 0;
+    static const bool fused_on = env_int("NARUTO_DEBUG_ARS_FUSED", 1) != 0;
     if (fused_on && n_cand <= kArsFusedMax) {
         // lookup, selection and gather in one launch (k_ars_fused); NARUTO_DEBUG_ARS_FUSED=0: the three launches below (same result)
         ArsArgs a{};
@@ -1797,16 +1804,15 @@ int naruto_active_ray_select_rows(uint32_t n_total, uint32_t base, uint32_t K, u
         hipLaunchKernelGGL(k_ars_fused<false>, dim3(1u + (n_copy + kArsFusedThreads - 1u) / kArsFusedThreads), dim3(kArsFusedThreads), 0, (hipStream_t)stream, a, AssembleArgs{});
         return check_launch("ars_fused");
     }
-    uint32_t* keys = reinterpret_cast<uint32_t*>(workspace);
-    uint32_t* sel = keys + n_cand;
+    const SelectWs w = select_ws(workspace, n_cand, K, kArsPadWords);
     hipLaunchKernelGGL(k_ars_lookup, dim3((n_cand + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, n_cand, base, rays_o, rays_d, target_d, uncert_vol,
-                       (int)vol_dims[0], (int)vol_dims[1], (int)vol_dims[2], bbox_min[0], bbox_min[1], bbox_min[2], voxel_scale, keys);
+                       (int)vol_dims[0], (int)vol_dims[1], (int)vol_dims[2], bbox_min[0], bbox_min[1], bbox_min[2], voxel_scale, w.keys);
     if (int rc = check_launch("ars_lookup")) return rc;
-    if (n_cand <= 1024u * kArsPer) hipLaunchKernelGGL(k_ars_select_small, dim3(1), dim3(1024), 0, (hipStream_t)stream, n_cand, K, keys, sel);
-    else hipLaunchKernelGGL(k_ars_select, dim3(1), dim3(1024), 0, (hipStream_t)stream, n_cand, K, keys, sel);
+    if (n_cand <= 1024u * kArsPer) hipLaunchKernelGGL(k_ars_select_small, dim3(1), dim3(1024), 0, (hipStream_t)stream, n_cand, K, w.keys, w.sel);
+    else hipLaunchKernelGGL(k_ars_select, dim3(1), dim3(1024), 0, (hipStream_t)stream, n_cand, K, w.keys, w.sel);
     if (int rc = check_launch("ars_select")) return rc;
     const uint32_t n_out = base + n_tail;
-    hipLaunchKernelGGL(k_ars_gather, dim3((n_out + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, n_out, K, base, n_total, n_tail, sel, rays_o, rays_d,
+    hipLaunchKernelGGL(k_ars_gather, dim3((n_out + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, n_out, K, base, n_total, n_tail, w.sel, rays_o, rays_d,
                        target_s, target_d, out_o, out_d, out_s, out_t, src_rows);
     return check_launch("ars_gather");
 }
@@ -1844,7 +1850,7 @@ int naruto_rays_to_world(uint32_t n, const float* d_cam, const int64_t* pose_id,
     return check_launch("rays_to_world");
 }
 
-size_t naruto_goal_targets_workspace(uint32_t n_voxels, uint32_t top_k) { return ((size_t)n_voxels + top_k + 64u) * sizeof(uint32_t); }
+size_t naruto_goal_targets_workspace(uint32_t n_voxels, uint32_t top_k) { return select_ws(nullptr, n_voxels, top_k, kGoalPadWords).total; }
 
 int naruto_goal_targets(const uint32_t* dims, const float* uncert_vol, uint32_t top_k, uint32_t top_k_subset, int32_t* targets, void* workspace, void* stream) {
     if (dims == nullptr || uncert_vol == nullptr || targets == nullptr || workspace == nullptr) return fail(NARUTO_ERR_INVALID, "goal_targets: NULL argument");
@@ -1852,14 +1858,13 @@ int naruto_goal_targets(const uint32_t* dims, const float* uncert_vol, uint32_t 
     if (n64 == 0 || n64 > 0x7FFFFFFFull) return fail(NARUTO_ERR_INVALID, "goal_targets: bad volume dimensions");
     const uint32_t n = (uint32_t)n64;
     if (top_k == 0 || top_k > n || top_k_subset == 0 || top_k_subset > top_k) return fail(NARUTO_ERR_INVALID, "goal_targets: need 1 <= subset <= top_k <= voxels");
-    uint32_t* keys = reinterpret_cast<uint32_t*>(workspace);
-    uint32_t* sel = keys + n;
+    const SelectWs w = select_ws(workspace, n, top_k, kGoalPadWords);
     const VolDims d{(int)dims[0], (int)dims[1], (int)dims[2]};
-    hipLaunchKernelGGL(k_topk_keys, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, n, uncert_vol, keys);
+    hipLaunchKernelGGL(k_topk_keys, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, n, uncert_vol, w.keys);
     if (int rc = check_launch("topk_keys")) return rc;
-    hipLaunchKernelGGL(k_ars_select, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, top_k, keys, sel);
+    hipLaunchKernelGGL(k_ars_select, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, top_k, w.keys, w.sel);
     if (int rc = check_launch("topk_select")) return rc;
-    hipLaunchKernelGGL(k_topk_thin, dim3((top_k_subset + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, sel, top_k, top_k_subset, d, targets);
+    hipLaunchKernelGGL(k_topk_thin, dim3((top_k_subset + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, w.sel, top_k, top_k_subset, d, targets);
     return check_launch("topk_thin");
 }
 
@@ -1900,20 +1905,24 @@ int rrt_plan(const NarutoRrtPlan* p, const char* who, RrtVol* vol) {
             return fail(NARUTO_ERR_INVALID, "%s: a sampling range has lo > hi", who);
     return NARUTO_OK;
 }
-int32_t* rrt_state(const NarutoRrtPlan* p) { return reinterpret_cast<int32_t*>(p->workspace); }
-double* rrt_goal(const NarutoRrtPlan* p) { return reinterpret_cast<double*>(reinterpret_cast<char*>(p->workspace) + kRrtGoalOffset); }
-int32_t* rrt_head(const NarutoRrtPlan* p) { return reinterpret_cast<int32_t*>(reinterpret_cast<char*>(p->workspace) + kRrtHeadOffset); }
+// workspace of the RRT over a volume: | state int32[16] (to kRrtGoalOffset) | goal fp64[4] (to kRrtHeadOffset) | head of every cell's node list int32[X*Y*Z] |
+struct RrtWs { int32_t* state; double* goal; int32_t* head; size_t total; };
+RrtWs rrt_ws(void* base, const RrtVol& vol) {
+    static_assert(kRrtGoalOffset >= (int)(kRrtStateInts * sizeof(int32_t)) && kRrtHeadOffset >= kRrtGoalOffset + (int)(4u * sizeof(double)), "sections overlap");
+    Carve c(base);
+    return {c.take<int32_t>(kRrtGoalOffset, 1u), c.take<double>(kRrtHeadOffset - kRrtGoalOffset, 1u), c.take<int32_t>((size_t)vol.X * vol.Y * vol.Z * sizeof(int32_t), 1u), c.size()};
+}
 }  // namespace
 
 size_t naruto_rrt_workspace(const uint32_t* dims) {
     RrtVol vol;
-    if (rrt_dims(dims, "rrt_workspace", &vol, nullptr)) return 0;
-    return (size_t)kRrtHeadOffset + (size_t)vol.X * vol.Y * vol.Z * sizeof(int32_t);
+    return rrt_dims(dims, "rrt_workspace", &vol, nullptr) ? 0 : rrt_ws(nullptr, vol).total;
 }
 
 int naruto_rrt_start(const NarutoRrtPlan* plan, const double* start, const double* goal, void* stream) {
     RrtVol vol;
     if (int rc = rrt_plan(plan, "rrt_start", &vol)) return rc;
+    const RrtWs w = rrt_ws(plan->workspace, vol);
     if (start == nullptr || goal == nullptr) return fail(NARUTO_ERR_INVALID, "rrt_start: NULL start or goal");
     bool inside = true;
     for (int a = 0; a < 3; ++a) {
@@ -1923,13 +1932,14 @@ int naruto_rrt_start(const NarutoRrtPlan* plan, const double* start, const doubl
     // the shell search's bound needs every node inside the grid; the nodes lie on segments between the start and in-grid points
     const uint32_t n = (uint32_t)(vol.X * vol.Y * vol.Z);
     hipLaunchKernelGGL(k_rrt_start, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, vol, D3{start[0], start[1], start[2]}, D3{goal[0], goal[1], goal[2]},
-                       inside ? 1 : 0, plan->nodes_xyz, plan->nodes_xyz32, plan->parent, plan->next, rrt_head(plan), rrt_state(plan), rrt_goal(plan));
+                       inside ? 1 : 0, plan->nodes_xyz, plan->nodes_xyz32, plan->parent, plan->next, w.head, w.state, w.goal);
     return check_launch("rrt_start");
 }
 
 int naruto_rrt_grow(const NarutoRrtPlan* plan, int mode, const double* rows, uint32_t n_rows, uint32_t max_iter, int restart, void* stream) {
     RrtVol vol;
     if (int rc = rrt_plan(plan, "rrt_grow", &vol)) return rc;
+    const RrtWs w = rrt_ws(plan->workspace, vol);
     if (mode != NARUTO_RRT_MODE_RUN && mode != NARUTO_RRT_MODE_FULL) return fail(NARUTO_ERR_INVALID, "rrt_grow: unknown mode %d", mode);
     if (n_rows != 0 && rows == nullptr) return fail(NARUTO_ERR_INVALID, "rrt_grow: NULL rows");
     if (n_rows > 0x7FFFFFFFu || max_iter > 0x7FFFFFFFu) return fail(NARUTO_ERR_INVALID, "rrt_grow: n_rows and max_iter must fit int32");
@@ -1938,7 +1948,7 @@ int naruto_rrt_grow(const NarutoRrtPlan* plan, int mode, const double* rows, uin
     a.step = plan->step_size; a.amp = plan->step_amplifier; a.thre = plan->collision_thre;
     a.direct = plan->enable_direct_line != 0; a.mode = mode; a.restart = restart != 0;
     a.xyz64 = plan->nodes_xyz; a.xyz32 = plan->nodes_xyz32; a.parent = plan->parent; a.next = plan->next;
-    a.head = rrt_head(plan); a.state = rrt_state(plan); a.goal = rrt_goal(plan);
+    a.head = w.head; a.state = w.state; a.goal = w.goal;
     a.rows = rows; a.n_rows = (int)n_rows; a.max_iter = (int)max_iter; a.cap = (int)plan->capacity;
     a.cell_threshold = (int)(plan->cell_threshold ? std::min(plan->cell_threshold, 0x7FFFFFFFu) : NARUTO_RRT_CELL_THRESHOLD);
     hipLaunchKernelGGL(k_rrt_grow, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
@@ -1963,31 +1973,27 @@ int naruto_segments_free(const uint32_t* dims, const float* sdf_vol, uint32_t n,
 int naruto_rrt_path(const NarutoRrtPlan* plan, int32_t* path, void* stream) {
     RrtVol vol;
     if (int rc = rrt_plan(plan, "rrt_path", &vol)) return rc;
+    const RrtWs w = rrt_ws(plan->workspace, vol);
     if (path == nullptr) return fail(NARUTO_ERR_INVALID, "rrt_path: NULL path");
-    hipLaunchKernelGGL(k_rrt_path, dim3(1), dim3(64), 0, (hipStream_t)stream, plan->parent, rrt_state(plan), (int)plan->capacity, path);
+    hipLaunchKernelGGL(k_rrt_path, dim3(1), dim3(64), 0, (hipStream_t)stream, plan->parent, w.state, (int)plan->capacity, path);
     return check_launch("rrt_path");
 }
 
 int naruto_reachable_mask(const NarutoRrtPlan* plan, float* mask, void* stream) {
     RrtVol vol;
     if (int rc = rrt_plan(plan, "reachable_mask", &vol)) return rc;
+    const RrtWs w = rrt_ws(plan->workspace, vol);
     if (mask == nullptr) return fail(NARUTO_ERR_INVALID, "reachable_mask: NULL mask");
     const uint32_t n = (uint32_t)(vol.X * vol.Y * vol.Z);
-    hipLaunchKernelGGL(k_reachable_mask, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, vol, (float)plan->step_size, plan->nodes_xyz32, rrt_head(plan),
-                       plan->next, rrt_state(plan), mask);
+    hipLaunchKernelGGL(k_reachable_mask, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, vol, (float)plan->step_size, plan->nodes_xyz32, w.head,
+                       plan->next, w.state, mask);
     return check_launch("reachable_mask");
 }
 
 // ---- N4: dense volume -> mesh (naruto_mesh.hip) ----------------------------------------------------------------------
 namespace {
-struct McWs {
-    uint8_t* cases;
-    uint8_t* flags;
-    uint2* prefix;
-    unsigned long long* block_total;
-    uint32_t n, n_blocks;
-};
-size_t mc_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
+// workspace of the mesh extraction over n voxels: | cases [n] | flags [n] | prefix [n] | one total per block of kMcBlockItems voxels |
+struct McWs { uint8_t* cases; uint8_t* flags; uint2* prefix; unsigned long long* block_total; uint32_t n, n_blocks; size_t total; };
 int mc_dims(const uint32_t* dims, const char* who, McDims* d, uint32_t* n) {
     if (dims == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL dims", who);
     const uint64_t n64 = (uint64_t)dims[0] * dims[1] * dims[2];
@@ -1998,15 +2004,9 @@ int mc_dims(const uint32_t* dims, const char* who, McDims* d, uint32_t* n) {
     return NARUTO_OK;
 }
 McWs mc_ws(void* workspace, uint32_t n) {
-    McWs w;
-    char* p = reinterpret_cast<char*>(workspace);
-    w.n = n;
-    w.n_blocks = (n + kMcBlockItems - 1u) / kMcBlockItems;
-    w.cases = reinterpret_cast<uint8_t*>(p); p += mc_align(n);
-    w.flags = reinterpret_cast<uint8_t*>(p); p += mc_align(n);
-    w.prefix = reinterpret_cast<uint2*>(p); p += mc_align((size_t)n * sizeof(uint2));
-    w.block_total = reinterpret_cast<unsigned long long*>(p);
-    return w;
+    const uint32_t n_blocks = (n + kMcBlockItems - 1u) / kMcBlockItems;
+    Carve c(workspace);
+    return {c.take<uint8_t>(n), c.take<uint8_t>(n), c.take<uint2>((size_t)n * sizeof(uint2)), c.take<unsigned long long>((size_t)n_blocks * sizeof(unsigned long long)), n, n_blocks, c.size()};
 }
 }  // namespace
 
@@ -2020,9 +2020,7 @@ int naruto_lattice_points(const uint32_t* dims, const float* tx, const float* ty
 
 size_t naruto_mesh_workspace(const uint32_t* dims) {
     McDims d; uint32_t n;
-    if (mc_dims(dims, "mesh_workspace", &d, &n)) return 0;
-    const size_t n_blocks = (n + kMcBlockItems - 1u) / kMcBlockItems;
-    return 2u * mc_align(n) + mc_align((size_t)n * sizeof(uint2)) + mc_align(n_blocks * sizeof(unsigned long long));
+    return mc_dims(dims, "mesh_workspace", &d, &n) ? 0 : mc_ws(nullptr, n).total;
 }
 
 int naruto_mesh_count(const uint32_t* dims, const float* sdf_vol, double isolevel, double truncation, void* workspace, uint64_t* counts, void* stream) {
@@ -2057,7 +2055,6 @@ int naruto_mesh_emit(const uint32_t* dims, const float* sdf_vol, double isolevel
 namespace {
 constexpr uint64_t kReconMaxCount = 0x7FFFFFFFull;
 constexpr uint64_t kNnGridDefaultCap = 1ull << 21;          // cells: 8 MB of starts; above it the cell edge grows
-size_t recon_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
 uint64_t nn_grid_cells(const NarutoNnGrid* g) { return (uint64_t)g->dims[0] * g->dims[1] * g->dims[2]; }
 int nn_grid_check(const NarutoNnGrid* g, const char* who) {
     if (g == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL grid", who);
@@ -2082,16 +2079,20 @@ NnGrid nn_grid_args(const NarutoNnGrid* g) {
     a.pts = reinterpret_cast<const float4*>(g->points);
     return a;
 }
-struct NnGridWs { uint32_t* cells; uint32_t* count; uint32_t* block_total; uint32_t n_blocks; };
+// workspace of the grid build: | each point's cell [n_points] | points per cell [cells] | one total per block of kGridScanItems cells |
+struct NnGridWs { uint32_t* cells; uint32_t* count; uint32_t* block_total; uint32_t n_blocks; size_t total; };
 NnGridWs nn_grid_ws(const NarutoNnGrid* g, void* workspace) {
-    NnGridWs w;
-    char* p = reinterpret_cast<char*>(workspace);
     const uint64_t cells = nn_grid_cells(g);
-    w.n_blocks = (uint32_t)((cells + kGridScanItems - 1u) / kGridScanItems);
-    w.cells = reinterpret_cast<uint32_t*>(p); p += recon_align((size_t)g->n_points * 4u);
-    w.count = reinterpret_cast<uint32_t*>(p); p += recon_align((size_t)cells * 4u);
-    w.block_total = reinterpret_cast<uint32_t*>(p);
-    return w;
+    const uint32_t n_blocks = (uint32_t)((cells + kGridScanItems - 1u) / kGridScanItems);
+    Carve c(workspace);
+    return {c.take<uint32_t>((size_t)g->n_points * 4u), c.take<uint32_t>((size_t)cells * 4u), c.take<uint32_t>((size_t)n_blocks * 4u), n_blocks, c.size()};
+}
+// workspace of the distance reduce over n values: | one partial sum | and one count | per workgroup of kReconThreads * kDistPer values
+struct DistWs { double* part_sum; unsigned long long* part_cnt; uint32_t parts; size_t total; };
+DistWs dist_ws(uint64_t n, void* workspace) {
+    const uint32_t parts = (uint32_t)((n + kReconThreads * kDistPer - 1u) / (kReconThreads * kDistPer));
+    Carve c(workspace);
+    return {c.take<double>((size_t)parts * 8u), c.take<unsigned long long>((size_t)parts * 8u), parts, c.size()};
 }
 int mesh_args_check(uint64_t n_faces, uint64_t n_vertices, const void* vertices, const int32_t* faces, const char* who) {
     if (n_faces == 0) return fail(NARUTO_ERR_INVALID, "%s: a mesh without faces has no surface to sample", who);
@@ -2161,10 +2162,7 @@ int naruto_nn_grid_plan(uint64_t n_points, const double* lo, const double* hi, d
 }
 
 size_t naruto_nn_grid_workspace(const NarutoNnGrid* grid) {
-    if (nn_grid_check(grid, "nn_grid_workspace")) return 0;
-    const uint64_t cells = nn_grid_cells(grid);
-    const size_t n_blocks = (size_t)((cells + kGridScanItems - 1u) / kGridScanItems);
-    return recon_align((size_t)grid->n_points * 4u) + recon_align((size_t)cells * 4u) + recon_align(n_blocks * 4u);
+    return nn_grid_check(grid, "nn_grid_workspace") ? 0 : nn_grid_ws(grid, nullptr).total;
 }
 
 int naruto_nn_grid_build(const NarutoNnGrid* grid, const float* points, void* workspace, void* stream) {
@@ -2222,9 +2220,7 @@ int naruto_nn_scan(uint64_t n_targets, const float* targets, uint64_t n_queries,
 }
 
 size_t naruto_dist_reduce_workspace(uint64_t n) {
-    if (n == 0 || n > kReconMaxCount) return 0;
-    const size_t parts = (size_t)((n + kReconThreads * kDistPer - 1u) / (kReconThreads * kDistPer));
-    return 2u * recon_align(parts * 8u);
+    return (n == 0 || n > kReconMaxCount) ? 0 : dist_ws(n, nullptr).total;
 }
 
 int naruto_dist_reduce(uint64_t n, const double* dist, double threshold, void* workspace, double* out, void* stream) {
@@ -2232,12 +2228,10 @@ int naruto_dist_reduce(uint64_t n, const double* dist, double threshold, void* w
     if (n > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "dist_reduce: counts beyond int32");
     if (std::isnan(threshold)) return fail(NARUTO_ERR_INVALID, "dist_reduce: the threshold is not a number");
     if (dist == nullptr || workspace == nullptr || out == nullptr) return fail(NARUTO_ERR_INVALID, "dist_reduce: NULL argument");
-    const uint32_t parts = (uint32_t)((n + kReconThreads * kDistPer - 1u) / (kReconThreads * kDistPer));
-    double* part_sum = reinterpret_cast<double*>(workspace);
-    unsigned long long* part_cnt = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + recon_align((size_t)parts * 8u));
-    hipLaunchKernelGGL(k_dist_partial, dim3(parts), dim3(kReconThreads), 0, (hipStream_t)stream, (uint32_t)n, dist, threshold, part_sum, part_cnt);
+    const DistWs w = dist_ws(n, workspace);
+    hipLaunchKernelGGL(k_dist_partial, dim3(w.parts), dim3(kReconThreads), 0, (hipStream_t)stream, (uint32_t)n, dist, threshold, w.part_sum, w.part_cnt);
     if (int rc = check_launch("dist_partial")) return rc;
-    hipLaunchKernelGGL(k_dist_finish, dim3(1), dim3(kReconThreads), 0, (hipStream_t)stream, (uint32_t)n, parts, part_sum, part_cnt, out);
+    hipLaunchKernelGGL(k_dist_finish, dim3(1), dim3(kReconThreads), 0, (hipStream_t)stream, (uint32_t)n, w.parts, w.part_sum, w.part_cnt, out);
     return check_launch("dist_finish");
 }
 
@@ -2265,21 +2259,19 @@ int cull_raster_sizes_check(const NarutoCullCam* cam, uint64_t n_vertices, uint6
         return fail(NARUTO_ERR_INVALID, "%s: faces x poses per call must stay below 2^28 (and x 2048-pixel chunks of the image below 2^36): use fewer poses per call", who);
     return NARUTO_OK;
 }
-struct CullWs { unsigned long long* counter; float4* camv; unsigned long long* ent_start; uint32_t* ent_id; };
-CullWs cull_ws(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses, void* workspace) {
-    CullWs w;
-    char* p = reinterpret_cast<char*>(workspace);
-    w.counter = reinterpret_cast<unsigned long long*>(p); p += 256;
-    w.camv = reinterpret_cast<float4*>(p); p += recon_align((size_t)n_vertices * n_poses * 16u);
-    w.ent_start = reinterpret_cast<unsigned long long*>(p); p += recon_align((size_t)n_faces * n_poses * 8u);
-    w.ent_id = reinterpret_cast<uint32_t*>(p);
-    return w;
+// workspace of the depth raster: | counter of large boxes | camera-space vertices [poses][vertices] | a large box's first chunk | and its face [poses][faces] |;
+// the simulator's 64-bit (depth, face) cells [poses][H][W] follow it (H = 0: the culling raster, which has none)
+struct CullWs { unsigned long long* counter; float4* camv; unsigned long long* ent_start; uint32_t* ent_id; unsigned long long* cells; size_t total; };
+CullWs cull_ws(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses, void* workspace, uint32_t H = 0, uint32_t W = 0) {
+    Carve c(workspace);
+    return {c.take<unsigned long long>(8u), c.take<float4>((size_t)n_vertices * n_poses * 16u), c.take<unsigned long long>((size_t)n_faces * n_poses * 8u),
+            c.take<uint32_t>((size_t)n_faces * n_poses * 4u), H != 0 ? c.take<unsigned long long>((size_t)n_poses * H * W * 8u) : nullptr, c.size()};
 }
 }  // namespace
 
 size_t naruto_render_depth_workspace(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses) {
     if (n_faces == 0 || n_vertices == 0 || n_poses == 0 || n_faces > kReconMaxCount || n_vertices > kReconMaxCount || n_poses > 65535u || n_faces * n_poses >= (1ull << 28)) return 0;
-    return 256u + recon_align((size_t)n_vertices * n_poses * 16u) + recon_align((size_t)n_faces * n_poses * 8u) + recon_align((size_t)n_faces * n_poses * 4u);
+    return cull_ws(n_vertices, n_faces, n_poses, nullptr).total;
 }
 
 int naruto_render_depth(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const uint8_t* face_mask,
@@ -2359,7 +2351,6 @@ int naruto_debug_atomic_min_rate(uint64_t n_words, uint32_t n_lanes, uint32_t it
 
 // ---- mesh simulator (naruto_sim.hip) --------------------------------------------------------------------------------------
 namespace {
-size_t sim_raster_ws(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses) { return naruto_render_depth_workspace(n_vertices, n_faces, n_poses); }
 int sim_fill2(uint64_t n_pairs, uint32_t w0, uint32_t w1, void* p, hipStream_t st, const char* who) {
     hipLaunchKernelGGL(k_sim_fill2, dim3((uint32_t)((n_pairs + kSimThreads - 1u) / kSimThreads)), dim3(kSimThreads), 0, st, n_pairs, w0, w1, reinterpret_cast<uint2*>(p));
     return check_launch(who);
@@ -2367,9 +2358,8 @@ int sim_fill2(uint64_t n_pairs, uint32_t w0, uint32_t w1, void* p, hipStream_t s
 }  // namespace
 
 size_t naruto_render_rgbd_workspace(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses, uint32_t H, uint32_t W) {
-    const size_t raster = sim_raster_ws(n_vertices, n_faces, n_poses);
-    if (raster == 0 || H == 0 || W == 0 || (uint64_t)H * W > (1ull << 30)) return 0;
-    return raster + recon_align((size_t)n_poses * H * W * 8u);
+    if (naruto_render_depth_workspace(n_vertices, n_faces, n_poses) == 0 || H == 0 || W == 0 || (uint64_t)H * W > (1ull << 30)) return 0;
+    return cull_ws(n_vertices, n_faces, n_poses, nullptr, H, W).total;
 }
 
 int naruto_render_rgbd(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const void* colors, int colors_f32,
@@ -2384,8 +2374,8 @@ int naruto_render_rgbd(const NarutoCullCam* cam, uint64_t n_vertices, const floa
     if (depth == nullptr && color == nullptr && face_id == nullptr) return fail(NARUTO_ERR_INVALID, "render_rgbd: no output");
     if (color != nullptr && colors == nullptr) return fail(NARUTO_ERR_INVALID, "render_rgbd: a colour image needs vertex colours");
     const CullCam c = cull_cam_args(cam);
-    const CullWs w = cull_ws(n_vertices, n_faces, n_poses, workspace);
-    unsigned long long* cells = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + sim_raster_ws(n_vertices, n_faces, n_poses));
+    const CullWs w = cull_ws(n_vertices, n_faces, n_poses, workspace, cam->H, cam->W);
+    unsigned long long* cells = w.cells;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t nv = (uint32_t)n_vertices, nf = (uint32_t)n_faces, cap = (uint32_t)(n_faces * n_poses), n_px = cam->H * cam->W;
     if (hipMemsetAsync(w.counter, 0, 8u, st) != hipSuccess) return check_launch("render_rgbd: memset");
@@ -2660,9 +2650,9 @@ TrackArgs track_args(const NarutoTrackStep* k, const NarutoTrainStep* t) {
 }
 }  // namespace
 
-size_t naruto_track_workspace(const NarutoField* f, uint32_t n_rays, uint32_t n_samples) {
+size_t naruto_track_workspace(const NarutoField*, uint32_t n_rays, uint32_t n_samples) {
     const uint64_t M = (uint64_t)n_rays * n_samples;
-    return M > (1ull << 29) ? 0u : naruto_query_bwd_points_workspace(f, (uint32_t)M);
+    return M > (1ull << 29) ? 0u : point_grad_ws(nullptr, (size_t)M).total;
 }
 
 int naruto_track_draw(const NarutoTrackStep* k, const NarutoTrainStep* t, void* stream) {
@@ -2695,7 +2685,7 @@ int naruto_track_backward(const NarutoField* f, const NarutoParams* p, const Nar
     NarutoPoints pts{};
     pts.rays_o = t->rays_o; pts.rays_d = t->rays_d; pts.z_vals = t->z_vals; pts.n_samples = S;
     if (int rc = check_points(&pts)) return rc;
-    float* gp = reinterpret_cast<float*>(k->workspace);
+    float* gp = point_grad_ws(k->workspace, M).d_x;
     const uint64_t n_gp = 3u * (uint64_t)M;
     hipLaunchKernelGGL(k_track_zero, dim3((uint32_t)((n_gp + 255u) / 256u)), dim3(256), 0, st, gp, n_gp);
     if (int rc = check_launch("track_zero")) return rc;
@@ -2755,7 +2745,7 @@ int ba_poses_launch(const NarutoField* f, const NarutoParams* p, const NarutoTra
     NarutoPoints pts{};
     pts.rays_o = t->rays_o; pts.rays_d = t->rays_d; pts.z_vals = t->z_vals; pts.n_samples = S;
     if (int rc = check_points(&pts)) return rc;
-    float* gp = reinterpret_cast<float*>(b->workspace);
+    float* gp = point_grad_ws(b->workspace, M).d_x;
     const uint64_t n_gp = 3u * (uint64_t)M;
     hipLaunchKernelGGL(k_track_zero, dim3((uint32_t)((n_gp + 255u) / 256u)), dim3(256), 0, st, gp, n_gp);
     if (int rc = check_launch("ba_poses: zero")) return rc;
@@ -2773,9 +2763,9 @@ int ba_poses_launch(const NarutoField* f, const NarutoParams* p, const NarutoTra
 }
 }  // namespace
 
-size_t naruto_ba_poses_workspace(const NarutoField* f, uint32_t n_rays, uint32_t n_samples) {
+size_t naruto_ba_poses_workspace(const NarutoField*, uint32_t n_rays, uint32_t n_samples) {
     const uint64_t M = (uint64_t)n_rays * n_samples;
-    return M > (1ull << 29) ? 0u : naruto_query_bwd_points_workspace(f, (uint32_t)M);
+    return M > (1ull << 29) ? 0u : point_grad_ws(nullptr, (size_t)M).total;
 }
 
 int naruto_ba_poses_init(const NarutoBAPoses* b, void* stream) {

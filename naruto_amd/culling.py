@@ -139,13 +139,11 @@ class _Raster:
     def __init__(self, v32: torch.Tensor, faces: torch.Tensor, cam: _lib.NarutoCullCam, chunk: int, plan, face_mask: Optional[torch.Tensor] = None):
         self.v, self.f, self.cam, self.mask = v32, faces, cam, face_mask
         self.threshold = _threshold(plan)
-        lib = _lib.load()
         # faces x poses per launch stays below 2^28 (the large route's list): a huge mesh gets a smaller chunk
         self.chunk = max(1, min(int(chunk), (2 ** 28 - 1) // max(len(faces), 1), 65535))
-        n = lib.naruto_render_depth_workspace(len(v32), len(faces), self.chunk)
-        if n == 0:
+        self.ws = _lib.workspace(_lib.load().naruto_render_depth_workspace(len(v32), len(faces), self.chunk), v32.device, torch.int64)
+        if self.ws.numel() == 0:
             raise ValueError(f"culling: a mesh of {len(v32)} vertices and {len(faces)} faces is beyond the depth render's sizes")
-        self.ws = torch.empty((n + 7) // 8, dtype=torch.int64, device=v32.device)
 
     def render(self, poses: torch.Tensor, out: torch.Tensor) -> None:
         """poses [B,4,4] float32 on the device, B <= chunk -> out [B,H,W] (+inf where nothing is hit)."""

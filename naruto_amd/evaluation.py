@@ -150,7 +150,7 @@ class PointGridHIP:
         start = torch.empty(cells + 1, dtype=torch.int32, device=self.device)
         pts = torch.empty(len(cloud), 4, dtype=torch.float32, device=self.device)
         grid.cell_start, grid.points = start.data_ptr(), pts.data_ptr()
-        ws = torch.empty((lib.naruto_nn_grid_workspace(C.byref(grid)) + 7) // 8, dtype=torch.int64, device=self.device)
+        ws = _lib.workspace(lib.naruto_nn_grid_workspace(C.byref(grid)), self.device, torch.int64)
         with torch.cuda.device(self.device):
             check(lib.naruto_nn_grid_build(C.byref(grid), cloud.data_ptr(), ws.data_ptr(), _stream()), "naruto_nn_grid_build")
         return start, pts
@@ -210,7 +210,7 @@ def reduce_distances(dist: torch.Tensor, threshold: float) -> torch.Tensor:
     if len(d) == 0:
         raise ValueError("reduce_distances: no distances")
     lib = _lib.load()
-    ws = torch.empty((lib.naruto_dist_reduce_workspace(len(d)) + 7) // 8, dtype=torch.int64, device=d.device)
+    ws = _lib.workspace(lib.naruto_dist_reduce_workspace(len(d)), d.device, torch.int64)
     out = torch.empty(2, dtype=torch.float64, device=d.device)
     with torch.cuda.device(d.device):
         check(lib.naruto_dist_reduce(len(d), d.data_ptr(), float(threshold), ws.data_ptr(), out.data_ptr(), _stream()), "naruto_dist_reduce")

@@ -256,10 +256,9 @@ def marching_cubes(sdf_vol: torch.Tensor, isolevel: float = 0.0, truncation: flo
     lib = _lib.load()
     vol = sdf_vol.contiguous()
     dims = (C.c_uint32 * 3)(*vol.shape)
-    ws_bytes = lib.naruto_mesh_workspace(dims)
-    if ws_bytes == 0:
+    ws = _lib.workspace(lib.naruto_mesh_workspace(dims), vol.device, torch.int64)
+    if ws.numel() == 0:
         raise ValueError(f"marching_cubes: unsupported volume shape {tuple(vol.shape)}: " + lib.naruto_last_error().decode("utf-8", "replace"))
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=vol.device)
     counts = torch.zeros(2, dtype=torch.int64, device=vol.device)
     with torch.cuda.device(vol.device):
         check(lib.naruto_mesh_count(dims, vol.data_ptr(), float(isolevel), float(truncation), ws.data_ptr(), counts.data_ptr(), _stream()), "naruto_mesh_count")

@@ -263,7 +263,7 @@ class _HashEncode(torch.autograd.Function):
             d_feat = _f32c(d_feat, "d_feat")
             d_table = torch.zeros_like(table)
             with _on_device(x.device):
-                ws = torch.empty((lib.naruto_scatter_workspace(ctx.handle.ptr, x.shape[0]) + 3) // 4, dtype=torch.float32, device=x.device)
+                ws = _lib.workspace(lib.naruto_scatter_workspace(ctx.handle.ptr, x.shape[0]), x.device)
                 check(lib.naruto_hash_encode_bwd(ctx.handle.ptr, x.shape[0], _p(x), _p(d_feat), None, _p(d_table), _p(ws), _stream()),
                       "naruto_hash_encode_bwd")
         return None, None, d_table
@@ -294,7 +294,7 @@ class _Smoothness(torch.autograd.Function):
         d_feat = torch.empty(n ** 3, 32, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         with _on_device(dev):
-            ws = torch.empty((lib.naruto_smoothness_workspace(sample_points) + 3) // 4, dtype=torch.float32, device=dev)
+            ws = _lib.workspace(lib.naruto_smoothness_workspace(sample_points), dev)
             check(lib.naruto_smoothness_fwd(handle.ptr, _p(table), sample_points, voxel_size, margin, _p(rand6), _p(x), _p(d_feat), _p(loss),
                                             _p(ws), _stream()), "naruto_smoothness_fwd")
         ctx.handle = handle
@@ -311,7 +311,7 @@ class _Smoothness(torch.autograd.Function):
         g = _f32c(g, "grad").reshape(1)
         d_table = torch.zeros_like(table)
         with _on_device(x.device):
-            ws = torch.empty((lib.naruto_scatter_workspace(ctx.handle.ptr, x.shape[0]) + 3) // 4, dtype=torch.float32, device=x.device)
+            ws = _lib.workspace(lib.naruto_scatter_workspace(ctx.handle.ptr, x.shape[0]), x.device)
             check(lib.naruto_hash_encode_bwd(ctx.handle.ptr, x.shape[0], _p(x), _p(d_feat), _p(g), _p(d_table), _p(ws), _stream()),
                   "naruto_hash_encode_bwd")
         return None, d_table, None, None, None, None
@@ -397,8 +397,7 @@ class _FieldQuery(torch.autograd.Function):
         d_x = d_o = d_d = None
         with _on_device(dev):
             if ctx.need_grad:
-                ws_bytes = lib.naruto_query_bwd_workspace(ctx.handle.ptr, M)
-                ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=dev)
+                ws = _lib.workspace(lib.naruto_query_bwd_workspace(ctx.handle.ptr, M), dev)
                 check(lib.naruto_query_bwd(ctx.handle.ptr, C.byref(ps), M, C.byref(pts), _p(feat), _p(d_raw), _p(d_geo), None, None,
                                            None, 0, C.byref(gs), _p(ws), _stream()), "naruto_query_bwd")
             if ctx.has_x and ctx.needs_input_grad[3]:
@@ -418,9 +417,7 @@ def point_grads(handle: FieldHandle, params: Dict[str, torch.Tensor], pts: Narut
     d_rays_d [N,3] (ray points), written (or added, ``accumulate``).  ``active`` / ``n_active``: naruto_compact_active's list."""
     lib = _lib.load()
     ps = _params_struct(params)
-    ws = None
-    if d_x is None:
-        ws = torch.empty((lib.naruto_query_bwd_points_workspace(handle.ptr, M) + 3) // 4, dtype=torch.float32, device=d_raw.device)
+    ws = _lib.workspace(lib.naruto_query_bwd_points_workspace(handle.ptr, M), d_raw.device) if d_x is None else None
     check(lib.naruto_query_bwd_points(handle.ptr, C.byref(ps), M, C.byref(pts), _p(d_raw), _p(d_geo), _p(active), _p(n_active), _p(d_x),
                                       _p(d_rays_o), _p(d_rays_d), _lib.BWD_POINTS_ACCUMULATE if accumulate else 0, _p(ws), _stream()),
           "naruto_query_bwd_points")
@@ -497,7 +494,7 @@ class _RenderLoss(torch.autograd.Function):
             st = _stream()
             check(lib.naruto_composite_fwd(handle.ptr, N, S, _p(raw), _p(z_vals), _p(rgb), _p(disp), _p(acc), None, _p(depth),
                                            _p(depth_var), _p(um), st), "naruto_composite_fwd")
-            ws = torch.empty(lib.naruto_loss_workspace(N) // 4, dtype=torch.float32, device=dev)
+            ws = _lib.workspace(lib.naruto_loss_workspace(N), dev)
             check(lib.naruto_loss_sums(handle.ptr, N, S, _p(raw), _p(z_vals), _p(rgb), _p(depth), _p(um), _p(target_rgb),
                                        _p(target_d), depth_trunc, rgb_missing, _p(sums), None if group is not None else _p(losses),
                                        _p(ws), st), "naruto_loss_sums")
@@ -586,7 +583,7 @@ class _RenderTrain(torch.autograd.Function):
             check(lib.naruto_query_fwd(handle.ptr, C.byref(ps), M, C.byref(pts), _p(raw), None, None, _p(feat), st), "naruto_query_fwd")
             check(lib.naruto_composite_fwd(handle.ptr, N, S, _p(raw), _p(z_vals), _p(rgb), _p(disp), _p(acc), None, _p(depth),
                                            _p(depth_var), _p(um), st), "naruto_composite_fwd")
-            ws = torch.empty(lib.naruto_loss_workspace(N) // 4, dtype=torch.float32, device=dev)
+            ws = _lib.workspace(lib.naruto_loss_workspace(N), dev)
             check(lib.naruto_loss_sums(handle.ptr, N, S, _p(raw), _p(z_vals), _p(rgb), _p(depth), _p(um), _p(target_rgb),
                                        _p(target_d), depth_trunc, rgb_missing, _p(sums), None if group is not None else _p(losses),
                                        _p(ws), st), "naruto_loss_sums")
@@ -596,7 +593,7 @@ class _RenderTrain(torch.autograd.Function):
                 n_total = int(n_rays_total) if n_rays_total else N * parallel.world_size(group)
                 check(lib.naruto_loss_finalize(_p(sums), n_total, S, _p(losses), st), "naruto_loss_finalize")
             if smooth is not None:
-                ws2 = torch.empty((lib.naruto_smoothness_workspace(sp) + 3) // 4, dtype=torch.float32, device=dev)
+                ws2 = _lib.workspace(lib.naruto_smoothness_workspace(sp), dev)
                 check(lib.naruto_smoothness_fwd(handle.ptr, _p(params["table"]), sp, vox, mar, _p(_f32c(rand6, "rand6")), _p(sm_x), _p(sm_d),
                                                 sm_loss.data_ptr(), _p(ws2), st), "naruto_smoothness_fwd")
         ctx.handle, ctx.depth_trunc, ctx.rgb_missing, ctx.n_total = handle, depth_trunc, rgb_missing, n_total
@@ -672,7 +669,7 @@ class _RenderTrain(torch.autograd.Function):
                 ex.x, ex.d_feat, ex.scale, ex.n = _p(sm_x), _p(sm_d), d_smooth.data_ptr(), sm_x.shape[0]
                 n_extra = sm_x.shape[0]
             if ctx.need_grad:
-                ws = torch.empty((lib.naruto_query_bwd_workspace(ctx.handle.ptr, M + n_extra) + 3) // 4, dtype=torch.float32, device=dev)
+                ws = _lib.workspace(lib.naruto_query_bwd_workspace(ctx.handle.ptr, M + n_extra), dev)
                 check(lib.naruto_query_bwd(ctx.handle.ptr, C.byref(ps), M, C.byref(pts), _p(feat), _p(d_raw), None, _p(active), _p(n_active),
                                            None if ex is None else C.byref(ex), flags, C.byref(gs), _p(ws), st), "naruto_query_bwd")
             # ray gradients (pose refinement / tracking): the same d_raw, over the same active list when there is one
@@ -814,7 +811,7 @@ class TrainStep:
         t.rgb, t.depth, t.uncert_map = _p(self.rgb), _p(self.depth), _p(self.uncert_map)
         t.sums, t.losses, t.d_raw = _p(self.sums), _p(self.losses), _p(self.d_raw)
         t.ray_count, t.ray_offset, t.active_idx, t.n_active = _p(self.ray_count), _p(self.ray_offset), _p(self.active_idx), _p(self.n_active)
-        self.ws = torch.empty((lib.naruto_train_workspace(handle.ptr, C.byref(t)) + 3) // 4, **f32)
+        self.ws = _lib.workspace(lib.naruto_train_workspace(handle.ptr, C.byref(t)), dev)
         t.workspace = _p(self.ws)
         if min_uncert_running is not None:      # float32[1] device word, +inf initially: every iteration's min(uncert_map) is folded into it
             assert min_uncert_running.is_cuda and min_uncert_running.dtype == torch.float32 and min_uncert_running.numel() == 1

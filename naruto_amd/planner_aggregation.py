@@ -69,7 +69,7 @@ class GoalSpaceAggregatorHIP:
         n = uncert.numel()
         k, sub = min(self.uncert_top_k, n), min(self.uncert_top_k_subset, min(self.uncert_top_k, n))
         targets = torch.empty(sub, 3, dtype=torch.int32, device=self.device)
-        ws = torch.empty((lib.naruto_goal_targets_workspace(n, k) + 3) // 4, dtype=torch.int32, device=self.device)
+        ws = _lib.workspace(lib.naruto_goal_targets_workspace(n, k), self.device, torch.int32)
         with torch.cuda.device(self.device):
             check(lib.naruto_goal_targets(self._dims, uncert.data_ptr(), k, sub, targets.data_ptr(), ws.data_ptr(), _stream()), "naruto_goal_targets")
         return targets

@@ -199,7 +199,7 @@ class RRTNarutoHIP:
             for a, (r, f) in enumerate(zip((self.x_range, self.y_range, self.z_range), (self.full_x_range, self.full_y_range, self.full_z_range))):
                 p.range[a][0], p.range[a][1] = float(r[0]), float(r[1])
                 p.full_range[a][0], p.full_range[a][1] = float(f[0]), float(f[1])
-            self._ws = torch.empty((lib.naruto_rrt_workspace(dims) + 3) // 4, dtype=torch.int32, device=self._device)
+            self._ws = _lib.workspace(lib.naruto_rrt_workspace(dims), self._device, torch.int32)
             p.workspace = self._ws.data_ptr()
             self._n_nodes = 0
             self._alloc_tree(int(self.initial_capacity))

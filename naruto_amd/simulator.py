@@ -182,10 +182,9 @@ class _RasterRGBD:
         self.sim, self.cam = sim, cam
         n_v, n_f = len(sim.v), len(sim.f)
         self.chunk = max(1, min(int(chunk), (2 ** 28 - 1) // max(n_f, 1), (2 ** 32 - 1) // (cam.H * cam.W), 65535))
-        n = _lib.load().naruto_render_rgbd_workspace(n_v, n_f, self.chunk, cam.H, cam.W)
-        if n == 0:
+        self.ws = _lib.workspace(_lib.load().naruto_render_rgbd_workspace(n_v, n_f, self.chunk, cam.H, cam.W), sim.device, torch.int64)
+        if self.ws.numel() == 0:
             raise ValueError(f"simulator: a mesh of {n_v} vertices and {n_f} faces at {cam.W} x {cam.H} is beyond the render's sizes")
-        self.ws = torch.empty((n + 7) // 8, dtype=torch.int64, device=sim.device)
 
     def render(self, poses: torch.Tensor, depth=None, color=None, face_id=None, keep_inf: bool = False) -> None:
         """poses [B,4,4] float32 on the device, B <= chunk -> depth [B,H,W], color [B,H,W,3], face_id [B,H,W] (each optional)."""

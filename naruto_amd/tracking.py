@@ -202,8 +202,7 @@ class TrackerHIP:
         self.trace_loss = torch.zeros(self.iters, **f32)
         self.trace_pose = torch.zeros(self.iters, 6, **f32)
         self.trace_d_pose = torch.zeros(self.iters, 6, **f32)
-        lib = _lib.load()
-        self.ws = torch.zeros((lib.naruto_track_workspace(model._handle().ptr, N, S) + 3) // 4, **f32)
+        self.ws = _lib.workspace(_lib.load().naruto_track_workspace(model._handle().ptr, N, S), dev, zero=True)
         k = _lib.NarutoTrackStep()
         k.n_rays, k.H, k.W, k.edge_h, k.edge_w = N, self.H, self.W, self.edge_h, self.edge_w
         k.direction, k.rgb, k.depth, k.rng = _p(self.direction), _p(self.rgb), _p(self.depth), _p(self.rng)
