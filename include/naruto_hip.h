@@ -619,6 +619,15 @@ typedef struct NarutoTrainStep {
                                                          (minimum; a NaN sticks) -- the reference's per-forward
                                                          `assert uncert_map.min() > 0` (scene_rep.py:280) as a value the host can
                                                          read whenever it likes, graph replays included; initialise to +inf   */
+    void *fwd_image;                                  /* optional, exact (fp32) mode: naruto_fwd_image_bytes() bytes, 16-byte aligned, prepared
+                                                         once by naruto_fwd_image_init -- the training forward's MLP weights in the order its
+                                                         matrix instructions read them.  A naruto_train_backward with a fused optimiser (opt !=
+                                                         NULL) rewrites every weight's entry in the launch that steps the weights.          */
+    uint32_t fwd_image_fresh;                         /* the CALLER's statement that fwd_image matches the weights in p: naruto_train_forward
+                                                         then copies it instead of re-deriving it in every workgroup (walk of S = 64 k <= 192
+                                                         samples, short rays).  True exactly when the last thing that changed the MLP weights
+                                                         was such a backward on THIS step (or naruto_fwd_image_init) -- the library cannot see
+                                                         a load_state_dict, another optimiser or a copy into the weights.  0: never read.   */
 } NarutoTrainStep;
 /* Optimiser in the backward (single process): the launch that finishes the gradients applies torch.optim.Adam
  * (amsgrad off, L2 weight decay; reference create_optimizer, coslam.py:409-419) to the table and the MLP weights in
@@ -640,6 +649,16 @@ int naruto_train_finalize(const NarutoField* f, const NarutoTrainStep* t, void* 
 int naruto_train_backward(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const NarutoGrads* g,
                           uint32_t flags, const NarutoFusedAdam* opt /* NULL: gradients only; else g's table / weight
                           pointers may be NULL (gradients not materialised) */, void* stream);
+
+/* NarutoTrainStep.fwd_image: its size (returned; optionally the image part's bytes and the number of MLP weights, 5 184), and its one-time
+ * preparation from the weights in p (one small launch + one upload; NOT inside a stream capture). */
+size_t naruto_fwd_image_bytes(size_t* image_bytes, uint32_t* n_weights);
+int naruto_fwd_image_init(const NarutoField* f, const NarutoParams* p, void* fwd_image, void* stream);
+/* tests: what one workgroup of the training forward stages from the weights in p, copied out (image_bytes bytes, 16-byte aligned), and -- host
+ * only -- where the finishing launch puts each weight: slots [n_weights] (low half: byte offset of the first piece / of the float; high half:
+ * byte stride to the other two pieces, 0 for col_w1's floats), zero_fill [image_bytes] or NULL (1: a byte of the staging's zero padding). */
+int naruto_debug_fwd_image(const NarutoField* f, const NarutoParams* p, void* out, void* stream);
+int naruto_debug_fwd_image_map(uint32_t* slots, uint8_t* zero_fill);
 
 /* Measurement aid (bench.py): ONLY the field-query launch of naruto_train_forward, exactly as the iteration issues it (one wave per ray
  * with early termination when S % 64 == 0 -- and then with the loss stage riding in the same launch, k_query_fwd_loss); t->z_vals

@@ -90,6 +90,7 @@ class NarutoTrainStep(C.Structure):
         ("sums", C.c_void_p), ("losses", C.c_void_p), ("d_raw", C.c_void_p),
         ("ray_count", C.c_void_p), ("ray_offset", C.c_void_p), ("active_idx", C.c_void_p), ("n_active", C.c_void_p),
         ("workspace", C.c_void_p), ("loss_weight_parts", C.c_void_p * 10), ("min_uncert_running", C.c_void_p),
+        ("fwd_image", C.c_void_p), ("fwd_image_fresh", C.c_uint32),
     ]
 
 
@@ -266,6 +267,10 @@ SIGNATURES = {
     "naruto_decoder_fwd": (_I, [_V, C.POINTER(NarutoParams), C.c_uint32, C.c_int, _V, _V, _V, _V]),
     "naruto_debug_train_query_fwd": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), _V]),
     "naruto_debug_fwd_timeline": (_I, [_V]),
+    "naruto_fwd_image_bytes": (C.c_size_t, [C.POINTER(C.c_size_t), C.POINTER(_U32)]),
+    "naruto_fwd_image_init": (_I, [_V, C.POINTER(NarutoParams), _V, _V]),
+    "naruto_debug_fwd_image": (_I, [_V, C.POINTER(NarutoParams), _V, _V]),
+    "naruto_debug_fwd_image_map": (_I, [_V, _V]),
     "naruto_debug_train_scatter": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), _V]),
     "naruto_debug_train_plan": (_I, [_V, C.POINTER(NarutoTrainStep), _I, _I, C.POINTER(_U32)]),
     "naruto_debug_render_plan": (_I, [_V, _U32, _U32, _I, _I, C.POINTER(_U32)]),

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <new>
+#include <vector>
 
 #include "naruto_field.hip"
 #include "naruto_binned.hip"
@@ -159,7 +160,8 @@ int ray_lds_attr() {
                        {lds_use(k_composite_fwd, bytes), lds_use(k_composite_bwd<true>, bytes), lds_use(k_composite_bwd<false>, bytes), lds_use(k_loss_stage, bytes),
                         lds_use(k_loss_bwd_fused, bytes), lds_use(k_query_fwd_loss<false, false>, kFwdLossMaxRayLds), lds_use(k_query_fwd_loss<true, false>, kFwdLossMaxRayLds),
                         lds_use(k_query_fwd_loss<false, true>, kFwdLossMaxRayLds), lds_use(k_query_fwd_loss<true, true>, kFwdLossMaxRayLds),
-                        lds_use(k_query_fwd_loss_short<false>, 16u * 1024u), lds_use(k_query_fwd_loss_short<true>, 16u * 1024u)},
+                        lds_use(k_query_fwd_loss_short<false>, 16u * 1024u), lds_use(k_query_fwd_loss_short<true>, 16u * 1024u),
+                        lds_use(k_query_fwd_loss_img, kFwdLossMaxRayLds), lds_use(k_query_fwd_loss_short_img, 16u * 1024u)},
                        "per-ray kernels: cannot reserve %zu bytes of LDS", bytes);
 }
 
@@ -925,6 +927,17 @@ TrainWs train_ws(const NarutoField* f, const NarutoTrainStep* t) {
     w.total = c.size();
     return w;
 }
+// NarutoTrainStep.fwd_image, the exact mode's forward weight image kept from one iteration to the next (naruto_field.hip, fwd_image_put):
+// | FwdLdsX3, 16-byte aligned | the slot of every MLP weight, uint32 [kNumWeights] |.  The caller's buffer, not part of the workspace above.
+struct FwdImageWs { void* image; uint32_t* slots; size_t total; };
+FwdImageWs fwd_image_ws(void* base) {
+    Carve c(base);
+    return {c.take<void>(kFwdImageBytes, 16u), c.take<uint32_t>((size_t)kNumWeights * sizeof(uint32_t), 16u), c.size()};
+}
+// the image a training forward may read: only on the caller's word that it is fresh, and only where a kernel takes one (exact mode, x3 chain)
+inline const void* fresh_fwd_image(const NarutoField* f, const NarutoTrainStep* t) {
+    return (kExactX3 && t->fwd_image != nullptr && t->fwd_image_fresh != 0u && f->desc.mlp_mode != NARUTO_MLP_BF16) ? fwd_image_ws(t->fwd_image).image : nullptr;
+}
 int train_check(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const char* who) {
     if (f == nullptr || p == nullptr || t == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL argument", who);
     if (p->table == nullptr || p->uncert_grid == nullptr || p->sdf_w0 == nullptr || p->sdf_w1 == nullptr || p->col_w0 == nullptr || p->col_w1 == nullptr)
@@ -939,6 +952,7 @@ int train_check(const NarutoField* f, const NarutoParams* p, const NarutoTrainSt
     if (t->perturb && t->rand == nullptr && t->rng == nullptr) return fail(NARUTO_ERR_INVALID, "%s: perturb needs rand or rng", who);
     if (t->smooth_points != 0 && t->rand6 == nullptr && t->rng == nullptr) return fail(NARUTO_ERR_INVALID, "%s: the smoothness term needs rand6 or rng", who);
     if (t->smooth_points != 0 && t->loss_weights == nullptr) return fail(NARUTO_ERR_INVALID, "%s: the smoothness term needs loss_weights", who);
+    if ((reinterpret_cast<uintptr_t>(t->fwd_image) & 15u) != 0u) return fail(NARUTO_ERR_INVALID, "%s: fwd_image must be 16-byte aligned", who);
     return NARUTO_OK;
 }
 // A2..A5 of the training forward: k_query_fwd over the batch's samples, one wave per ray with depth-ordered early termination
@@ -1161,7 +1175,9 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
         const uint32_t tail_blocks = wxa.on ? tv_encode_blocks(loss->tv.n * loss->tv.n * loss->tv.n, wxa.tv_groups) : loss->n_tv_blocks;
         const uint32_t R = pl.rays_per_row;
         const uint32_t sblocks = pl.blocks;
-        if (bfm) hipLaunchKernelGGL(k_query_fwd_loss_short<true>, dim3(sblocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, *loss, sblocks, wxa, R, g_fwd_timeline);
+        // (the weight image, where the caller called it fresh: the exact mode's kernel that copies it instead of staging the weights)
+        if (!bfm && wxa.w_img != nullptr) hipLaunchKernelGGL(k_query_fwd_loss_short_img, dim3(sblocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, *loss, sblocks, wxa, R, g_fwd_timeline);
+        else if (bfm) hipLaunchKernelGGL(k_query_fwd_loss_short<true>, dim3(sblocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, *loss, sblocks, wxa, R, g_fwd_timeline);
         else hipLaunchKernelGGL(k_query_fwd_loss_short<false>, dim3(sblocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, *loss, sblocks, wxa, R, g_fwd_timeline);
         if (fused != nullptr) *fused = true;
         return check_launch("query_fwd_loss_short");
@@ -1174,7 +1190,10 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
         const uint32_t tail_blocks = wxa.on ? tv_encode_blocks(loss->tv.n * loss->tv.n * loss->tv.n, wxa.tv_groups) : loss->n_tv_blocks;
 #define NARUTO_LAUNCH_WALK(BFV, SPV) hipLaunchKernelGGL((k_query_fwd_loss<BFV, SPV>), dim3(blocks + tail_blocks), dim3(256), ray_scratch_fwd_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, \
                                                         t->raw, t->feat_save, ee, *loss, blocks, wxa, g_fwd_timeline)
-        if (pl.split) { if (bfm) NARUTO_LAUNCH_WALK(true, true); else NARUTO_LAUNCH_WALK(false, true); }
+        if (pl.split && !bfm && wxa.w_img != nullptr)          // (the weight image, where the caller called it fresh)
+            hipLaunchKernelGGL(k_query_fwd_loss_img, dim3(blocks + tail_blocks), dim3(256), ray_scratch_fwd_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, ee, *loss, blocks, wxa,
+                               g_fwd_timeline);
+        else if (pl.split) { if (bfm) NARUTO_LAUNCH_WALK(true, true); else NARUTO_LAUNCH_WALK(false, true); }
         else { if (bfm) NARUTO_LAUNCH_WALK(true, false); else NARUTO_LAUNCH_WALK(false, false); }
 #undef NARUTO_LAUNCH_WALK
         if (fused != nullptr) *fused = true;
@@ -1340,6 +1359,7 @@ int naruto_train_forward(const NarutoField* f, const NarutoParams* p, const Naru
     // (the smoothness term is left to the backward: the single-process deferred tail, or the data-parallel SUMS_TV_LATER form)
     const bool deferred_ = (finalize == NARUTO_TRAIN_FWD_DEFER_TAIL || finalize == NARUTO_TRAIN_FWD_SUMS_TV_LATER) && tail_rides_in_backward(t);
     WalkExtra wx{};
+    wx.w_img = fresh_fwd_image(f, t);
     note_tv_left(t->workspace, finalize == NARUTO_TRAIN_FWD_SUMS_TV_LATER && tv_moved(f, t, deferred_));
     if (tv_moved(f, t, deferred_)) {
         wx.on = 1u;
@@ -1393,6 +1413,46 @@ int naruto_train_finalize(const NarutoField* f, const NarutoTrainStep* t, void* 
     return check_launch("loss_finalize_total");
 }
 
+size_t naruto_fwd_image_bytes(size_t* image_bytes, uint32_t* n_weights) {
+    if (image_bytes != nullptr) *image_bytes = kFwdImageBytes;
+    if (n_weights != nullptr) *n_weights = (uint32_t)kNumWeights;
+    return fwd_image_ws(nullptr).total;
+}
+
+namespace {
+const uint32_t* fwd_image_slots_host() {
+    static const std::vector<uint32_t> slots = [] { std::vector<uint32_t> s((size_t)kNumWeights); fwd_image_slot_map(s.data(), nullptr); return s; }();
+    return slots.data();
+}
+int fwd_image_args(const NarutoField* f, const NarutoParams* p, const void* buf, const char* who) {
+    if (f == nullptr || p == nullptr || buf == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL argument", who);
+    if (p->sdf_w0 == nullptr || p->sdf_w1 == nullptr || p->col_w0 == nullptr || p->col_w1 == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL weights", who);
+    if ((reinterpret_cast<uintptr_t>(buf) & 15u) != 0u) return fail(NARUTO_ERR_INVALID, "%s: the buffer must be 16-byte aligned", who);
+    return NARUTO_OK;
+}
+}  // namespace
+
+int naruto_fwd_image_init(const NarutoField* f, const NarutoParams* p, void* fwd_image, void* stream) {
+    if (int rc = fwd_image_args(f, p, fwd_image, "fwd_image_init")) return rc;
+    const FwdImageWs w = fwd_image_ws(fwd_image);
+    if (hipMemcpyAsync(w.slots, fwd_image_slots_host(), (size_t)kNumWeights * sizeof(uint32_t), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
+        return fail(NARUTO_ERR_LAUNCH, "fwd_image_init: slot upload: %s", hipGetErrorString(hipGetLastError()));
+    hipLaunchKernelGGL(k_fwd_image_init, dim3(1), dim3(256), 0, (hipStream_t)stream, *p, static_cast<FwdLdsX3*>(w.image));
+    return check_launch("fwd_image_init");
+}
+
+int naruto_debug_fwd_image(const NarutoField* f, const NarutoParams* p, void* out, void* stream) {
+    if (int rc = fwd_image_args(f, p, out, "debug_fwd_image")) return rc;
+    hipLaunchKernelGGL(k_debug_fwd_image, dim3(1), dim3(256), 0, (hipStream_t)stream, *p, static_cast<uint4*>(out));
+    return check_launch("debug_fwd_image");
+}
+
+int naruto_debug_fwd_image_map(uint32_t* slots, uint8_t* zero_fill) {
+    if (slots == nullptr) return fail(NARUTO_ERR_INVALID, "debug_fwd_image_map: NULL argument");
+    fwd_image_slot_map(slots, zero_fill);
+    return NARUTO_OK;
+}
+
 // profiling: device buffer of 16 x (workgroups) uint64 the packed training forward stamps s_memtime into (NULL: off) -- the per-step timeline of
 // k_query_fwd_loss_packed's first chunk, see its header
 int naruto_debug_fwd_timeline(void* device_buffer) {
@@ -1412,6 +1472,7 @@ int naruto_debug_train_query_fwd(const NarutoField* f, const NarutoParams* p, co
     // (the five-launch iteration's form of it -- depth sampling in the walk, the lattice encode in its tail workgroups -- where the trainer's
     // iteration takes that form; the jitter is whatever the step's generator state gives: timing only)
     WalkExtra wx{};
+    wx.w_img = fresh_fwd_image(f, t);
     const bool deferred = tail_rides_in_backward(t);
     if (tv_moved(f, t, deferred)) {
         const float* jitter = t->perturb ? t->rand : nullptr;
@@ -1526,6 +1587,8 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
             adam.lr[k] = opt->lr[k]; adam.eps[k] = opt->eps[k]; adam.wd[k] = opt->weight_decay[k];
         }
         adam.b1 = opt->beta1; adam.b2 = opt->beta2; adam.step_dev = opt->step_dev; adam.on = 1;
+        // the finishing launch keeps the forward's weight image in step with the weights it updates (exact mode; whoever reads it decides per forward)
+        if (kExactX3 && f->desc.mlp_mode != NARUTO_MLP_BF16) adam.fwd_img = t_in->fwd_image;
     }
     if (g == nullptr || t->loss_weights == nullptr || t->feat_save == nullptr || t->d_raw == nullptr || t->ray_count == nullptr || t->ray_offset == nullptr ||
         t->active_idx == nullptr || t->n_active == nullptr)

@@ -810,6 +810,85 @@ __device__ __forceinline__ void stage_fwd_weights_x3_via_lds(FwdLdsX3& L, float*
     fetch_raw_weights<NT>(raw, p, tid);
     stage_fwd_weights_x3_from<NT>(L, WSrcLds{raw, p}, tid);
 }
+// ---- the x3 image kept in global memory from one training iteration to the next ----
+// The image depends on the MLP weights alone, and in a chain of fused-Adam iterations those change exactly once per iteration, in the
+// finishing launch (wgrad_reduce_body -> adam_apply).  So that launch also writes each new weight's image slots (fwd_image_put: the same
+// split3, the 16-bit halves pack8x3 would have formed), and the training forward of the NEXT iteration copies the 33.4 KB with coalesced
+// 16-byte loads (FwdImageRegs) instead of fetching 22 KB of row-major weights, transposing them through the slabs and splitting them in
+// every one of its 512 workgroups.  Buffer: | FwdLdsX3 | the slot of every weight, uint32 [kNumWeights] | (fwd_image_ws in naruto_api.hip).
+// A slot word: low half = byte offset of the hi piece (of the float, for col_w1), high half = byte stride to the mid and lo pieces (0: col_w1).
+constexpr size_t kFwdImageBytes = sizeof(FwdLdsX3);
+static_assert(kFwdImageBytes % 16 == 0 && kFwdImageBytes < 65536, "copied in 16-byte pieces; a slot's offset fits 16 bits");
+constexpr int kWOffS1 = kHidden * kInSdf, kWOffC0 = kWOffS1 + kOut * kHidden, kWOffC1 = kWOffC0 + kHidden * kInCol;      // weights in the optimiser's order:
+constexpr int kNumWeights = kWOffC1 + 3 * kHidden;                                                                    // sdf_w0 | sdf_w1 | col_w0 | col_w1 = 5 184
+// The inverse of stage_fwd_weights_x3_from, by enumerating ITS index expressions (host; tests/test_gpu_fwd_image.py holds the two together
+// byte for byte).  zero_fill (optional, kFwdImageBytes bytes): 1 where the staging writes the zero padding (rows >= kOut, crow < 1).
+inline void fwd_image_slot_map(uint32_t* slots, uint8_t* zero_fill) {
+    for (int w = 0; w < kNumWeights; ++w) slots[w] = 0xFFFFFFFFu;
+    if (zero_fill != nullptr) for (size_t b = 0; b < kFwdImageBytes; ++b) zero_fill[b] = 0;
+    for (int e = 0; e < 11 * 64; ++e) {
+        const int t = e >> 6, l = e & 63, i = l & 31, hh = l >> 5;
+        for (int q = 0; q < 8; ++q) {
+            int w = -1;
+            if (t < 2) w = i * kInSdf + 2 * (8 * t + q) + hh;
+            else if (t < 5) w = i * kInSdf + kFeat + 16 * (t - 2) + 8 * hh + q;
+            else if (t < 8) w = kWOffC0 + i * kInCol + 16 * (t - 5) + 8 * hh + q;
+            else if (t == 8) { const int row = crow(q, hh); if (row >= 1) w = kWOffC0 + i * kInCol + kPos + row - 1; }
+            else if (i < kOut) w = kWOffS1 + i * kHidden + crow(8 * (t - 9) + q, hh);
+            size_t base, stride;
+            if (t < 5) { base = offsetof(FwdLdsX3, s0) + (size_t)(t * 64 + l) * 16u; stride = sizeof(u32x4_t) * 5 * 64; }
+            else if (t < 9) { base = offsetof(FwdLdsX3, c0) + (size_t)((t - 5) * 64 + l) * 16u; stride = sizeof(u32x4_t) * 4 * 64; }
+            else { base = offsetof(FwdLdsX3, s1) + (size_t)((t - 9) * 64 + l) * 16u; stride = sizeof(u32x4_t) * 2 * 64; }
+            base += 2u * (size_t)q;                                     // pk_hi16: value 2 k in the low half of word k, 2 k + 1 in the high half
+            if (w >= 0) slots[w] = (uint32_t)base | ((uint32_t)stride << 16);
+            else if (zero_fill != nullptr) for (int k = 0; k < 3; ++k) { zero_fill[base + k * stride] = 1; zero_fill[base + k * stride + 1] = 1; }
+        }
+    }
+    for (int e = 0; e < 3 * 16 * 2; ++e) {
+        const int c = e / 32, r = (e >> 1) & 15, hh = e & 1;
+        slots[kWOffC1 + c * kHidden + crow(r, hh)] = (uint32_t)(offsetof(FwdLdsX3, c1) + sizeof(float) * (size_t)e);
+    }
+}
+// weight w (optimiser order) has become p: its slots of the image
+__device__ __forceinline__ void fwd_image_put(void* __restrict__ img, int w, float p) {
+    char* const base = reinterpret_cast<char*>(img);
+    const uint32_t slot = reinterpret_cast<const uint32_t*>(base + kFwdImageBytes)[w];
+    char* const at = base + (slot & 0xFFFFu);
+    const uint32_t stride = slot >> 16;
+    if (stride == 0u) { *reinterpret_cast<float*>(at) = p; return; }
+    uint32_t h, m, l;
+    split3(p, h, m, l);
+    *reinterpret_cast<uint16_t*>(at) = (uint16_t)(h >> 16);
+    *reinterpret_cast<uint16_t*>(at + stride) = (uint16_t)(m >> 16);
+    *reinterpret_cast<uint16_t*>(at + 2u * stride) = (uint16_t)(l >> 16);
+}
+// a workgroup's copy of the image in two steps, so that the kernel can put latency of its own (the rays' fetch, the depth sampling) between the
+// loads and the LDS stores.  The empty statements are memory fences for the COMPILER only: left alone it sinks the loads down to the stores.
+template <int NT>
+struct FwdImageRegs {
+    static constexpr int n16 = (int)(kFwdImageBytes / 16), nq = (n16 + NT - 1) / NT;      // 2 136 pieces: nine per thread of 256
+    static_assert((nq - 1) * NT <= n16, "only a thread's last piece can lie past the end");
+    u32x4_t v[nq];
+    // (the pointer may come out of LDS, where the compiler has lost its address space: say it, or the loads are flat ones and count as LDS traffic too)
+    // (tid goes through an opaque copy: what depends on it -- addresses, the last piece's guard -- is then computed HERE, not hoisted out of the caller's
+    // loop and held in registers across its tiles)
+    __device__ __forceinline__ void load(const void* __restrict__ img, int tid) {
+        asm volatile("" : "+v"(tid));
+        const __attribute__((address_space(1))) u32x4_t* src = (const __attribute__((address_space(1))) u32x4_t*)img + tid;
+#pragma unroll
+        for (int q = 0; q < nq - 1; ++q) v[q] = src[q * NT];
+        v[nq - 1] = u32x4_t{0u, 0u, 0u, 0u};
+        if ((nq - 1) * NT + tid < n16) v[nq - 1] = src[(nq - 1) * NT];
+        asm volatile("" ::: "memory");
+    }
+    __device__ __forceinline__ void store(FwdLdsX3& L, int tid) const {
+        asm volatile("" : "+v"(tid) :: "memory");
+        u32x4_t* __restrict__ dst = reinterpret_cast<u32x4_t*>(&L) + tid;
+#pragma unroll
+        for (int q = 0; q < nq - 1; ++q) dst[q * NT] = v[q];
+        if ((nq - 1) * NT + tid < n16) dst[(nq - 1) * NT] = v[nq - 1];
+    }
+};
 // the matrix phase of a tile (fwd_mlp_tile's counterpart): hash part of the B operands from the slab
 // HALF (round 6): the tile's B points (32..63) are dead -- only the A chains run; the B lanes' outputs are unspecified (the caller writes zeros)
 // LANE_BLOB (round 6): OneBlob's form (closed / dense: 1e-6 apart) chosen per LANE instead of per tile -- a sample's outputs then depend on the sample alone,
@@ -2941,6 +3020,7 @@ struct AdamFuse {
     float b1, b2;
     const int32_t* step_dev;      // this step's 1-based number
     int on;
+    void* fwd_img;                // the training forward's weight image (FwdLdsX3 | slots, see fwd_image_put), or NULL: the MLP weights' step writes it too
 };
 struct AdamCoef { float bc1, bc2_sqrt; };
 __device__ __forceinline__ AdamCoef adam_coef(const AdamFuse& a) {
@@ -3022,7 +3102,20 @@ __device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ part
         if (!overwrite) s += gt[off];
         gt[off] = s;
     }
-    if (adam != nullptr && adam->on && adam->p[tensor] != nullptr) adam_apply(*adam, adam_coef(*adam), tensor, (size_t)off, s);
+    if (adam != nullptr && adam->on && adam->p[tensor] != nullptr) {
+        adam_apply(*adam, adam_coef(*adam), tensor, (size_t)off, s);
+        if constexpr (kExactX3) {
+            if (adam->fwd_img != nullptr) {
+                // The new weight is READ BACK behind a compiler fence rather than handed over by adam_apply: as a second use of that value it changed how
+                // the step's multiplies and adds were paired and fused (two v_pk_mul / v_pk_add became v_fmac), i.e. the weights' bits.  The step's code
+                // must not know that anybody looks at its result; the load is this thread's own store coming back, in 32 threads per block.
+                asm volatile("" ::: "memory");
+                const float pn = adam->p[tensor][off];
+                // (two weights share a 32-bit word of the image: 16-bit stores, no two threads touch the same bytes)
+                fwd_image_put(adam->fwd_img, (tensor == 1 ? 0 : (tensor == 2 ? kWOffS1 : (tensor == 3 ? kWOffC0 : kWOffC1))) + off, pn);
+            }
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ partials, uint32_t n_blocks, NarutoGrads g, int overwrite) {

@@ -184,14 +184,22 @@ struct WalkExtra {
     uint32_t tv_groups;          // level groups per lattice-encode workgroup (tv_encode_blocks)
     SampleArgs sa;
     const float* rand6; const uint64_t* rng; float* x_out;
+    // k_query_fwd_loss_img / k_query_fwd_loss_short_img: the x3 weight image the last iteration's finishing launch left in global memory (FwdImageRegs
+    // in naruto_field.hip); the launcher picks those kernels only when the CALLER states the image fresh (NarutoTrainStep.fwd_image_fresh)
+    const void* w_img;
 };
 
 // SPLIT: the tile in two phases through a per-wave LDS slab (fwd_tile_split) -- 32 KB per workgroup, so the launcher uses it only while two
 // workgroups still fit a CU next to the rays' images (up to 192 samples per ray); longer rays keep the register form (fwd_tile).
-template <bool BF, bool SPLIT>
-__global__ __launch_bounds__(256, 2) void k_query_fwd_loss(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, float* __restrict__ raw,
-                                                           float* __restrict__ feat_save, EarlyExit ee, LossStageArgs a, uint32_t n_fwd_blocks, WalkExtra wx,
-                                                           unsigned long long* __restrict__ timeline) {
+// IMAGE (k_query_fwd_loss_img, exact mode): the weights come as the x3 image in global memory (WalkExtra.w_img) -- a kernel of its own rather than a
+// branch in this one: with both prologues in one kernel the scalar registers spilled around the tile loop went from 134 to 143 - 147 (the
+// allocator splits the live ranges at the branch), past the budget this kernel is held to.  The copy comes first, then the barrier, then the rays
+// as before: sampling the first rays' depths between the image's loads and its LDS stores (a second inlined prepare_ray in front of the group
+// loop, or the image's 36 registers held across it) was built as well and came to 141 - 147 spilled scalars, 130 in the short kernel.
+template <bool BF, bool SPLIT, bool IMAGE = false>
+__device__ __forceinline__ void query_fwd_loss_body(const LevelTab& lt, const UncertTab& ut, const BoxTab& bt, const NarutoParams& p, const PointSrc& ps, uint32_t M,
+                                                    float* __restrict__ raw, float* __restrict__ feat_save, const EarlyExit& ee, const LossStageArgs& a,
+                                                    uint32_t n_fwd_blocks, const WalkExtra& wx, unsigned long long* __restrict__ timeline) {
     using Lds = std::conditional_t<BF, FwdLdsBf, std::conditional_t<SPLIT, FwdLdsExact, FwdLds>>;      // (two-phase tile, exact mode: the x3 chain)
     // profiling (naruto_debug_fwd_timeline; NULL otherwise): lane 0 of every WAVE stamps the 100 MHz counter into its row of 8 -- 0 start, 1 weights
     // staged, 2 depths sampled, 3 first tile's gathers, 4 first tile done, 5 all tiles done, 6 loss stage; slot 7 = tiles evaluated (tools/walk_timeline.py)
@@ -220,7 +228,13 @@ __global__ __launch_bounds__(256, 2) void k_query_fwd_loss(LevelTab lt, UncertTa
     // (two workgroups per CU at S = 128)
     __shared__ float ray_c[kRaysPerBlock][16];
     if (threadIdx.x == 0) { a_s = a; wx_s = wx; }
-    if constexpr (SPLIT && BF) stage_fwd_weights_bf_via_lds<256>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
+    constexpr bool kImage = IMAGE && std::is_same_v<Lds, FwdLdsX3>;      // (without the x3 chain there is no image: the kernel stages like the other)
+    if constexpr (kImage) {                                // nine 16-byte loads per thread, then their LDS stores
+        FwdImageRegs<256> wimg;
+        wimg.load(wx.w_img, threadIdx.x);
+        wimg.store(L, threadIdx.x);
+    }
+    else if constexpr (SPLIT && BF) stage_fwd_weights_bf_via_lds<256>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
     else if constexpr (SPLIT) stage_fwd_exact<256, sizeof(slabs)>(L, slabs, p, threadIdx.x);
     else if constexpr (BF) stage_fwd_weights_bf<256>(L, p, threadIdx.x);
     else stage_fwd_weights<256>(L, p, threadIdx.x);
@@ -234,33 +248,36 @@ __global__ __launch_bounds__(256, 2) void k_query_fwd_loss(LevelTab lt, UncertTa
     const uint32_t tpr = ee.tiles_per_ray, S = a.S;                  // tpr = ceil(S / 64): a ray's last tile may be partly filled (round 5)
     const uint32_t n_groups = (a.n_rays + (uint32_t)kRaysPerBlock - 1u) / (uint32_t)kRaysPerBlock;
     const RayScratch rs = ray_scratch_fwd(ray_lds, wave, S);
+    // Round 6: everything the ray needs from memory besides the table is requested HERE, once, and consumed from registers / the
+    // wave's LDS image -- the ray itself, its measured depth (early termination), its targets (loss stage), its depths (sampled into
+    // the image, or fetched).  Before, every tile re-read its depths and the ray from global memory (the depths right after
+    // writing them) and ee_after_tile / the loss stage fetched the measured depth again: two to three L2 round trips on the
+    // critical path of every tile, one more in front of the loss stage.  Same arithmetic on the same numbers: same bits.
+    // (through LDS, one lane each: as wave-uniform scalar loads they would sit in seven more scalar registers across the tile loop --
+    // this kernel spills those -- and as vector registers the loads would be issued by all 64 lanes)
+    auto prepare_ray = [&](uint32_t task) {
+        if (lane < 11) {
+            float v;
+            if (lane < 3) v = ps.rays_o[3 * task + lane];
+            else if (lane < 6) v = ps.rays_d[3 * task + lane - 3];
+            else if (lane == 6) v = ee.target_d[task];
+            else if (lane < 10) v = a_s.target_rgb[3 * (size_t)task + lane - 7];
+            else v = a_s.target_d[task];
+            ray_c[wave][lane < 7 ? lane : lane + 5] = v;
+        }
+        bool sampled = false;
+        if constexpr (SPLIT) if (wx.on) {
+            const SampleArgs& sa = wx_s.sa;
+            sample_z_ray(task, sa.target_d, sa.near_, sa.far_, sa.nu, sa.nr, sa.range_d, sa.rand, sa.rng, sa.z_vals, rs.c0, rs.c1, lane, rs.z);
+            sampled = true;
+        }
+        if (!sampled) for (uint32_t s = lane; s < S; s += 64u) rs.z[s] = ps.z_vals[(size_t)task * S + s];
+        wave_lds_sync();
+    };
     for (uint32_t group = blockIdx.x; group < n_groups; group += n_fwd_blocks) {          // uniform over the workgroup: barriers inside
         const uint32_t task = group * (uint32_t)kRaysPerBlock + (uint32_t)wave;
         if (task < a.n_rays) {
-            // Round 6: everything the ray needs from memory besides the table is requested HERE, once, and consumed from registers / the
-            // wave's LDS image -- the ray itself, its measured depth (early termination), its targets (loss stage), its depths (sampled into
-            // the image, or fetched).  Before, every tile re-read its depths and the ray from global memory (the depths right after
-            // writing them) and ee_after_tile / the loss stage fetched the measured depth again: two to three L2 round trips on the
-            // critical path of every tile, one more in front of the loss stage.  Same arithmetic on the same numbers: same bits.
-            // (through LDS, one lane each: as wave-uniform scalar loads they would sit in seven more scalar registers across the tile loop --
-            // this kernel spills those -- and as vector registers the loads would be issued by all 64 lanes)
-            if (lane < 11) {
-                float v;
-                if (lane < 3) v = ps.rays_o[3 * task + lane];
-                else if (lane < 6) v = ps.rays_d[3 * task + lane - 3];
-                else if (lane == 6) v = ee.target_d[task];
-                else if (lane < 10) v = a_s.target_rgb[3 * (size_t)task + lane - 7];
-                else v = a_s.target_d[task];
-                ray_c[wave][lane < 7 ? lane : lane + 5] = v;
-            }
-            bool sampled = false;
-            if constexpr (SPLIT) if (wx.on) {
-                const SampleArgs& sa = wx_s.sa;
-                sample_z_ray(task, sa.target_d, sa.near_, sa.far_, sa.nu, sa.nr, sa.range_d, sa.rand, sa.rng, sa.z_vals, rs.c0, rs.c1, lane, rs.z);
-                sampled = true;
-            }
-            if (!sampled) for (uint32_t s = lane; s < S; s += 64u) rs.z[s] = ps.z_vals[(size_t)task * S + s];
-            wave_lds_sync();
+            prepare_ray(task);
             if (group == blockIdx.x) stamp(2);
             EeState ees{false, 0.0f, 0.0f, 0.0f};
             const uint32_t ray0 = task * S;                              // the ray's first sample in the point list
@@ -332,6 +349,18 @@ __global__ __launch_bounds__(256, 2) void k_query_fwd_loss(LevelTab lt, UncertTa
         __syncthreads();                                   // terms are rewritten by the next group
     }
 }
+template <bool BF, bool SPLIT>
+__global__ __launch_bounds__(256, 2) void k_query_fwd_loss(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, float* __restrict__ raw,
+                                                           float* __restrict__ feat_save, EarlyExit ee, LossStageArgs a, uint32_t n_fwd_blocks, WalkExtra wx,
+                                                           unsigned long long* __restrict__ timeline) {
+    query_fwd_loss_body<BF, SPLIT>(lt, ut, bt, p, ps, M, raw, feat_save, ee, a, n_fwd_blocks, wx, timeline);
+}
+// exact mode, two-phase tile, wx.w_img != NULL
+__global__ __launch_bounds__(256, 2) void k_query_fwd_loss_img(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, float* __restrict__ raw,
+                                                               float* __restrict__ feat_save, EarlyExit ee, LossStageArgs a, uint32_t n_fwd_blocks, WalkExtra wx,
+                                                               unsigned long long* __restrict__ timeline) {
+    query_fwd_loss_body<false, true, true>(lt, ut, bt, p, ps, M, raw, feat_save, ee, a, n_fwd_blocks, wx, timeline);
+}
 template __global__ void k_query_fwd_loss<false, false>(LevelTab, UncertTab, BoxTab, NarutoParams, PointSrc, uint32_t, float*, float*, EarlyExit, LossStageArgs, uint32_t, WalkExtra, unsigned long long*);
 template __global__ void k_query_fwd_loss<true, false>(LevelTab, UncertTab, BoxTab, NarutoParams, PointSrc, uint32_t, float*, float*, EarlyExit, LossStageArgs, uint32_t, WalkExtra, unsigned long long*);
 template __global__ void k_query_fwd_loss<false, true>(LevelTab, UncertTab, BoxTab, NarutoParams, PointSrc, uint32_t, float*, float*, EarlyExit, LossStageArgs, uint32_t, WalkExtra, unsigned long long*);
@@ -349,10 +378,11 @@ template __global__ void k_query_fwd_loss<true, true>(LevelTab, UncertTab, BoxTa
 constexpr uint32_t kShortMaxRays = 8;
 inline uint32_t short_rays_per_block(uint32_t S) { const uint32_t r = 256u / (S ? S : 1u); return r > kShortMaxRays ? kShortMaxRays : (r < 1u ? 1u : r); }
 inline size_t short_lds_bytes(uint32_t S) { return (size_t)short_rays_per_block(S) * kRayFields * S * sizeof(float); }
-template <bool BF>
-__global__ __launch_bounds__(256, 2) void k_query_fwd_loss_short(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, float* __restrict__ raw,
-                                                                 float* __restrict__ feat_save, LossStageArgs a, uint32_t n_fwd_blocks, WalkExtra wx, uint32_t R,
-                                                                 unsigned long long* __restrict__ timeline) {
+// IMAGE (k_query_fwd_loss_short_img, exact mode): the weights come as the x3 image in global memory (WalkExtra.w_img), see query_fwd_loss_body
+template <bool BF, bool IMAGE = false>
+__device__ __forceinline__ void query_fwd_loss_short_body(const LevelTab& lt, const UncertTab& ut, const BoxTab& bt, const NarutoParams& p, const PointSrc& ps, uint32_t M,
+                                                          float* __restrict__ raw, float* __restrict__ feat_save, const LossStageArgs& a, uint32_t n_fwd_blocks,
+                                                          const WalkExtra& wx, uint32_t R, unsigned long long* __restrict__ timeline) {
     using Lds = std::conditional_t<BF, FwdLdsBf, FwdLdsExact>;
     __shared__ Lds L;
     __shared__ FwdSlab slabs[kRaysPerBlock];
@@ -395,8 +425,15 @@ __global__ __launch_bounds__(256, 2) void k_query_fwd_loss_short(LevelTab lt, Un
             rayc[r][c] = v;
         }
     };
+    constexpr bool kImage = IMAGE && std::is_same_v<Lds, FwdLdsX3>;
     fetch_targets(blockIdx.x * R);
-    if constexpr (BF) stage_fwd_weights_bf_via_lds<256>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
+    if constexpr (kImage) {                                // nine 16-byte loads per thread, then their LDS stores
+        FwdImageRegs<256> wimg;
+        wimg.load(wx.w_img, threadIdx.x);
+        wimg.store(L, threadIdx.x);
+        __syncthreads();                                   // (publishes tgt, as the staging's barrier does)
+    }
+    else if constexpr (BF) stage_fwd_weights_bf_via_lds<256>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
     else stage_fwd_exact<256, sizeof(slabs)>(L, slabs, p, threadIdx.x);      // (its barrier also publishes tgt)
     stamp(5);
     for (uint32_t group = blockIdx.x; group < n_groups; group += n_fwd_blocks) {          // uniform over the workgroup: barriers inside
@@ -481,6 +518,17 @@ __global__ __launch_bounds__(256, 2) void k_query_fwd_loss_short(LevelTab lt, Un
         __syncthreads();                                   // terms and the images are rewritten by the next group
     }
     stamp(7);
+}
+template <bool BF>
+__global__ __launch_bounds__(256, 2) void k_query_fwd_loss_short(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, float* __restrict__ raw,
+                                                                 float* __restrict__ feat_save, LossStageArgs a, uint32_t n_fwd_blocks, WalkExtra wx, uint32_t R,
+                                                                 unsigned long long* __restrict__ timeline) {
+    query_fwd_loss_short_body<BF>(lt, ut, bt, p, ps, M, raw, feat_save, a, n_fwd_blocks, wx, R, timeline);
+}
+__global__ __launch_bounds__(256, 2) void k_query_fwd_loss_short_img(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, float* __restrict__ raw,
+                                                                     float* __restrict__ feat_save, LossStageArgs a, uint32_t n_fwd_blocks, WalkExtra wx, uint32_t R,
+                                                                     unsigned long long* __restrict__ timeline) {
+    query_fwd_loss_short_body<false, true>(lt, ut, bt, p, ps, M, raw, feat_save, a, n_fwd_blocks, wx, R, timeline);
 }
 template __global__ void k_query_fwd_loss_short<false>(LevelTab, UncertTab, BoxTab, NarutoParams, PointSrc, uint32_t, float*, float*, LossStageArgs, uint32_t, WalkExtra, uint32_t, unsigned long long*);
 template __global__ void k_query_fwd_loss_short<true>(LevelTab, UncertTab, BoxTab, NarutoParams, PointSrc, uint32_t, float*, float*, LossStageArgs, uint32_t, WalkExtra, uint32_t, unsigned long long*);
@@ -1105,6 +1153,21 @@ __global__ __launch_bounds__(256) void k_compact(uint32_t n_rays, uint32_t S, co
         }
     }
     for (uint32_t k = lane; k < c; k += 64) active_idx[off + k] = n * S + k;
+}
+
+// ---- the forward weight image (naruto_fwd_image_init, naruto_debug_fwd_image) ----
+// the image from the weights as they are, written straight to global memory: the kernels' staging routine with L bound to the buffer (zero padding included)
+__global__ __launch_bounds__(256) void k_fwd_image_init(NarutoParams p, FwdLdsX3* __restrict__ image) {
+    stage_fwd_weights_x3_from<256>(*image, WSrcGlobal{p}, threadIdx.x);
+}
+// what a training forward's workgroup stages into LDS (the walk's and the short kernel's own call), copied out
+__global__ __launch_bounds__(256) void k_debug_fwd_image(NarutoParams p, uint4* __restrict__ out) {
+    __shared__ FwdLdsX3 L;
+    __shared__ FwdSlab slabs[kRaysPerBlock];
+    stage_fwd_exact<256, sizeof(slabs)>(L, slabs, p, threadIdx.x);
+    __syncthreads();
+    const uint4* src = reinterpret_cast<const uint4*>(&L);
+    for (uint32_t i = threadIdx.x; i < (uint32_t)(kFwdImageBytes / 16u); i += 256u) out[i] = src[i];
 }
 
 }  // namespace naruto

@@ -825,6 +825,7 @@ class TrainStep:
         self.flags = _lib.BWD_OVERWRITE_WEIGHT_GRADS | (_lib.BWD_OVERWRITE_TABLE_GRAD if handle_supports_overwrite(handle) else 0)
         self._zero_table = not handle_supports_overwrite(handle)
         self.opt = None                      # NarutoFusedAdam: set by fuse_adam()
+        self.fwd_image = None                # the forward's weight image (NarutoTrainStep.fwd_image): allocated by fuse_adam(), exact mode
         self._gs_nograd = None
         self.ba_poses = None                 # NarutoBAPoses: set by naruto_amd.ba_loop.FusedBA while it refines poses (naruto_train_backward_poses)
 
@@ -855,6 +856,20 @@ class TrainStep:
             for n in self.FLAT_NAMES:
                 setattr(gs, n, _p(self.grads[n]))
         self._gs_nograd = gs
+        if self.handle.mlp_mode == "fp32" and self.fwd_image is None:
+            # The training forward's weight image, kept in step with the weights by the launch that steps them.  Prepared here, once, from the
+            # weights as they are (outside any capture); a forward reads it only while fwd_image_fresh is set (MappingTrainer.capture(chain=...)).
+            lib = _lib.load()
+            self.fwd_image = _lib.workspace(lib.naruto_fwd_image_bytes(None, None), self.device, dtype=torch.uint8)
+            with _on_device(self.device):
+                check(lib.naruto_fwd_image_init(self.handle.ptr, C.byref(self.ps), _p(self.fwd_image), _stream()), "naruto_fwd_image_init")
+            self.t.fwd_image = _p(self.fwd_image)
+
+    def fwd_image_fresh(self, fresh: bool) -> bool:
+        """The caller's statement for the forwards issued from now on: the weight image matches the MLP weights, i.e. the last thing that changed
+        them was this step's own fused-Adam backward.  Returns whether a forward will use it (False: no image -- bf16 mode, no fused optimiser)."""
+        self.t.fwd_image_fresh = 1 if (fresh and self.fwd_image is not None and self.opt is not None) else 0
+        return bool(self.t.fwd_image_fresh)
 
     def _set_rng_mode(self, device_rng: bool):
         t, M = self.t, self.N * self.S

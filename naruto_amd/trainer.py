@@ -581,7 +581,8 @@ class MappingTrainer:
                 self.uncert_optim.step()
         return out
 
-    def capture(self, n_rays: int, smooth: bool = False, n_rays_total: int = 0, warmup: int = 3, prologue=None, first_prologue=None, on_buffers=None, chain=None):
+    def capture(self, n_rays: int, smooth: bool = False, n_rays_total: int = 0, warmup: int = 3, prologue=None, first_prologue=None, on_buffers=None, chain=None,
+                fwd_image: Optional[bool] = None):
         """Record the iteration into hipGraphs (static shapes: n_rays rays per call).
         ``prologue(rays_o, rays_d, target_rgb, target_d)``: launches recorded IN FRONT of the iteration inside the same graphs -- the
         ray assembly / active ray selection that fill the iteration's input buffers (naruto_amd.ba_loop.FusedBA); single process.
@@ -591,7 +592,11 @@ class MappingTrainer:
         is called once the graph's input buffers and the persistent TrainStep exist, before anything is launched.
         ``chain``: a list of uncert_step flags -- ONE more graph that holds len(chain) iterations back to back (the first with ``first_prologue``
         when given), replayed by ``step_chain()``: a whole ``global_BA`` call as one graph launch (the launch-to-launch gap between graphs, 5 - 8 us
-        on MI355X, is paid once per call instead of once per iteration)."""
+        on MI355X, is paid once per call instead of once per iteration).
+        ``fwd_image``: iterations 1 ... of the chain read the MLP weights from the image the preceding iteration's finishing launch left (ops.TrainStep.
+        fwd_image_fresh) instead of staging them in every workgroup -- inside the chain nothing else can have changed the weights.  Iteration 0 and
+        the per-iteration graphs never do: their predecessor is unknown (a load_state_dict, another optimiser, a copy into the weights).  Default
+        (None): on, unless the environment says NARUTO_FWD_WEIGHT_IMAGE=0 at capture time; single process, fused Adam, exact mode only."""
         dev = self.device
         self.model.n_rays_total = n_rays_total
         flat = torch.zeros(n_rays * 10, device=dev)
@@ -698,13 +703,23 @@ class MappingTrainer:
         st['chain'] = None
         if chain and not segmented:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode):
-                for i, u in enumerate(chain):
-                    pro = first_prologue if (i == 0 and first_prologue is not None) else prologue
-                    if pro is not None:
-                        pro(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'])
-                    ret, loss = self._iteration(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'], smooth, bool(u), check=False)
+            if fwd_image is None:
+                fwd_image = os.environ.get("NARUTO_FWD_WEIGHT_IMAGE", "1") != "0"
+            ts_img = self._train_step(n_rays, bool(smooth and self.config['training']['smooth_weight'] > 0)) if (fwd_image and self.direct) else None
+            try:
+                with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode):
+                    for i, u in enumerate(chain):
+                        pro = first_prologue if (i == 0 and first_prologue is not None) else prologue
+                        if pro is not None:
+                            pro(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'])
+                        if ts_img is not None:
+                            ts_img.fwd_image_fresh(i > 0)          # the launch in front of this forward is iteration i - 1's fused-Adam finish
+                        ret, loss = self._iteration(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'], smooth, bool(u), check=False)
+            finally:
+                if ts_img is not None:
+                    ts_img.fwd_image_fresh(False)
             st['chain'] = (g, ret, loss, len(chain))
+            st['chain_fwd_image'] = bool(ts_img is not None and ts_img.fwd_image is not None and ts_img.opt is not None)
         if self.direct and not segmented:
             # the graphs hold the ADDRESSES of this TrainStep's buffers: keep it alive with them, whatever the LRU cache below evicts
             tr_cfg = self.config['training']

@@ -23,6 +23,9 @@ for _ in range(5):
 n_wg = 4096
 buf = torch.zeros(n_wg * 8, dtype=torch.int64, device=dev)
 lib = _lib.load()
+if os.environ.get("NARUTO_TIMELINE_FWD_IMAGE") == "1":
+    # the stamped step reads the weight image the preceding step's finishing launch left (as iterations 1 ... of a chained graph do)
+    assert tr._train_step(n_rays, True).fwd_image_fresh(True)
 lib.naruto_debug_fwd_timeline(buf.data_ptr())
 step()
 torch.cuda.synchronize()
