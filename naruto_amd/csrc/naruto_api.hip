@@ -659,6 +659,50 @@ int naruto_smoothness_fwd(const NarutoField* f, const float* table, uint32_t sam
     return check_launch("tv_finalize");
 }
 
+}  // extern "C"
+
+namespace {
+// The flat launch of the field query (64-sample tiles over the flat point list; measured in tools/fwd_lab.hip / profiles/r04_fwd_lab.txt): four-wave
+// workgroups up to one per CU; between one and two per CU two-wave workgroups, so that no CU holds more tiles than it must (see k_query_fwd; 1 376
+// tiles: 42.2 us against 45.6 as eight-wave ones); from two per CU on ONE persistent eight-wave workgroup per CU (one weight image, the waves walk
+// their tiles: 76.5 -> 69.0 us at 4 096 tiles).  NARUTO_DEBUG_FWD_SMALL_WG=0: no two-wave form (A/B timing).
+// big_wg_on: naruto_query_fwd alone passes NARUTO_DEBUG_FWD_SHAPE here (0: no eight-wave form); the training forward's plan does not read that knob.
+struct FlatShape { uint32_t blocks, threads; };
+FlatShape flat_fwd_shape(const NarutoField* f, uint32_t n_tiles, bool big_wg_on = true) {
+    static const bool small_wg_on = env_int("NARUTO_DEBUG_FWD_SMALL_WG", 1) != 0;
+    const uint32_t cu = cu_count(f);
+    if (small_wg_on && n_tiles > cu * 4u && n_tiles < cu * 8u) return {(n_tiles + 1u) / 2u, 128u};
+    if (big_wg_on && n_tiles >= cu * 8u) return {cu, 512u};
+    return {(n_tiles + 3u) / 4u < cu * 4u ? (n_tiles + 3u) / 4u : cu * 4u, 256u};
+}
+// k_query_fwd / k_query_fwd_bf in that shape.  walk: the unfused depth-ordered walk (ee.tiles_per_ray != 0; colour, 256 threads) has an
+// instantiation of its own, so that the flat launches carry none of its code.
+int launch_flat_fwd(const NarutoField* f, const NarutoParams& p, const PointSrc& ps, uint32_t M, float* raw, float* sdf_uncert, float* geo, float* feat_save,
+                    const EarlyExit& ee, bool color, FlatShape sh, bool walk, hipStream_t st) {
+    const bool bf = f->desc.mlp_mode == NARUTO_MLP_BF16;
+    if (walk && (!color || sh.threads != 256u)) return fail(NARUTO_ERR_INVALID, "query_fwd: the walk is a colour launch of 256 threads");
+#define NARUTO_FLAT(KERNEL, COLOR, NT, EE) \
+    hipLaunchKernelGGL((KERNEL<COLOR, NT, EE>), dim3(sh.blocks), dim3(NT), 0, st, f->lt, f->ut, f->bt, p, ps, M, raw, sdf_uncert, geo, feat_save, ee)
+#define NARUTO_FLAT_NT(KERNEL, COLOR)                                   \
+    do {                                                                \
+        if (sh.threads == 128u) NARUTO_FLAT(KERNEL, COLOR, 128, false); \
+        else if (sh.threads == 512u) NARUTO_FLAT(KERNEL, COLOR, 512, false); \
+        else NARUTO_FLAT(KERNEL, COLOR, 256, false);                    \
+    } while (0)
+    if (!walk && color && bf) NARUTO_FLAT_NT(k_query_fwd_bf, true);
+    else if (!walk && color) NARUTO_FLAT_NT(k_query_fwd, true);
+    else if (!walk && bf) NARUTO_FLAT_NT(k_query_fwd_bf, false);
+    else if (!walk) NARUTO_FLAT_NT(k_query_fwd, false);
+    else if (bf) NARUTO_FLAT(k_query_fwd_bf, true, 256, true);
+    else NARUTO_FLAT(k_query_fwd, true, 256, true);
+#undef NARUTO_FLAT_NT
+#undef NARUTO_FLAT
+    return check_launch("query_fwd");
+}
+}  // namespace
+
+extern "C" {
+
 int naruto_query_fwd(const NarutoField* f, const NarutoParams* p, uint32_t M, const NarutoPoints* pts, float* raw, float* sdf_uncert,
                      float* geo, float* feat_save, void* stream) {
     if (f == nullptr || p == nullptr) return fail(NARUTO_ERR_INVALID, "query_fwd: NULL argument");
@@ -672,35 +716,8 @@ int naruto_query_fwd(const NarutoField* f, const NarutoParams* p, uint32_t M, co
     if (feat_save != nullptr && M > (1u << 29)) return fail(NARUTO_ERR_INVALID, "query_fwd: feat_save is addressed with 32-bit byte offsets: at most 2^29 points per call");
     NarutoParams pp = *p;
     if (!color) { pp.col_w0 = p->sdf_w0; pp.col_w1 = p->sdf_w0; }       // staged but unused; keep the loads in bounds
-    const uint32_t n_tiles = (M + 63u) / 64u;
-    uint32_t blocks = (n_tiles + 3u) / 4u;
-    const uint32_t cap = cu_count(f) * 4u;
-    if (blocks > cap) blocks = cap;
-    const PointSrc ps = make_points(pts);
-    const EarlyExit none{};
-    const bool bf = f->desc.mlp_mode == NARUTO_MLP_BF16;
-    // between one and two four-wave workgroups per CU: two-wave workgroups instead, so that no CU holds more tiles than it must
-    // (see k_query_fwd).  NARUTO_DEBUG_FWD_SMALL_WG=0: the four-wave form everywhere (A/B timing).
-    static const bool small_wg_on = env_int("NARUTO_DEBUG_FWD_SMALL_WG", 1) != 0;
-    const bool small_wg = small_wg_on && n_tiles > cu_count(f) * 4u && n_tiles < cu_count(f) * 8u;
-    const hipStream_t st = (hipStream_t)stream;
-    // launch shape (fp32, phase-split tiles; measured in tools/fwd_lab.hip / profiles/r04_fwd_lab.txt): from 8 tiles per CU on, ONE persistent 8-wave
-    // workgroup per CU (one weight image, the waves walk their tiles: 76.5 -> 69.0 us at 4 096 tiles); below that the smaller forms spread the tiles better
-    // (1 376 tiles: 42.2 us as 2-wave workgroups, 45.6 as 8-wave ones).  NARUTO_DEBUG_FWD_SHAPE=0: the old shapes everywhere (A/B timing).
-    static const bool big_wg_on = env_int("NARUTO_DEBUG_FWD_SHAPE", 1) != 0;
-    const bool big_wg = big_wg_on && kFwdSplit && n_tiles >= cu_count(f) * 8u;
-#define NARUTO_LAUNCH_FWD(KERNEL, COLOR)                                                                                                                      \
-    do {                                                                                                                                                        \
-        if (small_wg) hipLaunchKernelGGL((KERNEL<COLOR, 128>), dim3((n_tiles + 1u) / 2u), dim3(128), 0, st, f->lt, f->ut, f->bt, pp, ps, M, raw, sdf_uncert, geo, feat_save, none); \
-        else if (big_wg) hipLaunchKernelGGL((KERNEL<COLOR, 512>), dim3(cu_count(f)), dim3(512), 0, st, f->lt, f->ut, f->bt, pp, ps, M, raw, sdf_uncert, geo, feat_save, none); \
-        else hipLaunchKernelGGL((KERNEL<COLOR, 256>), dim3(blocks), dim3(256), 0, st, f->lt, f->ut, f->bt, pp, ps, M, raw, sdf_uncert, geo, feat_save, none);  \
-    } while (0)
-    if (color && bf) NARUTO_LAUNCH_FWD(k_query_fwd_bf, true);
-    else if (color) NARUTO_LAUNCH_FWD(k_query_fwd, true);
-    else if (bf) NARUTO_LAUNCH_FWD(k_query_fwd_bf, false);
-    else NARUTO_LAUNCH_FWD(k_query_fwd, false);
-#undef NARUTO_LAUNCH_FWD
-    return check_launch("query_fwd");
+    static const bool big_wg_on = env_int("NARUTO_DEBUG_FWD_SHAPE", 1) != 0;      // 0: the shapes from before the eight-wave form (A/B timing)
+    return launch_flat_fwd(f, pp, make_points(pts), M, raw, sdf_uncert, geo, feat_save, EarlyExit{}, color, flat_fwd_shape(f, (M + 63u) / 64u, big_wg_on), false, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -936,7 +953,7 @@ FwdImageWs fwd_image_ws(void* base) {
 }
 // the image a training forward may read: only on the caller's word that it is fresh, and only where a kernel takes one (exact mode, x3 chain)
 inline const void* fresh_fwd_image(const NarutoField* f, const NarutoTrainStep* t) {
-    return (kExactX3 && t->fwd_image != nullptr && t->fwd_image_fresh != 0u && f->desc.mlp_mode != NARUTO_MLP_BF16) ? fwd_image_ws(t->fwd_image).image : nullptr;
+    return (t->fwd_image != nullptr && t->fwd_image_fresh != 0u && f->desc.mlp_mode != NARUTO_MLP_BF16) ? fwd_image_ws(t->fwd_image).image : nullptr;
 }
 int train_check(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const char* who) {
     if (f == nullptr || p == nullptr || t == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL argument", who);
@@ -955,25 +972,23 @@ int train_check(const NarutoField* f, const NarutoParams* p, const NarutoTrainSt
     if ((reinterpret_cast<uintptr_t>(t->fwd_image) & 15u) != 0u) return fail(NARUTO_ERR_INVALID, "%s: fwd_image must be 16-byte aligned", who);
     return NARUTO_OK;
 }
-// A2..A5 of the training forward: k_query_fwd over the batch's samples, one wave per ray with depth-ordered early termination
-// when the samples per ray are a multiple of 64 (otherwise flat 64-sample tiles)
-// loss != NULL: the loss stage may ride in the field query's launch (k_query_fwd_loss: the depth-ordered walk only); *fused tells
-// The five-launch iteration (round 4, see WalkExtra in naruto_train.hip): where the training forward is the depth-ordered walk in its
-// two-phase form and forward + backward are issued as one iteration (deferred tail), the walk samples its own depths, its tail workgroups
-// encode the smoothness lattice, the term itself is evaluated by workgroups of the backward's first launch and its value lands in the
-// losses with the backward's last launch -- k_sample_encode has no launch of its own.  NARUTO_TV_MOVE=0: the six-launch form (same bits).
-// ONE decision, used by everyone who has to know which launch form the training forward takes (the forward itself, the backward's
-// moved smoothness term, the debug re-launches): the round-4 form re-derived the walk's conditions by hand in tv_moved().
-//   Flat    64-sample tiles over the flat point list (k_query_fwd), loss stage and depth sampling in launches of their own
-//   Walk    one wave per ray, front to back (k_query_fwd_loss when the loss stage rides along, k_query_fwd<EE> otherwise); since round 5
-//           also for sample counts that are not a multiple of 64 -- the ray's last tile is partly filled, its dead lanes issue no loads --
-//           so that the shipped 32 + 11 sampling gets the five-launch iteration too (fused form only; NARUTO_WALK_PARTIAL: 0 never,
-//           1 (default) up to NARUTO_WALK_PARTIAL_MAX tiles per CU, 2 always)
+// A2..A5 of the training forward.  ONE decision, used by everyone who has to know which launch form it takes (the forward itself, the backward's
+// moved smoothness term, the debug re-launches):
+//   Flat    64-sample tiles over the flat point list (k_query_fwd in flat_fwd_shape), loss stage and depth sampling in launches of their own;
+//           where every other form falls back to
+//   Walk    one wave per ray, front to back with depth-ordered early termination (k_query_fwd_loss when the loss stage rides along -- `fused` --,
+//           k_query_fwd<EE> otherwise: S a multiple of 64 only); since round 5 the fused form also takes sample counts that are not a multiple
+//           of 64 -- the ray's last tile is partly filled, its dead lanes issue no loads -- (NARUTO_WALK_PARTIAL: 0 never, 1 (default) up to
+//           NARUTO_WALK_PARTIAL_MAX tiles per CU, 2 always)
 //   Packed  k_query_fwd_loss_packed (see launch_train_query)
 //   Short   S <= 64 (round 5): a workgroup packs 256 / S rays into its four waves' tiles (k_query_fwd_loss_short), loss stage inside, one row
-//           of loss partials per workgroup -- the shipped 32 + 11 sampling in five launches without a second round of workgroups
+//           of loss partials per workgroup -- the shipped 32 + 11 sampling without a second round of workgroups
 //   Sorted  tables no cache holds (round 6): the flat field query in Morton order of the samples a consumer can see (naruto_sorted.hip), loss stage
 //           in its own launch; feat_save sample-major
+// The five-launch iteration (round 4, see WalkExtra in naruto_train.hip; `tv_moved`): where the form is the fused Walk in its two-phase form, or Short,
+// and forward + backward are issued as one iteration (deferred tail), the forward samples its own depths, its tail workgroups encode the smoothness
+// lattice, the term itself is evaluated by workgroups of the backward's first launch and its value lands in the losses with the backward's last
+// launch -- k_sample_encode has no launch of its own.  NARUTO_TV_MOVE=0: the six-launch form (same bits).
 enum class FwdForm { Flat, Walk, Packed, Short, Sorted };
 struct TrainFwdPlan {
     FwdForm form;
@@ -998,15 +1013,9 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
     // 0.171 -> 0.159 ms, the BA batch 0.1875 -> 0.1795 -- and loses beyond (8 192 x 43: 0.391 -> 0.408, 131 072 x 43: 4.86 -> 4.92)
     static const uint32_t partial_max = (uint32_t)env_int("NARUTO_WALK_PARTIAL_MAX", 8);
     const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d;
-    static const bool small_wg_on = env_int("NARUTO_DEBUG_FWD_SMALL_WG", 1) != 0;
     static const int pack_waves = env_int("NARUTO_PACK_WAVES", 8);
-    TrainFwdPlan pl{FwdForm::Flat, false, false, false, 0u, (uint32_t)kRaysPerBlock, 0u, 256u, 0u, 0u};
-    // the flat launch, where every other form falls back to: 64-sample tiles; between one and two four-wave workgroups per CU (2 048 rays
-    // x 43 samples: 1 376 tiles) two-wave workgroups (see k_query_fwd), from two per CU on one eight-wave workgroup per CU
-    const uint32_t n_tiles = (uint32_t)(((uint64_t)N * S + 63u) / 64u);
-    if (small_wg_on && n_tiles > cu_count(f) * 4u && n_tiles < cu_count(f) * 8u) { pl.blocks = (n_tiles + 1u) / 2u; pl.threads = 128u; }
-    else if (kFwdSplit && n_tiles >= cu_count(f) * 8u) { pl.blocks = cu_count(f); pl.threads = 512u; }
-    else pl.blocks = (n_tiles + 3u) / 4u < cu_count(f) * 4u ? (n_tiles + 3u) / 4u : cu_count(f) * 4u;
+    const FlatShape flat = flat_fwd_shape(f, (uint32_t)(((uint64_t)N * S + 63u) / 64u));
+    TrainFwdPlan pl{FwdForm::Flat, false, false, false, 0u, (uint32_t)kRaysPerBlock, flat.blocks, flat.threads, 0u, 0u};
     const bool exact = S % 64u == 0u && S > 64u;
     const bool can_fuse = with_loss && !no_fuse && ray_scratch_bytes(S) <= kFwdLossMaxRayLds;
     bool packed_on = packed_mode == 2 || ((packed_mode == 1 || packed_mode == 3) && !exact);
@@ -1017,13 +1026,13 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
     const bool big_table = (size_t)f->n_entries * 2u * sizeof(float) > ((size_t)64u << 20);
     // (cache-resident tables too once the batch is millions of samples -- 131 072 x 43 at T = 2^16: 5.05 -> 4.71 ms -- but not below: 8 192 x 43 0.349 -> 0.380)
     const bool big_batch = (uint64_t)N * S >= 4000000ull && S <= 64u;
-    if (with_loss && kFwdSplit && (sorted_mode == 2 || (sorted_mode == 1 && (big_table || big_batch) && packed_mode == 1)) && (uint64_t)N * S < 0x0FFFFFFFull) {
+    if (with_loss && (sorted_mode == 2 || (sorted_mode == 1 && (big_table || big_batch) && packed_mode == 1)) && (uint64_t)N * S < 0x0FFFFFFFull) {
         pl.form = FwdForm::Sorted;
         pl.blocks = cu_count(f);            // the list queries (k_query_fwd_list)
         pl.threads = 512u;
         return pl;
     }
-    if (packed_on && with_loss && !no_fuse && kFwdSplit && S <= 4095u && N >= 1u) {
+    if (packed_on && with_loss && !no_fuse && S <= 4095u && N >= 1u) {
         // workgroup shape: 8 waves x 1 per CU, or 4 waves x 2 per CU (NARUTO_PACK_WAVES); rows (of four rays) a workgroup holds at a time: as many as
         // the LDS next to the weights, the feature slabs and the tiles' points takes, at most three
         const uint32_t W = pack_waves == 4 ? 4u : 8u, per_cu = W == 4u ? 2u : 1u;
@@ -1042,7 +1051,7 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
         }
         return pl;
     }
-    if (S <= 64u && can_fuse && kFwdSplit && partial_mode != 0) {
+    if (S <= 64u && can_fuse && partial_mode != 0) {
         const uint32_t R = short_rays_per_block(S);
         if (partial_mode == 2 || (uint64_t)((N + R - 1u) / R) * 4u <= (uint64_t)cu_count(f) * partial_max) {
             pl.form = FwdForm::Short;
@@ -1066,14 +1075,10 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
     pl.threads = 256u;
     pl.fused = can_fuse;
     // (two workgroups per CU: static LDS -- weight images, four slabs, the loss rows -- + the rays' images within half a CU's 160 KB)
-    pl.split = pl.fused && kFwdSplit && sizeof(FwdLdsExact) + (size_t)kRaysPerBlock * sizeof(FwdSlab) + ray_scratch_fwd_bytes(S) + 256u <= (size_t)80u * 1024u;
+    pl.split = pl.fused && sizeof(FwdLdsX3) + (size_t)kRaysPerBlock * sizeof(FwdSlab) + ray_scratch_fwd_bytes(S) + 256u <= (size_t)80u * 1024u;
     pl.tv_moved = tv_on && deferred && t->smooth_points != 0 && pl.fused && pl.split;
     return pl;
 }
-// The five-launch iteration (round 4, see WalkExtra in naruto_train.hip): where the training forward is the depth-ordered walk in its
-// two-phase form and forward + backward are issued as one iteration (deferred tail), the walk samples its own depths, its tail workgroups
-// encode the smoothness lattice, the term itself is evaluated by workgroups of the backward's first launch and its value lands in the
-// losses with the backward's last launch -- k_sample_encode has no launch of its own.  NARUTO_TV_MOVE=0: the six-launch form (same bits).
 // level groups per lattice-encode workgroup where the encode rides as tail role of the training forward (NARUTO_TV_TAIL_GROUPS: 1, 2, 4)
 inline uint32_t tv_tail_groups() {
     static const uint32_t g = (uint32_t)env_int("NARUTO_TV_TAIL_GROUPS", 1);
@@ -1199,20 +1204,8 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
         if (fused != nullptr) *fused = true;
         return check_launch("query_fwd_loss");
     }
-    // flat tiles in the plan's workgroup shape (see train_fwd_plan), or the unfused walk
-    const bool walk = ee.tiles_per_ray != 0u;          // the depth-ordered walk has its own instantiation: the flat launches carry none of its code (full tiles only: S = 64 k)
-    if (f->desc.mlp_mode == NARUTO_MLP_BF16) {
-        if (walk) hipLaunchKernelGGL((k_query_fwd_bf<true, 256, true>), dim3(blocks), dim3(256), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-        else if (pl.threads == 128u) hipLaunchKernelGGL((k_query_fwd_bf<true, 128>), dim3(blocks), dim3(128), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-        else if (pl.threads == 512u) hipLaunchKernelGGL((k_query_fwd_bf<true, 512>), dim3(blocks), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-        else hipLaunchKernelGGL((k_query_fwd_bf<true, 256>), dim3(blocks), dim3(256), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-    } else {
-        if (walk) hipLaunchKernelGGL((k_query_fwd<true, 256, true>), dim3(blocks), dim3(256), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-        else if (pl.threads == 128u) hipLaunchKernelGGL((k_query_fwd<true, 128>), dim3(blocks), dim3(128), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-        else if (pl.threads == 512u) hipLaunchKernelGGL((k_query_fwd<true, 512>), dim3(blocks), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);      // see naruto_query_fwd
-        else hipLaunchKernelGGL((k_query_fwd<true, 256>), dim3(blocks), dim3(256), 0, st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee);
-    }
-    return check_launch("query_fwd");
+    // flat tiles in the plan's workgroup shape, or the unfused walk (full tiles only: S = 64 k)
+    return launch_flat_fwd(f, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee, true, {blocks, pl.threads}, ee.tiles_per_ray != 0u, st);
 }
 TvArgs tv_args(const NarutoTrainStep* t) {
     TvArgs a{};
@@ -1286,7 +1279,7 @@ RenderPlan render_plan(const NarutoField* f, uint32_t n_rays, uint32_t S, bool b
     const uint32_t cap = cu_count(f) * 4u;
     if (S <= 64u) {
         const uint32_t R8 = render_packed8_rays(S);
-        if (kFwdSplit && wide != 0 && R8 >= 8u && (wide == 2 || (!bf && (n_rays + R8 - 1u) / R8 >= cu_count(f)))) {
+        if (wide != 0 && R8 >= 8u && (wide == 2 || (!bf && (n_rays + R8 - 1u) / R8 >= cu_count(f)))) {
             pl.form = RenderForm::Packed8;
             pl.rays_per_group = R8;
             pl.blocks = (n_rays + R8 - 1u) / R8 < cu_count(f) ? (n_rays + R8 - 1u) / R8 : cu_count(f);
@@ -1294,7 +1287,7 @@ RenderPlan render_plan(const NarutoField* f, uint32_t n_rays, uint32_t S, bool b
             pl.threads = 512u;
             pl.dyn_lds = render_packed_lds_bytes(S, R8);
             pl.reserved = render_packed8_reserve();
-            pl.static_lds = (bf ? sizeof(FwdLdsBf) : sizeof(FwdLdsExact)) + (kFwdSplit ? 8u : 1u) * sizeof(FwdSlab);
+            pl.static_lds = (bf ? sizeof(FwdLdsBf) : sizeof(FwdLdsX3)) + 8u * sizeof(FwdSlab);
             return pl;
         }
         pl.form = RenderForm::Packed4;
@@ -1304,7 +1297,7 @@ RenderPlan render_plan(const NarutoField* f, uint32_t n_rays, uint32_t S, bool b
         pl.threads = 256u;
         pl.dyn_lds = render_packed_lds_bytes(S);
         pl.reserved = render_packed_lds_bytes(64u);
-        pl.static_lds = (bf ? sizeof(FwdLdsBf) : sizeof(FwdLds)) + (kFwdSplit ? 4u : 1u) * sizeof(FwdSlab);
+        pl.static_lds = (bf ? sizeof(FwdLdsBf) : sizeof(FwdLds)) + 4u * sizeof(FwdSlab);
         return pl;
     }
     pl.form = RenderForm::Ray;
@@ -1588,7 +1581,7 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
         }
         adam.b1 = opt->beta1; adam.b2 = opt->beta2; adam.step_dev = opt->step_dev; adam.on = 1;
         // the finishing launch keeps the forward's weight image in step with the weights it updates (exact mode; whoever reads it decides per forward)
-        if (kExactX3 && f->desc.mlp_mode != NARUTO_MLP_BF16) adam.fwd_img = t_in->fwd_image;
+        if (f->desc.mlp_mode != NARUTO_MLP_BF16) adam.fwd_img = t_in->fwd_image;
     }
     if (g == nullptr || t->loss_weights == nullptr || t->feat_save == nullptr || t->d_raw == nullptr || t->ray_count == nullptr || t->ray_offset == nullptr ||
         t->active_idx == nullptr || t->n_active == nullptr)

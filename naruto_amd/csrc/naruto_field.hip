@@ -55,7 +55,7 @@ struct FwdLds {
 // Where the staging reads the nn.Linear weights from: the parameters themselves (one 64-byte line per lane and load -- the rows are 320 /
 // 252 bytes apart --, which is what a workgroup's staging costs: ~2 500 line requests through the CU's L1, 4.4 us measured in
 // k_query_fwd_loss_short, tools/short_timeline.py), or a raw copy in LDS that the workgroup fetched with COALESCED loads first (344 lines)
-// and reads back transposed, conflict-free thanks to odd row strides (stage_fwd_weights_via_lds below).
+// and reads back transposed, conflict-free thanks to odd row strides (stage_fwd_weights below).
 struct WSrcGlobal {
     const NarutoParams& p;
     __device__ __forceinline__ float sdf_w0(int i, int c) const { return p.sdf_w0[i * kInSdf + c]; }
@@ -109,9 +109,8 @@ __device__ __forceinline__ void fetch_raw_weights(float* __restrict__ raw, const
     __syncthreads();
 }
 
-// NT (threads per workgroup) is a compile-time constant so that the loops unroll completely and all of a thread's loads
-// (strided reads of the row-major weights: one cache line per lane) are in flight together; with a runtime stride the
-// 22 (forward) / 62 (backward) loads per thread were issued one L2 round trip after the other
+// One name per operation on a weight image, overloaded on the image type (FwdLds here, FwdLdsX3 and FwdLdsBf below): stage_fwd_weights_from /
+// stage_fwd_weights, fwd_mlp_tile, fwd_tile, fwd_tile_split.
 template <int NT, typename SRC>
 __device__ __forceinline__ void stage_fwd_weights_from(FwdLds& L, const SRC& w, int tid) {
     constexpr int nthreads = NT;
@@ -152,15 +151,6 @@ __device__ __forceinline__ void stage_fwd_weights_from(FwdLds& L, const SRC& w, 
         const int c = e / 32, r = (e >> 1) & 15, hh = e & 1;
         L.c1[e] = w.col_w1(c * kHidden + crow(r, hh));
     }
-}
-template <int NT>
-__device__ __forceinline__ void stage_fwd_weights(FwdLds& L, const NarutoParams& p, int tid) { stage_fwd_weights_from<NT>(L, WSrcGlobal{p}, tid); }
-// through the raw area (>= kFwdRawFloats floats of LDS the caller does not need yet -- the feature slabs); the caller's barrier behind the
-// staging also releases the raw area
-template <int NT>
-__device__ __forceinline__ void stage_fwd_weights_via_lds(FwdLds& L, float* __restrict__ raw, const NarutoParams& p, int tid) {
-    fetch_raw_weights<NT>(raw, p, tid);
-    stage_fwd_weights_from<NT>(L, WSrcLds{raw, p}, tid);
 }
 
 // ---- smoothness lattice (see the comment block at k_tv_encode below) ----
@@ -246,17 +236,9 @@ __device__ __forceinline__ void tv_encode_body(const LevelTab& lt, const BoxTab&
     }
 }
 
-#ifndef NARUTO_GATHER_GROUP
-#define NARUTO_GATHER_GROUP 1
-#endif
 #ifndef NARUTO_FWD_MINWAVES
 #define NARUTO_FWD_MINWAVES 2
 #endif
-constexpr int kGatherGroup = NARUTO_GATHER_GROUP;
-#ifndef NARUTO_EE_LANE_SKIP
-#define NARUTO_EE_LANE_SKIP 1
-#endif
-constexpr bool kEeLaneSkip = NARUTO_EE_LANE_SKIP != 0;      // A/B knob: lane-level skip inside evaluated tiles (ee_lane_live)
 
 // Depth-ordered early termination for the TRAINING forward (tiles_per_ray != 0: rays with depth-sorted samples, S a
 // multiple of 64, one wave walks one ray front to back).  What the losses, the compositing and the backward can see of
@@ -420,7 +402,7 @@ __device__ __forceinline__ void fwd_tile(const FwdLds& L, const LevelTab& lt, co
         float la = live ? 1.0f : 0.0f, lb = la;
         if constexpr (MASK) swap32(la, lb);
         const bool liveA = MASK ? la != 0.0f : true, liveB = MASK ? lb != 0.0f : true;
-        // levels in a real loop (unrolled by kGatherGroup): the gathers of a group are in flight together, the code
+        // levels in a real loop (unrolled by kGroup): the gathers of a group are in flight together, the code
         // stays an order of magnitude smaller than the fully unrolled form.
         // Lane layout of the gathers: both halves of the wave work on the same 32 points -- round A on points 0..31,
         // round B on points 32..63 -- and lane half hh fetches the four corners with x offset hh (hash_level_half_rt).
@@ -428,23 +410,26 @@ __device__ __forceinline__ void fwd_tile(const FwdLds& L, const LevelTab& lt, co
         // B operand of the MFMA tile.
         float xa = x, xb = x, ya = y, yb = y, za = z, zb = z;
         swap32(xa, xb); swap32(ya, yb); swap32(za, zb);        // xa = x of points (0..31 | 0..31), xb = (32..63 | 32..63)
-        static_assert(kLevels % kGatherGroup == 0, "levels are gathered in whole groups");
+        // kGroup is 1 (larger groups were tried and lost), but the nest keeps its three-step shape here and in the bf16 overload: written as
+        // one straight body the compiler threads the index computations' and the masked loads' branches into each other, and every kernel
+        // that runs the register form (k_render_fwd, k_query_fwd_loss<*, false>, k_query_fwd_bf) comes out with different code.
+        constexpr int kGroup = 1;
 #pragma unroll 1
-        for (int T0 = 0; T0 < kLevels; T0 += kGatherGroup) {
-        HalfCorners ha[kGatherGroup], hb[kGatherGroup];
+        for (int T0 = 0; T0 < kLevels; T0 += kGroup) {
+        HalfCorners ha[kGroup], hb[kGroup];
 #pragma unroll
-        for (int g = 0; g < kGatherGroup; ++g) {
+        for (int g = 0; g < kGroup; ++g) {
             ha[g] = hash_level_half_index(lt, T0 + g, xa, ya, za, (uint32_t)hh);
             hb[g] = hash_level_half_index(lt, T0 + g, xb, yb, zb, (uint32_t)hh);
         }
-        float2 va[kGatherGroup][4], vb[kGatherGroup][4];
+        float2 va[kGroup][4], vb[kGroup][4];
 #pragma unroll
-        for (int g = 0; g < kGatherGroup; ++g) {
+        for (int g = 0; g < kGroup; ++g) {
             hash_level_half_load(lt, T0 + g, table, ha[g], va[g], liveA);
             hash_level_half_load(lt, T0 + g, table, hb[g], vb[g], liveB);
         }
 #pragma unroll
-        for (int g = 0; g < kGatherGroup; ++g) {
+        for (int g = 0; g < kGroup; ++g) {
             const int T = T0 + g;
             const float2 pa = hash_level_half_blend(ha[g], va[g]);
             const float2 pb = hash_level_half_blend(hb[g], vb[g]);
@@ -522,13 +507,9 @@ __device__ __forceinline__ void fwd_tile(const FwdLds& L, const LevelTab& lt, co
 // the load order exact (it degrades to "wait for everything" at control-flow merges whose paths carry different VMEM operations),
 // while the level constants are fetched when needed instead of all living in SGPRs.  Full tiles only (no exec-masked stores).
 // ------------------------------------------------------------------------------------------------------------------------------
-#ifndef NARUTO_FWD_SPLIT
-#define NARUTO_FWD_SPLIT 1
-#endif
 #ifndef NARUTO_FWD_GATHER_PRIO
 #define NARUTO_FWD_GATHER_PRIO 3
 #endif
-constexpr bool kFwdSplit = NARUTO_FWD_SPLIT != 0;
 struct FwdSlab { float feat[kLevels][2][64]; };          // [level][tile half][lane]: the MFMA B operands of the hash part
 
 // dead lanes (MASK: ee_lane_live) fetch entry 0 of the level -- one shared line per instruction instead of a branch around the loads --
@@ -608,13 +589,9 @@ __device__ __forceinline__ void fwd_gather_tile(const LevelTab& lt, const float2
 // gather phase is bound by the CUs' own line rate), and the next tile's a-priori-needed lanes fetched during this tile's gather phase
 // (+6 us on tile 0 for -5 on tile 1).
 // ------------------------------------------------------------------------------------------------------------------------------
-#ifndef NARUTO_WALK_HALF
-#define NARUTO_WALK_HALF 1
-#endif
-constexpr bool kWalkHalf = NARUTO_WALK_HALF != 0;
 // gather phase of a tile BEHIND a ray's first (the chip's memory path is idle by then: what such a tile costs is its chain of dependent round
 // trips, not lines).  HALF: the live lanes all lie in [0, 32) -- points 0..31 only (lane half hh fetches their corners with x offset hh), eight
-// levels in flight, features -> slab half 0 + feat_save rows mA; slab half 1 is not written (fwd_mlp_tile_x3<.., true> does not read it).
+// levels in flight, features -> slab half 0 + feat_save rows mA; slab half 1 is not written (the x3 fwd_mlp_tile with HALF does not read it).
 // Otherwise both halves as fwd_gather_tile<true>, but FOUR levels in flight instead of two.
 template <bool HALF>
 __device__ __forceinline__ void fwd_gather_tile_deep(const LevelTab& lt, const float2* __restrict__ table, float x, float y, float z, float* __restrict__ feat_save,
@@ -773,7 +750,7 @@ __device__ __forceinline__ f32x16 mfma16x3(const u32x4_t (&w)[3], const Pack3& x
     return acc;
 }
 template <int NT, typename SRC>
-__device__ __forceinline__ void stage_fwd_weights_x3_from(FwdLdsX3& L, const SRC& w, int tid) {
+__device__ __forceinline__ void stage_fwd_weights_from(FwdLdsX3& L, const SRC& w, int tid) {
 #pragma unroll
     for (int e0 = 0; e0 < 11 * 64; e0 += NT) {
         const int e = e0 + tid;
@@ -805,11 +782,6 @@ __device__ __forceinline__ void stage_fwd_weights_x3_from(FwdLdsX3& L, const SRC
         L.c1[e] = w.col_w1(c * kHidden + crow(r, hh));
     }
 }
-template <int NT>
-__device__ __forceinline__ void stage_fwd_weights_x3_via_lds(FwdLdsX3& L, float* __restrict__ raw, const NarutoParams& p, int tid) {
-    fetch_raw_weights<NT>(raw, p, tid);
-    stage_fwd_weights_x3_from<NT>(L, WSrcLds{raw, p}, tid);
-}
 // ---- the x3 image kept in global memory from one training iteration to the next ----
 // The image depends on the MLP weights alone, and in a chain of fused-Adam iterations those change exactly once per iteration, in the
 // finishing launch (wgrad_reduce_body -> adam_apply).  So that launch also writes each new weight's image slots (fwd_image_put: the same
@@ -821,7 +793,7 @@ constexpr size_t kFwdImageBytes = sizeof(FwdLdsX3);
 static_assert(kFwdImageBytes % 16 == 0 && kFwdImageBytes < 65536, "copied in 16-byte pieces; a slot's offset fits 16 bits");
 constexpr int kWOffS1 = kHidden * kInSdf, kWOffC0 = kWOffS1 + kOut * kHidden, kWOffC1 = kWOffC0 + kHidden * kInCol;      // weights in the optimiser's order:
 constexpr int kNumWeights = kWOffC1 + 3 * kHidden;                                                                    // sdf_w0 | sdf_w1 | col_w0 | col_w1 = 5 184
-// The inverse of stage_fwd_weights_x3_from, by enumerating ITS index expressions (host; tests/test_gpu_fwd_image.py holds the two together
+// The inverse of stage_fwd_weights_from(FwdLdsX3&), by enumerating ITS index expressions (host; tests/test_gpu_fwd_image.py holds the two together
 // byte for byte).  zero_fill (optional, kFwdImageBytes bytes): 1 where the staging writes the zero padding (rows >= kOut, crow < 1).
 inline void fwd_image_slot_map(uint32_t* slots, uint8_t* zero_fill) {
     for (int w = 0; w < kNumWeights; ++w) slots[w] = 0xFFFFFFFFu;
@@ -889,12 +861,12 @@ struct FwdImageRegs {
         if ((nq - 1) * NT + tid < n16) dst[(nq - 1) * NT] = v[nq - 1];
     }
 };
-// the matrix phase of a tile (fwd_mlp_tile's counterpart): hash part of the B operands from the slab
+// the x3 image's matrix phase of a tile: hash part of the B operands from the slab
 // HALF (round 6): the tile's B points (32..63) are dead -- only the A chains run; the B lanes' outputs are unspecified (the caller writes zeros)
 // LANE_BLOB (round 6): OneBlob's form (closed / dense: 1e-6 apart) chosen per LANE instead of per tile -- a sample's outputs then depend on the sample alone,
 // whatever tile it shares: the Morton-ordered forward, whose tiles are composed by atomics, stays bitwise reproducible
-template <bool COLOR, bool HALF = false, bool LANE_BLOB = false>
-__device__ __forceinline__ void fwd_mlp_tile_x3(const FwdLdsX3& L, const FwdSlab& sl, float x, float y, float z, float* __restrict__ geo, uint32_t M, uint32_t mA, uint32_t mB,
+template <bool COLOR, bool LANE_BLOB = false, bool HALF = false>
+__device__ __forceinline__ void fwd_mlp_tile(const FwdLdsX3& L, const FwdSlab& sl, float x, float y, float z, float* __restrict__ geo, uint32_t M, uint32_t mA, uint32_t mB,
                                                 int lane, FwdTileOut& out) {
     const int hh = lane >> 5;
     f32x16 hA = zero16(), hB = zero16(), cA = zero16(), cB = zero16();
@@ -972,107 +944,8 @@ __device__ __forceinline__ void fwd_mlp_tile_x3(const FwdLdsX3& L, const FwdSlab
     }
 }
 
-#ifndef NARUTO_EXACT_X3
-#define NARUTO_EXACT_X3 1
-#endif
-// the exact (fp32) mode's forward kernels run their matrix phase as the x3 chain wherever they use the two-phase tile (NARUTO_EXACT_X3=0:
-// the fp32 matrix instruction there too; the register-form tile -- rays of more than 192 samples, the inference render -- keeps it)
-constexpr bool kExactX3 = NARUTO_EXACT_X3 != 0 && kFwdSplit;
-using FwdLdsExact = std::conditional_t<kExactX3, FwdLdsX3, FwdLds>;
-template <bool COLOR, bool MASK>
-__device__ __forceinline__ void fwd_tile_split(const FwdLdsX3& L, FwdSlab& sl, const LevelTab& lt, const float2* __restrict__ table, float x, float y, float z,
-                                               float* __restrict__ feat_save, float* __restrict__ geo, uint32_t M, uint32_t mA, uint32_t mB, int lane, FwdTileOut& out,
-                                               bool live = true) {
-    if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(NARUTO_FWD_GATHER_PRIO);
-    fwd_gather_tile<MASK>(lt, table, x, y, z, feat_save, M, mA, mB, lane, sl, live);
-    if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(0);
-    fwd_mlp_tile_x3<COLOR>(L, sl, x, y, z, geo, M, mA, mB, lane, out);
-}
-// weight staging of whichever image the kernel holds: through the raw area (the slabs) when it is large enough
-template <int NT, size_t RAW_BYTES>
-__device__ __forceinline__ void stage_fwd_exact(FwdLds& L, void* raw, const NarutoParams& p, int tid) {
-    if constexpr (RAW_BYTES >= kFwdRawFloats * sizeof(float)) stage_fwd_weights_via_lds<NT>(L, reinterpret_cast<float*>(raw), p, tid);
-    else stage_fwd_weights<NT>(L, p, tid);
-}
-// hop 2 alone: the raw area already holds the weights (RawWeights::store + a barrier by the caller)
-template <int NT>
-__device__ __forceinline__ void stage_fwd_exact_from_raw(FwdLds& L, const float* raw, const NarutoParams& p, int tid) { stage_fwd_weights_from<NT>(L, WSrcLds{raw, p}, tid); }
-template <int NT>
-__device__ __forceinline__ void stage_fwd_exact_from_raw(FwdLdsX3& L, const float* raw, const NarutoParams& p, int tid) { stage_fwd_weights_x3_from<NT>(L, WSrcLds{raw, p}, tid); }
-template <int NT, size_t RAW_BYTES>
-__device__ __forceinline__ void stage_fwd_exact(FwdLdsX3& L, void* raw, const NarutoParams& p, int tid) {
-    if constexpr (RAW_BYTES >= kFwdRawFloats * sizeof(float)) stage_fwd_weights_x3_via_lds<NT>(L, reinterpret_cast<float*>(raw), p, tid);
-    else stage_fwd_weights_x3_from<NT>(L, WSrcGlobal{p}, tid);
-}
-
-// one FULL tile (all 64 points < M), both phases; same results as fwd_tile<COLOR, MASK>
-template <bool COLOR, bool MASK>
-__device__ __forceinline__ void fwd_tile_split(const FwdLds& L, FwdSlab& sl, const LevelTab& lt, const float2* __restrict__ table, float x, float y, float z,
-                                               float* __restrict__ feat_save, float* __restrict__ geo, uint32_t M, uint32_t mA, uint32_t mB, int lane, FwdTileOut& out,
-                                               bool live = true) {
-    if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(NARUTO_FWD_GATHER_PRIO);
-    fwd_gather_tile<MASK>(lt, table, x, y, z, feat_save, M, mA, mB, lane, sl, live);
-    if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(0);
-    fwd_mlp_tile<COLOR>(L, sl, x, y, z, geo, M, mA, mB, lane, out);
-}
-
-// NT = threads per workgroup: 256, or 128 for launches of between one and two 256-thread workgroups per CU -- the time of this kernel
-// grows with the tiles a CU holds (measured: 10 us + 5.8 us per tile and CU), so 1 376 tiles (2 048 rays x 43 samples, the reference's
-// real batch) as 344 workgroups of four put eight tiles on 88 CUs and four on the rest; as 688 workgroups of two no CU holds more than six.
-template <bool COLOR, int NT = 256, bool EE = false>
-__global__ __launch_bounds__(NT, NARUTO_FWD_MINWAVES) void k_query_fwd(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps,
-                                                   uint32_t M, float* __restrict__ raw, float* __restrict__ sdf_uncert,
-                                                   float* __restrict__ geo, float* __restrict__ feat_save, EarlyExit ee) {
-    __shared__ FwdLdsExact L;
-    __shared__ FwdSlab slabs[kFwdSplit ? NT / 64 : 1];
-    stage_fwd_exact<NT, sizeof(slabs)>(L, slabs, p, threadIdx.x);
-    __syncthreads();
-    constexpr uint32_t kW = NT / 64;
-    const int lane = threadIdx.x & 63, wave = kFwdSplit ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
-    const int hh = lane >> 5, j = lane & 31;
-    const uint32_t n_tiles = (M + 63u) / 64u;
-    const float2* __restrict__ table = reinterpret_cast<const float2*>(p.table);
-    const uint32_t tpr = EE ? ee.tiles_per_ray : 0u;                 // EE: the depth-ordered walk (one wave per ray); otherwise flat tiles, no walk code at all
-    const uint32_t n_tasks = tpr ? n_tiles / tpr : n_tiles;          // rays, or tiles of the flat point list
-    for (uint32_t task = blockIdx.x * kW + wave; task < n_tasks; task += gridDim.x * kW) {
-    EeState ees{false, 0.0f, 0.0f, 0.0f};
-    for (uint32_t tq = 0; tq < (tpr ? tpr : 1u); ++tq) {
-        const uint32_t tile = tpr ? task * tpr + tq : task;
-        const uint32_t m_raw = tile * 64u + lane;
-        const bool valid = m_raw < M;
-        const uint32_t m = valid ? m_raw : M - 1u;       // padding lanes redo the last point, stores masked
-        float x, y, z;
-        load_point(ps, bt, m, x, y, z);
-        const bool live = (EE && tq > 0u && kEeLaneSkip) ? ee_lane_live(ees, ee, task, ps.z_vals[m]) : true;
-        const float u = live ? uncert_sample(ut, p.uncert_grid, x, y, z) : 0.0f;
-
-        FwdTileOut to;
-        const bool live_out = live;
-        if (kFwdSplit && tile * 64u + 63u < M)
-            fwd_tile_split<COLOR, EE>(L, slabs[kFwdSplit ? wave : 0], lt, table, x, y, z, feat_save, geo, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to, live);
-        else if constexpr (kExactX3)        // the list's last, partly filled tile: the same two phases with its padding lanes switched off (one chain per kernel)
-            fwd_tile_split<COLOR, true>(L, slabs[wave], lt, table, x, y, z, feat_save, geo, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to, live && valid);
-        else
-            fwd_tile<COLOR, EE>(L, lt, table, x, y, z, feat_save, geo, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to, live);
-        if (!live_out) { to.rgb[0] = 0.0f; to.rgb[1] = 0.0f; to.rgb[2] = 0.0f; to.sdf = 0.0f; }
-        const float sdf = to.sdf;
-        const float u_out = live_out ? u : 0.0f;
-        if (sdf_uncert != nullptr && valid) reinterpret_cast<float2*>(sdf_uncert)[m] = make_float2(sdf, u_out);
-        if constexpr (COLOR) {
-            if (raw != nullptr && valid) {
-                float* o = raw + (size_t)m * 5;
-                o[0] = to.rgb[0]; o[1] = to.rgb[1]; o[2] = to.rgb[2]; o[3] = sdf; o[4] = u_out;
-            }
-        }
-        if (EE && tq + 1u < tpr) {
-            if (ee_after_tile(ees, ee, ps, m, tq, (tile + 1u) * 64u, (task + 1u) * tpr * 64u, task, sdf, lane, raw)) break;
-        }
-    }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// bf16 "speed mode" of the same kernel (NarutoFieldDesc.mlp_mode = 1): the MLP products run on v_mfma_f32_32x32x16_bf16 --
+// bf16 "speed mode" of the forward kernels (NarutoFieldDesc.mlp_mode = 1): the MLP products run on v_mfma_f32_32x32x16_bf16 --
 // bf16 operands (round to nearest even), fp32 accumulation -- at 16x the matrix rate of the exact fp32 form.  Everything
 // else (gathers, trilinear blend, OneBlob, the 32 -> 3 colour layer, compositing) stays fp32.  The reference has the same
 // switch: its optional tcnn FullyFusedMLP decoder computes in half precision (reference src/slam/coslam/model/decoder.py:43-59).
@@ -1094,7 +967,7 @@ struct FwdLdsBf {
 };
 
 template <int NT, typename SRC>
-__device__ __forceinline__ void stage_fwd_weights_bf_from(FwdLdsBf& L, const SRC& w, int tid) {
+__device__ __forceinline__ void stage_fwd_weights_from(FwdLdsBf& L, const SRC& w, int tid) {
 #pragma unroll
     for (int e0 = 0; e0 < 11 * 64; e0 += NT) {
         const int e = e0 + tid;
@@ -1122,12 +995,18 @@ __device__ __forceinline__ void stage_fwd_weights_bf_from(FwdLdsBf& L, const SRC
         L.c1[e] = w.col_w1(c * kHidden + crow(r, hh));
     }
 }
-template <int NT>
-__device__ __forceinline__ void stage_fwd_weights_bf(FwdLdsBf& L, const NarutoParams& p, int tid) { stage_fwd_weights_bf_from<NT>(L, WSrcGlobal{p}, tid); }
-template <int NT>
-__device__ __forceinline__ void stage_fwd_weights_bf_via_lds(FwdLdsBf& L, float* __restrict__ raw, const NarutoParams& p, int tid) {
-    fetch_raw_weights<NT>(raw, p, tid);
-    stage_fwd_weights_bf_from<NT>(L, WSrcLds{raw, p}, tid);
+// Staging of whichever image the kernel holds.  NT (threads per workgroup) is a compile-time constant so that the loops unroll completely and
+// all of a thread's loads are in flight together.  RAW_BYTES: size of an LDS area the caller does not need yet (raw: its feature slabs); when it
+// holds kFwdRawFloats floats the weights go through it (coalesced loads, transposed read-back), otherwise they are read from the parameters, one
+// 64-byte line per lane and load.  The caller's barrier behind the staging also releases the raw area.
+template <int NT, size_t RAW_BYTES = 0, typename LDS>
+__device__ __forceinline__ void stage_fwd_weights(LDS& L, const NarutoParams& p, int tid, void* raw = nullptr) {
+    if constexpr (RAW_BYTES >= kFwdRawFloats * sizeof(float)) {
+        fetch_raw_weights<NT>(reinterpret_cast<float*>(raw), p, tid);
+        stage_fwd_weights_from<NT>(L, WSrcLds{reinterpret_cast<const float*>(raw), p}, tid);
+    } else {
+        stage_fwd_weights_from<NT>(L, WSrcGlobal{p}, tid);
+    }
 }
 
 __device__ __forceinline__ u32x4_t pack8(const float (&v)[8]) {
@@ -1210,7 +1089,7 @@ __device__ __forceinline__ void fwd_tail_bf(const FwdLdsBf& L, f32x16& hA, f32x1
 }
 
 template <bool COLOR, bool MASK = false>
-__device__ __forceinline__ void fwd_tile_bf(const FwdLdsBf& L, const LevelTab& lt, const float2* __restrict__ table, float x, float y, float z,
+__device__ __forceinline__ void fwd_tile(const FwdLdsBf& L, const LevelTab& lt, const float2* __restrict__ table, float x, float y, float z,
                                             float* __restrict__ feat_save, float* __restrict__ geo, uint32_t M, uint32_t mA, uint32_t mB, int lane, FwdTileOut& out,
                                             bool live = true) {
     const int hh = lane >> 5;
@@ -1220,26 +1099,26 @@ __device__ __forceinline__ void fwd_tile_bf(const FwdLdsBf& L, const LevelTab& l
         const bool liveA = MASK ? la != 0.0f : true, liveB = MASK ? lb != 0.0f : true;
         float xa = x, xb = x, ya = y, yb = y, za = z, zb = z;
         swap32(xa, xb); swap32(ya, yb); swap32(za, zb);        // xa = x of points (0..31 | 0..31), xb = (32..63 | 32..63)
-        static_assert(8 % kGatherGroup == 0, "a K block of eight levels is gathered in whole groups");
+        constexpr int kGroup = 1;                              // (see fwd_tile on FwdLds)
 #pragma unroll 1
         for (int kb = 0; kb < 2; ++kb) {
             float fa[8], fb[8];
 #pragma unroll
-            for (int e0 = 0; e0 < 8; e0 += kGatherGroup) {
-            HalfCorners ha[kGatherGroup], hb[kGatherGroup];
+            for (int e0 = 0; e0 < 8; e0 += kGroup) {
+            HalfCorners ha[kGroup], hb[kGroup];
 #pragma unroll
-            for (int g = 0; g < kGatherGroup; ++g) {
+            for (int g = 0; g < kGroup; ++g) {
                 ha[g] = hash_level_half_index(lt, 8 * kb + e0 + g, xa, ya, za, (uint32_t)hh);
                 hb[g] = hash_level_half_index(lt, 8 * kb + e0 + g, xb, yb, zb, (uint32_t)hh);
             }
-            float2 va[kGatherGroup][4], vb[kGatherGroup][4];
+            float2 va[kGroup][4], vb[kGroup][4];
 #pragma unroll
-            for (int g = 0; g < kGatherGroup; ++g) {
+            for (int g = 0; g < kGroup; ++g) {
                 hash_level_half_load(lt, 8 * kb + e0 + g, table, ha[g], va[g], liveA);
                 hash_level_half_load(lt, 8 * kb + e0 + g, table, hb[g], vb[g], liveB);
             }
 #pragma unroll
-            for (int g = 0; g < kGatherGroup; ++g) {
+            for (int g = 0; g < kGroup; ++g) {
                 const int e = e0 + g;
                 const int T = 8 * kb + e;
                 const float2 pa = hash_level_half_blend(ha[g], va[g]);
@@ -1265,7 +1144,7 @@ __device__ __forceinline__ void fwd_tile_bf(const FwdLdsBf& L, const LevelTab& l
 
 // the bf16 mode's matrix phase: the two hash K blocks from the slab, then the tail
 template <bool COLOR, bool LANE_BLOB = false>
-__device__ __forceinline__ void fwd_mlp_tile_bf(const FwdLdsBf& L, const FwdSlab& sl, float x, float y, float z, float* __restrict__ geo, uint32_t M, uint32_t mA, uint32_t mB,
+__device__ __forceinline__ void fwd_mlp_tile(const FwdLdsBf& L, const FwdSlab& sl, float x, float y, float z, float* __restrict__ geo, uint32_t M, uint32_t mA, uint32_t mB,
                                                 int lane, FwdTileOut& out) {
     f32x16 hA = zero16(), hB = zero16(), cA = zero16(), cB = zero16();
 #pragma unroll
@@ -1279,15 +1158,72 @@ __device__ __forceinline__ void fwd_mlp_tile_bf(const FwdLdsBf& L, const FwdSlab
     }
     fwd_tail_bf<COLOR, LANE_BLOB>(L, hA, hB, cA, cB, x, y, z, geo, M, mA, mB, lane, out);
 }
-// phase-split form of a FULL bf16 tile (see fwd_tile_split): the same gather phase, then the two hash K blocks from the slab
-template <bool COLOR, bool MASK>
-__device__ __forceinline__ void fwd_tile_split_bf(const FwdLdsBf& L, FwdSlab& sl, const LevelTab& lt, const float2* __restrict__ table, float x, float y, float z,
-                                                  float* __restrict__ feat_save, float* __restrict__ geo, uint32_t M, uint32_t mA, uint32_t mB, int lane, FwdTileOut& out,
-                                                  bool live = true) {
+// The two-phase tile on any of the three images: the gather phase at raised priority, then the image's matrix phase.  A FULL tile (all 64 points
+// < M) unless MASK switches the padding lanes off through `live`; same results as fwd_tile<COLOR, MASK> where the image has one.
+template <bool COLOR, bool MASK, typename LDS>
+__device__ __forceinline__ void fwd_tile_split(const LDS& L, FwdSlab& sl, const LevelTab& lt, const float2* __restrict__ table, float x, float y, float z,
+                                               float* __restrict__ feat_save, float* __restrict__ geo, uint32_t M, uint32_t mA, uint32_t mB, int lane, FwdTileOut& out,
+                                               bool live = true) {
     if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(NARUTO_FWD_GATHER_PRIO);
     fwd_gather_tile<MASK>(lt, table, x, y, z, feat_save, M, mA, mB, lane, sl, live);
     if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(0);
-    fwd_mlp_tile_bf<COLOR>(L, sl, x, y, z, geo, M, mA, mB, lane, out);
+    fwd_mlp_tile<COLOR>(L, sl, x, y, z, geo, M, mA, mB, lane, out);
+}
+
+// The flat field query: k_query_fwd (exact mode: the x3 image) and, with the same body but for its image and its last, partly filled tile
+// (the register form), k_query_fwd_bf.  The body is written out twice: moved into one inlined function on the image type, all fourteen
+// instantiations came out with different code (profiles/query_fwd_shared_body_ab.txt).
+// NT = threads per workgroup: 256, or 128 for launches of between one and two 256-thread workgroups per CU -- the time of this kernel
+// grows with the tiles a CU holds (measured: 10 us + 5.8 us per tile and CU), so 1 376 tiles (2 048 rays x 43 samples, the reference's
+// real batch) as 344 workgroups of four put eight tiles on 88 CUs and four on the rest; as 688 workgroups of two no CU holds more than six.
+template <bool COLOR, int NT = 256, bool EE = false>
+__global__ __launch_bounds__(NT, NARUTO_FWD_MINWAVES) void k_query_fwd(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps,
+                                                   uint32_t M, float* __restrict__ raw, float* __restrict__ sdf_uncert,
+                                                   float* __restrict__ geo, float* __restrict__ feat_save, EarlyExit ee) {
+    __shared__ FwdLdsX3 L;
+    __shared__ FwdSlab slabs[NT / 64];
+    stage_fwd_weights<NT, sizeof(slabs)>(L, p, threadIdx.x, slabs);
+    __syncthreads();
+    constexpr uint32_t kW = NT / 64;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int j = lane & 31;
+    const uint32_t n_tiles = (M + 63u) / 64u;
+    const float2* __restrict__ table = reinterpret_cast<const float2*>(p.table);
+    const uint32_t tpr = EE ? ee.tiles_per_ray : 0u;                 // EE: the depth-ordered walk (one wave per ray); otherwise flat tiles, no walk code at all
+    const uint32_t n_tasks = tpr ? n_tiles / tpr : n_tiles;          // rays, or tiles of the flat point list
+    for (uint32_t task = blockIdx.x * kW + wave; task < n_tasks; task += gridDim.x * kW) {
+    EeState ees{false, 0.0f, 0.0f, 0.0f};
+    for (uint32_t tq = 0; tq < (tpr ? tpr : 1u); ++tq) {
+        const uint32_t tile = tpr ? task * tpr + tq : task;
+        const uint32_t m_raw = tile * 64u + lane;
+        const bool valid = m_raw < M;
+        const uint32_t m = valid ? m_raw : M - 1u;       // padding lanes redo the last point, stores masked
+        float x, y, z;
+        load_point(ps, bt, m, x, y, z);
+        const bool live = (EE && tq > 0u) ? ee_lane_live(ees, ee, task, ps.z_vals[m]) : true;
+        const float u = live ? uncert_sample(ut, p.uncert_grid, x, y, z) : 0.0f;
+
+        FwdTileOut to;
+        const bool live_out = live;
+        if (tile * 64u + 63u < M)
+            fwd_tile_split<COLOR, EE>(L, slabs[wave], lt, table, x, y, z, feat_save, geo, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to, live);
+        else        // the list's last, partly filled tile: the same two phases with its padding lanes switched off (one chain per kernel)
+            fwd_tile_split<COLOR, true>(L, slabs[wave], lt, table, x, y, z, feat_save, geo, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to, live && valid);
+        if (!live_out) { to.rgb[0] = 0.0f; to.rgb[1] = 0.0f; to.rgb[2] = 0.0f; to.sdf = 0.0f; }
+        const float sdf = to.sdf;
+        const float u_out = live_out ? u : 0.0f;
+        if (sdf_uncert != nullptr && valid) reinterpret_cast<float2*>(sdf_uncert)[m] = make_float2(sdf, u_out);
+        if constexpr (COLOR) {
+            if (raw != nullptr && valid) {
+                float* o = raw + (size_t)m * 5;
+                o[0] = to.rgb[0]; o[1] = to.rgb[1]; o[2] = to.rgb[2]; o[3] = sdf; o[4] = u_out;
+            }
+        }
+        if (EE && tq + 1u < tpr) {
+            if (ee_after_tile(ees, ee, ps, m, tq, (tile + 1u) * 64u, (task + 1u) * tpr * 64u, task, sdf, lane, raw)) break;
+        }
+    }
+    }
 }
 
 // 2, not 3, waves per SIMD: at 3 (<= 168 registers) the kernel spills 65 registers and the forward takes 65 us instead of 51
@@ -1299,13 +1235,12 @@ __global__ __launch_bounds__(NT, NARUTO_FWD_BF_MINWAVES) void k_query_fwd_bf(Lev
                                                       uint32_t M, float* __restrict__ raw, float* __restrict__ sdf_uncert,
                                                       float* __restrict__ geo, float* __restrict__ feat_save, EarlyExit ee) {
     __shared__ FwdLdsBf L;
-    __shared__ FwdSlab slabs[kFwdSplit ? NT / 64 : 1];
-    if constexpr (sizeof(slabs) >= kFwdRawFloats * sizeof(float)) stage_fwd_weights_bf_via_lds<NT>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
-    else stage_fwd_weights_bf<NT>(L, p, threadIdx.x);
+    __shared__ FwdSlab slabs[NT / 64];
+    stage_fwd_weights<NT, sizeof(slabs)>(L, p, threadIdx.x, slabs);
     __syncthreads();
     constexpr uint32_t kW = NT / 64;
-    const int lane = threadIdx.x & 63, wave = kFwdSplit ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
-    const int hh = lane >> 5, j = lane & 31;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int j = lane & 31;
     const uint32_t n_tiles = (M + 63u) / 64u;
     const float2* __restrict__ table = reinterpret_cast<const float2*>(p.table);
     const uint32_t tpr = EE ? ee.tiles_per_ray : 0u;
@@ -1319,14 +1254,14 @@ __global__ __launch_bounds__(NT, NARUTO_FWD_BF_MINWAVES) void k_query_fwd_bf(Lev
         const uint32_t m = valid ? m_raw : M - 1u;
         float x, y, z;
         load_point(ps, bt, m, x, y, z);
-        const bool live = (EE && tq > 0u && kEeLaneSkip) ? ee_lane_live(ees, ee, task, ps.z_vals[m]) : true;
+        const bool live = (EE && tq > 0u) ? ee_lane_live(ees, ee, task, ps.z_vals[m]) : true;
         const float u = live ? uncert_sample(ut, p.uncert_grid, x, y, z) : 0.0f;
 
         FwdTileOut to;
-        if (kFwdSplit && tile * 64u + 63u < M)
-            fwd_tile_split_bf<COLOR, EE>(L, slabs[kFwdSplit ? wave : 0], lt, table, x, y, z, feat_save, geo, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to, live);
+        if (tile * 64u + 63u < M)
+            fwd_tile_split<COLOR, EE>(L, slabs[wave], lt, table, x, y, z, feat_save, geo, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to, live);
         else
-            fwd_tile_bf<COLOR, EE>(L, lt, table, x, y, z, feat_save, geo, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to, live);
+            fwd_tile<COLOR, EE>(L, lt, table, x, y, z, feat_save, geo, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to, live);
         if (!live) { to.rgb[0] = 0.0f; to.rgb[1] = 0.0f; to.rgb[2] = 0.0f; to.sdf = 0.0f; }
         const float sdf = to.sdf;
         if (sdf_uncert != nullptr && valid) reinterpret_cast<float2*>(sdf_uncert)[m] = make_float2(sdf, u);
@@ -1474,9 +1409,6 @@ __device__ __forceinline__ unsigned long long to_fix40(float v) { return to_fix4
 // has ulp 2^-40 while |v| < 2^11, so the add -- or the fma that forms v -- rounds v to the nearest multiple of 2^-40 and leaves
 // that integer, two's complement, in the mantissa: bits(M + v) - bits(M).  bits(M) = 0x40B80000'00000000: the low word is zero, the
 // subtraction is ONE 32-bit add on the high word, and a product of doubles costs what a product of floats does.
-#ifndef NARUTO_FIX_F64
-#define NARUTO_FIX_F64 1
-#endif
 constexpr double kFixMagic = 6144.0;
 constexpr float kFixMagicRange = 2047.0f;
 __device__ __forceinline__ unsigned long long fix40_bits(double magic_sum) {
@@ -1486,7 +1418,7 @@ __device__ __forceinline__ unsigned long long fix40_bits(double magic_sum) {
 // a sum of contributions: through the magic number when the caller knows |v| < 2^11, else the fp32 split
 template <bool MAGIC>
 __device__ __forceinline__ unsigned long long to_fix40_sum(float v) {
-    if constexpr (MAGIC && NARUTO_FIX_F64) return fix40_bits((double)v + kFixMagic);
+    if constexpr (MAGIC) return fix40_bits((double)v + kFixMagic);
     else return to_fix40(v);
 }
 
@@ -1501,7 +1433,6 @@ __device__ __forceinline__ void fix_add_rel(unsigned long long* __restrict__ acc
 // A point with a cotangent beyond the magic number's range (not a gradient any more) takes the fp32 split, which reaches 2^22; a
 // NaN / Inf cotangent adds nothing.  (Positions are this library's own: o + t d of finite rays.)
 __device__ __forceinline__ void fix_add_corners(unsigned long long* __restrict__ acc, const uint32_t (&idx)[8], uint32_t chunk_base, const float (&f)[6], float g) {
-#if NARUTO_FIX_F64
     if (__builtin_expect(fabsf(g) <= kFixMagicRange, 1)) {             // per LANE: what a point adds does not depend on its wave
         const double gd = (double)g;
         const double gx0 = gd * (double)f[0], gx1 = gd * (double)f[1];
@@ -1516,7 +1447,6 @@ __device__ __forceinline__ void fix_add_corners(unsigned long long* __restrict__
         return;
     }
     if (!(fabsf(g) < 4194304.0f)) return;                   // NaN / Inf / beyond the fixed point's range: the point adds nothing (as on the dense levels)
-#endif
 #pragma unroll
     for (int c = 0; c < 8; ++c) fix_add_rel(acc, idx[c] - chunk_base, (f[c & 1] * f[2 + ((c >> 1) & 1)] * f[4 + (c >> 2)]) * g);
 }
@@ -1545,7 +1475,6 @@ __device__ __forceinline__ void hash_corner_addr8(const LevelTab& lt, float x, f
 }
 __device__ __forceinline__ void fix_add_corners8(unsigned long long* __restrict__ acc, const uint32_t (&a8)[8], const float (&f)[6], float g) {
     char* __restrict__ base = reinterpret_cast<char*>(acc);
-#if NARUTO_FIX_F64
     if (__builtin_expect(fabsf(g) <= kFixMagicRange, 1)) {             // per LANE: what a point adds does not depend on its wave
         const double gd = (double)g;
         const double gx0 = gd * (double)f[0], gx1 = gd * (double)f[1];
@@ -1559,7 +1488,6 @@ __device__ __forceinline__ void fix_add_corners8(unsigned long long* __restrict_
         return;
     }
     if (!(fabsf(g) < 4194304.0f)) return;                   // NaN / Inf / beyond the fixed point's range: the point adds nothing (as on the dense levels)
-#endif
 #pragma unroll
     for (int c = 0; c < 8; ++c) fix_add_rel(acc, a8[c] >> 3, (f[c & 1] * f[2 + ((c >> 1) & 1)] * f[4 + (c >> 2)]) * g);
 }
@@ -1782,11 +1710,8 @@ struct UncertScatter {
     uint32_t first;             // list entries before this one carry no cotangent (a multiple of 4: 16-byte aligned rows)
 };
 
-#ifndef NARUTO_UNC_COMPACT
-#define NARUTO_UNC_COMPACT 1
-#endif
-constexpr uint32_t kUncBatch = (uint32_t)kScatterThreads * 8u;      // list entries per scan of the uncertainty units (NARUTO_UNC_COMPACT): 16 KB of queue
-constexpr size_t kScatterLdsBytes = (size_t)kChunk * sizeof(unsigned long long) + (NARUTO_UNC_COMPACT ? (size_t)kUncBatch * sizeof(uint16_t) + 16u : 0u);      // image + queue + its count
+constexpr uint32_t kUncBatch = (uint32_t)kScatterThreads * 8u;      // list entries per scan of the uncertainty units: 16 KB of queue
+constexpr size_t kScatterLdsBytes = (size_t)kChunk * sizeof(unsigned long long) + (size_t)kUncBatch * sizeof(uint16_t) + 16u;      // image + queue + its count
 __global__ __launch_bounds__(kScatterThreads) void k_hash_scatter_lds(LevelTab lt, BoxTab bt, PointSrc ps, uint32_t M, const float* __restrict__ d_feat,
                                                                        size_t stride_m, size_t stride_l, ScatterPlan plan,
                                                                        float* __restrict__ partial, size_t n_params,
@@ -1821,14 +1746,7 @@ __global__ __launch_bounds__(kScatterThreads) void k_hash_scatter_lds(LevelTab l
         if (timeline != nullptr && threadIdx.x == 0) timeline[(size_t)blockIdx.x * 8u + 4u] = 0x10000ull + ub;
         // the smoothness lattice at the front of the list carries no raw[...,4] cotangent: the units share the points behind it
         const uint32_t first = unc.first < M ? unc.first : M, Mu = M - first;
-        // cyclic shares, as the dense units' (the list behind the lattice dealt out wave by wave), or contiguous ones (long lists)
-        const uint32_t per = ((Mu + unc.n_splits - 1u) / unc.n_splits + 3u) & ~3u;
-        const uint32_t c_lo = first + (split * per < Mu ? split * per : Mu);
-        const uint32_t m_hi = plan.cyclic ? M : (c_lo + per < M ? c_lo + per : M);
-        const uint32_t u_first = plan.cyclic ? first + ((threadIdx.x >> 6) * unc.n_splits + split) * 512u + (threadIdx.x & 63u) * 8u : c_lo + threadIdx.x * 8u;
-        const uint32_t u_step = plan.cyclic ? (kScatterThreads / 64u) * unc.n_splits * 512u : kScatterThreads * 8u;
         const uint32_t chunk_base = chunk * kChunk;
-#if NARUTO_UNC_COMPACT
         // Round 5: scan + compaction.  Every workgroup of the grid's units used to run the full per-point arithmetic on every point of the list,
         // although only the points near ITS chunk (one in twelve at the headline) add anything -- and a branch on that buys nothing: the 64
         // lanes of a wave sit on 64 different points, some lane always hits, the wave executes the hit path at every step.  So, per batch of
@@ -1904,74 +1822,6 @@ __global__ __launch_bounds__(kScatterThreads) void k_hash_scatter_lds(LevelTab l
                 __syncthreads();                          // the queue is rewritten by the next batch
             }
         }
-#else
-        // consecutive list entries are consecutive samples of a ray and stay in one voxel for a few samples: a thread walks a run of
-        // 8 points and sums the corner contributions in registers while the base voxel does not change (fewer, less conflicting LDS adds)
-        for (uint32_t r0 = u_first; r0 < m_hi; r0 += u_step) {
-            float rx[8], ry[8], rz[8], rg[8];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t b4 = r0 + 4u * h;
-                const float4 X = *reinterpret_cast<const float4*>(ps.xsoa + b4), Y = *reinterpret_cast<const float4*>(ps.xsoa + ps.M + b4);
-                const float4 Z = *reinterpret_cast<const float4*>(ps.xsoa + 2u * ps.M + b4), G = *reinterpret_cast<const float4*>(unc.g + b4);
-                rx[4 * h] = X.x; rx[4 * h + 1] = X.y; rx[4 * h + 2] = X.z; rx[4 * h + 3] = X.w;
-                ry[4 * h] = Y.x; ry[4 * h + 1] = Y.y; ry[4 * h + 2] = Y.z; ry[4 * h + 3] = Y.w;
-                rz[4 * h] = Z.x; rz[4 * h + 1] = Z.y; rz[4 * h + 2] = Z.z; rz[4 * h + 3] = Z.w;
-                rg[4 * h] = G.x; rg[4 * h + 1] = G.y; rg[4 * h + 2] = G.z; rg[4 * h + 3] = G.w;
-            }
-            // (keeps the 16-byte loads whole and up front: left alone, the compiler sinks the first point's three coordinates into the
-            // "cotangent is not zero" branch as scalar loads -- a memory round trip inside the run)
-            asm volatile("" : "+v"(rx[0]), "+v"(ry[0]), "+v"(rz[0]));
-            // (round 5: the base voxel as ONE packed key -- compared per point, expanded into the eight corner indices only when a run of
-            // equal keys is flushed; the per-point form derived and compared all eight indices: ~100 instructions a point, and these
-            // twelve workgroups were what the launch waited for.  Same sums in the same order: same bits.)
-            uint32_t cur = 0xFFFFFFFFu;
-            float a0[8];
-            bool have = false;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) a0[c] = 0.0f;
-            bool magic_ok = true;                                                         // as in the dense units
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                rg[k] = fabsf(rg[k]) < 4194304.0f ? rg[k] : 0.0f;
-                magic_ok = magic_ok & ((r0 + (uint32_t)k >= m_hi) | (fabsf(rg[k]) <= kFixMagicRange / 8.0f));
-            }
-            auto flush_as = [&](auto magic_c) {
-                constexpr bool MAGIC = decltype(magic_c)::value;
-                int32_t ci[8];
-                uncert_base_corners(unc.ut, cur, ci);
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const uint32_t rel = (uint32_t)ci[c] - chunk_base;                        // idx -1 (outside the grid) wraps out of every chunk
-                    if (rel < kChunk) atomicAdd(acc + rel, to_fix40_sum<MAGIC>(a0[c]));
-                    a0[c] = 0.0f;
-                }
-            };
-            auto flush = [&]() {
-                if (!have) return;
-                if (magic_ok) flush_as(std::true_type{});
-                else flush_as(std::false_type{});
-            };
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (r0 + (uint32_t)k >= m_hi) break;
-                if (rg[k] == 0.0f) continue;
-                float fx, fy, fz;
-                const uint32_t key = uncert_base(unc.ut, rx[k], ry[k], rz[k], fx, fy, fz);
-                if (!have || key != cur) {
-                    flush();
-                    cur = key;
-                    have = true;
-                }
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const float w = ((c & 1) ? fx : 1.0f - fx) * ((c & 2) ? fy : 1.0f - fy) * ((c & 4) ? fz : 1.0f - fz);      // uncert_corners' weights
-                    a0[c] = fmaf(w, rg[k], a0[c]);
-                }
-            }
-            flush();
-        }
-#endif
         __syncthreads();
         stamp(2);
         const uint32_t n_e = plan.uncert_voxels - chunk_base < kChunk ? plan.uncert_voxels - chunk_base : kChunk;
@@ -2688,7 +2538,7 @@ constexpr size_t kBwdBfLdsBytes = sizeof(BwdLdsBf) > kAccFloats * sizeof(float) 
 
 template <int NT>
 __device__ __forceinline__ void stage_bwd_weights_bf(BwdLdsBf& L, const NarutoParams& p, int tid) {
-    stage_fwd_weights_bf<NT>(L.f, p, tid);
+    stage_fwd_weights<NT>(L.f, p, tid);
 #pragma unroll
     for (int e0 = 0; e0 < 13 * 64; e0 += NT) {
         const int e = e0 + tid;
@@ -3104,16 +2954,14 @@ __device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ part
     }
     if (adam != nullptr && adam->on && adam->p[tensor] != nullptr) {
         adam_apply(*adam, adam_coef(*adam), tensor, (size_t)off, s);
-        if constexpr (kExactX3) {
-            if (adam->fwd_img != nullptr) {
-                // The new weight is READ BACK behind a compiler fence rather than handed over by adam_apply: as a second use of that value it changed how
-                // the step's multiplies and adds were paired and fused (two v_pk_mul / v_pk_add became v_fmac), i.e. the weights' bits.  The step's code
-                // must not know that anybody looks at its result; the load is this thread's own store coming back, in 32 threads per block.
-                asm volatile("" ::: "memory");
-                const float pn = adam->p[tensor][off];
-                // (two weights share a 32-bit word of the image: 16-bit stores, no two threads touch the same bytes)
-                fwd_image_put(adam->fwd_img, (tensor == 1 ? 0 : (tensor == 2 ? kWOffS1 : (tensor == 3 ? kWOffC0 : kWOffC1))) + off, pn);
-            }
+        if (adam->fwd_img != nullptr) {
+            // The new weight is READ BACK behind a compiler fence rather than handed over by adam_apply: as a second use of that value it changed how
+            // the step's multiplies and adds were paired and fused (two v_pk_mul / v_pk_add became v_fmac), i.e. the weights' bits.  The step's code
+            // must not know that anybody looks at its result; the load is this thread's own store coming back, in 32 threads per block.
+            asm volatile("" ::: "memory");
+            const float pn = adam->p[tensor][off];
+            // (two weights share a 32-bit word of the image: 16-bit stores, no two threads touch the same bytes)
+            fwd_image_put(adam->fwd_img, (tensor == 1 ? 0 : (tensor == 2 ? kWOffS1 : (tensor == 3 ? kWOffC0 : kWOffC1))) + off, pn);
         }
     }
 }

@@ -25,8 +25,7 @@ __global__ __launch_bounds__(256, 2) void k_render_fwd(LevelTab lt, UncertTab ut
     using Lds = std::conditional_t<BF, FwdLdsBf, FwdLds>;
     __shared__ Lds L;
     extern __shared__ float ray_lds[];
-    if constexpr (BF) stage_fwd_weights_bf<256>(L, p, threadIdx.x);
-    else stage_fwd_weights<256>(L, p, threadIdx.x);
+    stage_fwd_weights<256>(L, p, threadIdx.x);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t S = a.nu + a.nr;
@@ -56,8 +55,7 @@ __global__ __launch_bounds__(256, 2) void k_render_fwd(LevelTab lt, UncertTab ut
             const float u = uncert_sample(ut, p.uncert_grid, x, y, z);
             FwdTileOut to;
             // (the single-chain tile: this kernel's rays may take up to 128 KB of dynamic LDS at 1 024 samples, which leaves no room for feature slabs)
-            if constexpr (BF) fwd_tile_bf<true>(L, lt, table, x, y, z, nullptr, nullptr, 0u, 0u, 0u, lane, to);
-            else fwd_tile<true>(L, lt, table, x, y, z, nullptr, nullptr, 0u, 0u, 0u, lane, to);
+            fwd_tile<true>(L, lt, table, x, y, z, nullptr, nullptr, 0u, 0u, 0u, lane, to);
             if (valid) {
                 rs.c0[s] = to.rgb[0]; rs.c1[s] = to.rgb[1]; rs.c2[s] = to.rgb[2];
                 rs.sdf[s] = to.sdf;
@@ -130,20 +128,17 @@ inline size_t render_packed_lds_bytes(uint32_t S, uint32_t rays = kPackRays) { r
 // NT = 256: four waves, kPackRays rays per group, two workgroups per CU, the fp32 matrix instruction (FwdLds: next to the four slabs and the rays'
 // images the x3 weight images do not fit half a CU's LDS).
 // NT = 512 (round 6): ONE eight-wave workgroup per CU -- one copy of the weight images instead of two, which is what makes room for them in
-// their three-piece form: the exact mode's matrix phase runs on the XDL pipe (fwd_mlp_tile_x3, as in the training forward since round 5) beside
-// the other waves' gathers, staged through the slabs (stage_fwd_exact); R rays per group as the LDS allows (32 at 43 samples).  The launcher
+// their three-piece form: the exact mode's matrix phase runs on the XDL pipe (the x3 fwd_mlp_tile, as in the training forward since round 5) beside
+// the other waves' gathers, staged through the slabs; R rays per group as the LDS allows (32 at 43 samples).  The launcher
 // uses it from one group per CU upwards (4 096 rays at 43 samples).
 template <bool BF, int NT>
 __global__ __launch_bounds__(NT, NT == 256 ? NARUTO_RENDER_PACKED_MINWAVES : 1) void k_render_fwd_packed(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, RenderArgs a, uint32_t rays_per_group) {
     constexpr uint32_t kW = NT / 64;
-    using Lds = std::conditional_t<BF, FwdLdsBf, std::conditional_t<NT == 512, FwdLdsExact, FwdLds>>;
+    using Lds = std::conditional_t<BF, FwdLdsBf, std::conditional_t<NT == 512, FwdLdsX3, FwdLds>>;
     __shared__ Lds L;
-    __shared__ FwdSlab slabs[kFwdSplit ? kW : 1];
+    __shared__ FwdSlab slabs[kW];
     extern __shared__ float ray_lds[];
-    if constexpr (BF && NT == 512) stage_fwd_weights_bf_via_lds<NT>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
-    else if constexpr (BF) stage_fwd_weights_bf<NT>(L, p, threadIdx.x);
-    else if constexpr (NT == 512) stage_fwd_exact<NT, sizeof(slabs)>(L, slabs, p, threadIdx.x);
-    else stage_fwd_weights<NT>(L, p, threadIdx.x);
+    stage_fwd_weights<NT, NT == 512 ? sizeof(slabs) : 0>(L, p, threadIdx.x, slabs);      // (the four-wave form stages straight from the parameters)
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));     // scalar: see k_query_fwd_loss
     const uint32_t S = a.nu + a.nr;
@@ -178,10 +173,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? NARUTO_RENDER_PACKED_MINWAVES : 1) 
             const float u = uncert_sample(ut, p.uncert_grid, x, y, z);
             FwdTileOut to;
             // (nothing is saved here, so the phase-split form also takes tiles whose tail lanes are padding)
-            if constexpr (BF && kFwdSplit) fwd_tile_split_bf<true, false>(L, slabs[wave], lt, table, x, y, z, nullptr, nullptr, 0u, 0u, 0u, lane, to);
-            else if constexpr (BF) fwd_tile_bf<true>(L, lt, table, x, y, z, nullptr, nullptr, 0u, 0u, 0u, lane, to);
-            else if constexpr (kFwdSplit) fwd_tile_split<true, false>(L, slabs[wave], lt, table, x, y, z, nullptr, nullptr, 0u, 0u, 0u, lane, to);
-            else fwd_tile<true>(L, lt, table, x, y, z, nullptr, nullptr, 0u, 0u, 0u, lane, to);
+            fwd_tile_split<true, false>(L, slabs[wave], lt, table, x, y, z, nullptr, nullptr, 0u, 0u, 0u, lane, to);
             if (valid) {
                 rs.c0[s] = to.rgb[0]; rs.c1[s] = to.rgb[1]; rs.c2[s] = to.rgb[2];
                 rs.sdf[s] = to.sdf;
@@ -213,7 +205,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? NARUTO_RENDER_PACKED_MINWAVES : 1) 
 }
 // rays per group of the eight-wave form: what the LDS next to the weight images (exact mode's: the larger) and eight slabs takes, at most 32
 inline uint32_t render_packed8_rays(uint32_t S) {
-    const size_t fixed = sizeof(FwdLdsExact) + 8u * sizeof(FwdSlab) + 1024u;
+    const size_t fixed = sizeof(FwdLdsX3) + 8u * sizeof(FwdSlab) + 1024u;
     const size_t room = (size_t)160u * 1024u > fixed ? (size_t)160u * 1024u - fixed : 0u;
     const uint32_t r = (uint32_t)(room / ((size_t)kRayFields * S * sizeof(float)));
     return r > 32u ? 32u : r;

@@ -181,11 +181,10 @@ template <bool BF>
 __global__ __launch_bounds__(512, 1) void k_query_fwd_list(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, const uint32_t* __restrict__ list,
                                                            const float4* __restrict__ pts, const uint32_t* __restrict__ n_dev, float* __restrict__ raw,
                                                            float* __restrict__ feat_save) {
-    using Lds = std::conditional_t<BF, FwdLdsBf, FwdLdsExact>;
+    using Lds = std::conditional_t<BF, FwdLdsBf, FwdLdsX3>;
     __shared__ Lds L;
     __shared__ FwdSlab slabs[8];
-    if constexpr (BF) stage_fwd_weights_bf_via_lds<512>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
-    else stage_fwd_exact<512, sizeof(slabs)>(L, slabs, p, threadIdx.x);
+    stage_fwd_weights<512, sizeof(slabs)>(L, p, threadIdx.x, slabs);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int j = lane & 31;
@@ -225,9 +224,7 @@ __global__ __launch_bounds__(512, 1) void k_query_fwd_list(LevelTab lt, UncertTa
             }
         }
         // (OneBlob's form per LANE: the tiles here are composed by the counting sort's atomics, and a sample's bits must not depend on its neighbours)
-        if constexpr (BF) fwd_mlp_tile_bf<true, true>(L, slabs[wave], x, y, z, nullptr, 0u, 0u, 0u, lane, to);
-        else if constexpr (kExactX3) fwd_mlp_tile_x3<true, false, true>(L, slabs[wave], x, y, z, nullptr, 0u, 0u, 0u, lane, to);
-        else fwd_mlp_tile<true>(L, slabs[wave], x, y, z, nullptr, 0u, 0u, 0u, lane, to);
+        fwd_mlp_tile<true, true>(L, slabs[wave], x, y, z, nullptr, 0u, 0u, 0u, lane, to);
         if (valid) {
             float* __restrict__ o = raw + (size_t)m * 5;
             o[0] = to.rgb[0]; o[1] = to.rgb[1]; o[2] = to.rgb[2]; o[3] = to.sdf; o[4] = u;

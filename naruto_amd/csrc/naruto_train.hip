@@ -200,7 +200,8 @@ template <bool BF, bool SPLIT, bool IMAGE = false>
 __device__ __forceinline__ void query_fwd_loss_body(const LevelTab& lt, const UncertTab& ut, const BoxTab& bt, const NarutoParams& p, const PointSrc& ps, uint32_t M,
                                                     float* __restrict__ raw, float* __restrict__ feat_save, const EarlyExit& ee, const LossStageArgs& a,
                                                     uint32_t n_fwd_blocks, const WalkExtra& wx, unsigned long long* __restrict__ timeline) {
-    using Lds = std::conditional_t<BF, FwdLdsBf, std::conditional_t<SPLIT, FwdLdsExact, FwdLds>>;      // (two-phase tile, exact mode: the x3 chain)
+    using Lds = std::conditional_t<BF, FwdLdsBf, std::conditional_t<SPLIT, FwdLdsX3, FwdLds>>;      // (two-phase tile, exact mode: the x3 chain)
+    constexpr bool kX3 = std::is_same_v<Lds, FwdLdsX3>;
     // profiling (naruto_debug_fwd_timeline; NULL otherwise): lane 0 of every WAVE stamps the 100 MHz counter into its row of 8 -- 0 start, 1 weights
     // staged, 2 depths sampled, 3 first tile's gathers, 4 first tile done, 5 all tiles done, 6 loss stage; slot 7 = tiles evaluated (tools/walk_timeline.py)
     auto stamp = [&](int k) {
@@ -228,16 +229,12 @@ __device__ __forceinline__ void query_fwd_loss_body(const LevelTab& lt, const Un
     // (two workgroups per CU at S = 128)
     __shared__ float ray_c[kRaysPerBlock][16];
     if (threadIdx.x == 0) { a_s = a; wx_s = wx; }
-    constexpr bool kImage = IMAGE && std::is_same_v<Lds, FwdLdsX3>;      // (without the x3 chain there is no image: the kernel stages like the other)
-    if constexpr (kImage) {                                // nine 16-byte loads per thread, then their LDS stores
+    if constexpr (IMAGE && kX3) {                          // nine 16-byte loads per thread, then their LDS stores (only the x3 chain has an image)
         FwdImageRegs<256> wimg;
         wimg.load(wx.w_img, threadIdx.x);
         wimg.store(L, threadIdx.x);
     }
-    else if constexpr (SPLIT && BF) stage_fwd_weights_bf_via_lds<256>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
-    else if constexpr (SPLIT) stage_fwd_exact<256, sizeof(slabs)>(L, slabs, p, threadIdx.x);
-    else if constexpr (BF) stage_fwd_weights_bf<256>(L, p, threadIdx.x);
-    else stage_fwd_weights<256>(L, p, threadIdx.x);
+    else stage_fwd_weights<256, sizeof(slabs)>(L, p, threadIdx.x, slabs);      // (through the slabs where SPLIT has them)
     __syncthreads();
     stamp(1);
     // the wave index as a SCALAR: everything derived from it (the ray, its tiles, the wave's LDS image) then lives in SGPRs instead of
@@ -296,29 +293,24 @@ __device__ __forceinline__ void query_fwd_loss_body(const LevelTab& lt, const Un
                 const float x = __fdiv_rn(__fsub_rn(fmaf(rc[3], zv, rc[0]), bt.bmin[0]), bt.bext[0]);
                 const float y = __fdiv_rn(__fsub_rn(fmaf(rc[4], zv, rc[1]), bt.bmin[1]), bt.bext[1]);
                 const float z = __fdiv_rn(__fsub_rn(fmaf(rc[5], zv, rc[2]), bt.bmin[2]), bt.bext[2]);
-                const bool live = valid && ((tq > 0u && kEeLaneSkip) ? ee_lane_live_r(ees, ee.trunc_sc, td_ee, zv) : true);
+                const bool live = valid && (tq > 0u ? ee_lane_live_r(ees, ee.trunc_sc, td_ee, zv) : true);
                 const float u = live ? uncert_sample(ut, p.uncert_grid, x, y, z) : 0.0f;
                 FwdTileOut to;
                 const bool live_out = live;
-                if constexpr (SPLIT) {                       // the tile in two phases (fwd_tile_split / fwd_tile_split_bf), with a stamp between them
+                if constexpr (SPLIT) {                       // the tile in two phases (fwd_tile_split), with a stamp between them
                     // round 6: a tile behind the first whose live lanes (a prefix: depths are sorted) end within its first 32 points runs as a HALF
                     // tile -- A points only, eight levels' gathers in flight, the A matrix chains (fwd_gather_tile_deep<true>).  (A third unrolled gather -- both halves, four levels in flight, for
                     // the full tiles behind the first -- was measured: the kernel's code outgrows the instruction cache, 60 -> 89 us.)
                     bool half = false;
-                    if constexpr (kWalkHalf && !BF && kExactX3) half = tq > 0u && !__any(live && lane >= 32);
+                    if constexpr (kX3) half = tq > 0u && !__any(live && lane >= 32);      // (the half tile exists for the x3 image only)
                     if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(NARUTO_FWD_GATHER_PRIO);
                     if (half) fwd_gather_tile_deep<true>(lt, table, x, y, z, feat_save, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, slabs[wave], live);
                     else fwd_gather_tile<true>(lt, table, x, y, z, feat_save, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, slabs[wave], live);
                     if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(0);
                     if (tq == 0u && group == blockIdx.x) stamp(3);
-                    if constexpr (BF) fwd_mlp_tile_bf<true>(L, slabs[wave], x, y, z, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to);
-                    else if constexpr (kExactX3) {
-                        if (half) fwd_mlp_tile_x3<true, true>(L, slabs[wave], x, y, z, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to);
-                        else fwd_mlp_tile_x3<true>(L, slabs[wave], x, y, z, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to);
-                    }
+                    if (half) { if constexpr (kX3) fwd_mlp_tile<true, false, true>(L, slabs[wave], x, y, z, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to); }
                     else fwd_mlp_tile<true>(L, slabs[wave], x, y, z, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to);
                 }
-                else if constexpr (BF) fwd_tile_bf<true, true>(L, lt, table, x, y, z, feat_save, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to, live);
                 else fwd_tile<true, true>(L, lt, table, x, y, z, feat_save, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to, live);
                 if (!live_out) { to.rgb[0] = 0.0f; to.rgb[1] = 0.0f; to.rgb[2] = 0.0f; to.sdf = 0.0f; }
                 const float u_out = live_out ? u : 0.0f;
@@ -383,7 +375,7 @@ template <bool BF, bool IMAGE = false>
 __device__ __forceinline__ void query_fwd_loss_short_body(const LevelTab& lt, const UncertTab& ut, const BoxTab& bt, const NarutoParams& p, const PointSrc& ps, uint32_t M,
                                                           float* __restrict__ raw, float* __restrict__ feat_save, const LossStageArgs& a, uint32_t n_fwd_blocks,
                                                           const WalkExtra& wx, uint32_t R, unsigned long long* __restrict__ timeline) {
-    using Lds = std::conditional_t<BF, FwdLdsBf, FwdLdsExact>;
+    using Lds = std::conditional_t<BF, FwdLdsBf, FwdLdsX3>;
     __shared__ Lds L;
     __shared__ FwdSlab slabs[kRaysPerBlock];
     __shared__ double red[4];
@@ -425,16 +417,14 @@ __device__ __forceinline__ void query_fwd_loss_short_body(const LevelTab& lt, co
             rayc[r][c] = v;
         }
     };
-    constexpr bool kImage = IMAGE && std::is_same_v<Lds, FwdLdsX3>;
     fetch_targets(blockIdx.x * R);
-    if constexpr (kImage) {                                // nine 16-byte loads per thread, then their LDS stores
+    if constexpr (IMAGE && !BF) {                               // nine 16-byte loads per thread, then their LDS stores
         FwdImageRegs<256> wimg;
         wimg.load(wx.w_img, threadIdx.x);
         wimg.store(L, threadIdx.x);
         __syncthreads();                                   // (publishes tgt, as the staging's barrier does)
     }
-    else if constexpr (BF) stage_fwd_weights_bf_via_lds<256>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
-    else stage_fwd_exact<256, sizeof(slabs)>(L, slabs, p, threadIdx.x);      // (its barrier also publishes tgt)
+    else stage_fwd_weights<256, sizeof(slabs)>(L, p, threadIdx.x, slabs);      // (through the slabs; its barrier also publishes tgt)
     stamp(5);
     for (uint32_t group = blockIdx.x; group < n_groups; group += n_fwd_blocks) {          // uniform over the workgroup: barriers inside
         const uint32_t ray_first = group * R;
@@ -482,15 +472,15 @@ __device__ __forceinline__ void query_fwd_loss_short_body(const LevelTab& lt, co
             const float z = __fdiv_rn(__fsub_rn(pz, bt.bmin[2]), bt.bext[2]);
             const float u = valid ? uncert_sample(ut, p.uncert_grid, x, y, z) : 0.0f;
             const uint32_t t0 = ray_first * S + (uint32_t)wave * 64u;          // the tile's first row of the flat point list
+            const uint32_t mA = t0 + (uint32_t)j, mB = mA + 32u;
             FwdTileOut to;
-            if constexpr (BF) fwd_tile_split_bf<true, true>(L, slabs[wave], lt, table, x, y, z, feat_save, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to, valid);
-            else {                                         // fwd_tile_split, with a stamp between its phases
+            if constexpr (BF) fwd_tile_split<true, true>(L, slabs[wave], lt, table, x, y, z, feat_save, nullptr, M, mA, mB, lane, to, valid);
+            else {                                         // fwd_tile_split, with a stamp between its phases (exact mode only)
                 if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(NARUTO_FWD_GATHER_PRIO);
-                fwd_gather_tile<true>(lt, table, x, y, z, feat_save, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, slabs[wave], valid);
+                fwd_gather_tile<true>(lt, table, x, y, z, feat_save, M, mA, mB, lane, slabs[wave], valid);
                 if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(0);
                 stamp(2);
-                if constexpr (kExactX3) fwd_mlp_tile_x3<true>(L, slabs[wave], x, y, z, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to);
-                else fwd_mlp_tile<true>(L, slabs[wave], x, y, z, nullptr, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, to);
+                fwd_mlp_tile<true>(L, slabs[wave], x, y, z, nullptr, M, mA, mB, lane, to);
             }
             if (valid) {
                 float* o = raw + (size_t)(t0 + (uint32_t)lane) * 5;
@@ -638,8 +628,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_query_fwd_loss_packed(LevelTa
         else __syncthreads();
         return;
     }
-    if constexpr (BF) stage_fwd_weights_bf<64 * WAVES>(L, p, threadIdx.x);
-    else stage_fwd_weights<64 * WAVES>(L, p, threadIdx.x);
+    stage_fwd_weights<64 * WAVES>(L, p, threadIdx.x);
     __syncthreads();
     stamp();                                        // 1: weights staged
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1158,13 +1147,13 @@ __global__ __launch_bounds__(256) void k_compact(uint32_t n_rays, uint32_t S, co
 // ---- the forward weight image (naruto_fwd_image_init, naruto_debug_fwd_image) ----
 // the image from the weights as they are, written straight to global memory: the kernels' staging routine with L bound to the buffer (zero padding included)
 __global__ __launch_bounds__(256) void k_fwd_image_init(NarutoParams p, FwdLdsX3* __restrict__ image) {
-    stage_fwd_weights_x3_from<256>(*image, WSrcGlobal{p}, threadIdx.x);
+    stage_fwd_weights_from<256>(*image, WSrcGlobal{p}, threadIdx.x);
 }
 // what a training forward's workgroup stages into LDS (the walk's and the short kernel's own call), copied out
 __global__ __launch_bounds__(256) void k_debug_fwd_image(NarutoParams p, uint4* __restrict__ out) {
     __shared__ FwdLdsX3 L;
     __shared__ FwdSlab slabs[kRaysPerBlock];
-    stage_fwd_exact<256, sizeof(slabs)>(L, slabs, p, threadIdx.x);
+    stage_fwd_weights<256, sizeof(slabs)>(L, p, threadIdx.x, slabs);
     __syncthreads();
     const uint4* src = reinterpret_cast<const uint4*>(&L);
     for (uint32_t i = threadIdx.x; i < (uint32_t)(kFwdImageBytes / 16u); i += 256u) out[i] = src[i];

@@ -5,8 +5,8 @@ What the speed mode changes -- and nothing else -- is where operands are rounded
 before a matrix product with fp32 accumulation (``v_mfma_f32_32x32x16_bf16``).  Rounding points in the kernels
 (naruto_amd/csrc/naruto_field.hip):
 
-  forward  k_query_fwd_bf / fwd_tile_bf
-    * the weights of sdf layer 0, sdf layer 1 and colour layer 0, when staged into LDS (stage_fwd_weights_bf: ``pk_bf16`` of eight
+  forward  k_query_fwd_bf / fwd_tile on FwdLdsBf
+    * the weights of sdf layer 0, sdf layer 1 and colour layer 0, when staged into LDS (stage_fwd_weights_from on FwdLdsBf: ``pk_bf16`` of eight
       consecutive K entries)                                                                         -> bf(W) below
     * the 32 hash features and the 48 OneBlob values entering sdf layer 0 / colour layer 0 (``pack8(fa)``, ``pack8(lo8)`` ...)   -> bf(x)
     * relu(h) entering sdf layer 1 (``pack8_acc<true>(hA, 8 * kb)``)                                 -> bf(relu(h))

@@ -279,6 +279,17 @@ def _bf16_emulated_raw(ora, x):
     return raw, out
 
 
+# Both sides round intermediate activations to bf16; where an fp32 sum lands within its accumulation-order noise of a bf16
+# rounding boundary the two can round it to neighbouring bf16 values (a 2^-8 relative step on ONE operand).  So: nearly every
+# element agrees to fp32 accuracy, a handful may differ by such a step -- and nothing by more.
+def _close_up_to_bf16_flips(a, b, what):
+    a, b = a.detach().float().cpu(), b.detach().float().cpu()
+    err = (a - b).abs()
+    tight = err <= 2e-5 + 1e-5 * b.abs()
+    assert float(tight.float().mean()) > 0.998, f"{what}: only {float(tight.float().mean()):.4f} of the elements agree to fp32 accuracy"
+    assert float(err.max()) <= 2e-3 * float(b.abs().max()), f"{what}: max err {float(err.max()):.3e} at scale {float(b.abs().max()):.3e}"
+
+
 @pytest.mark.parametrize("hash_size", [12, 16])
 def test_bf16_mode_matches_its_restatement(gpu, hash_size):
     """decoder.mlp_precision = 'bf16' (v_mfma_f32_32x32x16_bf16): raw, sdf / uncertainty and geo features against a torch
@@ -296,24 +307,41 @@ def test_bf16_mode_matches_its_restatement(gpu, hash_size):
     with torch.no_grad():
         got = m.query_color_sdf(x.to(gpu))
         su, geo = m.query_sdf(x.to(gpu), return_geo=True, return_uncert=True)
-    # Both sides round intermediate activations to bf16; where an fp32 sum lands within its accumulation-order noise of a bf16
-    # rounding boundary the two can round it to neighbouring bf16 values (a 2^-8 relative step on ONE operand).  So: nearly every
-    # element agrees to fp32 accuracy, a handful may differ by such a step -- and nothing by more.
-    def close_up_to_bf16_flips(a, b, what):
-        a, b = a.detach().float().cpu(), b.detach().float().cpu()
-        err = (a - b).abs()
-        tight = err <= 2e-5 + 1e-5 * b.abs()
-        assert float(tight.float().mean()) > 0.998, f"{what}: only {float(tight.float().mean()):.4f} of the elements agree to fp32 accuracy"
-        assert float(err.max()) <= 2e-3 * float(b.abs().max()), f"{what}: max err {float(err.max()):.3e} at scale {float(b.abs().max()):.3e}"
-    close_up_to_bf16_flips(got, want, "bf16.raw")
-    close_up_to_bf16_flips(su[:, 0], out[:, 0], "bf16.sdf")
-    close_up_to_bf16_flips(geo, out[:, 1:], "bf16.geo")
+    _close_up_to_bf16_flips(got, want, "bf16.raw")
+    _close_up_to_bf16_flips(su[:, 0], out[:, 0], "bf16.sdf")
+    _close_up_to_bf16_flips(geo, out[:, 1:], "bf16.geo")
     # and the distance to the exact (fp32) network is the bf16 rounding of the operands: ~2^-9 relative per product
     exact = ora.query_color_sdf(x).detach()
     err = (got.cpu() - exact).abs().max(0).values
     scale = exact.abs().max(0).values
     assert (err[:4] <= 2e-2 * scale[:4] + 1e-4).all(), f"bf16 vs fp32 network: {err.tolist()} at scales {scale.tolist()}"
     assert float(err[4]) <= 4e-6                              # the uncertainty channel does not pass through the MLPs
+
+
+def test_query_fwd_flat_launch_shapes(gpu):
+    """naruto_query_fwd in each of its three flat launch shapes, both MLP modes, against the oracle (exact mode) and the bf16
+    restatement, at the neighbouring tests' tolerances.  The shapes go by tiles (of 64 points) per compute unit: 4 per CU is the last
+    count of four-wave workgroups (256 threads), 6 per CU takes two-wave workgroups (128), and from 8 per CU on one eight-wave
+    workgroup per CU walks the list (512) -- here 21 points short of 8 per CU, so that the last tile is partly filled.  One point
+    list, one reference: the smaller cases are its prefixes."""
+    cu = torch.cuda.get_device_properties(gpu).multi_processor_count
+    cfg = H.office_cfg(12)
+    ora = H.make_oracle(cfg, 0.3, 73)
+    cfg_bf = H.office_cfg(12)
+    cfg_bf["decoder"]["mlp_precision"] = "bf16"
+    m, m_bf = H.make_hip_from_oracle(cfg, ora, gpu).eval(), H.make_hip_from_oracle(cfg_bf, ora, gpu).eval()
+    assert m_bf._handle().mlp_mode == "bf16"
+    n_max = 8 * cu * 64 - 21
+    x = torch.from_numpy(np.random.RandomState(73).uniform(-0.2, 1.2, (n_max, 3)).astype(np.float32))
+    with torch.no_grad():
+        want = ora.query_color_sdf(x).reshape(-1, 5)
+    want_bf, _ = _bf16_emulated_raw(ora, x)
+    xg = x.to(gpu)
+    for n, shape in ((4 * cu * 64, "256 threads"), (6 * cu * 64, "128 threads"), (n_max, "512 threads")):
+        with torch.no_grad():
+            got, got_bf = m.query_color_sdf(xg[:n]), m_bf.query_color_sdf(xg[:n])
+        H.assert_close(got, want[:n], TOL_OUT, f"{n} points ({shape}): raw")
+        _close_up_to_bf16_flips(got_bf, want_bf[:n], f"{n} points ({shape}): bf16 raw")
 
 
 def test_bf16_mode_backward_matches_its_restatement(gpu):

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256, MINW) void k_mlp_only_x3(BoxTab bt, NarutoPara
                                                            float* __restrict__ raw) {
     __shared__ FwdLdsX3 L;
     __shared__ FwdSlab slabs[4];
-    stage_fwd_weights_x3_via_lds<256>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
+    stage_fwd_weights<256, sizeof(slabs)>(L, p, threadIdx.x, slabs);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int hh = lane >> 5, j = lane & 31;
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256, MINW) void k_mlp_only_x3(BoxTab bt, NarutoPara
             slabs[wave].feat[T][1][lane] = mB < M ? fs[mB * 2u + hh] : 0.0f;
         }
         FwdTileOut to;
-        fwd_mlp_tile_x3<true>(L, slabs[wave], x, y, z, nullptr, M, mA, mB, lane, to);
+        fwd_mlp_tile<true>(L, slabs[wave], x, y, z, nullptr, M, mA, mB, lane, to);
         if (valid) {
             float* o = raw + (size_t)m * 5;
             o[0] = to.rgb[0]; o[1] = to.rgb[1]; o[2] = to.rgb[2]; o[3] = to.sdf; o[4] = u_in[m];
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_only_slab(BoxTab bt, NarutoParam
                                                           float* __restrict__ raw) {
     __shared__ FwdLds L;
     __shared__ FwdSlab slabs[4];
-    stage_fwd_weights_via_lds<256>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
+    stage_fwd_weights<256, sizeof(slabs)>(L, p, threadIdx.x, slabs);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int hh = lane >> 5, j = lane & 31;
@@ -249,7 +249,7 @@ __global__ __launch_bounds__(NT, 2) void k_query_fwd_x3(LevelTab lt, UncertTab u
                                                         float* __restrict__ feat_save) {
     __shared__ FwdLdsX3 L;
     __shared__ FwdSlab slabs[NT / 64];
-    stage_fwd_weights_x3_via_lds<NT>(L, reinterpret_cast<float*>(slabs), p, threadIdx.x);
+    stage_fwd_weights<NT, sizeof(slabs)>(L, p, threadIdx.x, slabs);
     __syncthreads();
     constexpr uint32_t kW = NT / 64;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(NT, 2) void k_query_fwd_x3(LevelTab lt, UncertTab u
         __builtin_amdgcn_s_setprio(NARUTO_FWD_GATHER_PRIO);
         fwd_gather_tile<false>(lt, table, x, y, z, feat_save, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, slabs[wave], true);
         __builtin_amdgcn_s_setprio(0);
-        fwd_mlp_tile_x3<true>(L, slabs[wave], x, y, z, nullptr, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to);
+        fwd_mlp_tile<true>(L, slabs[wave], x, y, z, nullptr, M, tile * 64u + (uint32_t)j, tile * 64u + (uint32_t)j + 32u, lane, to);
         if (valid) {
             float* o = raw + (size_t)m * 5;
             o[0] = to.rgb[0]; o[1] = to.rgb[1]; o[2] = to.rgb[2]; o[3] = to.sdf; o[4] = u;
