@@ -413,6 +413,26 @@ int naruto_goal_aggregate(const uint32_t* dims, const float* uncert_vol, const f
                           const int32_t* goal_idx, uint32_t n_targets, const int32_t* targets, float min_dist,
                           float max_dist, float safe_sdf, float* collections, float* aggregated, void* stream);
 
+/* The planner's goal search (reference goal_search_v2, naruto_planner.py:462-510) on the outputs of naruto_goal_aggregate, where
+ * they are: one launch of one workgroup, one small buffer to read back.
+ *   goal   = argmax of aggregated[G].  TIE RULE (ours: the reference's np.argpartition(a, -1)[-1] has none): among equal maxima
+ *            the LOWEST flat index.  Values are ordered by the integer key naruto_goal_targets uses (NaN above +inf, +0 above -0).
+ *   look-at = the top m = min(obs_per_goal, K) entries of row `goal` of collections[G,K], value descending, TIES: target index
+ *            ascending; n_lookat = max(number of those m that are > 0, 1) (:501-502): the caller keeps the first n_lookat.
+ * out (8-byte aligned, NARUTO_GOAL_SEARCH_BYTES(m) bytes, slot r = rank r):
+ *   int32  head[8]          {goal flat index, goal_vxl x, y, z (= goal_idx[goal]), n_lookat, m, 0, 0}
+ *   double lookat_loc[m][3] vox * voxel_size + bbox_min in fp64, product rounded before the sum (planner.py:99)
+ *   int32  lookat_idx[m]    index into targets
+ *   int32  lookat_vxl[m][3] targets[lookat_idx]
+ *   float  lookat_val[m]
+ * bbox_min: HOST double[3].  NARUTO_ERR_INVALID for G == 0, K == 0, obs_per_goal == 0 or K > 4096.  The result does not depend
+ * on the launch shape: every comparison is on integer keys and indices. */
+#define NARUTO_GOAL_SEARCH_HEAD_INTS 8
+#define NARUTO_GOAL_SEARCH_BYTES(m) (4u * NARUTO_GOAL_SEARCH_HEAD_INTS + 44u * (size_t)(m))
+int naruto_goal_search(uint32_t n_goals, uint32_t n_targets, const float* aggregated, const float* collections,
+                       const int32_t* targets, const int32_t* goal_idx, uint32_t obs_per_goal, const double* bbox_min,
+                       double voxel_size, void* out, void* stream);
+
 /* N4 ("next" row) -- the dense volume -> mesh path (reference src/slam/coslam/coslam_utils.py:100-226 extract_mesh,
  * callers coslam.py:421-492).  The reference pushes a host-built lattice through query_sdf in 65 536-point chunks with a
  * copy per chunk and runs the third-party `marching_cubes` module on the CPU (coslam_utils.py:26,145).

@@ -138,6 +138,9 @@ class NarutoCullCam(C.Structure):
 
 SIM_KEEP_INF = 1
 
+GOAL_SEARCH_HEAD_INTS = 8                # naruto_goal_search's out: int32 head[8], then 11 four-byte words per look-at slot
+GOAL_SEARCH_MAX_TARGETS = 4096
+
 RRT_MODE_RUN, RRT_MODE_FULL = 0, 1
 RRT_DONE, RRT_NEED_ROWS, RRT_NEED_ROOM = 0, 1, 2
 RRT_CELL_THRESHOLD = 2048
@@ -226,6 +229,7 @@ SIGNATURES = {
     "naruto_goal_targets_workspace": (C.c_size_t, [_U32, _U32]),
     "naruto_goal_targets": (_I, [C.POINTER(_U32), _V, _U32, _U32, _V, _V, _V]),
     "naruto_goal_aggregate": (_I, [C.POINTER(_U32), _V, _V, _U32, _V, _U32, _V, _F, _F, _F, _V, _V, _V]),
+    "naruto_goal_search": (_I, [_U32, _U32, _V, _V, _V, _V, _U32, C.POINTER(C.c_double), C.c_double, _V, _V]),
     "naruto_rrt_workspace": (C.c_size_t, [C.POINTER(_U32)]),
     "naruto_rrt_start": (_I, [C.POINTER(NarutoRrtPlan), C.POINTER(C.c_double), C.POINTER(C.c_double), _V]),
     "naruto_rrt_grow": (_I, [C.POINTER(NarutoRrtPlan), _I, _V, _U32, _U32, _I, _V]),

@@ -1938,6 +1938,20 @@ int naruto_goal_aggregate(const uint32_t* dims, const float* uncert_vol, const f
     return check_launch("goal_aggregate");
 }
 
+int naruto_goal_search(uint32_t n_goals, uint32_t n_targets, const float* aggregated, const float* collections, const int32_t* targets, const int32_t* goal_idx,
+                       uint32_t obs_per_goal, const double* bbox_min, double voxel_size, void* out, void* stream) {
+    if (aggregated == nullptr || collections == nullptr || targets == nullptr || goal_idx == nullptr || bbox_min == nullptr || out == nullptr)
+        return fail(NARUTO_ERR_INVALID, "goal_search: NULL argument");
+    if (n_goals == 0 || n_targets == 0 || obs_per_goal == 0) return fail(NARUTO_ERR_INVALID, "goal_search: need at least one goal, one target and obs_per_goal >= 1");
+    if (n_goals == 0xFFFFFFFFu) return fail(NARUTO_ERR_INVALID, "goal_search: too many goals");
+    if (n_targets > kGoalSearchMaxTargets) return fail(NARUTO_ERR_INVALID, "goal_search: at most %u targets (got %u)", kGoalSearchMaxTargets, n_targets);
+    if (((uintptr_t)out & 7u) != 0u) return fail(NARUTO_ERR_INVALID, "goal_search: out must be 8-byte aligned");
+    const uint32_t m = obs_per_goal < n_targets ? obs_per_goal : n_targets;
+    const GoalSearchFrame fr{bbox_min[0], bbox_min[1], bbox_min[2], voxel_size};
+    hipLaunchKernelGGL(k_goal_search, dim3(1), dim3(1024), 0, (hipStream_t)stream, n_goals, n_targets, aggregated, collections, targets, goal_idx, m, fr, (int32_t*)out);
+    return check_launch("goal_search");
+}
+
 // ---- the planner's local RRT (naruto_rrt.hip) --------------------------------------------------------------------------
 namespace {
 int rrt_dims(const uint32_t* dims, const char* who, RrtVol* vol, const float* sdf) {

@@ -78,4 +78,94 @@ __global__ __launch_bounds__(256) void k_goal_aggregate(VolDims d, const float* 
     if (lane == 0) aggregated[g] = acc;
 }
 
+// ---- goal search (reference goal_search_v2, naruto_planner.py:462-510) ---------------------------------------------------------
+// One workgroup, one launch: the goal is the argmax of aggregated[G] (ties: lowest flat index), the look-at targets are the top
+// m = min(obs_per_goal, K) entries of the goal's row of collections[G,K] (value descending, then target index ascending).  Values are
+// ordered by the key of k_topk_keys above (~sortable_key: ascending key = descending value, NaN first), so every comparison is an
+// integer one and the result does not depend on the number of threads or on which lane meets which element.
+
+constexpr uint32_t kGoalSearchMaxTargets = 4096;      // the row's keys sit in LDS (16 KiB)
+constexpr uint32_t kGoalSearchHeadInts = NARUTO_GOAL_SEARCH_HEAD_INTS;
+
+struct GoalSearchFrame { double bx, by, bz, voxel; };
+
+// min over the wave of the pair (hi, lo) in lexicographic order
+__device__ __forceinline__ void wave_min_pair(uint32_t& hi, uint32_t& lo) {
+    const uint32_t k = wave_min_u32(hi);
+    lo = wave_min_u32(hi == k ? lo : 0xFFFFFFFFu);
+    hi = k;
+}
+
+// vox2loc (planner.py:99): vox * voxel_size + bbox[:, 0] in fp64, the product rounded before the sum (no fused multiply-add)
+__device__ __forceinline__ void goal_search_loc(int32_t tx, int32_t ty, int32_t tz, const GoalSearchFrame& fr, double* __restrict__ loc) {
+#pragma clang fp contract(off)
+    const double px = (double)tx * fr.voxel, py = (double)ty * fr.voxel, pz = (double)tz * fr.voxel;
+    loc[0] = px + fr.bx;
+    loc[1] = py + fr.by;
+    loc[2] = pz + fr.bz;
+}
+
+// out: int32 head[8] = {goal flat index, goal_vxl[3], n_lookat, m, 0, 0}; double lookat_loc[m][3]; int32 lookat_idx[m];
+// int32 lookat_vxl[m][3]; float lookat_val[m] -- slot r holds the entry of rank r.
+__global__ __launch_bounds__(1024) void k_goal_search(uint32_t n_goals, uint32_t n_targets, const float* __restrict__ aggregated,
+                                                      const float* __restrict__ collections, const int32_t* __restrict__ targets,
+                                                      const int32_t* __restrict__ goal_idx, uint32_t m, GoalSearchFrame fr, int32_t* __restrict__ out) {
+    __shared__ uint32_t s_key[kGoalSearchMaxTargets];
+    __shared__ uint32_t s_whi[16], s_wlo[16];
+    __shared__ uint32_t s_goal, s_positive;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, n_waves = blockDim.x >> 6;
+
+    // (1) argmax: per thread the smallest (key, index) of its strided share, then the wave, then the workgroup
+    uint32_t hi = 0xFFFFFFFFu, lo = 0xFFFFFFFFu;
+    for (uint32_t g = tid; g < n_goals; g += blockDim.x) {
+        const uint32_t key = ~sortable_key(aggregated[g]);
+        if (key < hi || (key == hi && g < lo)) { hi = key; lo = g; }
+    }
+    wave_min_pair(hi, lo);
+    if (lane == 0) { s_whi[wave] = hi; s_wlo[wave] = lo; }
+    __syncthreads();
+    if (wave == 0) {
+        hi = lane < n_waves ? s_whi[lane] : 0xFFFFFFFFu;
+        lo = lane < n_waves ? s_wlo[lane] : 0xFFFFFFFFu;
+        wave_min_pair(hi, lo);
+        if (lane == 0) { s_goal = lo; s_positive = 0u; }
+    }
+    __syncthreads();
+    const uint32_t goal = s_goal;                                          // < n_goals: n_goals >= 1 and every index is below 2^32 - 1
+
+    // (2) the goal's row: rank of entry k = how many entries come before it in (key, index) order
+    const float* __restrict__ row = collections + (size_t)goal * n_targets;
+    for (uint32_t k = tid; k < n_targets; k += blockDim.x) s_key[k] = ~sortable_key(row[k]);
+    __syncthreads();
+    double* __restrict__ loc = reinterpret_cast<double*>(out + kGoalSearchHeadInts);
+    int32_t* __restrict__ idx = out + kGoalSearchHeadInts + 6u * m;
+    int32_t* __restrict__ vxl = idx + m;
+    float* __restrict__ val = reinterpret_cast<float*>(vxl + 3u * m);
+    for (uint32_t k = tid; k < n_targets; k += blockDim.x) {
+        const uint32_t mine = s_key[k];
+        uint32_t rank = 0u;
+        for (uint32_t j = 0u; j < n_targets && rank < m; ++j) {
+            const uint32_t other = s_key[j];
+            rank += (other < mine || (other == mine && j < k)) ? 1u : 0u;
+        }
+        if (rank < m) {
+            const float v = row[k];
+            const int32_t tx = targets[3u * k], ty = targets[3u * k + 1u], tz = targets[3u * k + 2u];
+            idx[rank] = (int32_t)k;
+            vxl[3u * rank] = tx; vxl[3u * rank + 1u] = ty; vxl[3u * rank + 2u] = tz;
+            val[rank] = v;
+            goal_search_loc(tx, ty, tz, fr, loc + 3u * rank);
+            if (v > 0.0f) atomicAdd(&s_positive, 1u);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        out[0] = (int32_t)goal;
+        out[1] = goal_idx[3u * goal]; out[2] = goal_idx[3u * goal + 1u]; out[3] = goal_idx[3u * goal + 2u];
+        out[4] = (int32_t)(s_positive > 0u ? s_positive : 1u);               // :502: max(#positive among the top m, 1)
+        out[5] = (int32_t)m;
+        out[6] = 0; out[7] = 0;
+    }
+}
+
 }  // namespace naruto

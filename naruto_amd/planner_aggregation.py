@@ -4,7 +4,7 @@ Mirror of the two pieces of ``NarutoPlanner`` (reference src/planner/naruto_plan
 uncertainty volumes of ``get_map_volumes``: ``init_data`` (:110-137, the goal-space lattice) and
 ``uncertainty_aggregation_v2`` (:596-735).  Same attribute names, same return value
 ``(goal_space_valid, {'gs_aggre_uncerts', 'topk_uncert_vxl', 'gs_uncert_collections'})``; the rest of the planner
-(RRT, rotation planning, collision checks) is out of scope and keeps using these outputs unchanged.
+(goal search, RRT, rotation planning, collision checks: naruto_amd/planner.py) uses these outputs unchanged.
 
 Differences to know about:
   * the target observations: the reference takes ``np.argpartition(uncert, -top_k)[-top_k_subset:]``, i.e. whichever subset
