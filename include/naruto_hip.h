@@ -396,6 +396,21 @@ int naruto_assemble_select(const NarutoRayBatch* b, uint32_t base, uint32_t K, u
 int naruto_sample_distinct(uint64_t n, uint32_t count, uint64_t seed, uint64_t counter, int64_t* out, void* stream);
 uint64_t naruto_perm_index(uint64_t i, uint64_t n, uint64_t seed, uint64_t counter, uint64_t salt);
 
+/* A mapped frame between the simulator and the mapping loop, without torch launches or host round trips in between.
+ * naruto_frame_ingest: direction [n_pixels,3] (the cached camera-ray table, batch['direction']), rgb [n_pixels,3], depth [n_pixels],
+ * fp32 device -> rays [n_pixels,7] = torch.cat([direction, rgb, depth[..., None]], -1) bit for bit, and *n_valid (device, 8 bytes) = the
+ * number of pixels with depth > 0 && depth <= depth_trunc (keyframe.py:28, coslam.py:322; NaN is invalid).  The count is an integer sum
+ * (one integer atomic per workgroup): exact, whatever the launch plan.
+ * naruto_keyframe_row: row [rays_per_kf,7] of the keyframe store from that buffer (keyframe.py:38-60): stored ray i = pixel
+ * perm(i mod n_take) of the population [0, n), n = *n_valid (NULL: n_pixels -- filter_depth off), n_take = min(n, rays_per_kf), perm the
+ * permutation of naruto_sample_distinct(n, ., seed, counter) (salt 1).  With n_valid the draw indexes the UNFILTERED pixel list as the
+ * reference does (the store's "reference" mode).  n = 0 leaves the row untouched.  Both run on the caller's stream without host
+ * synchronisation, scratch allocation or float atomics. */
+int naruto_frame_ingest(uint64_t n_pixels, const float* direction, const float* rgb, const float* depth, float depth_trunc, float* rays,
+                        uint64_t* n_valid, void* stream);
+int naruto_keyframe_row(const float* frame_rays, uint64_t n_pixels, const uint64_t* n_valid, uint32_t rays_per_kf, uint64_t seed,
+                        uint64_t counter, float* row, void* stream);
+
 /* N3 ("next" row) -- the planner's uncertainty aggregation in goal space (reference src/planner/naruto_planner.py,
  * NarutoPlanner.uncertainty_aggregation_v2 :596-735), consuming the volumes of naruto_map_volumes.
  * naruto_goal_targets: the target observations (:629-632) -- the top_k largest uncertainty voxels (ties: lower flat index),

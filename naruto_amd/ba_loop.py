@@ -329,20 +329,28 @@ class FusedBA:
         return {"n_steps": int(state[0]), "iterations": int(state[1]), "pose": pb["trace_pose"][:n, :P].cpu().clone(),
                 "grad": pb["trace_grad"][:n, :P].cpu().clone(), "init_c2w": self._init_c2w.clone(), "pose6": pb["pose6"][:P].cpu().clone()}
 
-    def prepare(self, current_rays: torch.Tensor, poses_all: torch.Tensor, uncert_vol=None, smooth: bool = True, optimize_poses: Optional[bool] = None):
+    def prepare(self, current_rays: Optional[torch.Tensor], poses_all: torch.Tensor, uncert_vol=None, smooth: bool = True, optimize_poses: Optional[bool] = None,
+                n_valid: Optional[int] = None):
         """Per ``global_BA`` call: the current frame's rays [H*W,7], all poses [P,4,4] (the current frame's LAST), optionally the
         planner's refreshed uncertainty volume.  One count of the valid-depth pixels is read back (the reference does the same
         filtering on the host, coslam.py:332-337); everything else is asynchronous.  ``optimize_poses`` (default: the constructor's):
-        refine the keyframe poses during the call (module docstring); the matrices are converted to (omega, t) on the host."""
+        refine the keyframe poses during the call (module docstring); the matrices are converted to (omega, t) on the host.
+        ``current_rays=None``: ``self.current`` has been filled by the caller (``keyframe_store.frame_ingest(..., out=ba.current, ...)``) and
+        ``n_valid`` is that launch's count of valid-depth pixels (needed with ``mapping.filter_depth``): the copy and the count are skipped."""
         dev = self.device
         if _PARKED_GRAPHS and not torch.cuda.is_current_stream_capturing():
             del _PARKED_GRAPHS[:]
         want_poses = self.optimize_poses if optimize_poses is None else bool(optimize_poses)
         if want_poses:
             self._check_pose_refinement()
-        cur = current_rays.to(dev, torch.float32).reshape(-1, 7)
-        assert cur.shape[0] == self.current.shape[0], "current_rays: one row per pixel of the frame the store was built for"
-        self.current.copy_(cur, non_blocking=True)
+        if current_rays is None:
+            assert n_valid is not None or not self.filter_depth, "current_rays=None with mapping.filter_depth: pass the ingest's n_valid"
+            cur = self.current
+        else:
+            assert n_valid is None, "n_valid belongs to current_rays=None (the count is taken from the rays given)"
+            cur = current_rays.to(dev, torch.float32).reshape(-1, 7)
+            assert cur.shape[0] == self.current.shape[0], "current_rays: one row per pixel of the frame the store was built for"
+            self.current.copy_(cur, non_blocking=True)
         P = poses_all.shape[0]
         assert P <= self.poses.shape[0], "more poses than FusedBA(max_poses=...)"
         self.poses[:P].copy_(poses_all.to(dev, torch.float32), non_blocking=True)
@@ -355,8 +363,11 @@ class FusedBA:
             from .tracking import matrices_to_pose6
             host6 = matrices_to_pose6(poses_all).float().pin_memory()
             self._pose_buffers()["pose_init"][:P].copy_(host6, non_blocking=True)
-        n_valid = cur.shape[0]
-        if self.filter_depth:
+        if current_rays is None:
+            n_valid = int(n_valid) if self.filter_depth else cur.shape[0]
+        elif not self.filter_depth:
+            n_valid = cur.shape[0]
+        else:
             n_valid = int(((cur[:, -1] > 0.0) & (cur[:, -1] <= self.config["cam"]["depth_trunc"])).sum().item())
         turn = self._dyn_turn
         self._dyn_turn ^= 1
@@ -445,13 +456,85 @@ class FusedBA:
             pro(*bufs)
         return tr.step(*bufs, smooth=smooth, uncert_step=(i + 1) % 5 == 0)
 
-    def global_BA(self, current_rays: torch.Tensor, poses_all: torch.Tensor, n_iters: Optional[int] = None, uncert_vol=None, smooth: bool = True,
-                  optimize_poses: Optional[bool] = None):
+    def global_BA(self, current_rays: Optional[torch.Tensor], poses_all: torch.Tensor, n_iters: Optional[int] = None, uncert_vol=None, smooth: bool = True,
+                  optimize_poses: Optional[bool] = None, n_valid: Optional[int] = None):
         """The optimisation loop of one ``global_BA`` call (coslam.py:293-399).  ``optimize_poses`` (default: the constructor's, which
         follows ``tracking.disable``; off in every shipped config): refine the keyframe poses during the call as the reference's pose
-        optimiser does (module docstring); read them with ``refined_poses()`` afterwards."""
-        self.prepare(current_rays, poses_all, uncert_vol, smooth, optimize_poses)
+        optimiser does (module docstring); read them with ``refined_poses()`` afterwards.  ``current_rays=None`` with ``n_valid``: see ``prepare``."""
+        self.prepare(current_rays, poses_all, uncert_vol, smooth, optimize_poses, n_valid=n_valid)
         return self.call_iterations(n_iters, smooth)
+
+    def first_frame_mapping(self, pose: torch.Tensor, n_iters: Optional[int] = None):
+        """The optimisation loop of the reference's ``first_frame_mapping`` (coslam.py:197-219) on the device, over the frame in
+        ``self.current`` (``keyframe_store.frame_ingest(..., out=ba.current, ...)``): every iteration draws ``mapping.sample`` distinct
+        pixels out of ALL H*W (``select_samples`` does not filter by depth; no keyframe is stored yet, no active rays) -- the batch assembly
+        with ``n_global = 0``, keyed by the trainer's {seed, iteration counter} and prefetched by the preceding iteration's last launch like a
+        ``global_BA`` batch --, forms the rays with the single ``pose`` [4,4], and takes a training step without the smoothness term.  The
+        network's Adam steps every iteration; the uncertainty grid's gradient is zeroed once, accumulates over all iterations, is stepped
+        once at the end and is NOT zeroed afterwards (``MappingTrainer.first_frame_mapping``'s contract).  ``n_iters`` defaults to
+        ``mapping.first_iters``.  Replayed as per-iteration graphs; the next ``prepare`` captures the ``global_BA`` graphs afresh."""
+        dev, tr = self.device, self.trainer
+        mp = self.config['mapping']
+        n_iters = int(mp['first_iters']) if n_iters is None else int(n_iters)
+        n = int(mp['sample'])
+        n_pix = self.current.shape[0]
+        assert n <= n_pix, "mapping.sample exceeds the frame's pixel count"
+        if _PARKED_GRAPHS and not torch.cuda.is_current_stream_capturing():
+            del _PARKED_GRAPHS[:]
+        self._detach_poses()
+        self._pose_on = False
+        self._shape = None                     # the graphs below replace a global_BA call's
+        self.poses[:1].copy_(pose.to(dev, torch.float32).reshape(1, 4, 4), non_blocking=True)
+        self._n_poses = 1
+        self.dyn.copy_(torch.tensor([0, 1, n_pix], dtype=torch.int64), non_blocking=False)
+        self._n_cur_pop = n_pix
+        store, rng = self.store, tr.iter_state
+        kw = dict(filter_depth=False, rng=rng, dyn=self.dyn, n_cur=n, n_cur_pop=n_pix)
+
+        def prologue(rays_o, rays_d, target_rgb, target_d):
+            store.assemble_batch(0, self.current, self.poses, 0, out=(rays_o, rays_d, target_rgb, target_d), **kw)
+
+        def arm(bufs, ts):
+            b, keep = store.next_batch_struct(0, self.current, self.poses, 0, bufs, **kw)
+            assert ts.opt is not None, "prefetch needs the optimiser in the backward (MappingTrainer(fused_adam=True))"
+            import ctypes as C
+            self._disarm_prefetch()
+            ts._next_batch_keep = (b, keep)
+            ts.opt.next_batch = C.cast(C.pointer(b), C.c_void_p)
+            self._armed = ts
+
+        with torch.no_grad():
+            tr.model.uncert_grid.grad.zero_()
+        out = None
+        if self.use_graph:
+            with _no_collection():
+                if self.prefetch:
+                    tr.capture(n, smooth=False, prologue=None, first_prologue=prologue, on_buffers=lambda ro, rd, tc, td, ts: arm((ro, rd, tc, td), ts))
+                else:
+                    tr.capture(n, smooth=False, prologue=prologue)
+            bufs = tr.ray_buffers()
+            for i in range(n_iters):
+                out = tr.step(*bufs, smooth=False, uncert_step=False, first=(i == 0))
+        else:
+            f = torch.zeros(n * 10, dtype=torch.float32, device=dev)
+            from .trainer import unpack_rays
+            bufs = unpack_rays(f, n)
+            tr._graphs = None
+            self._disarm_prefetch()
+            if self.prefetch:
+                arm(bufs, tr._train_step(n, False))
+            for i in range(n_iters):
+                if i == 0 or not self.prefetch:
+                    prologue(*bufs)
+                out = tr.step(*bufs, smooth=False, uncert_step=False)
+        with torch.no_grad():
+            tr.uncert_optim.step()
+        # the finishing launch of the last iteration drew one more batch into buffers nobody reads; take the draw off the training step
+        # so that a plain trainer.step on it afterwards assembles nothing
+        if self.use_graph:
+            self._drop_graphs()
+        self._disarm_prefetch()
+        return out
 
     def call_iterations(self, n_iters: Optional[int] = None, smooth: bool = True):
         """The iterations of the current ``global_BA`` call (after ``prepare``): one launch of the call graph when the call has the

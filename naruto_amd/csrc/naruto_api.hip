@@ -26,6 +26,7 @@
 #include "naruto_recon.hip"
 #include "naruto_cull.hip"
 #include "naruto_sim.hip"
+#include "naruto_frame.hip"
 
 using namespace naruto;
 
@@ -2512,6 +2513,31 @@ int naruto_sample_distinct(uint64_t n, uint32_t count, uint64_t seed, uint64_t c
     hipLaunchKernelGGL(k_sample_distinct, dim3((count + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, n, count, (uint64_t)0, half_bits_for(n),
                        mix_key(seed, counter, 1), out);
     return check_launch("sample_distinct");
+}
+
+int naruto_frame_ingest(uint64_t n_pixels, const float* direction, const float* rgb, const float* depth, float depth_trunc, float* rays,
+                        uint64_t* n_valid, void* stream) {
+    if (direction == nullptr || rgb == nullptr || depth == nullptr || rays == nullptr || n_valid == nullptr) return fail(NARUTO_ERR_INVALID, "frame_ingest: NULL argument");
+    if (n_pixels == 0 || n_pixels > (1ull << 32)) return fail(NARUTO_ERR_INVALID, "frame_ingest: %llu pixels out of range", (unsigned long long)n_pixels);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(n_valid, 0, 8u, st) != hipSuccess) return check_launch("frame_ingest: memset");
+    const uint64_t n_words = n_pixels * 7u;
+    // at most 8 workgroups per CU's worth of grid: beyond that the grid-stride loop takes over (one atomic per workgroup)
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_words + kFrameThreads - 1u) / kFrameThreads, 256u * 8u);
+    hipLaunchKernelGGL(k_frame_ingest, dim3(blocks), dim3(kFrameThreads), 0, st, n_words, reinterpret_cast<const uint32_t*>(direction),
+                       reinterpret_cast<const uint32_t*>(rgb), reinterpret_cast<const uint32_t*>(depth), depth_trunc, reinterpret_cast<uint32_t*>(rays),
+                       reinterpret_cast<unsigned long long*>(n_valid));
+    return check_launch("frame_ingest");
+}
+
+int naruto_keyframe_row(const float* frame_rays, uint64_t n_pixels, const uint64_t* n_valid, uint32_t rays_per_kf, uint64_t seed, uint64_t counter,
+                        float* row, void* stream) {
+    if (frame_rays == nullptr || row == nullptr) return fail(NARUTO_ERR_INVALID, "keyframe_row: NULL argument");
+    if (n_pixels == 0 || n_pixels > (1ull << 32) || rays_per_kf == 0) return fail(NARUTO_ERR_INVALID, "keyframe_row: sizes out of range");
+    hipLaunchKernelGGL(k_keyframe_row, dim3((rays_per_kf + kFrameThreads - 1u) / kFrameThreads), dim3(kFrameThreads), 0, (hipStream_t)stream,
+                       reinterpret_cast<const uint32_t*>(frame_rays), n_pixels, reinterpret_cast<const unsigned long long*>(n_valid), rays_per_kf,
+                       mix_key(seed, counter, 1), reinterpret_cast<uint32_t*>(row));
+    return check_launch("keyframe_row");
 }
 
 namespace {

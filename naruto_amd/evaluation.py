@@ -303,6 +303,19 @@ def calc_3d_mesh_metric(mesh_gt, mesh_rec, n_samples: int = 200000, threshold: f
     return ReconEvaluatorHIP(mesh_gt, n_samples, threshold, seed).evaluate_mesh(mesh_rec)
 
 
+def trajectory_length(poses) -> float:
+    """The number of the reference's src/evaluation/eval_traj_length.py:64-73 (result key ``traj_len(m)``): the sum over consecutive
+    poses of the norm of (P_i^-1 P_{i-1})[:3, 3].  ``poses``: [P,4,4], or the frame id -> [4,4] dict of a checkpoint (visited in
+    key order 0, 1, ..., as the reference indexes it).  Evaluated in float64 on the host."""
+    if isinstance(poses, dict):
+        poses = [poses[k] for k in sorted(poses)]
+    if len(poses) == 0:
+        return 0.0
+    p = torch.stack([torch.as_tensor(q).detach().to("cpu", torch.float64).reshape(4, 4) for q in poses])
+    rel = torch.linalg.inv(p[1:]) @ p[:-1]
+    return float(torch.linalg.norm(rel[:, :3, 3], dim=-1).sum())
+
+
 def update_results_file(results: Dict[str, float], file_path: str) -> None:
     """``key,value`` lines; keys already in the file are updated in place, new ones appended (general_utils.py:163-188's format)."""
     merged: Dict[str, float] = {}

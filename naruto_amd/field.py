@@ -420,21 +420,35 @@ def _map_lattice(bounding_box: torch.Tensor, voxel_size: float) -> torch.Tensor:
     return q
 
 
-def get_map_volumes(query_fn, bounding_box: torch.Tensor, voxel_size: float):
+def get_map_volumes(query_fn, bounding_box: torch.Tensor, voxel_size: float, to_host: bool = True, out: Optional[torch.Tensor] = None):
     """Planner query path (reference src/slam/coslam/coslam_utils.py:58-97): dense lattice -> [uncert_vol,
     sdf_vol] as numpy.  The lattice is cached on the device, the reference's discarded ``embed=True`` pass
     (coslam_utils.py:86-87) is skipped, the post-processing is one kernel and both volumes come back in one
-    device-to-host copy."""
+    device-to-host copy.
+    ``to_host=False``: the two [X,Y,Z] float32 volumes stay on the device (views of one [2,X*Y*Z] tensor) and nothing synchronises --
+    ``NarutoPlannerHIP.main`` and ``ActiveRaySamplerHIP.set_volume`` take them as they are.  ``out`` (with ``to_host=False``): a
+    caller-owned contiguous float32 device tensor of 2*X*Y*Z elements to write into; the returned volumes are views of it, so their
+    addresses do not change from call to call."""
     import ctypes as C
     from . import _lib
     q = _map_lattice(bounding_box, voxel_size)
+    shape = tuple(q.shape[:-1])
     with torch.no_grad():
         su = query_fn(q, embed=False, return_uncert=True).contiguous()
         M = su.numel() // 2
-        out = torch.empty(2, M, dtype=torch.float32, device=su.device)
+        if out is not None:
+            if to_host:
+                raise ValueError("get_map_volumes(out=...) keeps the volumes on the device: pass to_host=False")
+            if not (out.is_cuda and out.device == su.device and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 2 * M):
+                raise RuntimeError(f"get_map_volumes: out must be a contiguous float32 tensor of {2 * M} elements on {su.device}")
+            out = out.view(2, M)
+        else:
+            out = torch.empty(2, M, dtype=torch.float32, device=su.device)
         with torch.cuda.device(su.device):
             _lib.check(_lib.load().naruto_map_volumes(M, su.data_ptr(), out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                        "naruto_map_volumes")
+        if not to_host:
+            return [out[0].view(shape), out[1].view(shape)]
         # one device-to-host copy into a cached PINNED buffer (a pageable destination costs a staging copy and ~0.1 ms more)
         key = ("pinned", 2 * M)
         pin = _LATTICE_CACHE.get(key)
@@ -444,5 +458,4 @@ def get_map_volumes(query_fn, bounding_box: torch.Tensor, voxel_size: float):
         pin.copy_(out, non_blocking=True)
         torch.cuda.current_stream(su.device).synchronize()
         host = pin.numpy()
-    shape = tuple(q.shape[:-1])
     return [host[0].reshape(shape).copy(), host[1].reshape(shape).copy()]

@@ -32,6 +32,22 @@ def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def frame_ingest(direction: torch.Tensor, rgb: torch.Tensor, depth: torch.Tensor, depth_trunc: float, out: torch.Tensor, n_valid: torch.Tensor):
+    """One frame -> ``out`` [H*W,7] = ``torch.cat([direction, rgb, depth[..., None]], -1).reshape(-1, 7)`` bit for bit, and ``n_valid``
+    (int64 [1], device) = the number of pixels with ``0 < depth <= depth_trunc`` (keyframe.py:28, coslam.py:322), in one launch
+    (``naruto_frame_ingest``) on the current stream.  direction / rgb [...,H,W,3], depth [...,H,W]: contiguous fp32 device tensors."""
+    n = depth.numel()
+    for t, c, name in ((direction, 3, "direction"), (rgb, 3, "rgb"), (depth, 1, "depth"), (out, 7, "out")):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n * c):
+            raise RuntimeError(f"frame_ingest: {name} must be a contiguous fp32 device tensor of {n} x {c} elements")
+    if not (n_valid.is_cuda and n_valid.dtype == torch.int64 and n_valid.numel() >= 1):
+        raise RuntimeError("frame_ingest: n_valid must be an int64 device tensor")
+    with torch.cuda.device(out.device):
+        check(_lib.load().naruto_frame_ingest(n, direction.data_ptr(), rgb.data_ptr(), depth.data_ptr(), float(depth_trunc), out.data_ptr(),
+                                              n_valid.data_ptr(), _stream()), "naruto_frame_ingest")
+    return out, n_valid
+
+
 class KeyFrameStoreHIP:
     def __init__(self, config: Dict, H: int, W: int, num_kf: int, num_rays_to_save: int, device, seed: int = 0,
                  filter_depth_mode: str = "reference"):
@@ -102,6 +118,33 @@ class KeyFrameStoreHIP:
             kept = kept.repeat(reps, 1)[:self.num_rays_to_save]
         self.rays[len(self) - 1] = kept
 
+    def add_keyframe_device(self, frame_rays: torch.Tensor, frame_id, filter_depth: bool = False, n_valid: Optional[torch.Tensor] = None,
+                            n_valid_host: Optional[int] = None):
+        """``add_keyframe`` from an ingested frame, without leaving the device (``naruto_keyframe_row``): ``frame_rays`` is the [H*W,7]
+        buffer ``naruto_frame_ingest`` wrote (``ops.frame_ingest``; ``FusedBA.current``), ``n_valid`` the device word it counted the
+        valid-depth pixels into (int64 [1]; needed with ``filter_depth``).  The draw's population is read from that word by the kernel: no
+        ``nonzero``, no gather, no host value.  Same seed, same sequence of frames: rows and ids equal ``add_keyframe``'s bit for bit.
+        The draw counter advances once per call, as ``add_keyframe``'s does -- except that ``add_keyframe`` leaves it alone for a filtered
+        frame WITHOUT any valid pixel, which the host cannot see here: a caller that knows the count (``CoSLAMNarutoHIP`` reads it back to
+        size the BA batch) passes it as ``n_valid_host`` and the counter follows ``add_keyframe`` in that case too.
+        ``frame_id``: int or int64 tensor, as ``batch['frame_id']``."""
+        if filter_depth and self.filter_depth_mode == "valid_only":
+            raise NotImplementedError("add_keyframe_device draws from the unfiltered pixel list (filter_depth_mode='reference'); "
+                                      "'valid_only' needs the compacted list of add_keyframe")
+        if not (frame_rays.is_cuda and frame_rays.dtype == torch.float32 and frame_rays.is_contiguous() and frame_rays.numel() == self.total_pixels * 7):
+            raise RuntimeError(f"add_keyframe_device: frame_rays must be a contiguous fp32 device tensor [{self.total_pixels},7]")
+        if filter_depth:
+            if n_valid is None or not (n_valid.is_cuda and n_valid.dtype == torch.int64 and n_valid.numel() >= 1):
+                raise RuntimeError("add_keyframe_device(filter_depth=True): n_valid must be the int64 device word of the ingest")
+        self.attach_ids(frame_id if isinstance(frame_id, torch.Tensor) else torch.tensor([frame_id]))
+        if filter_depth and n_valid_host is not None and int(n_valid_host) <= 0:
+            return                                   # as in the reference: the id is attached, no rays are stored (and nothing was drawn)
+        self.counter += 1
+        with torch.cuda.device(self.device):
+            check(_lib.load().naruto_keyframe_row(frame_rays.data_ptr(), self.total_pixels, n_valid.data_ptr() if filter_depth else None,
+                                                  self.num_rays_to_save, self.seed, self.counter, self.rays[len(self) - 1].data_ptr(), _stream()),
+                  "naruto_keyframe_row")
+
     def sample_global_rays(self, bs: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Co-SLAM KeyFrameDatabase.sample_global_rays: bs distinct stored rays [bs,7] and their frame ids [bs]."""
         n_kf = len(self)
@@ -124,13 +167,14 @@ class KeyFrameStoreHIP:
     def _draw(self, sample_num, current_rays, poses_all, min_pixels_cur, filter_depth, rng, dyn, n_cur, n_cur_pop):
         """The NarutoRayBatch of one draw (everything but the output buffers) + what it keeps alive."""
         n_kf = len(self)
-        assert n_kf > 0, "no keyframe stored yet"
+        assert n_kf > 0 or sample_num == 0, "no keyframe stored yet"            # (sample_num == 0: first-frame mapping draws from the frame alone)
         cur = current_rays.to(self.device, torch.float32).reshape(-1, 7).contiguous()
         poses = poses_all.to(self.device, torch.float32).contiguous()
         fixed = n_cur is not None
         if fixed:
             assert n_cur_pop is not None and not (filter_depth and self.filter_depth_mode == "valid_only"), "fixed sizes: pass n_cur_pop (reference mode)"
         else:
+            assert n_kf > 0, "no keyframe stored yet: pass n_cur / n_cur_pop"
             n_cur = max(sample_num // n_kf, int(min_pixels_cur))
             n_cur_pop = cur.shape[0]
         cur_list = None

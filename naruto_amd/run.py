@@ -1,0 +1,176 @@
+"""An exploration run with this library alone: the loop of the reference's src/naruto/main.py:90-146 over ``MeshSimHIP`` (in
+Habitat's place), ``CoSLAMNarutoHIP`` and ``NarutoPlannerHIP``.
+
+Per step: the modules' step counters, ``sim.simulate(c2w)``, ``slam.online_recon_step(i, color, depth, c2w)``,
+``planner.main(uncert_sdf, c2w, is_new_vols)`` (the planner keeps the last volumes it was given; ``is_new_vols`` tells it when they are
+fresh).  After the loop: the final mesh at ``mesh.voxel_final`` (``mesh_<num_iter>_final.ply``) and the checkpoint
+(``ckpt_<num_iter>_final.pt``).  With a predefined trajectory (the reference's passive mapping, ``enable_active_planning = False``) the
+pose of step i is the trajectory's and the planner is skipped.
+
+Command line::
+
+    python -m naruto_amd.run --config <coslam.yaml> --mesh <scene.ply> --num_iter N --result_dir D [--start x y z] [--traj traj.txt]
+                             [--no_active_ray] [--seed S] [--planner key=value ...]
+
+``--config`` is a Co-SLAM yaml (``naruto_amd.config.load_config``).  The reference's ``.py`` config files are not read: the planner's
+settings are ``naruto_amd.planner.DEFAULTS`` (the values of the reference's configs/default.py, restated as data) with ``--planner
+key=value`` overrides, and the SLAM keywords (voxel size 0.1, 500 active rays out of a 4x oversampled batch) are ``CoSLAMNarutoHIP``'s
+defaults.  ``--traj`` reads a Replica trajectory file: sixteen numbers per line, camera-to-world row-major, columns 1 and 2 of the
+rotation negated as the reference's ``load_Replica_pose`` does.  The run's trajectory length goes to ``<result_dir>/results.txt`` as
+``traj_len(m),<value>`` (``evaluation.update_results_file``'s format).
+"""
+
+from __future__ import annotations
+
+import ast
+import os
+import time
+from typing import Callable, Dict, List, Optional
+
+import numpy as np
+import torch
+
+PHASES = ("Simulation", "SLAM", "Planning")
+
+
+def load_replica_traj(path: str) -> torch.Tensor:
+    """[N,4,4] float32 camera-to-world poses of a Replica ``traj.txt`` (pose_loader.py:78-91: one pose per line, 16 numbers; columns 1
+    and 2 of the upper three rows change sign)."""
+    poses = []
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            if not line.strip():
+                continue
+            vals = line.split()
+            if len(vals) != 16:
+                raise ValueError(f"{path}:{n}: expected 16 numbers per pose, got {len(vals)}")
+            c2w = np.array(list(map(float, vals))).reshape(4, 4)
+            c2w[:3, 1] *= -1
+            c2w[:3, 2] *= -1
+            poses.append(torch.from_numpy(c2w).float())
+    if not poses:
+        raise ValueError(f"{path}: no pose")
+    return torch.stack(poses)
+
+
+def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optional[Callable] = None, traj: Optional[torch.Tensor] = None) -> Dict:
+    """main.py:90-146.  ``planner`` is set up by the caller (``update_sim``, ``init_data``, ``init_local_planner``) or None with ``traj``
+    ([N,4,4], N >= num_iter: the pose of step i is ``traj[i]``).  ``on_step(i, c2w, vols, state)`` is called at the end of every step.
+    Returns ``poses`` [num_iter,4,4] (the pose each frame was taken at), ``states`` (the planner's state after each step), ``fresh``
+    (the steps that produced new volumes), ``timing`` {phase: {"total_s", "calls", "mean_s"}} from host timers around each phase (the
+    SLAM phase ends with whatever the step waited for, not with a device synchronisation), ``mesh`` and ``ckpt_path`` of the final
+    save."""
+    if planner is None and traj is None:
+        raise ValueError("run_exploration: a planner or a predefined trajectory")
+    if traj is not None and len(traj) < num_iter:
+        raise ValueError(f"run_exploration: the trajectory has {len(traj)} poses, the run {num_iter} steps")
+    c2w = torch.as_tensor(start_c2w if traj is None else traj[0]).detach().to("cpu", torch.float32).reshape(4, 4).clone()
+    spent = {k: [0.0, 0] for k in PHASES}
+
+    def timed(name, fn, *args):
+        t0 = time.perf_counter()
+        out = fn(*args)
+        spent[name][0] += time.perf_counter() - t0
+        spent[name][1] += 1
+        return out
+
+    poses, states, fresh = [], [], []
+    uncert_sdf = None
+    for i in range(int(num_iter)):
+        for module in (sim, slam, planner):
+            if module is not None and hasattr(module, "update_step"):
+                module.update_step(i)
+        if traj is not None:
+            c2w = traj[i].detach().to("cpu", torch.float32).clone()
+        poses.append(c2w.clone())
+        color, depth = timed("Simulation", lambda: sim.simulate(c2w.numpy().copy(), no_print=True))
+        vols = timed("SLAM", slam.online_recon_step, i, color, depth, c2w)
+        if vols is not None:
+            uncert_sdf = vols
+            fresh.append(i)
+        if planner is not None:
+            c2w = timed("Planning", planner.main, uncert_sdf, c2w.numpy(), vols is not None)
+            c2w = torch.as_tensor(c2w).detach().to("cpu", torch.float32).reshape(4, 4)
+            states.append(planner.state)
+        if on_step is not None:
+            on_step(i, poses[-1], vols, states[-1] if states else None)
+    mesh = slam.save_mesh(int(num_iter), voxel_size=slam.config["mesh"]["voxel_final"], suffix="_final")
+    ckpt_path = slam.save_ckpt(int(num_iter), suffix="_final") if slam.result_dir is not None else None
+    timing = {k: {"total_s": t, "calls": n, "mean_s": t / n if n else 0.0} for k, (t, n) in spent.items()}
+    return {"poses": torch.stack(poses) if poses else torch.zeros(0, 4, 4), "states": states, "fresh": fresh, "timing": timing, "mesh": mesh,
+            "ckpt_path": ckpt_path}
+
+
+def _planner_overrides(items: List[str]) -> Dict:
+    out = {}
+    for item in items or []:
+        key, sep, val = item.partition("=")
+        if not sep or not key:
+            raise ValueError(f"--planner {item!r}: expected key=value")
+        try:
+            out[key] = ast.literal_eval(val)
+        except (ValueError, SyntaxError):
+            out[key] = val
+    return out
+
+
+def parse_args(argv=None):
+    import argparse
+    parser = argparse.ArgumentParser(prog="python -m naruto_amd.run", description="Run an exploration on a mesh: simulate, map, plan.")
+    parser.add_argument("--config", type=str, required=True, help="Co-SLAM yaml config (inherit_from chains are followed)")
+    parser.add_argument("--mesh", type=str, required=True, help="scene mesh the simulator renders (.ply)")
+    parser.add_argument("--num_iter", type=int, required=True, help="number of steps")
+    parser.add_argument("--result_dir", type=str, required=True, help="meshes, checkpoints and results.txt go here")
+    parser.add_argument("--start", type=float, nargs=3, metavar=("X", "Y", "Z"), help="start position (identity rotation); default: the bound's centre")
+    parser.add_argument("--traj", type=str, help="predefined Replica trajectory (passive mapping: the planner is skipped)")
+    parser.add_argument("--no_active_ray", action="store_true", help="switch the active ray sampler off")
+    parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--dataset", type=str, default="NARUTO", choices=["Replica", "MP3D", "NARUTO"], help="the planner's collision rule")
+    parser.add_argument("--planner", type=str, nargs="*", default=[], metavar="KEY=VALUE", help="planner settings over naruto_amd.planner.DEFAULTS")
+    args = parser.parse_args(argv)
+    if args.num_iter <= 0:
+        parser.error("--num_iter must be positive")
+    if not args.mesh.lower().endswith(".ply"):
+        parser.error(f"--mesh {args.mesh}: only .ply meshes are read")
+    if args.traj is not None and args.start is not None:
+        parser.error("--start and --traj exclude each other: the trajectory's first pose is the start")
+    args.planner = _planner_overrides(args.planner)
+    return args
+
+
+def main(argv=None) -> Dict:
+    args = parse_args(argv)
+    from . import config as cfgmod
+    from .evaluation import trajectory_length, update_results_file
+    from .planner import DEFAULTS, NarutoPlannerHIP
+    from .simulator import MeshSimHIP
+    from .slam import CoSLAMNarutoHIP
+    unknown = set(args.planner) - set(DEFAULTS)
+    if unknown:
+        raise ValueError(f"--planner: unknown keys {sorted(unknown)}")
+    cfg = cfgmod.load_config(args.config)
+    traj = load_replica_traj(args.traj) if args.traj else None
+    np.random.seed(args.seed)                      # the planner's RRT draws from numpy's generator
+    os.makedirs(args.result_dir, exist_ok=True)
+    slam = CoSLAMNarutoHIP(cfg, active_ray=not args.no_active_ray, num_frames=args.num_iter, seed=args.seed, result_dir=args.result_dir)
+    sim = MeshSimHIP(args.mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=slam.device)
+    planner = None
+    if traj is None:
+        planner = NarutoPlannerHIP(dataset=args.dataset, device=slam.device, **args.planner)
+        planner.update_sim(sim)
+        planner.init_data(cfg["mapping"]["bound"])
+        planner.init_local_planner()
+    start = torch.eye(4)
+    start[:3, 3] = torch.tensor(args.start if args.start is not None else [0.5 * (b[0] + b[1]) for b in cfg["mapping"]["bound"]])
+    out = run_exploration(slam, sim, planner, start, args.num_iter, traj=traj)
+    length = trajectory_length(out["poses"])
+    update_results_file({"traj_len(m)": length}, os.path.join(args.result_dir, "results.txt"))
+    torch.cuda.synchronize(slam.device)
+    for k, v in out["timing"].items():
+        print(f"{k}: {v['total_s']:.3f} s over {v['calls']} calls")
+    print(f"trajectory length {length:.2f} m; final mesh {len(out['mesh'].vertices)} vertices; checkpoint {out['ckpt_path']}")
+    return out
+
+
+if __name__ == "__main__":
+    main()

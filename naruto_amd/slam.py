@@ -1,0 +1,257 @@
+"""CoSLAMNarutoHIP: the object the reference's run loop drives (``CoSLAMNaruto``, reference src/slam/coslam/coslam.py), assembled from
+the device pieces of this package -- ``MappingTrainer`` / ``FusedBA`` (mapping iteration and ``global_BA`` loop), ``KeyFrameStoreHIP``,
+``ActiveRaySamplerHIP``, ``get_map_volumes``, ``extract_mesh`` -- with a frame going from the simulator into the mapping loop
+without a detour through torch expressions or the host (``naruto_frame_ingest`` / ``naruto_keyframe_row``).  It needs neither
+``mmengine`` nor the Co-SLAM third-party tree.
+
+PARITY UNPINNED.  ``CoSLAMNaruto`` inherits from Co-SLAM's ``CoSLAM`` and uses its ``get_camera_rays``, ``KeyFrameDatabase`` and
+``select_samples``, none of which is in the reference tree.  What this class does is therefore restated here:
+
+  * Camera rays (``init_cam_rays``, coslam.py:122-144): H, W, fx, fy, cx, cy are the config's values FLOOR-divided by
+    ``data.downsample`` -- the reference's ``//``, which also drops the half pixel of cx = 599.5 -- and ``rays_d`` [H,W,3] holds
+    ((i - cx)/fx, -(j - cy)/fy, -1) for column i, row j: x right, y up, looking along -z, this package's convention throughout.
+  * ``online_recon_step(i, color, depth, c2w)`` (coslam.py:537-633), in this order:
+      1. the mesh is saved at ``mesh.voxel_eval`` when ``i % mesh.vis == 0``;
+      2. frame 0: ``est_c2w_data[0] = c2w``; ``mapping.first_iters`` iterations of first-frame mapping (coslam.py:197-219:
+         ``mapping.sample`` distinct pixels out of all H*W per iteration, no smoothness term, the network's Adam every iteration, the
+         uncertainty grid's gradient zeroed once, stepped once at the end and kept); frame 0 becomes a keyframe; map volumes;
+      3. any other frame: ``est_c2w_data[i] = c2w`` (``tracking.disable``; see below);
+      4. when ``i % mapping.map_every == 0``: ``global_BA`` over the keyframes stored BEFORE this frame, with the poses
+         ``est_c2w_data[0, keyframe_every, ... < i]`` and the current one last (coslam.py:259-267), AND THEN the map volumes;
+      5. when ``i % mapping.keyframe_every == 0``: the frame becomes a keyframe (``mapping.filter_depth`` as configured);
+      6. with active rays, the cached uncertainty volume becomes the new one.
+    It returns None, or [uncert_vol, sdf_vol] when step 2 or 4 made new ones.
+  * The random draws (keyframe pixels, batch rays, depth jitter) are this package's keyed streams, not Python's ``random``: the drawn
+    sets differ from the reference's by construction, their distribution does not (``keyframe_store``, ``ba_loop``).
+
+What differs on purpose:
+
+  * the volumes come back as float32 DEVICE tensors [X,Y,Z] -- views of one buffer this object owns and OVERWRITES at the next mapped
+    frame (clone them to keep them).  ``NarutoPlannerHIP.main`` and ``ActiveRaySamplerHIP.set_volume`` take them as they are;
+  * the keyframe store holds ``num_frames // keyframe_every + 1`` keyframes -- sized by the run, not by the dataset placeholder of
+    20 000 frames the reference sizes it by (4.6 GB at 1200 x 680);
+  * ``est_c2w_data`` is indexable by frame id like the reference's dict but backed by one [num_frames,4,4] device tensor, so the
+    keyframe poses of a ``global_BA`` call are a strided slice of it;
+  * a frame that neither maps nor becomes a keyframe launches nothing.  A mapped frame waits once for the host: the 8-byte count of
+    valid-depth pixels, which sizes the current-frame draw (the reference filters on the host at the same place, coslam.py:322-325).
+
+Out of scope: camera tracking and pose refinement inside ``global_BA`` (``tracking.disable: False``).  The pieces exist
+(``naruto_amd.tracking.TrackerHIP``, ``FusedBA(optimize_poses=True)``); wiring them in here is the follow-up, and the constructor raises
+``NotImplementedError`` for such a config.  Every shipped config has ``tracking.disable: True``.
+"""
+
+from __future__ import annotations
+
+import json
+import os
+from typing import Dict, Iterator, List, Optional
+
+import torch
+
+from .active_ray_sampler import ActiveRaySamplerHIP
+from .ba_loop import FusedBA
+from .field import _map_lattice, get_map_volumes
+from .keyframe_store import KeyFrameStoreHIP, frame_ingest
+from .mesh import extract_mesh
+from .trainer import MappingTrainer
+
+
+def step_schedule(i: int, config: Dict) -> Dict[str, bool]:
+    """What ``online_recon_step`` does at frame ``i`` (coslam.py:571, 579, 607, 622): ``mesh`` saved, ``first`` frame mapping, ``map``
+    (``global_BA`` + volumes), ``keyframe`` added, ``volumes`` returned."""
+    mp = config["mapping"]
+    first = i == 0
+    mapped = (not first) and i % int(mp["map_every"]) == 0
+    return {"mesh": i % int(config["mesh"]["vis"]) == 0, "first": first, "map": mapped,
+            "keyframe": first or i % int(mp["keyframe_every"]) == 0, "volumes": first or mapped}
+
+
+def camera_rays(H: int, W: int, fx: float, fy: float, cx: float, cy: float) -> torch.Tensor:
+    """[H,W,3] camera-frame ray table ((i - cx)/fx, -(j - cy)/fy, -1), float32 (module docstring)."""
+    i = torch.arange(W, dtype=torch.float32)[None, :].expand(H, W)
+    j = torch.arange(H, dtype=torch.float32)[:, None].expand(H, W)
+    return torch.stack([(i - cx) / fx, -(j - cy) / fy, -torch.ones(H, W)], -1).contiguous()
+
+
+class DevicePoses:
+    """``est_c2w_data``: frame id -> [4,4], as the reference's dict, over one [num_frames,4,4] float32 device tensor (``tensor``)."""
+
+    def __init__(self, num_frames: int, device):
+        self.tensor = torch.zeros(int(num_frames), 4, 4, dtype=torch.float32, device=device)
+        self._have = [False] * int(num_frames)
+
+    def __setitem__(self, i: int, c2w) -> None:
+        self.tensor[i].copy_(torch.as_tensor(c2w).to(torch.float32).reshape(4, 4), non_blocking=True)
+        self._have[i] = True
+
+    def __getitem__(self, i: int) -> torch.Tensor:
+        if not self._have[i]:
+            raise KeyError(i)
+        return self.tensor[i]
+
+    def __contains__(self, i) -> bool:
+        return isinstance(i, int) and 0 <= i < len(self._have) and self._have[i]
+
+    def __len__(self) -> int:
+        return sum(self._have)
+
+    def keys(self) -> Iterator[int]:
+        return (i for i, h in enumerate(self._have) if h)
+
+    def as_dict(self) -> Dict[int, torch.Tensor]:
+        """frame id -> [4,4] on the host (one copy): what ``save_ckpt`` writes and ``culling.poses_from_checkpoint`` reads."""
+        host = self.tensor.cpu()
+        return {i: host[i].clone() for i in self.keys()}
+
+
+class CoSLAMNarutoHIP:
+    def __init__(self, config: Dict, voxel_size: float = 0.1, active_ray: Optional[bool] = None, act_ray_num_uncert_sample: int = 500,
+                 act_ray_oversample_mul: int = 4, num_frames: int = 2000, seed: Optional[int] = 0, result_dir: Optional[str] = None, device="cuda"):
+        """``config``: a Co-SLAM config (``naruto_amd.config.load_config``); it is kept and, as in the reference's ``override_config``,
+        ``mapping.active_ray`` is overwritten when ``active_ray`` is given.  ``num_frames``: the length of the run (sizes the keyframe store
+        and the pose tensor).  ``seed``: keys the keyframe store's draws and, through ``torch.manual_seed`` (None: left alone), the
+        network's initial values and the trainer's in-kernel random streams.  ``result_dir``: meshes and checkpoints go under
+        ``<result_dir>/coslam`` (None: ``save_*`` need an explicit directory)."""
+        tk = config.get("tracking") or {}
+        if not bool(tk.get("disable", True)):
+            raise NotImplementedError("CoSLAMNarutoHIP: tracking.disable: False (camera tracking and pose refinement during the run) is not wired in; "
+                                      "the pieces are naruto_amd.tracking.TrackerHIP and FusedBA(optimize_poses=True)")
+        self.config = config
+        if active_ray is not None:
+            config["mapping"]["active_ray"] = bool(active_ray)
+        self.device = torch.device(device)
+        self.voxel_size = float(voxel_size)
+        self.result_dir = result_dir
+        self.step = 0
+        self.num_frames = int(num_frames)
+        mp, cam, ds = config["mapping"], config["cam"], config["data"]["downsample"]
+        self.H, self.W = cam["H"] // ds, cam["W"] // ds
+        self.fx, self.fy, self.cx, self.cy = cam["fx"] // ds, cam["fy"] // ds, cam["cx"] // ds, cam["cy"] // ds
+        self.rays_d = camera_rays(self.H, self.W, self.fx, self.fy, self.cx, self.cy).to(self.device)
+        self.bounding_box = torch.tensor(mp["bound"], dtype=torch.float32, device=self.device)
+        self.marching_cube_bound = torch.tensor(mp["marching_cubes_bound"], dtype=torch.float32, device=self.device)
+        self.est_c2w_data = DevicePoses(self.num_frames, self.device)
+        self.est_c2w_data_rel = DevicePoses(self.num_frames, self.device)
+        if seed is not None:
+            torch.manual_seed(int(seed))
+        self.trainer = MappingTrainer(config, self.bounding_box, self.device, uncert_voxel=self.voxel_size, fused_adam=True)
+        self.model = self.trainer.model
+        self.num_rays_to_save = int(self.H * self.W * mp["n_pixels"])
+        num_kf = self.num_frames // int(mp["keyframe_every"]) + 1
+        self.keyframeDatabase = KeyFrameStoreHIP(config, self.H, self.W, num_kf, self.num_rays_to_save, self.device, seed=int(seed or 0))
+        self.active_ray_sampler = None
+        if mp.get("active_ray", False):
+            if not 0 < int(act_ray_num_uncert_sample) <= int(mp["sample"]):
+                raise ValueError(f"CoSLAMNarutoHIP: act_ray_num_uncert_sample = {act_ray_num_uncert_sample} active rays do not fit a batch of "
+                                 f"mapping.sample = {mp['sample']} rays")
+            self.active_ray_sampler = ActiveRaySamplerHIP(config=config, num_uncert_sample=act_ray_num_uncert_sample, oversample_mul=act_ray_oversample_mul)
+        self.ba = FusedBA(self.trainer, self.keyframeDatabase, self.active_ray_sampler, max_poses=num_kf + 1)
+        self.cached_uncert = None
+        self.filter_depth = bool(mp.get("filter_depth", False))
+        self._n_valid = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._n_valid_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+        self._n_valid_event = torch.cuda.Event()
+        lattice = _map_lattice(self.bounding_box, self.voxel_size)
+        self._vol_shape = tuple(lattice.shape[:-1])
+        self._vols = torch.zeros(2, *self._vol_shape, dtype=torch.float32, device=self.device)
+        if result_dir is not None:
+            os.makedirs(os.path.join(result_dir, "coslam"), exist_ok=True)
+            with open(os.path.join(result_dir, "coslam", "config.json"), "w", encoding="utf-8") as fh:
+                fh.write(json.dumps(config, indent=4))
+
+    # ---------------------------------------------------------------------------------------------
+    def update_step(self, step: int) -> None:
+        self.step = int(step)
+
+    def _ingest(self, color: torch.Tensor, depth: torch.Tensor) -> None:
+        """The frame into ``FusedBA.current`` ([H*W,7]) and its valid-depth count into the device word: one launch."""
+        color = color.to(self.device, torch.float32).contiguous()
+        depth = depth.to(self.device, torch.float32).contiguous()
+        frame_ingest(self.rays_d, color, depth, float(self.config["cam"]["depth_trunc"]), self.ba.current, self._n_valid)
+
+    def _read_n_valid(self) -> int:
+        """The step's one wait for the host: 8 bytes through pinned memory."""
+        self._n_valid_host.copy_(self._n_valid, non_blocking=True)
+        self._n_valid_event.record(torch.cuda.current_stream(self.device))
+        self._n_valid_event.synchronize()
+        return int(self._n_valid_host[0])
+
+    def _volumes(self) -> List[torch.Tensor]:
+        return get_map_volumes(self.model.query_sdf, self.bounding_box, self.voxel_size, to_host=False, out=self._vols)
+
+    def online_recon_step(self, i: int, color: torch.Tensor, depth: torch.Tensor, c2w: torch.Tensor) -> Optional[List[torch.Tensor]]:
+        """One step of the run loop (module docstring).  color [H,W,3], depth [H,W], c2w [4,4] camera-to-world.  Returns None or
+        [uncert_vol, sdf_vol]: float32 device tensors [X,Y,Z], views of a buffer this object overwrites at the next mapped frame."""
+        i = int(i)
+        cfg, mp = self.config, self.config["mapping"]
+        todo = step_schedule(i, cfg)
+        vols = None
+        with torch.cuda.device(self.device):
+            if todo["mesh"]:
+                self.save_mesh(i, voxel_size=cfg["mesh"]["voxel_eval"])
+            if todo["first"]:
+                self.est_c2w_data[0] = c2w
+                self.est_c2w_data_rel[0] = c2w
+                self._ingest(color, depth)
+                self.ba.first_frame_mapping(self.est_c2w_data.tensor[0], int(mp["first_iters"]))
+                n_valid = self._read_n_valid() if self.filter_depth else None
+                self.keyframeDatabase.add_keyframe_device(self.ba.current, i, self.filter_depth, self._n_valid, n_valid_host=n_valid)
+                vols = self._volumes()
+            else:
+                self.est_c2w_data[i] = c2w
+                if todo["map"] or todo["keyframe"]:
+                    self._ingest(color, depth)
+                n_valid = None
+                if todo["map"]:
+                    n_valid = self._read_n_valid() if self.filter_depth else None
+                    every = int(mp["keyframe_every"])
+                    poses_all = torch.cat([self.est_c2w_data.tensor[0:i:every], self.est_c2w_data.tensor[i:i + 1]], 0)
+                    self.ba.global_BA(None, poses_all, uncert_vol=self.cached_uncert if self.active_ray_sampler is not None else None, n_valid=n_valid)
+                    vols = self._volumes()
+                if todo["keyframe"]:
+                    self.keyframeDatabase.add_keyframe_device(self.ba.current, i, self.filter_depth, self._n_valid, n_valid_host=n_valid)
+        if self.active_ray_sampler is not None and vols is not None:
+            self.cached_uncert = vols[0]
+        return vols
+
+    # ---------------------------------------------------------------------------------------------
+    def _savedir(self, kind: str, given: Optional[str]) -> str:
+        if given is not None:
+            return given
+        if self.result_dir is None:
+            raise ValueError(f"CoSLAMNarutoHIP: no result_dir was given; pass the {kind} directory")
+        return os.path.join(self.result_dir, "coslam", kind)
+
+    def save_mesh(self, i: Optional[int] = None, voxel_size: float = 0.05, suffix: str = "", mesh_savedir: Optional[str] = None):
+        """coslam.py:421-458: ``mesh_<i>.ply`` (default: the current step) coloured by ``query_color``, or rendered along the vertex
+        normals with ``mesh.render_color``.  Without a ``result_dir`` and a directory nothing is written; the mesh is returned."""
+        path = ""
+        if mesh_savedir is not None or self.result_dir is not None:
+            path = os.path.join(self._savedir("mesh", mesh_savedir), f"mesh_{self.step if i is None else i:04}{suffix}.ply")
+        color_func = self.model.render_surface_color if self.config["mesh"]["render_color"] else self.model.query_color
+        return extract_mesh(self.model.query_sdf, self.config, self.bounding_box, color_func=color_func, marching_cube_bound=self.marching_cube_bound,
+                            voxel_size=voxel_size, mesh_savepath=path)
+
+    def save_uncert_mesh(self, i: Optional[int] = None, voxel_size: float = 0.05, suffix: str = "", mesh_savedir: Optional[str] = None):
+        """coslam.py:460-492: the mesh coloured by the uncertainty."""
+        path = ""
+        if mesh_savedir is not None or self.result_dir is not None:
+            path = os.path.join(self._savedir("uncert_mesh", mesh_savedir), f"mesh_{self.step if i is None else i:04}{suffix}.ply")
+        return extract_mesh(self.model.query_sdf, self.config, self.bounding_box, color_func=None, marching_cube_bound=self.marching_cube_bound,
+                            voxel_size=voxel_size, render_uncert=True, mesh_savepath=path)
+
+    def save_ckpt(self, i: Optional[int] = None, suffix: str = "", ckpt_savedir: Optional[str] = None) -> str:
+        """coslam.py:494-517: {'pose', 'pose_rel', 'model'}; the poses as frame id -> [4,4] dicts (``culling.poses_from_checkpoint``)."""
+        savedir = self._savedir("checkpoint", ckpt_savedir)
+        os.makedirs(savedir, exist_ok=True)
+        path = os.path.join(savedir, f"ckpt_{self.step if i is None else i:04}{suffix}.pt")
+        model = {k: v.detach().cpu() for k, v in self.model.state_dict().items()}
+        torch.save({"pose": self.est_c2w_data.as_dict(), "pose_rel": self.est_c2w_data_rel.as_dict(), "model": model}, path)
+        return path
+
+    @torch.no_grad()
+    def predict_sdf(self, points: torch.Tensor) -> torch.Tensor:
+        """coslam.py:519-535 / coslam_utils.py:35-56: points [N,K,3] in field coordinates -> sdf [N,K] (units of ``training.trunc``)."""
+        bb = self.bounding_box
+        q = (points.to(self.device, torch.float32) - bb[:, 0]) / (bb[:, 1] - bb[:, 0])
+        return self.model.query_sdf(q, embed=False, return_uncert=True)[..., 0]
