@@ -411,6 +411,29 @@ int naruto_frame_ingest(uint64_t n_pixels, const float* direction, const float* 
 int naruto_keyframe_row(const float* frame_rays, uint64_t n_pixels, const uint64_t* n_valid, uint32_t rays_per_kf, uint64_t seed,
                         uint64_t counter, float* row, void* stream);
 
+/* The pose chain of a tracked run (tracking.disable: False; reference coslam.py:595-602 tracks every frame, :264-281 and :378-407 refine the
+ * keyframe poses in global_BA and write them back to est_c2w_data; Co-SLAM's predict_current_pose, the relative pose tracking_render stores
+ * and convert_relative_pose are not in the reference tree: parity unpinned, restated here).  est / rel are est_c2w_data / est_c2w_data_rel
+ * as [num_frames,4,4] row-major float32 camera-to-world matrices on the device; kf(i) = (i / keyframe_every) * keyframe_every.  Arithmetic
+ * in fp64, every output rounded to fp32 once, copies move the bits; one thread per pose, no atomics, no allocation, no synchronisation.
+ *   naruto_pose_log      pose6[p] = (omega, t) of c2w[p], p < P: the unit quaternion through the largest of 4w^2, 4x^2, 4y^2, 4z^2, w >= 0,
+ *                        omega = 2 atan2(|v|, w) v / |v| (2 v / w below |v| = 1e-12) -- naruto_amd.tracking.matrices_to_pose6, branch for branch
+ *   naruto_pose_predict  est[i] = est[i-1] when i == 1 or const_speed == 0, else (est[i-1] @ inv(est[i-2])) @ est[i-1] (predict_current_pose);
+ *                        inv is the general affine inverse (adjugate of the 3x3 block over its determinant, then -A^-1 t), not R^T.
+ *                        pose6_out [6] = naruto_pose_log of est[i] AS STORED (rounded): the tracker's initial pose.  1 <= i < num_frames
+ *   naruto_pose_commit   est[i] = c2w [4,4], the tracker's result; when i % keyframe_every != 0: rel[i] = est[i] @ inv(est[kf(i)])
+ *   naruto_pose_scatter  coslam.py:401-407: est[k * keyframe_every] = refined[k] for k = 1 .. P-2 and est[cur_id] = refined[P-1] iff optim_cur;
+ *                        est[0] is never written.  refined [P,4,4] (NarutoBAPoses.poses after the call) must not overlap est
+ *   naruto_pose_resolve  convert_relative_pose: out[i] = est[i] for a keyframe, rel[i] @ est[kf(i)] otherwise, i < n; out [n,4,4]
+ * naruto_debug_pose_log is naruto_pose_log's code on the host (host arrays, nothing launched). */
+int naruto_pose_log(uint32_t P, const float* c2w, float* pose6, void* stream);
+int naruto_pose_predict(float* est, uint32_t num_frames, uint32_t i, int32_t const_speed, float* pose6_out, void* stream);
+int naruto_pose_commit(float* est, float* rel, uint32_t num_frames, uint32_t i, uint32_t keyframe_every, const float* c2w, void* stream);
+int naruto_pose_scatter(float* est, uint32_t num_frames, const float* refined, uint32_t P, uint32_t keyframe_every, uint32_t cur_id,
+                        int32_t optim_cur, void* stream);
+int naruto_pose_resolve(const float* est, const float* rel, uint32_t n, uint32_t keyframe_every, float* out, void* stream);
+int naruto_debug_pose_log(uint32_t P, const float* c2w, float* pose6);
+
 /* N3 ("next" row) -- the planner's uncertainty aggregation in goal space (reference src/planner/naruto_planner.py,
  * NarutoPlanner.uncertainty_aggregation_v2 :596-735), consuming the volumes of naruto_map_volumes.
  * naruto_goal_targets: the target observations (:629-632) -- the top_k largest uncertainty voxels (ties: lower flat index),

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_sim.hip", "naruto_frame.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_sim.hip", "naruto_frame.hip", "naruto_posechain.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -228,6 +228,12 @@ SIGNATURES = {
     "naruto_perm_index": (_U64, [_U64, _U64, _U64, _U64, _U64]),
     "naruto_frame_ingest": (_I, [_U64, _V, _V, _V, _F, _V, _V, _V]),
     "naruto_keyframe_row": (_I, [_V, _U64, _V, _U32, _U64, _U64, _V, _V]),
+    "naruto_pose_log": (_I, [_U32, _V, _V, _V]),
+    "naruto_pose_predict": (_I, [_V, _U32, _U32, C.c_int32, _V, _V]),
+    "naruto_pose_commit": (_I, [_V, _V, _U32, _U32, _U32, _V, _V]),
+    "naruto_pose_scatter": (_I, [_V, _U32, _V, _U32, _U32, _U32, C.c_int32, _V]),
+    "naruto_pose_resolve": (_I, [_V, _V, _U32, _U32, _V, _V]),
+    "naruto_debug_pose_log": (_I, [_U32, _V, _V]),
     "naruto_goal_targets_workspace": (C.c_size_t, [_U32, _U32]),
     "naruto_goal_targets": (_I, [C.POINTER(_U32), _V, _U32, _U32, _V, _V, _V]),
     "naruto_goal_aggregate": (_I, [C.POINTER(_U32), _V, _V, _U32, _V, _U32, _V, _F, _F, _F, _V, _V, _V]),

@@ -25,8 +25,9 @@ call with P poses (``poses_all``, the current frame's last; ray id -1 means the 
 1. Pose optimisation is OFF for the call when fewer than 2 keyframes are stored or the caller does not ask for it (coslam.py:264): the
    call is then the plain call, launch for launch and bit for bit.
 2. Otherwise pose 0 is fixed, poses 1 .. P-2 are parameters, pose P-1 (the current frame) is one iff ``mapping.optim_cur``
-   (coslam.py:273-281).  A parameter pose starts from ``(matrix_to_axis_angle(R), t)`` of the caller's matrix -- converted on the host
-   in fp64, rounded to fp32 -- and from the first iteration on its rays are formed from ``R(omega)`` (Rodrigues, evaluated on the
+   (coslam.py:273-281).  A parameter pose starts from ``(matrix_to_axis_angle(R), t)`` of the caller's matrix -- converted in fp64 and
+   rounded to fp32, on the host or, with ``pose_init_on_device`` (the run loop: ``CoSLAMNarutoHIP(track=True)``), by ``naruto_pose_log`` on
+   the device without waiting for the host -- and from the first iteration on its rays are formed from ``R(omega)`` (Rodrigues, evaluated on the
    device for the initial matrices and after every step alike), not from the caller's matrix.  Fixed poses keep the caller's bits.
 3. Every iteration is the ordinary mapping iteration (forward, losses incl. smoothness, backward, Adam on the network, uncertainty grid
    every 5th) AND the gradient of the same total loss w.r.t. every parameter pose, taken at the parameters the forward used,
@@ -330,13 +331,15 @@ class FusedBA:
                 "grad": pb["trace_grad"][:n, :P].cpu().clone(), "init_c2w": self._init_c2w.clone(), "pose6": pb["pose6"][:P].cpu().clone()}
 
     def prepare(self, current_rays: Optional[torch.Tensor], poses_all: torch.Tensor, uncert_vol=None, smooth: bool = True, optimize_poses: Optional[bool] = None,
-                n_valid: Optional[int] = None):
+                n_valid: Optional[int] = None, pose_init_on_device: bool = False):
         """Per ``global_BA`` call: the current frame's rays [H*W,7], all poses [P,4,4] (the current frame's LAST), optionally the
         planner's refreshed uncertainty volume.  One count of the valid-depth pixels is read back (the reference does the same
         filtering on the host, coslam.py:332-337); everything else is asynchronous.  ``optimize_poses`` (default: the constructor's):
         refine the keyframe poses during the call (module docstring); the matrices are converted to (omega, t) on the host.
         ``current_rays=None``: ``self.current`` has been filled by the caller (``keyframe_store.frame_ingest(..., out=ba.current, ...)``) and
-        ``n_valid`` is that launch's count of valid-depth pixels (needed with ``mapping.filter_depth``): the copy and the count are skipped."""
+        ``n_valid`` is that launch's count of valid-depth pixels (needed with ``mapping.filter_depth``): the copy and the count are skipped.
+        ``pose_init_on_device``: the (omega, t) of the P poses come from ``naruto_pose_log`` over ``self.poses[:P]`` on the device instead
+        of the host conversion -- same branches and formulas, no wait for the host (the run loop's tracked frames)."""
         dev = self.device
         if _PARKED_GRAPHS and not torch.cuda.is_current_stream_capturing():
             del _PARKED_GRAPHS[:]
@@ -359,10 +362,15 @@ class FusedBA:
         self._n_poses = P
         pose_on = bool(want_poses and n_kf >= 2 and P >= 2)            # coslam.py:264
         if pose_on:
-            # (omega, t) of every pose, fp64 on the host, through pinned memory (the caching host allocator keeps the block until the copy ran)
-            from .tracking import matrices_to_pose6
-            host6 = matrices_to_pose6(poses_all).float().pin_memory()
-            self._pose_buffers()["pose_init"][:P].copy_(host6, non_blocking=True)
+            # (omega, t) of every pose: on the device from the rows just copied (naruto_pose_log), or fp64 on the host, through pinned
+            # memory (the caching host allocator keeps the block until the copy ran)
+            if pose_init_on_device:
+                from .pose_chain import pose_log
+                pose_log(self.poses[:P], out=self._pose_buffers()["pose_init"][:P])
+            else:
+                from .tracking import matrices_to_pose6
+                host6 = matrices_to_pose6(poses_all).float().pin_memory()
+                self._pose_buffers()["pose_init"][:P].copy_(host6, non_blocking=True)
         if current_rays is None:
             n_valid = int(n_valid) if self.filter_depth else cur.shape[0]
         elif not self.filter_depth:
@@ -457,11 +465,11 @@ class FusedBA:
         return tr.step(*bufs, smooth=smooth, uncert_step=(i + 1) % 5 == 0)
 
     def global_BA(self, current_rays: Optional[torch.Tensor], poses_all: torch.Tensor, n_iters: Optional[int] = None, uncert_vol=None, smooth: bool = True,
-                  optimize_poses: Optional[bool] = None, n_valid: Optional[int] = None):
+                  optimize_poses: Optional[bool] = None, n_valid: Optional[int] = None, pose_init_on_device: bool = False):
         """The optimisation loop of one ``global_BA`` call (coslam.py:293-399).  ``optimize_poses`` (default: the constructor's, which
         follows ``tracking.disable``; off in every shipped config): refine the keyframe poses during the call as the reference's pose
-        optimiser does (module docstring); read them with ``refined_poses()`` afterwards.  ``current_rays=None`` with ``n_valid``: see ``prepare``."""
-        self.prepare(current_rays, poses_all, uncert_vol, smooth, optimize_poses, n_valid=n_valid)
+        optimiser does (module docstring); read them with ``refined_poses()`` afterwards.  ``current_rays=None`` with ``n_valid``, ``pose_init_on_device``: see ``prepare``."""
+        self.prepare(current_rays, poses_all, uncert_vol, smooth, optimize_poses, n_valid=n_valid, pose_init_on_device=pose_init_on_device)
         return self.call_iterations(n_iters, smooth)
 
     def first_frame_mapping(self, pose: torch.Tensor, n_iters: Optional[int] = None):

@@ -27,6 +27,7 @@
 #include "naruto_cull.hip"
 #include "naruto_sim.hip"
 #include "naruto_frame.hip"
+#include "naruto_posechain.hip"
 
 using namespace naruto;
 
@@ -2540,6 +2541,48 @@ int naruto_keyframe_row(const float* frame_rays, uint64_t n_pixels, const uint64
     return check_launch("keyframe_row");
 }
 
+int naruto_pose_log(uint32_t P, const float* c2w, float* pose6, void* stream) {
+    if (c2w == nullptr || pose6 == nullptr) return fail(NARUTO_ERR_INVALID, "pose_log: NULL argument");
+    if (P == 0) return fail(NARUTO_ERR_INVALID, "pose_log: no pose");
+    hipLaunchKernelGGL(k_pose_log, dim3((P + kPoseChainThreads - 1u) / kPoseChainThreads), dim3(kPoseChainThreads), 0, (hipStream_t)stream, P, c2w, pose6);
+    return check_launch("pose_log");
+}
+
+int naruto_pose_predict(float* est, uint32_t num_frames, uint32_t i, int32_t const_speed, float* pose6_out, void* stream) {
+    if (est == nullptr || pose6_out == nullptr) return fail(NARUTO_ERR_INVALID, "pose_predict: NULL argument");
+    if (i < 1u || i >= num_frames) return fail(NARUTO_ERR_INVALID, "pose_predict: frame %u of %u (the first frame is given, not predicted)", i, num_frames);
+    hipLaunchKernelGGL(k_pose_predict, dim3(1), dim3(kPoseChainThreads), 0, (hipStream_t)stream, est, i, const_speed, pose6_out);
+    return check_launch("pose_predict");
+}
+
+int naruto_pose_commit(float* est, float* rel, uint32_t num_frames, uint32_t i, uint32_t keyframe_every, const float* c2w, void* stream) {
+    if (est == nullptr || rel == nullptr || c2w == nullptr) return fail(NARUTO_ERR_INVALID, "pose_commit: NULL argument");
+    if (keyframe_every == 0u) return fail(NARUTO_ERR_INVALID, "pose_commit: keyframe_every = 0");
+    if (i < 1u || i >= num_frames) return fail(NARUTO_ERR_INVALID, "pose_commit: frame %u of %u (the first frame is given, not tracked)", i, num_frames);
+    hipLaunchKernelGGL(k_pose_commit, dim3(1), dim3(kPoseChainThreads), 0, (hipStream_t)stream, est, rel, i, keyframe_every, c2w);
+    return check_launch("pose_commit");
+}
+
+int naruto_pose_scatter(float* est, uint32_t num_frames, const float* refined, uint32_t P, uint32_t keyframe_every, uint32_t cur_id, int32_t optim_cur,
+                        void* stream) {
+    if (est == nullptr || refined == nullptr) return fail(NARUTO_ERR_INVALID, "pose_scatter: NULL argument");
+    if (P == 0u || keyframe_every == 0u) return fail(NARUTO_ERR_INVALID, "pose_scatter: P = %u poses, keyframe_every = %u", P, keyframe_every);
+    if (cur_id >= num_frames) return fail(NARUTO_ERR_INVALID, "pose_scatter: current frame %u of %u", cur_id, num_frames);
+    if (P > 2u && (uint64_t)(P - 2u) * keyframe_every >= (uint64_t)num_frames)
+        return fail(NARUTO_ERR_INVALID, "pose_scatter: keyframe %u at frame %llu of %u", P - 2u, (unsigned long long)(P - 2u) * keyframe_every, num_frames);
+    hipLaunchKernelGGL(k_pose_scatter, dim3((P + kPoseChainThreads - 1u) / kPoseChainThreads), dim3(kPoseChainThreads), 0, (hipStream_t)stream, est, refined, P,
+                       keyframe_every, cur_id, optim_cur);
+    return check_launch("pose_scatter");
+}
+
+int naruto_pose_resolve(const float* est, const float* rel, uint32_t n, uint32_t keyframe_every, float* out, void* stream) {
+    if (est == nullptr || rel == nullptr || out == nullptr) return fail(NARUTO_ERR_INVALID, "pose_resolve: NULL argument");
+    if (n == 0u || keyframe_every == 0u) return fail(NARUTO_ERR_INVALID, "pose_resolve: n = %u frames, keyframe_every = %u", n, keyframe_every);
+    hipLaunchKernelGGL(k_pose_resolve, dim3((n + kPoseChainThreads - 1u) / kPoseChainThreads), dim3(kPoseChainThreads), 0, (hipStream_t)stream, est, rel, n,
+                       keyframe_every, out);
+    return check_launch("pose_resolve");
+}
+
 namespace {
 // NarutoRayBatch -> the kernels' argument block (need_out: the batch's own output buffers are written)
 int assemble_args(const NarutoRayBatch* b, bool need_out, AssembleArgs& a, const char* who) {
@@ -2920,6 +2963,12 @@ int naruto_debug_rodrigues(const double* w, const double* G, double* R, double* 
     if (w == nullptr || (d_w != nullptr && G == nullptr)) return fail(NARUTO_ERR_INVALID, "debug_rodrigues: NULL argument");
     if (R != nullptr) rodrigues(w, R);
     if (d_w != nullptr) rodrigues_vjp(w, G, d_w);
+    return NARUTO_OK;
+}
+
+int naruto_debug_pose_log(uint32_t P, const float* c2w, float* pose6) {
+    if (c2w == nullptr || pose6 == nullptr) return fail(NARUTO_ERR_INVALID, "debug_pose_log: NULL argument");
+    for (uint32_t p = 0; p < P; ++p) pose_log(c2w + 16 * (size_t)p, pose6 + 6 * (size_t)p);
     return NARUTO_OK;
 }
 

@@ -91,6 +91,78 @@ __host__ __device__ inline void track_write_c2w(float* c2w, const float p[6]) {
     c2w[12] = 0.0f; c2w[13] = 0.0f; c2w[14] = 0.0f; c2w[15] = 1.0f;
 }
 
+// ---- the pose chain's arithmetic (naruto_posechain.hip): [4,4] row-major camera-to-world matrices, fp32 in memory, fp64 in registers,
+// every result rounded to fp32 once
+
+__host__ __device__ inline void pose_load(const float* m, double M[16]) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) M[i] = (double)m[i];
+}
+
+__host__ __device__ inline void pose_store(float* m, const double M[16]) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) m[i] = (float)M[i];
+}
+
+// C = A @ B
+__host__ __device__ inline void pose_mul(const double A[16], const double B[16], double C[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s += A[4 * i + k] * B[4 * k + j];
+            C[4 * i + j] = s;
+        }
+}
+
+// the inverse of the affine map [A t; 0 0 0 1]: adj(A) / det(A), then -A^-1 t.  General: A need not be a rotation (a tracked or
+// refined pose is R(omega) rounded to fp32, and torch.linalg.inv, which this restates, does not assume one either)
+__host__ __device__ inline void pose_affine_inverse(const double M[16], double inv[16]) {
+    const double a = M[0], b = M[1], c = M[2], d = M[4], e = M[5], f = M[6], g = M[8], h = M[9], k = M[10];
+    const double c00 = e * k - f * h, c01 = c * h - b * k, c02 = b * f - c * e;
+    const double c10 = f * g - d * k, c11 = a * k - c * g, c12 = c * d - a * f;
+    const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
+    const double r = 1.0 / (a * c00 + b * c10 + c * c20);
+    const double A[9] = {c00 * r, c01 * r, c02 * r, c10 * r, c11 * r, c12 * r, c20 * r, c21 * r, c22 * r};
+    const double t[3] = {M[3], M[7], M[11]};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        inv[4 * i] = A[3 * i]; inv[4 * i + 1] = A[3 * i + 1]; inv[4 * i + 2] = A[3 * i + 2];
+        inv[4 * i + 3] = -(A[3 * i] * t[0] + A[3 * i + 1] * t[1] + A[3 * i + 2] * t[2]);
+    }
+    inv[12] = 0.0; inv[13] = 0.0; inv[14] = 0.0; inv[15] = 1.0;
+}
+
+// (omega, t) of a camera-to-world matrix: naruto_amd.tracking.matrices_to_pose6, branch for branch -- the unit quaternion through the
+// largest of 4w^2, 4x^2, 4y^2, 4z^2 (the first of equal ones), w >= 0 (angle in [0, pi]), omega = 2 atan2(|v|, w) v / |v|, and
+// 2 v / w below |v| = 1e-12
+__host__ __device__ inline void pose_log(const float* c2w, float pose6[6]) {
+    double M[16];
+    pose_load(c2w, M);
+    const double d0 = M[0], d1 = M[5], d2 = M[10];
+    const double cand[4] = {1.0 + d0 + d1 + d2, 1.0 + d0 - d1 - d2, 1.0 - d0 + d1 - d2, 1.0 - d0 - d1 + d2};
+    int br = 0;
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (cand[i] > cand[br]) br = i;
+    const double cb = cand[br] > 1e-300 ? cand[br] : 1e-300;
+    const double s = 2.0 * sqrt(cb), q4 = s / 4.0;
+    const double x = M[9] - M[6], y = M[2] - M[8], z = M[4] - M[1];
+    const double xy = M[1] + M[4], xz = M[2] + M[8], yz = M[6] + M[9];
+    double q[4];
+    if (br == 0)      { q[0] = q4;    q[1] = x / s;  q[2] = y / s;  q[3] = z / s;  }
+    else if (br == 1) { q[0] = x / s; q[1] = q4;     q[2] = xy / s; q[3] = xz / s; }
+    else if (br == 2) { q[0] = y / s; q[1] = xy / s; q[2] = q4;     q[3] = yz / s; }
+    else              { q[0] = z / s; q[1] = xz / s; q[2] = yz / s; q[3] = q4;     }
+    if (q[0] < 0.0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
+    const double n = sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double scale = n < 1e-12 ? 2.0 / q[0] : 2.0 * atan2(n, q[0]) / n;
+    pose6[0] = (float)(q[1] * scale); pose6[1] = (float)(q[2] * scale); pose6[2] = (float)(q[3] * scale);
+    pose6[3] = (float)M[3]; pose6[4] = (float)M[7]; pose6[5] = (float)M[11];
+}
+
 // torch.optim.Adam (single tensor, no weight decay, amsgrad off) on the six components of a pose, step number `step` (1-based): moments
 // in fp32, bias corrections in fp64; lr_rot for omega, lr_trans for t.  p, m, v are updated in place.
 __host__ __device__ inline void pose_adam_step(float p[6], const float g[6], float m[6], float v[6], int32_t step, float lr_rot, float lr_trans, float beta1,

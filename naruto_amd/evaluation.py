@@ -316,6 +316,29 @@ def trajectory_length(poses) -> float:
     return float(torch.linalg.norm(rel[:, :3, 3], dim=-1).sum())
 
 
+def ate(est, gt) -> Dict[str, float]:
+    """Absolute trajectory error of the estimated camera positions against the true ones after the best RIGID alignment (rotation and
+    translation, no scale): ``{"ate_rmse_cm", "ate_mean_cm"}``.  ``est`` / ``gt``: [N,4,4] camera-to-world poses (or [N,3] positions),
+    N >= 3, in metres.  Parity unpinned -- Co-SLAM's ``pose_evaluation`` is not in the reference tree; the contract: with e_i, g_i the
+    positions and their centroids removed, H = sum e_i g_i^T = U S V^T, R = V diag(1, 1, det(V U^T)) U^T (Horn / Kabsch with the
+    determinant correction: a rotation, never a reflection), t = mean(g) - R mean(e); the errors are |R e_i + t - g_i|, reported as
+    their root mean square and their mean, in centimetres.  fp64 numpy on the host, once per run (as ``trajectory_length``)."""
+    def positions(x):
+        a = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)).astype(np.float64)
+        return a[:, :3, 3] if a.ndim == 3 else a.reshape(-1, 3)
+    e, g = positions(est), positions(gt)
+    if e.shape != g.shape:
+        raise ValueError(f"ate: {e.shape[0]} estimated poses against {g.shape[0]} true ones")
+    if e.shape[0] < 3:
+        raise ValueError(f"ate: a rigid alignment needs at least 3 poses, got {e.shape[0]}")
+    ce, cg = e.mean(0), g.mean(0)
+    U, _, Vt = np.linalg.svd((e - ce).T @ (g - cg))
+    D = np.diag([1.0, 1.0, float(np.sign(np.linalg.det(Vt.T @ U.T))) or 1.0])
+    R = Vt.T @ D @ U.T
+    err = np.linalg.norm((e - ce) @ R.T + cg - g, axis=1)
+    return {"ate_rmse_cm": float(np.sqrt((err * err).mean()) * 100.0), "ate_mean_cm": float(err.mean() * 100.0)}
+
+
 def update_results_file(results: Dict[str, float], file_path: str) -> None:
     """``key,value`` lines; keys already in the file are updated in place, new ones appended (general_utils.py:163-188's format)."""
     merged: Dict[str, float] = {}

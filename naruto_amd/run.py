@@ -10,14 +10,16 @@ pose of step i is the trajectory's and the planner is skipped.
 Command line::
 
     python -m naruto_amd.run --config <coslam.yaml> --mesh <scene.ply> --num_iter N --result_dir D [--start x y z] [--traj traj.txt]
-                             [--no_active_ray] [--seed S] [--planner key=value ...]
+                             [--no_active_ray] [--seed S] [--track] [--planner key=value ...]
 
 ``--config`` is a Co-SLAM yaml (``naruto_amd.config.load_config``).  The reference's ``.py`` config files are not read: the planner's
 settings are ``naruto_amd.planner.DEFAULTS`` (the values of the reference's configs/default.py, restated as data) with ``--planner
 key=value`` overrides, and the SLAM keywords (voxel size 0.1, 500 active rays out of a 4x oversampled batch) are ``CoSLAMNarutoHIP``'s
 defaults.  ``--traj`` reads a Replica trajectory file: sixteen numbers per line, camera-to-world row-major, columns 1 and 2 of the
 rotation negated as the reference's ``load_Replica_pose`` does.  The run's trajectory length goes to ``<result_dir>/results.txt`` as
-``traj_len(m),<value>`` (``evaluation.update_results_file``'s format).
+``traj_len(m),<value>`` (``evaluation.update_results_file``'s format).  ``--track`` estimates the camera poses during the run
+(``CoSLAMNarutoHIP(track=True)``) and adds ``ate_rmse(cm)`` / ``ate_mean(cm)``: the estimated trajectory against the poses the frames were
+taken at (``evaluation.ate``).
 """
 
 from __future__ import annotations
@@ -59,7 +61,9 @@ def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optio
     Returns ``poses`` [num_iter,4,4] (the pose each frame was taken at), ``states`` (the planner's state after each step), ``fresh``
     (the steps that produced new volumes), ``timing`` {phase: {"total_s", "calls", "mean_s"}} from host timers around each phase (the
     SLAM phase ends with whatever the step waited for, not with a device synchronisation), ``mesh`` and ``ckpt_path`` of the final
-    save."""
+    save.  When ``slam`` tracks (``CoSLAMNarutoHIP(track=True)``): also ``est_poses`` [num_iter,4,4] (``slam.resolved_poses()``, on the
+    host) and ``ate`` (``evaluation.ate(est_poses, poses)``; None below 3 steps).  The planner keeps receiving the COMMANDED pose, the
+    one the frame was rendered at, not the estimate -- as the reference's loop does (main.py:135-137)."""
     if planner is None and traj is None:
         raise ValueError("run_exploration: a planner or a predefined trajectory")
     if traj is not None and len(traj) < num_iter:
@@ -97,8 +101,13 @@ def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optio
     mesh = slam.save_mesh(int(num_iter), voxel_size=slam.config["mesh"]["voxel_final"], suffix="_final")
     ckpt_path = slam.save_ckpt(int(num_iter), suffix="_final") if slam.result_dir is not None else None
     timing = {k: {"total_s": t, "calls": n, "mean_s": t / n if n else 0.0} for k, (t, n) in spent.items()}
-    return {"poses": torch.stack(poses) if poses else torch.zeros(0, 4, 4), "states": states, "fresh": fresh, "timing": timing, "mesh": mesh,
-            "ckpt_path": ckpt_path}
+    out = {"poses": torch.stack(poses) if poses else torch.zeros(0, 4, 4), "states": states, "fresh": fresh, "timing": timing, "mesh": mesh,
+           "ckpt_path": ckpt_path}
+    if getattr(slam, "track", False):
+        from .evaluation import ate
+        out["est_poses"] = slam.resolved_poses().cpu()
+        out["ate"] = ate(out["est_poses"], out["poses"]) if len(poses) >= 3 else None
+    return out
 
 
 def _planner_overrides(items: List[str]) -> Dict:
@@ -125,6 +134,7 @@ def parse_args(argv=None):
     parser.add_argument("--traj", type=str, help="predefined Replica trajectory (passive mapping: the planner is skipped)")
     parser.add_argument("--no_active_ray", action="store_true", help="switch the active ray sampler off")
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--track", action="store_true", help="estimate the camera poses during the run (tracking + pose refinement); adds the ATE to results.txt")
     parser.add_argument("--dataset", type=str, default="NARUTO", choices=["Replica", "MP3D", "NARUTO"], help="the planner's collision rule")
     parser.add_argument("--planner", type=str, nargs="*", default=[], metavar="KEY=VALUE", help="planner settings over naruto_amd.planner.DEFAULTS")
     args = parser.parse_args(argv)
@@ -152,7 +162,7 @@ def main(argv=None) -> Dict:
     traj = load_replica_traj(args.traj) if args.traj else None
     np.random.seed(args.seed)                      # the planner's RRT draws from numpy's generator
     os.makedirs(args.result_dir, exist_ok=True)
-    slam = CoSLAMNarutoHIP(cfg, active_ray=not args.no_active_ray, num_frames=args.num_iter, seed=args.seed, result_dir=args.result_dir)
+    slam = CoSLAMNarutoHIP(cfg, active_ray=not args.no_active_ray, num_frames=args.num_iter, seed=args.seed, result_dir=args.result_dir, track=args.track)
     sim = MeshSimHIP(args.mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=slam.device)
     planner = None
     if traj is None:
@@ -164,7 +174,10 @@ def main(argv=None) -> Dict:
     start[:3, 3] = torch.tensor(args.start if args.start is not None else [0.5 * (b[0] + b[1]) for b in cfg["mapping"]["bound"]])
     out = run_exploration(slam, sim, planner, start, args.num_iter, traj=traj)
     length = trajectory_length(out["poses"])
-    update_results_file({"traj_len(m)": length}, os.path.join(args.result_dir, "results.txt"))
+    results = {"traj_len(m)": length}
+    if out.get("ate") is not None:
+        results.update({"ate_rmse(cm)": out["ate"]["ate_rmse_cm"], "ate_mean(cm)": out["ate"]["ate_mean_cm"]})
+    update_results_file(results, os.path.join(args.result_dir, "results.txt"))
     torch.cuda.synchronize(slam.device)
     for k, v in out["timing"].items():
         print(f"{k}: {v['total_s']:.3f} s over {v['calls']} calls")

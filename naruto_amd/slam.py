@@ -15,7 +15,7 @@ PARITY UNPINNED.  ``CoSLAMNaruto`` inherits from Co-SLAM's ``CoSLAM`` and uses i
       2. frame 0: ``est_c2w_data[0] = c2w``; ``mapping.first_iters`` iterations of first-frame mapping (coslam.py:197-219:
          ``mapping.sample`` distinct pixels out of all H*W per iteration, no smoothness term, the network's Adam every iteration, the
          uncertainty grid's gradient zeroed once, stepped once at the end and kept); frame 0 becomes a keyframe; map volumes;
-      3. any other frame: ``est_c2w_data[i] = c2w`` (``tracking.disable``; see below);
+      3. any other frame: ``est_c2w_data[i] = c2w`` (``tracking.disable``), or the frame is tracked (``track=True``; see below);
       4. when ``i % mapping.map_every == 0``: ``global_BA`` over the keyframes stored BEFORE this frame, with the poses
          ``est_c2w_data[0, keyframe_every, ... < i]`` and the current one last (coslam.py:259-267), AND THEN the map volumes;
       5. when ``i % mapping.keyframe_every == 0``: the frame becomes a keyframe (``mapping.filter_depth`` as configured);
@@ -35,9 +35,26 @@ What differs on purpose:
   * a frame that neither maps nor becomes a keyframe launches nothing.  A mapped frame waits once for the host: the 8-byte count of
     valid-depth pixels, which sizes the current-frame draw (the reference filters on the host at the same place, coslam.py:322-325).
 
-Out of scope: camera tracking and pose refinement inside ``global_BA`` (``tracking.disable: False``).  The pieces exist
-(``naruto_amd.tracking.TrackerHIP``, ``FusedBA(optimize_poses=True)``); wiring them in here is the follow-up, and the constructor raises
-``NotImplementedError`` for such a config.  Every shipped config has ``tracking.disable: True``.
+CAMERA TRACKING (``CoSLAMNarutoHIP(..., track=True)``; the reference's ``tracking.disable: False`` branch, coslam.py:595-602, 264-281,
+378-407; Co-SLAM's ``predict_current_pose``, ``tracking_render`` and ``convert_relative_pose`` are not in the reference tree: parity
+unpinned, restated in ``naruto_amd.tracking`` and ``naruto_amd.pose_chain``).  The ``c2w`` argument is used for frame 0 only.  Every
+other frame i, in the reference's order:
+
+  1. ``pose_predict``: ``est[i]`` <- the constant-speed prediction (``tracking.const_speed``), and its (omega, t) into the tracker;
+  2. ``TrackerHIP.track_device``: the frame into the tracker's buffers, one replay of its captured call;
+  3. ``pose_commit``: ``est[i]`` <- the tracked pose, ``rel[i] = est[i] @ inv(est[kf(i)])`` for a frame that is no keyframe;
+  4. on a mapped frame: ``global_BA`` refining the keyframe poses (``FusedBA(optimize_poses=True)``, the initial (omega, t) from
+     ``naruto_pose_log`` on the device), ``pose_scatter`` writing ``ba.poses`` back to ``est`` (coslam.py:401-407), the map volumes;
+  5. the keyframe add.
+
+All pose arithmetic runs on the device (csrc/naruto_posechain.hip): a tracked frame that does not map never waits for the host, a
+mapped one waits once, for the same 8-byte count as without tracking.  ``resolved_poses()`` gives every frame's pose relative to its
+(refined) keyframe; ``save_ckpt`` writes the raw ``pose`` / ``pose_rel`` as the reference does.  The tracker is captured once, at the end
+of frame 0, and keeps its own random word (derived from ``seed``).  ``track=False`` is the object without any of this, launch for launch.
+
+A config with ``tracking.disable: False`` and no ``track=True`` is refused (``NotImplementedError``) before the library is touched:
+tracking is switched on by the keyword, whatever ``tracking.disable`` says.  Out of scope: ``tracking.iter_point > 0`` (``tracking_pc``),
+other ``training.rot_rep`` (both refused by ``tracking.tracking_settings``), data-parallel pose refinement.
 """
 
 from __future__ import annotations
@@ -49,10 +66,11 @@ from typing import Dict, Iterator, List, Optional
 import torch
 
 from .active_ray_sampler import ActiveRaySamplerHIP
-from .ba_loop import FusedBA
+from .ba_loop import FusedBA, _no_collection
 from .field import _map_lattice, get_map_volumes
 from .keyframe_store import KeyFrameStoreHIP, frame_ingest
 from .mesh import extract_mesh
+from .pose_chain import pose_commit, pose_log, pose_predict, pose_resolve, pose_scatter
 from .trainer import MappingTrainer
 
 
@@ -95,6 +113,10 @@ class DevicePoses:
     def __len__(self) -> int:
         return sum(self._have)
 
+    def mark(self, i: int) -> None:
+        """Row ``i`` of ``tensor`` was written on the device (``naruto_amd.pose_chain``): it counts as set."""
+        self._have[int(i)] = True
+
     def keys(self) -> Iterator[int]:
         return (i for i, h in enumerate(self._have) if h)
 
@@ -106,16 +128,23 @@ class DevicePoses:
 
 class CoSLAMNarutoHIP:
     def __init__(self, config: Dict, voxel_size: float = 0.1, active_ray: Optional[bool] = None, act_ray_num_uncert_sample: int = 500,
-                 act_ray_oversample_mul: int = 4, num_frames: int = 2000, seed: Optional[int] = 0, result_dir: Optional[str] = None, device="cuda"):
+                 act_ray_oversample_mul: int = 4, num_frames: int = 2000, seed: Optional[int] = 0, result_dir: Optional[str] = None, device="cuda",
+                 track: bool = False):
         """``config``: a Co-SLAM config (``naruto_amd.config.load_config``); it is kept and, as in the reference's ``override_config``,
         ``mapping.active_ray`` is overwritten when ``active_ray`` is given.  ``num_frames``: the length of the run (sizes the keyframe store
         and the pose tensor).  ``seed``: keys the keyframe store's draws and, through ``torch.manual_seed`` (None: left alone), the
         network's initial values and the trainer's in-kernel random streams.  ``result_dir``: meshes and checkpoints go under
-        ``<result_dir>/coslam`` (None: ``save_*`` need an explicit directory)."""
+        ``<result_dir>/coslam`` (None: ``save_*`` need an explicit directory).  ``track``: estimate the camera poses during the run
+        (module docstring) with ``tracking_settings(config)``, whatever ``tracking.disable`` says."""
         tk = config.get("tracking") or {}
-        if not bool(tk.get("disable", True)):
-            raise NotImplementedError("CoSLAMNarutoHIP: tracking.disable: False (camera tracking and pose refinement during the run) is not wired in; "
-                                      "the pieces are naruto_amd.tracking.TrackerHIP and FusedBA(optimize_poses=True)")
+        self.track = bool(track)
+        if not self.track and not bool(tk.get("disable", True)):
+            raise NotImplementedError("CoSLAMNarutoHIP: tracking.disable: False asks for camera tracking and pose refinement during the run; they are "
+                                      "switched on by the keyword track=True (naruto_amd.tracking.TrackerHIP, FusedBA(optimize_poses=True)), not by the config")
+        self.tracking = None
+        if self.track:
+            from .tracking import tracking_settings
+            self.tracking = tracking_settings(config)          # refuses iter_point > 0 and other rot_rep, before anything is built
         self.config = config
         if active_ray is not None:
             config["mapping"]["active_ray"] = bool(active_ray)
@@ -145,7 +174,12 @@ class CoSLAMNarutoHIP:
                 raise ValueError(f"CoSLAMNarutoHIP: act_ray_num_uncert_sample = {act_ray_num_uncert_sample} active rays do not fit a batch of "
                                  f"mapping.sample = {mp['sample']} rays")
             self.active_ray_sampler = ActiveRaySamplerHIP(config=config, num_uncert_sample=act_ray_num_uncert_sample, oversample_mul=act_ray_oversample_mul)
-        self.ba = FusedBA(self.trainer, self.keyframeDatabase, self.active_ray_sampler, max_poses=num_kf + 1)
+        self.ba = FusedBA(self.trainer, self.keyframeDatabase, self.active_ray_sampler, max_poses=num_kf + 1, optimize_poses=True if self.track else None)
+        self.tracker = None
+        if self.track:
+            from .tracking import TrackerHIP
+            # the tracker's own random word: the seed's, moved off the keyframe store's and the trainer's streams
+            self.tracker = TrackerHIP(self.model, config, self.H, self.W, device=self.device, rng_seed=(int(seed or 0) * 0x9E3779B1 + 0x7F4A7C15) % (1 << 62))
         self.cached_uncert = None
         self.filter_depth = bool(mp.get("filter_depth", False))
         self._n_valid = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -176,6 +210,46 @@ class CoSLAMNarutoHIP:
         self._n_valid_event.synchronize()
         return int(self._n_valid_host[0])
 
+    def _capture_tracker(self, color: torch.Tensor, depth: torch.Tensor) -> None:
+        """End of frame 0: the tracker's call recorded as one graph, warmed up on frame 0 itself from its own pose (the warm-up and the
+        capture put the tracker's random word back; ``est`` is not touched)."""
+        tr = self.tracker
+        with torch.no_grad():
+            tr.direction.copy_(self.rays_d)
+            tr.rgb.copy_(color.to(self.device, torch.float32))
+            tr.depth.copy_(depth.to(self.device, torch.float32))
+        pose_log(self.est_c2w_data.tensor[0], out=tr.pose_init)
+        with _no_collection():
+            tr.capture()
+
+    def _track(self, i: int, color: torch.Tensor, depth: torch.Tensor, every: int):
+        """Frame ``i > 0`` of a tracked run: predict, track, commit (module docstring) -- launches only.  Returns the frame as the
+        float32 device tensors the tracker took."""
+        color = color.to(self.device, torch.float32).contiguous()
+        depth = depth.to(self.device, torch.float32).contiguous()
+        est, rel = self.est_c2w_data, self.est_c2w_data_rel
+        if (i - 1) not in est or (i % every != 0 and (i // every) * every not in est):
+            raise KeyError(f"CoSLAMNarutoHIP: frame {i} is tracked from frame {i - 1} (and stored relative to keyframe {(i // every) * every}); "
+                           "step the frames in order")
+        pose_predict(est.tensor, i, bool(self.tracking["const_speed"]), self.tracker.pose_init)
+        tracked = self.tracker.track_device(self.rays_d, color, depth)
+        pose_commit(est.tensor, rel.tensor, i, every, tracked)
+        est.mark(i)
+        if i % every != 0:
+            rel.mark(i)
+        return color, depth
+
+    def resolved_poses(self) -> torch.Tensor:
+        """Co-SLAM's ``convert_relative_pose`` over the frames stepped so far, [n,4,4] float32 on the device: a keyframe's pose as it
+        stands (refined by the ``global_BA`` calls since), any other frame's relative pose applied to its keyframe's
+        (``naruto_pose_resolve``).  Without tracking: the poses given."""
+        n = max((k for k in self.est_c2w_data.keys()), default=-1) + 1
+        if n == 0:
+            return torch.zeros(0, 4, 4, dtype=torch.float32, device=self.device)
+        if not self.track:
+            return self.est_c2w_data.tensor[:n].clone()
+        return pose_resolve(self.est_c2w_data.tensor, self.est_c2w_data_rel.tensor, n, int(self.config["mapping"]["keyframe_every"]))
+
     def _volumes(self) -> List[torch.Tensor]:
         return get_map_volumes(self.model.query_sdf, self.bounding_box, self.voxel_size, to_host=False, out=self._vols)
 
@@ -197,16 +271,27 @@ class CoSLAMNarutoHIP:
                 n_valid = self._read_n_valid() if self.filter_depth else None
                 self.keyframeDatabase.add_keyframe_device(self.ba.current, i, self.filter_depth, self._n_valid, n_valid_host=n_valid)
                 vols = self._volumes()
+                if self.track:
+                    self._capture_tracker(color, depth)
             else:
-                self.est_c2w_data[i] = c2w
+                every = int(mp["keyframe_every"])
+                if self.track:
+                    color, depth = self._track(i, color, depth, every)
+                else:
+                    self.est_c2w_data[i] = c2w
                 if todo["map"] or todo["keyframe"]:
                     self._ingest(color, depth)
                 n_valid = None
                 if todo["map"]:
                     n_valid = self._read_n_valid() if self.filter_depth else None
-                    every = int(mp["keyframe_every"])
                     poses_all = torch.cat([self.est_c2w_data.tensor[0:i:every], self.est_c2w_data.tensor[i:i + 1]], 0)
-                    self.ba.global_BA(None, poses_all, uncert_vol=self.cached_uncert if self.active_ray_sampler is not None else None, n_valid=n_valid)
+                    uncert = self.cached_uncert if self.active_ray_sampler is not None else None
+                    if self.track:
+                        self.ba.global_BA(None, poses_all, uncert_vol=uncert, n_valid=n_valid, optimize_poses=True, pose_init_on_device=True)
+                        if self.ba._pose_on:               # coslam.py:401-407: a call that refined poses writes them back
+                            pose_scatter(self.est_c2w_data.tensor, self.ba.poses, poses_all.shape[0], every, i, bool(mp.get("optim_cur", True)))
+                    else:
+                        self.ba.global_BA(None, poses_all, uncert_vol=uncert, n_valid=n_valid)
                     vols = self._volumes()
                 if todo["keyframe"]:
                     self.keyframeDatabase.add_keyframe_device(self.ba.current, i, self.filter_depth, self._n_valid, n_valid_host=n_valid)

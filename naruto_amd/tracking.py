@@ -155,7 +155,9 @@ class TrackerHIP:
 
     ``track(direction, rgb, depth, init_c2w, rand=None)``: the frame's camera-frame ray directions, colours and depths
     (``[H,W,3] [H,W,3] [H,W]`` float32 on the device) and the initial camera-to-world pose [4,4]; returns the tracked pose [4,4].
-    ``rand`` [iter, N, S]: each iteration's depth jitter instead of the device's own draw."""
+    ``rand`` [iter, N, S]: each iteration's depth jitter instead of the device's own draw.  ``track`` converts the initial pose on the host
+    (one wait per call); ``track_device`` takes it from ``pose_init`` on the device, where the run loop's pose chain puts it
+    (``naruto_amd.pose_chain``, ``CoSLAMNarutoHIP(track=True)``)."""
 
     def __init__(self, model, config: Dict, H: int, W: int, device=None, rng_seed: Optional[int] = None):
         self.tk = tk = tracking_settings(config)
@@ -264,6 +266,22 @@ class TrackerHIP:
             else:
                 self._run(rand)
         return self.c2w.clone()
+
+    def track_device(self, direction, rgb, depth) -> torch.Tensor:
+        """One frame whose initial pose is ALREADY in ``self.pose_init`` as (omega, t) -- ``pose_chain.pose_predict(est, i, const_speed,
+        tracker.pose_init)`` wrote it on the device: only the frame is copied, then the captured call is replayed (or run).  Nothing
+        goes to the host.  Returns ``self.c2w`` itself, the [4,4] buffer the next call overwrites (``pose_chain.pose_commit`` reads it on
+        the same stream)."""
+        check_frame(direction, rgb, depth, self.H, self.W)
+        with torch.no_grad():
+            self.direction.copy_(direction)
+            self.rgb.copy_(rgb)
+            self.depth.copy_(depth)
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self._run(None)
+        return self.c2w
 
     def capture(self, warmup: int = 1):
         """Record one call (draw, iteration 0's rays, ``iter`` iterations; no parallel branches) as ONE hipGraph.  Later ``track``
