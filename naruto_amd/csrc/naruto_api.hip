@@ -6,7 +6,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <mutex>
 #include <new>
+#include <unordered_set>
 #include <vector>
 
 #include "naruto_field.hip"
@@ -78,6 +80,16 @@ int check_points(const NarutoPoints* pts) {
     if (pts->x == nullptr && (pts->rays_o == nullptr || pts->rays_d == nullptr || pts->z_vals == nullptr || pts->n_samples == 0))
         return fail(NARUTO_ERR_INVALID, "points: give x, or rays_o + rays_d + z_vals + n_samples");
     return NARUTO_OK;
+}
+
+// The parameter tensors an entry point reads must be there: the encoding (table, uncertainty grid), the SDF net, the colour net.  `what` is the
+// refusal's text after "<who>: ".
+constexpr uint32_t kParamsEncoding = 1u, kParamsSdf = 2u, kParamsColour = 4u, kParamsAll = 7u;
+int check_params(const NarutoParams* p, const char* who, uint32_t need = kParamsAll, const char* what = "NULL parameter") {
+    const bool missing = ((need & kParamsEncoding) != 0u && (p->table == nullptr || p->uncert_grid == nullptr)) ||
+                         ((need & kParamsSdf) != 0u && (p->sdf_w0 == nullptr || p->sdf_w1 == nullptr)) ||
+                         ((need & kParamsColour) != 0u && (p->col_w0 == nullptr || p->col_w1 == nullptr));
+    return missing ? fail(NARUTO_ERR_INVALID, "%s: %s", who, what) : NARUTO_OK;
 }
 
 uint32_t cu_count(const NarutoField* f) { return f->n_cu > 0 ? (uint32_t)f->n_cu : 256u; }
@@ -708,12 +720,13 @@ extern "C" {
 int naruto_query_fwd(const NarutoField* f, const NarutoParams* p, uint32_t M, const NarutoPoints* pts, float* raw, float* sdf_uncert,
                      float* geo, float* feat_save, void* stream) {
     if (f == nullptr || p == nullptr) return fail(NARUTO_ERR_INVALID, "query_fwd: NULL argument");
-    if (p->table == nullptr || p->uncert_grid == nullptr || p->sdf_w0 == nullptr || p->sdf_w1 == nullptr)
-        return fail(NARUTO_ERR_INVALID, "query_fwd: NULL parameter");
+    if (int rc = check_params(p, "query_fwd", kParamsEncoding | kParamsSdf)) return rc;
     if (M == 0) return NARUTO_OK;                     // empty batch: its (NULL) point pointers are not an error
     if (int rc = check_points(pts)) return rc;
     const bool color = raw != nullptr;
-    if (color && (p->col_w0 == nullptr || p->col_w1 == nullptr)) return fail(NARUTO_ERR_INVALID, "query_fwd: colour net parameters missing");
+    if (color) {
+        if (int rc = check_params(p, "query_fwd", kParamsColour, "colour net parameters missing")) return rc;
+    }
     if (!color && sdf_uncert == nullptr && geo == nullptr && feat_save == nullptr) return fail(NARUTO_ERR_INVALID, "query_fwd: no output requested");
     if (feat_save != nullptr && M > (1u << 29)) return fail(NARUTO_ERR_INVALID, "query_fwd: feat_save is addressed with 32-bit byte offsets: at most 2^29 points per call");
     NarutoParams pp = *p;
@@ -734,30 +747,53 @@ BwdWs bwd_ws(const NarutoField* f, void* workspace, uint32_t cap) {
             c.take<float>((size_t)kBwdMaxBlocks * kAccFloats * sizeof(float), 1u), c.take<float>(naruto_scatter_workspace(f, cap), 1u), c.take<uint32_t>(64u, 1u), c.size()};
 }
 
-// n_front > 0 (fused training path): list positions [0, n_front) were filled by the caller (smoothness lattice: points
-// and weighted feature cotangents), this launch's points follow; n_list_dev = device word holding n_front + n_active.
-int query_bwd_impl(const NarutoField* f, const NarutoParams* p, uint32_t M, const NarutoPoints* pts, const float* feat_save,
-                   const float* d_raw, const float* d_geo, const uint32_t* active_idx, const uint32_t* n_active, const NarutoExtraPoints* extra,
-                   uint32_t flags, const NarutoGrads* g, void* workspace, void* stream, uint32_t n_front, const uint32_t* n_list_dev,
-                   const AdamFuse* adam = nullptr, const void* w_img = nullptr, const TvLate* tv_late = nullptr, const AssembleArgs* next = nullptr,
-                   bool feat_sample_major = false) {
-    // (feat_sample_major: feat_save is [M][16][2] -- the Morton-ordered forward of the large tables wrote it, see naruto_sorted.hip)
-    const uint32_t feat_M = feat_sample_major ? 1u : M, feat_mul = feat_sample_major ? (uint32_t)kLevels : 1u;
-    if ((active_idx == nullptr) != (n_active == nullptr)) return fail(NARUTO_ERR_INVALID, "query_bwd: active_idx and n_active go together");
-    if (n_front > 0 && (extra != nullptr || n_list_dev == nullptr)) return fail(NARUTO_ERR_INVALID, "query_bwd: front list excludes extra points");
-    const uint32_t E = n_front > 0 ? n_front : ((extra != nullptr && g != nullptr && g->table != nullptr) ? extra->n : 0u);
-    if (n_front == 0 && E > 0 && (extra->x == nullptr || extra->d_feat == nullptr)) return fail(NARUTO_ERR_INVALID, "query_bwd: extra points need x and d_feat");
+// the scatter's point list as a point source: x [3][cap] in the query backward's workspace (BwdWs.x_soa), one "sample" per point
+PointSrc list_points(const float* x_soa, uint32_t cap) {
+    PointSrc ps{};
+    ps.xsoa = x_soa;
+    ps.M = cap;
+    ps.S = 1;
+    return ps;
+}
+
+// What a query backward is given besides the field and the parameters.  naruto_query_bwd fills the public call's arguments; the rest is the fused
+// training path (naruto_train_backward) and stays zero otherwise.
+struct QueryBwd {
+    uint32_t M;
+    const NarutoPoints* pts;
+    const float* feat_save; const float* d_raw; const float* d_geo;
+    const uint32_t* active_idx; const uint32_t* n_active;
+    const NarutoExtraPoints* extra;
+    uint32_t flags;
+    const NarutoGrads* g;
+    void* workspace;
+    hipStream_t stream;
+    // n_front > 0: list positions [0, n_front) were filled by the caller (smoothness lattice: points and weighted feature cotangents), this
+    // launch's points follow; n_list_dev = device word holding n_front + n_active
+    uint32_t n_front;
+    const uint32_t* n_list_dev;
+    const AdamFuse* adam;           // the optimiser steps in the launch that finishes the gradients
+    const void* w_img;              // the MLP backward's weight images, prepared by k_loss_bwd_fused
+    const TvLate* tv_late;          // the moved smoothness term's value lands in the losses with that launch (needs adam)
+    const AssembleArgs* next;       // ... which also assembles the next iteration's ray batch (needs adam)
+    bool feat_sample_major;         // feat_save is [M][16][2] -- the Morton-ordered forward of the large tables wrote it, see naruto_sorted.hip
+};
+int query_bwd_impl(const NarutoField* f, const NarutoParams* p, const QueryBwd& q) {
+    const uint32_t M = q.M, n_front = q.n_front;
+    const NarutoGrads* g = q.g;
+    const hipStream_t st = q.stream;
+    const uint32_t feat_M = q.feat_sample_major ? 1u : M, feat_mul = q.feat_sample_major ? (uint32_t)kLevels : 1u;
+    if ((q.active_idx == nullptr) != (q.n_active == nullptr)) return fail(NARUTO_ERR_INVALID, "query_bwd: active_idx and n_active go together");
+    if (n_front > 0 && (q.extra != nullptr || q.n_list_dev == nullptr)) return fail(NARUTO_ERR_INVALID, "query_bwd: front list excludes extra points");
+    const uint32_t E = n_front > 0 ? n_front : ((q.extra != nullptr && g != nullptr && g->table != nullptr) ? q.extra->n : 0u);
+    if (n_front == 0 && E > 0 && (q.extra->x == nullptr || q.extra->d_feat == nullptr)) return fail(NARUTO_ERR_INVALID, "query_bwd: extra points need x and d_feat");
     const uint32_t cap = list_cap(M + E);            // leading dimension of the scatter's point list
-    if (f == nullptr || p == nullptr || g == nullptr || feat_save == nullptr || d_raw == nullptr || workspace == nullptr)
+    if (f == nullptr || p == nullptr || g == nullptr || q.feat_save == nullptr || q.d_raw == nullptr || q.workspace == nullptr)
         return fail(NARUTO_ERR_INVALID, "query_bwd: NULL argument");
-    if (p->table == nullptr || p->uncert_grid == nullptr || p->sdf_w0 == nullptr || p->sdf_w1 == nullptr || p->col_w0 == nullptr || p->col_w1 == nullptr)
-        return fail(NARUTO_ERR_INVALID, "query_bwd: NULL parameter");
+    if (int rc = check_params(p, "query_bwd")) return rc;
     if (M == 0) return NARUTO_OK;
-    if (int rc = check_points(pts)) return rc;
-    const BwdWs w = bwd_ws(f, workspace, cap);
-    float* d_feat = w.d_feat; float* x_soa = w.x_soa; float* partials = w.partials; float* scatter_ws = w.scatter_ws;
-    void* scatter_ws_ptr = w.scatter_ws;
-    uint32_t* n_total = w.n_total;
+    if (int rc = check_points(q.pts)) return rc;
+    const BwdWs w = bwd_ws(f, q.workspace, cap);
     const bool bf = f->desc.mlp_mode == NARUTO_MLP_BF16;
     const uint32_t n_tiles = bf ? (M + 63u) / 64u : (M + 31u) / 32u;
     const uint32_t waves = bf ? 4u : (uint32_t)kBwdWaves;
@@ -767,95 +803,75 @@ int query_bwd_impl(const NarutoField* f, const NarutoParams* p, uint32_t M, cons
     static const int dbg_blocks = env_int("NARUTO_DEBUG_BWD_BLOCKS", 0);       // profiling knob
     if (dbg_blocks > 0 && (uint32_t)dbg_blocks < max_blocks) max_blocks = (uint32_t)dbg_blocks;
     if (blocks > max_blocks) blocks = max_blocks;
-    const PointSrc ps = make_points(pts);
+    const PointSrc ps = make_points(q.pts);
     static bool attr_set = false;
     if (int rc = reserve_lds(attr_set, {lds_use(k_query_bwd, sizeof(BwdLds)), lds_use(k_query_bwd_bf, kBwdBfLdsBytes)}, "query_bwd: cannot reserve %zu bytes of LDS", sizeof(BwdLds)))
         return rc;
     // the uncertainty grid's gradient: through the scatter (row 3 of the point list) unless the grid is too large for that
     const bool unc_scatter = g->uncert_grid != nullptr && f->plan.n_uncert != 0;
     const int unc_atomic = (g->uncert_grid != nullptr && f->plan.n_uncert == 0) ? 1 : 0;
-    const float* unc_g = unc_scatter ? x_soa + 3u * (size_t)cap : nullptr;
+    const float* unc_g = unc_scatter ? w.x_soa + 3u * (size_t)cap : nullptr;
     float* d_unc = unc_scatter ? g->uncert_grid : nullptr;
-    float* x_list = (g->table != nullptr || adam != nullptr || unc_scatter) ? x_soa : nullptr;
-    const bool phase_mlp = (flags & NARUTO_TRAIN_BWD_TABLE_ONLY) == 0u;        // phases: see naruto_train_backward
-    const bool phase_table = (flags & NARUTO_TRAIN_BWD_MLP_ONLY) == 0u;
+    float* x_list = (g->table != nullptr || q.adam != nullptr || unc_scatter) ? w.x_soa : nullptr;
+    const bool phase_mlp = (q.flags & NARUTO_TRAIN_BWD_TABLE_ONLY) == 0u;        // phases: see naruto_train_backward
+    const bool phase_table = (q.flags & NARUTO_TRAIN_BWD_MLP_ONLY) == 0u;
     if (!phase_mlp) { /* the point list, d_feat and the wgrad partials are those of the preceding MLP-only call */ }
     else if (bf)
-        hipLaunchKernelGGL(k_query_bwd_bf, dim3(blocks), dim3(256), kBwdBfLdsBytes, (hipStream_t)stream, f->lt, f->ut, f->bt, *p, ps, M, cap, feat_save, d_raw,
-                           d_geo, d_feat, x_list, g->uncert_grid, partials, active_idx, n_active, n_front, unc_atomic, w_img, feat_M, feat_mul);
+        hipLaunchKernelGGL(k_query_bwd_bf, dim3(blocks), dim3(256), kBwdBfLdsBytes, st, f->lt, f->ut, f->bt, *p, ps, M, cap, q.feat_save, q.d_raw,
+                           q.d_geo, w.d_feat, x_list, g->uncert_grid, w.partials, q.active_idx, q.n_active, n_front, unc_atomic, q.w_img, feat_M, feat_mul);
     else
-        hipLaunchKernelGGL(k_query_bwd, dim3(blocks), dim3(64 * kBwdWaves), sizeof(BwdLds), (hipStream_t)stream, f->lt, f->ut, f->bt, *p, ps, M, cap, feat_save, d_raw,
-                           d_geo, d_feat, x_list, g->uncert_grid, partials, active_idx, n_active, n_front, unc_atomic, w_img, feat_M, feat_mul);
+        hipLaunchKernelGGL(k_query_bwd, dim3(blocks), dim3(64 * kBwdWaves), sizeof(BwdLds), st, f->lt, f->ut, f->bt, *p, ps, M, cap, q.feat_save, q.d_raw,
+                           q.d_geo, w.d_feat, x_list, g->uncert_grid, w.partials, q.active_idx, q.n_active, n_front, unc_atomic, q.w_img, feat_M, feat_mul);
     if (int rc = check_launch("query_bwd")) return rc;
-    if (adam != nullptr) {
+    const PointSrc pss = list_points(w.x_soa, cap);
+    if (q.adam != nullptr) {
         if (!phase_mlp || !phase_table) return fail(NARUTO_ERR_INVALID, "query_bwd: the fused optimiser runs the backward in one piece");
         // optimiser in the backward: the tiled scatter without its reduce, then ONE launch finishes the tiled levels' table
         // gradient + the weight gradients and steps them; the binned scatter's last kernel steps the larger levels itself
-        PointSrc pss{};
-        pss.xsoa = x_soa;
-        pss.M = cap;
-        pss.S = 1;
-        const uint32_t* cnt = n_front > 0 ? n_list_dev : n_active;
-        if (int rc = launch_scatter(f, pss, cnt != nullptr ? cap : M, d_feat, (size_t)2, (size_t)2 * (size_t)cap, g->table, scatter_ws, (hipStream_t)stream, cnt,
-                                    nullptr, 1, false, adam, unc_g, d_unc, n_front))
+        const uint32_t* cnt = n_front > 0 ? q.n_list_dev : q.n_active;
+        const uint32_t Ml = cnt != nullptr ? cap : M;
+        if (int rc = launch_scatter(f, pss, Ml, w.d_feat, (size_t)2, (size_t)2 * (size_t)cap, g->table, w.scatter_ws, st, cnt, nullptr, 1, false, q.adam, unc_g, d_unc, n_front))
             return rc;
         const size_t n_params = (size_t)f->n_tiled_entries * 2u;
         const uint32_t n_table_blocks = (uint32_t)((n_params / 4u + 255u) / 256u);
         UncertReduce ur{};
         if (unc_scatter) {
-            const uint32_t Ml = cnt != nullptr ? cap : M;
-            ur.d_uncert = d_unc; ur.partial = ::scatter_ws(f, scatter_ws_ptr, Ml).unc_partial; ur.n_voxels = f->plan.uncert_voxels; ur.n_splits = uncert_splits(f, Ml);
+            ur.d_uncert = d_unc; ur.partial = scatter_ws(f, w.scatter_ws, Ml).unc_partial; ur.n_voxels = f->plan.uncert_voxels; ur.n_splits = uncert_splits(f, Ml);
             ur.voxels_pad = uncert_pad(f);
         }
         const uint32_t n_unc_blocks = unc_scatter ? (ur.n_voxels + 255u) / 256u : 0u;
-        const TvLate tvl = tv_late != nullptr ? *tv_late : TvLate{};
+        const TvLate tvl = q.tv_late != nullptr ? *q.tv_late : TvLate{};
         const uint32_t n_finish = n_table_blocks + kAccFloats / 32 + n_unc_blocks + (tvl.n_tv_blocks != 0u ? 1u : 0u);
-        if (next != nullptr) {
-            const uint32_t n_asm = (next->n_global + next->n_cur + 255u) / 256u;
-            hipLaunchKernelGGL(k_bwd_finish_next, dim3(n_finish + n_asm), dim3(256), 0, (hipStream_t)stream, f->lt, scatter_ws,
-                               level_splits(f, cnt != nullptr ? cap : M),
-                               n_params, partial_plane(f), partials, blocks, *g, *adam, n_table_blocks, ur, tvl, n_unc_blocks, n_asm, *next);
+        if (q.next != nullptr) {
+            const uint32_t n_asm = (q.next->n_global + q.next->n_cur + 255u) / 256u;
+            hipLaunchKernelGGL(k_bwd_finish_next, dim3(n_finish + n_asm), dim3(256), 0, st, f->lt, w.scatter_ws, level_splits(f, Ml),
+                               n_params, partial_plane(f), w.partials, blocks, *g, *q.adam, n_table_blocks, ur, tvl, n_unc_blocks, n_asm, *q.next);
             return check_launch("bwd_finish_next");
         }
-        hipLaunchKernelGGL(k_bwd_finish, dim3(n_table_blocks + kAccFloats / 32 + n_unc_blocks + (tvl.n_tv_blocks != 0u ? 1u : 0u)), dim3(256), 0, (hipStream_t)stream, f->lt, scatter_ws,
-                           level_splits(f, cnt != nullptr ? cap : M),
-                           n_params, partial_plane(f), partials, blocks, *g, *adam, n_table_blocks, ur, tvl, n_unc_blocks);
+        hipLaunchKernelGGL(k_bwd_finish, dim3(n_finish), dim3(256), 0, st, f->lt, w.scatter_ws, level_splits(f, Ml),
+                           n_params, partial_plane(f), w.partials, blocks, *g, *q.adam, n_table_blocks, ur, tvl, n_unc_blocks);
         return check_launch("bwd_finish");
     }
     const bool want_w = g->sdf_w0 || g->sdf_w1 || g->col_w0 || g->col_w1;
     if (want_w && phase_mlp) {
-        hipLaunchKernelGGL(k_wgrad_reduce, dim3(kAccFloats / 32), dim3(256), 0, (hipStream_t)stream, partials, blocks, *g,
-                           (int)(flags & NARUTO_BWD_OVERWRITE_WEIGHT_GRADS));
+        hipLaunchKernelGGL(k_wgrad_reduce, dim3(kAccFloats / 32), dim3(256), 0, st, w.partials, blocks, *g, (int)(q.flags & NARUTO_BWD_OVERWRITE_WEIGHT_GRADS));
         if (int rc = check_launch("wgrad_reduce")) return rc;
     }
     if (!phase_table) return NARUTO_OK;
-    if (n_front > 0) {
-        if (g->table == nullptr && !unc_scatter) return NARUTO_OK;
-        PointSrc pss{};
-        pss.xsoa = x_soa;
-        pss.M = cap;
-        pss.S = 1;
-        return launch_scatter(f, pss, cap, d_feat, (size_t)2, (size_t)2 * (size_t)cap, g->table, scatter_ws, (hipStream_t)stream, n_list_dev, nullptr,
-                              (int)(flags & NARUTO_BWD_OVERWRITE_TABLE_GRAD), true, nullptr, unc_g, d_unc, n_front);
+    if (g->table == nullptr && !unc_scatter) return NARUTO_OK;
+    if (n_front > 0)
+        return launch_scatter(f, pss, cap, w.d_feat, (size_t)2, (size_t)2 * (size_t)cap, g->table, w.scatter_ws, st, q.n_list_dev, nullptr,
+                              (int)(q.flags & NARUTO_BWD_OVERWRITE_TABLE_GRAD), true, nullptr, unc_g, d_unc, n_front);
+    const uint32_t* count_dev = q.n_active;
+    if (E > 0) {          // the smoothness lattice rides along in the same scatter launch
+        hipLaunchKernelGGL(k_append_points, dim3((E * kLevels + 255u) / 256u), dim3(256), 0, st, E, q.extra->x, q.extra->d_feat, q.extra->scale,
+                           q.n_active, M, cap, w.x_soa, w.d_feat, w.n_total);
+        if (int rc = check_launch("append_points")) return rc;
+        count_dev = w.n_total;
     }
-    if (g->table != nullptr || unc_scatter) {
-        PointSrc pss{};
-        pss.xsoa = x_soa;
-        pss.M = cap;
-        pss.S = 1;
-        const uint32_t* count_dev = n_active;
-        if (E > 0) {          // the smoothness lattice rides along in the same scatter launch
-            hipLaunchKernelGGL(k_append_points, dim3((E * kLevels + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, E, extra->x, extra->d_feat, extra->scale,
-                               n_active, M, cap, x_soa, d_feat, n_total);
-            if (int rc = check_launch("append_points")) return rc;
-            count_dev = n_total;
-        }
-        // host-side point count: the padded capacity only bounds a device-side count; without one the list holds exactly M points
-        if (int rc = launch_scatter(f, pss, count_dev != nullptr ? cap : M, d_feat, (size_t)2, (size_t)2 * (size_t)cap, g->table, scatter_ws, (hipStream_t)stream, count_dev, nullptr,
-                                    (int)(flags & NARUTO_BWD_OVERWRITE_TABLE_GRAD), true, nullptr, unc_g, d_unc))
-            return rc;
-    }
-    return NARUTO_OK;
+    // host-side point count: the padded capacity only bounds a device-side count; without one the list holds exactly M points
+    return launch_scatter(f, pss, count_dev != nullptr ? cap : M, w.d_feat, (size_t)2, (size_t)2 * (size_t)cap, g->table, w.scatter_ws, st, count_dev, nullptr,
+                          (int)(q.flags & NARUTO_BWD_OVERWRITE_TABLE_GRAD), true, nullptr, unc_g, d_unc);
 }
 }  // namespace
 
@@ -866,7 +882,11 @@ size_t naruto_query_bwd_workspace(const NarutoField* f, uint32_t M) { return bwd
 int naruto_query_bwd(const NarutoField* f, const NarutoParams* p, uint32_t M, const NarutoPoints* pts, const float* feat_save,
                      const float* d_raw, const float* d_geo, const uint32_t* active_idx, const uint32_t* n_active, const NarutoExtraPoints* extra,
                      uint32_t flags, const NarutoGrads* g, void* workspace, void* stream) {
-    return query_bwd_impl(f, p, M, pts, feat_save, d_raw, d_geo, active_idx, n_active, extra, flags, g, workspace, stream, 0u, nullptr);
+    QueryBwd q{};
+    q.M = M; q.pts = pts; q.feat_save = feat_save; q.d_raw = d_raw; q.d_geo = d_geo;
+    q.active_idx = active_idx; q.n_active = n_active; q.extra = extra;
+    q.flags = flags; q.g = g; q.workspace = workspace; q.stream = (hipStream_t)stream;
+    return query_bwd_impl(f, p, q);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -878,8 +898,7 @@ int naruto_query_bwd_points(const NarutoField* f, const NarutoParams* p, uint32_
                             const uint32_t* active_idx, const uint32_t* n_active, float* d_x, float* d_rays_o, float* d_rays_d, uint32_t flags,
                             void* workspace, void* stream) {
     if (f == nullptr || p == nullptr || pts == nullptr || d_raw == nullptr) return fail(NARUTO_ERR_INVALID, "query_bwd_points: NULL argument");
-    if (p->table == nullptr || p->uncert_grid == nullptr || p->sdf_w0 == nullptr || p->sdf_w1 == nullptr || p->col_w0 == nullptr || p->col_w1 == nullptr)
-        return fail(NARUTO_ERR_INVALID, "query_bwd_points: NULL parameter");
+    if (int rc = check_params(p, "query_bwd_points")) return rc;
     if ((active_idx == nullptr) != (n_active == nullptr)) return fail(NARUTO_ERR_INVALID, "query_bwd_points: active_idx and n_active go together");
     if ((flags & ~NARUTO_BWD_POINTS_ACCUMULATE) != 0u) return fail(NARUTO_ERR_INVALID, "query_bwd_points: unknown flags 0x%x", flags);
     if (int rc = check_points(pts)) return rc;
@@ -920,11 +939,19 @@ int naruto_query_bwd_points(const NarutoField* f, const NarutoParams* p, uint32_
 namespace {
 struct TrainWs {
     float* terms; float* tv_feat; double* tv_partial; void* bwd; double* fold; uint32_t* block_sums; void* w_img; float* w10;
-    uint32_t* sort;               // the Morton-ordered forward's buffers (naruto_sorted.hip): count | cursor | base [3][kSortCells], n_list + totals [320], cells | list | list2 [3][M], pts [M] float4
+    void* sort;                   // the Morton-ordered forward's buffers: sort_ws
     uint32_t n3, n_tv_blocks;
     size_t total;
 };
-inline size_t sort_ws_words(size_t M) { return 3u * (size_t)kSortCells + 320u + 7u * ((M + 63u) / 64u * 64u); }
+// the Morton-ordered forward's buffers (naruto_sorted.hip) for M samples, Mp = M rounded up to whole 64-sample tiles; unpadded:
+// | count | cursor | base [3][kSortCells] | the two list lengths, 6 unused words, k_sort_sum's totals at word 8 [320] | cells | list | list2 [3][Mp] | pts [Mp] float4 |
+struct SortWs { uint32_t* count; uint32_t* cursor; uint32_t* base; uint32_t* n_list; uint32_t* cells; uint32_t* list; uint32_t* list2; float4* pts; size_t total; };
+SortWs sort_ws(void* base, size_t M) {
+    const size_t per_cell = (size_t)kSortCells * sizeof(uint32_t), per_sample = (M + 63u) / 64u * 64u * sizeof(uint32_t);
+    Carve c(base);
+    return {c.take<uint32_t>(per_cell, 1u), c.take<uint32_t>(per_cell, 1u), c.take<uint32_t>(per_cell, 1u), c.take<uint32_t>(320u * sizeof(uint32_t), 1u),
+            c.take<uint32_t>(per_sample, 1u), c.take<uint32_t>(per_sample, 1u), c.take<uint32_t>(per_sample, 1u), c.take<float4>(4u * per_sample, 1u), c.size()};
+}
 TrainWs train_ws(const NarutoField* f, const NarutoTrainStep* t) {
     TrainWs w{};
     const uint32_t S = t->n_samples_d + t->n_range_d;
@@ -942,7 +969,7 @@ TrainWs train_ws(const NarutoField* f, const NarutoTrainStep* t) {
     w.w_img = c.take<void>(bwd_weight_image_bytes());
     w.w10 = c.take<float>(16u * sizeof(float));          // gathered loss_weight_parts
     w.bwd = c.take<void>(bwd_ws(f, nullptr, list_cap((uint32_t)(M + w.n3))).total);
-    w.sort = c.take<uint32_t>(sort_ws_words(M) * sizeof(uint32_t));     // (every plan: the plan is not known here, and it is 12 B per sample)
+    w.sort = c.take<void>(sort_ws(nullptr, M).total);    // (every plan: the plan is not known here; 28 B per sample in whole tiles + 3 MB of cell arrays + 1 280 B)
     w.total = c.size();
     return w;
 }
@@ -957,10 +984,44 @@ FwdImageWs fwd_image_ws(void* base) {
 inline const void* fresh_fwd_image(const NarutoField* f, const NarutoTrainStep* t) {
     return (t->fwd_image != nullptr && t->fwd_image_fresh != 0u && f->desc.mlp_mode != NARUTO_MLP_BF16) ? fwd_image_ws(t->fwd_image).image : nullptr;
 }
+TvArgs tv_args(const NarutoTrainStep* t) {
+    TvArgs a{};
+    if (t->smooth_points == 0) return a;
+    a.n = t->smooth_points - 1;
+    a.voxel = t->smooth_voxel;
+    a.margin = t->smooth_margin;
+    a.grid_size = (float)(t->smooth_points - 1) * t->smooth_voxel;
+    a.inv_p3 = 1.0f / ((float)t->smooth_points * (float)t->smooth_points * (float)t->smooth_points);
+    return a;
+}
+// What every training entry point derives from (f, t), once per call: the batch's counts, the capacity of the backward's point list (the
+// smoothness lattice in front of the samples), the two workspace layouts and the lattice's arguments in that list's layout.
+struct TrainCtx {
+    uint32_t N, S, M;       // rays, samples per ray, samples
+    uint32_t cap;           // list_cap(M + n3)
+    TrainWs w;
+    BwdWs bw;               // over w.bwd
+    TvArgs tva;             // cap filled in
+    // depth sampling of the batch's rays (k_sample_encode, or the walk itself where the plan moved it there)
+    SampleArgs sample_args(const NarutoTrainStep* t) const {
+        const float* jitter = t->perturb ? t->rand : nullptr;
+        const uint64_t* jitter_rng = (t->perturb && t->rand == nullptr) ? t->rng : nullptr;
+        return SampleArgs{N, t->target_d, t->near_, t->far_, t->n_samples_d, t->n_range_d, t->range_d, jitter, jitter_rng, t->z_vals, (N + 3u) / 4u};
+    }
+};
+TrainCtx train_ctx(const NarutoField* f, const NarutoTrainStep* t) {
+    TrainCtx c{};
+    c.N = t->n_rays; c.S = t->n_samples_d + t->n_range_d; c.M = c.N * c.S;
+    c.w = train_ws(f, t);
+    c.cap = list_cap(c.M + c.w.n3);
+    c.bw = bwd_ws(f, c.w.bwd, c.cap);
+    c.tva = tv_args(t);
+    c.tva.cap = c.cap;
+    return c;
+}
 int train_check(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const char* who) {
     if (f == nullptr || p == nullptr || t == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL argument", who);
-    if (p->table == nullptr || p->uncert_grid == nullptr || p->sdf_w0 == nullptr || p->sdf_w1 == nullptr || p->col_w0 == nullptr || p->col_w1 == nullptr)
-        return fail(NARUTO_ERR_INVALID, "%s: NULL parameter", who);
+    if (int rc = check_params(p, who)) return rc;
     if (t->rays_o == nullptr || t->rays_d == nullptr || t->target_rgb == nullptr || t->target_d == nullptr || t->z_vals == nullptr || t->raw == nullptr ||
         t->feat_save == nullptr || t->sums == nullptr || t->losses == nullptr || t->workspace == nullptr)
         return fail(NARUTO_ERR_INVALID, "%s: NULL buffer in NarutoTrainStep", who);
@@ -1081,28 +1142,31 @@ TrainFwdPlan train_fwd_plan(const NarutoField* f, const NarutoTrainStep* t, bool
     pl.tv_moved = tv_on && deferred && t->smooth_points != 0 && pl.fused && pl.split;
     return pl;
 }
-// level groups per lattice-encode workgroup where the encode rides as tail role of the training forward (NARUTO_TV_TAIL_GROUPS: 1, 2, 4)
-inline uint32_t tv_tail_groups() {
-    static const uint32_t g = (uint32_t)env_int("NARUTO_TV_TAIL_GROUPS", 1);
-    return g;
+// What the walk of plan `pl` does besides the field query: it may read the weight image, and where the plan moved the smoothness term it samples
+// its rays' depths and its tail workgroups encode the lattice (NARUTO_TV_TAIL_GROUPS: level groups per lattice-encode workgroup, 1, 2 or 4)
+WalkExtra walk_extra(const NarutoField* f, const NarutoTrainStep* t, const TrainCtx& c, const TrainFwdPlan& pl) {
+    static const uint32_t tv_groups = (uint32_t)env_int("NARUTO_TV_TAIL_GROUPS", 1);
+    WalkExtra wx{};
+    wx.w_img = fresh_fwd_image(f, t);
+    if (!pl.tv_moved) return wx;
+    wx.on = 1u;
+    wx.tv_groups = tv_groups;
+    wx.sa = c.sample_args(t);
+    wx.rand6 = t->rand6; wx.rng = t->rng; wx.x_out = c.bw.x_soa;
+    return wx;
 }
-inline bool tv_moved(const NarutoField* f, const NarutoTrainStep* t, bool deferred) { return train_fwd_plan(f, t, true, deferred).tv_moved; }
 // rows of per-workgroup partial sums the FUSED loss stage of the plan's form leaves (the stand-alone k_loss_stage: one per kRaysPerBlock rays)
-inline uint32_t loss_rows(const NarutoField* f, const NarutoTrainStep* t, bool deferred) {
-    const uint32_t R = train_fwd_plan(f, t, true, deferred).rays_per_row;
-    return (t->n_rays + R - 1u) / R;
-}
-int launch_train_query(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, hipStream_t st, const LossStageArgs* loss = nullptr,
-                       bool* fused = nullptr, const WalkExtra* walk_extra = nullptr, bool deferred = false) {
+inline uint32_t loss_rows(const TrainFwdPlan& pl, uint32_t n_rays) { return (n_rays + pl.rays_per_row - 1u) / pl.rays_per_row; }
+// The field query of the training forward in the form `pl` (a plan with the loss stage: train_fwd_plan(f, t, true, ...)); *fused tells whether the
+// loss stage rode in it.  wx.on goes with pl.tv_moved: the caller left k_sample_encode out because the plan has the walk sample its own depths.
+int launch_train_query(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const TrainCtx& c, const TrainFwdPlan& pl, hipStream_t st,
+                       const LossStageArgs& loss, const WalkExtra& wx, bool* fused) {
     if (fused != nullptr) *fused = false;
-    const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d, M = N * S;
-    const TrainFwdPlan pl = train_fwd_plan(f, t, loss != nullptr, deferred);
-    const bool wx_on = walk_extra != nullptr && walk_extra->on != 0u;
-    // the caller skipped k_sample_encode because the plan said the walk samples its own depths: any other form here would read stale depths
-    if (wx_on != pl.tv_moved) return fail(NARUTO_ERR_INVALID, "train query: the caller's launch plan (depth sampling in the walk: %d) is not the launcher's (%d)", (int)wx_on, (int)pl.tv_moved);
+    const uint32_t N = c.N, S = c.S, M = c.M;
     PointSrc ps{};
     ps.rays_o = t->rays_o; ps.rays_d = t->rays_d; ps.z_vals = t->z_vals; ps.S = S;
     const uint32_t blocks = pl.blocks;
+    const bool bfm = f->desc.mlp_mode == NARUTO_MLP_BF16;
     EarlyExit ee{};
     if (pl.form == FwdForm::Walk) {      // depth-ordered early termination: one wave per ray, front to back
         ee.target_d = t->target_d;
@@ -1122,24 +1186,21 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
     // agree with the other launch shapes to the distance between OneBlob's closed and dense forms, ~1e-6 (which form a point gets depends on
     // the tile it shares).  NARUTO_PACK_ONE_PASS=1: every sample in the first pass (measured: 0.200 / 0.180 ms at the two batches above).
     if (pl.form == FwdForm::Sorted) {
-        const TrainWs w = train_ws(f, t);
-        const size_t Mp = ((size_t)M + 63u) / 64u * 64u;
+        const SortWs sw = sort_ws(c.w.sort, M);
         SortArgs sa{};
         sa.M = M; sa.S = S; sa.target_d = t->target_d; sa.trunc_sc = f->desc.trunc * f->desc.sc_factor;
-        sa.count = w.sort; sa.cursor = w.sort + kSortCells; sa.base = w.sort + 2u * (size_t)kSortCells; sa.n_list = w.sort + 3u * (size_t)kSortCells;
-        sa.cells = sa.n_list + 320; sa.list = sa.cells + Mp; sa.list2 = sa.list + Mp; sa.pts = reinterpret_cast<float4*>(sa.list2 + Mp);
+        sa.count = sw.count; sa.cursor = sw.cursor; sa.base = sw.base; sa.n_list = sw.n_list;
+        sa.cells = sw.cells; sa.list = sw.list; sa.list2 = sw.list2; sa.pts = sw.pts;
         hipLaunchKernelGGL(k_sort_zero, dim3(2u * kSortCells / 4u / 256u), dim3(256), 0, st, reinterpret_cast<uint4*>(sa.count), 2u * kSortCells / 4u);
-        const bool bfm = f->desc.mlp_mode == NARUTO_MLP_BF16;
         const uint32_t mblocks = (M + 256u * kSortPer - 1u) / (256u * kSortPer);
         hipLaunchKernelGGL(k_sort_count, dim3(mblocks), dim3(256), 0, st, sa, ps, f->bt, t->raw);
         hipLaunchKernelGGL(k_sort_sum, dim3(256), dim3(256), 0, st, sa, sa.n_list + 8);          // (the totals: 256 words behind the two list lengths)
         hipLaunchKernelGGL(k_sort_scan, dim3(256), dim3(256), 0, st, sa, sa.n_list + 8);
         hipLaunchKernelGGL(k_sort_fill, dim3(mblocks), dim3(256), 0, st, sa, ps, f->bt);
         if (int rc = check_launch("sort_count / scan / fill")) return rc;
-        const uint32_t qblocks = cu_count(f);
 #define NARUTO_LAUNCH_LIST(LISTV, PTSV, NV) do { \
-            if (bfm) hipLaunchKernelGGL(k_query_fwd_list<true>, dim3(qblocks), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, LISTV, PTSV, NV, t->raw, t->feat_save); \
-            else hipLaunchKernelGGL(k_query_fwd_list<false>, dim3(qblocks), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, LISTV, PTSV, NV, t->raw, t->feat_save); } while (0)
+            if (bfm) hipLaunchKernelGGL(k_query_fwd_list<true>, dim3(blocks), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, LISTV, PTSV, NV, t->raw, t->feat_save); \
+            else hipLaunchKernelGGL(k_query_fwd_list<false>, dim3(blocks), dim3(512), 0, st, f->lt, f->ut, f->bt, *p, ps, LISTV, PTSV, NV, t->raw, t->feat_save); } while (0)
         NARUTO_LAUNCH_LIST(sa.list, sa.pts, sa.n_list);
         if (int rc = check_launch("query_fwd_list")) return rc;
         hipLaunchKernelGGL(k_sort_more, dim3((N + 255u) / 256u), dim3(256), 0, st, sa, N, t->z_vals, t->raw);
@@ -1157,18 +1218,16 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
         if (int rc = W == 4u ? reserve_lds(attr_set[1], {lds_use(k_query_fwd_loss_packed<false, 4>, lds_free), lds_use(k_query_fwd_loss_packed<true, 4>, lds_free)}, cannot, lds_free)
                              : reserve_lds(attr_set[0], {lds_use(k_query_fwd_loss_packed<false, 8>, lds_free), lds_use(k_query_fwd_loss_packed<true, 8>, lds_free)}, cannot, lds_free))
             return rc;
-        const uint32_t pblocks = pl.blocks;
         EarlyExit pe{};
         pe.target_d = t->target_d;
         pe.trunc_sc = f->desc.trunc * f->desc.sc_factor;
-        const bool bfm = f->desc.mlp_mode == NARUTO_MLP_BF16;
         static const int one_pass_env = env_int("NARUTO_PACK_ONE_PASS", -1);
         const bool one_pass = one_pass_env == 1;
         uint32_t rays_cap = rows * (uint32_t)kRaysPerBlock;
         if (one_pass && rays_cap * S > 64u * W && 64u * W / S >= 1u) rays_cap = 64u * W / S;           // one pass: all of a chunk's samples in one group of tiles
         const uint32_t rows_arg = rays_cap | (one_pass ? 0x100u : 0u);
-#define NARUTO_LAUNCH_PACKED(BFV, WV) hipLaunchKernelGGL((k_query_fwd_loss_packed<BFV, WV>), dim3(pblocks + loss->n_tv_blocks), dim3(64 * WV), need, st, f->lt, f->ut, f->bt, *p, ps, M, \
-                                                         t->raw, t->feat_save, pe, *loss, pblocks, rows_arg, g_fwd_timeline)
+#define NARUTO_LAUNCH_PACKED(BFV, WV) hipLaunchKernelGGL((k_query_fwd_loss_packed<BFV, WV>), dim3(blocks + loss.n_tv_blocks), dim3(64 * WV), need, st, f->lt, f->ut, f->bt, *p, ps, M, \
+                                                         t->raw, t->feat_save, pe, loss, blocks, rows_arg, g_fwd_timeline)
         if (W == 4u) { if (bfm) NARUTO_LAUNCH_PACKED(true, 4); else NARUTO_LAUNCH_PACKED(false, 4); }
         else { if (bfm) NARUTO_LAUNCH_PACKED(true, 8); else NARUTO_LAUNCH_PACKED(false, 8); }
 #undef NARUTO_LAUNCH_PACKED
@@ -1177,28 +1236,22 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
     }
     if (pl.form == FwdForm::Short) {
         if (int rc = ray_lds_attr()) return rc;
-        const bool bfm = f->desc.mlp_mode == NARUTO_MLP_BF16;
-        const WalkExtra wxa = walk_extra != nullptr ? *walk_extra : WalkExtra{};
-        const uint32_t tail_blocks = wxa.on ? tv_encode_blocks(loss->tv.n * loss->tv.n * loss->tv.n, wxa.tv_groups) : loss->n_tv_blocks;
-        const uint32_t R = pl.rays_per_row;
-        const uint32_t sblocks = pl.blocks;
+        const uint32_t tail_blocks = wx.on ? tv_encode_blocks(loss.tv.n * loss.tv.n * loss.tv.n, wx.tv_groups) : loss.n_tv_blocks;
         // (the weight image, where the caller called it fresh: the exact mode's kernel that copies it instead of staging the weights)
-        if (!bfm && wxa.w_img != nullptr) hipLaunchKernelGGL(k_query_fwd_loss_short_img, dim3(sblocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, *loss, sblocks, wxa, R, g_fwd_timeline);
-        else if (bfm) hipLaunchKernelGGL(k_query_fwd_loss_short<true>, dim3(sblocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, *loss, sblocks, wxa, R, g_fwd_timeline);
-        else hipLaunchKernelGGL(k_query_fwd_loss_short<false>, dim3(sblocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, *loss, sblocks, wxa, R, g_fwd_timeline);
+        if (!bfm && wx.w_img != nullptr) hipLaunchKernelGGL(k_query_fwd_loss_short_img, dim3(blocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, loss, blocks, wx, pl.rays_per_row, g_fwd_timeline);
+        else if (bfm) hipLaunchKernelGGL(k_query_fwd_loss_short<true>, dim3(blocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, loss, blocks, wx, pl.rays_per_row, g_fwd_timeline);
+        else hipLaunchKernelGGL(k_query_fwd_loss_short<false>, dim3(blocks + tail_blocks), dim3(256), short_lds_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, loss, blocks, wx, pl.rays_per_row, g_fwd_timeline);
         if (fused != nullptr) *fused = true;
         return check_launch("query_fwd_loss_short");
     }
     if (pl.form == FwdForm::Walk && pl.fused) {
         if (int rc = ray_lds_attr()) return rc;
         // the two-phase tile costs 32 KB of slabs per workgroup: only while two workgroups still share a CU (S <= 192), see k_query_fwd_loss
-        const bool bfm = f->desc.mlp_mode == NARUTO_MLP_BF16;
-        const WalkExtra wxa = walk_extra != nullptr ? *walk_extra : WalkExtra{};
-        const uint32_t tail_blocks = wxa.on ? tv_encode_blocks(loss->tv.n * loss->tv.n * loss->tv.n, wxa.tv_groups) : loss->n_tv_blocks;
+        const uint32_t tail_blocks = wx.on ? tv_encode_blocks(loss.tv.n * loss.tv.n * loss.tv.n, wx.tv_groups) : loss.n_tv_blocks;
 #define NARUTO_LAUNCH_WALK(BFV, SPV) hipLaunchKernelGGL((k_query_fwd_loss<BFV, SPV>), dim3(blocks + tail_blocks), dim3(256), ray_scratch_fwd_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, \
-                                                        t->raw, t->feat_save, ee, *loss, blocks, wxa, g_fwd_timeline)
-        if (pl.split && !bfm && wxa.w_img != nullptr)          // (the weight image, where the caller called it fresh)
-            hipLaunchKernelGGL(k_query_fwd_loss_img, dim3(blocks + tail_blocks), dim3(256), ray_scratch_fwd_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, ee, *loss, blocks, wxa,
+                                                        t->raw, t->feat_save, ee, loss, blocks, wx, g_fwd_timeline)
+        if (pl.split && !bfm && wx.w_img != nullptr)          // (the weight image, where the caller called it fresh)
+            hipLaunchKernelGGL(k_query_fwd_loss_img, dim3(blocks + tail_blocks), dim3(256), ray_scratch_fwd_bytes(S), st, f->lt, f->ut, f->bt, *p, ps, M, t->raw, t->feat_save, ee, loss, blocks, wx,
                                g_fwd_timeline);
         else if (pl.split) { if (bfm) NARUTO_LAUNCH_WALK(true, true); else NARUTO_LAUNCH_WALK(false, true); }
         else { if (bfm) NARUTO_LAUNCH_WALK(true, false); else NARUTO_LAUNCH_WALK(false, false); }
@@ -1208,16 +1261,6 @@ int launch_train_query(const NarutoField* f, const NarutoParams* p, const Naruto
     }
     // flat tiles in the plan's workgroup shape, or the unfused walk (full tiles only: S = 64 k)
     return launch_flat_fwd(f, *p, ps, M, t->raw, nullptr, nullptr, t->feat_save, ee, true, {blocks, pl.threads}, ee.tiles_per_ray != 0u, st);
-}
-TvArgs tv_args(const NarutoTrainStep* t) {
-    TvArgs a{};
-    if (t->smooth_points == 0) return a;
-    a.n = t->smooth_points - 1;
-    a.voxel = t->smooth_voxel;
-    a.margin = t->smooth_margin;
-    a.grid_size = (float)(t->smooth_points - 1) * t->smooth_voxel;
-    a.inv_p3 = 1.0f / ((float)t->smooth_points * (float)t->smooth_points * (float)t->smooth_points);
-    return a;
 }
 // NARUTO_TRAIN_FWD_DEFER_TAIL / NARUTO_TRAIN_BWD_DEFERRED_TAIL apply up to kFusedTailMaxRays rays; beyond that both calls run the ordinary path
 inline bool tail_rides_in_backward(const NarutoTrainStep* t) { return t->n_rays <= kFusedTailMaxRays && t->ray_count != nullptr; }
@@ -1232,17 +1275,17 @@ LossTailArgs loss_tail_args(const NarutoTrainStep* t, const TrainWs& w, uint32_t
     tl.min_run = t->min_uncert_running;
     return tl;
 }
-LossStageArgs loss_stage_args(const NarutoField* f, const NarutoTrainStep* t, const TrainWs& w, const BwdWs& bw, const TvArgs& tva) {
-    const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d;
+LossStageArgs loss_stage_args(const NarutoField* f, const NarutoTrainStep* t, const TrainCtx& c) {
+    const TrainWs& w = c.w;
     LossStageArgs a{};
-    a.n_rays = N; a.S = S;
+    a.n_rays = c.N; a.S = c.S;
     a.trunc = f->desc.trunc; a.sc_factor = f->desc.sc_factor; a.trunc_sc = f->desc.trunc * f->desc.sc_factor;
     a.depth_trunc = t->depth_trunc; a.rgb_missing = t->rgb_missing; a.white_bkgd = f->desc.white_bkgd;
     a.raw = t->raw; a.z_vals = t->z_vals; a.target_rgb = t->target_rgb; a.target_d = t->target_d;
     a.rgb = t->rgb; a.depth = t->depth; a.uncert_map = t->uncert_map;
     a.partials = reinterpret_cast<double*>(w.terms);       // n_rays/4 x 16 doubles fit the n_rays x 16 floats of the modular path
-    a.n_ray_blocks = (N + kRaysPerBlock - 1) / kRaysPerBlock;
-    a.tv = tva; a.tv_feat = w.tv_feat; a.tv_d_list = bw.d_feat; a.tv_partial = w.tv_partial;
+    a.n_ray_blocks = (c.N + kRaysPerBlock - 1) / kRaysPerBlock;
+    a.tv = c.tva; a.tv_feat = w.tv_feat; a.tv_d_list = c.bw.d_feat; a.tv_partial = w.tv_partial;
     a.tv_scale_dev = t->loss_weights != nullptr ? t->loss_weights + 8 : nullptr;
     a.tv_scale_host = t->smooth_grad_scale != 0.0f ? t->smooth_grad_scale : 1.0f;
     a.n_tv_blocks = t->smooth_points != 0 ? w.n_tv_blocks : 0u;
@@ -1322,63 +1365,54 @@ size_t naruto_train_workspace(const NarutoField* f, const NarutoTrainStep* t) {
 }
 
 // (advisor, round 5) NARUTO_TRAIN_FWD_SUMS_TV_LATER and NARUTO_TRAIN_BWD_TV_MOVED must be paired: a forward that LEFT the smoothness term to the backward,
-// followed by a backward that is not told so, would silently drop the term (no value, stale cotangents on the front list).  The last forwards' decisions are
-// remembered per training workspace (host side, a handful of entries) and naruto_train_backward refuses the mismatch.
+// followed by a backward that is not told so, would silently drop the term (no value, stale cotangents on the front list).  The training workspaces whose
+// LAST forward left the term are kept in a set (host side, under a mutex: fields and steps may be used from several threads): every forward inserts or
+// erases its workspace, naruto_train_backward looks its own up and refuses the mismatch.  The one limit: a workspace freed in that state whose address is
+// handed out again passes the flag on to the new owner until that one's first forward.
 namespace {
-struct TvLeft { const void* ws; bool left; };
-TvLeft g_tv_left[16] = {};
-int g_tv_left_next = 0;
+std::mutex g_tv_later_mutex;
+std::unordered_set<const void*> g_tv_later;
 void note_tv_left(const void* ws, bool left) {
-    for (auto& e : g_tv_left) if (e.ws == ws) { e.left = left; return; }
-    g_tv_left[g_tv_left_next] = TvLeft{ws, left};
-    g_tv_left_next = (g_tv_left_next + 1) % 16;
+    const std::lock_guard<std::mutex> lock(g_tv_later_mutex);
+    if (left) g_tv_later.insert(ws);
+    else g_tv_later.erase(ws);
 }
 bool tv_was_left(const void* ws) {
-    for (const auto& e : g_tv_left) if (e.ws == ws) return e.left;
-    return false;
+    const std::lock_guard<std::mutex> lock(g_tv_later_mutex);
+    return g_tv_later.count(ws) != 0u;
 }
 }  // namespace
 
 int naruto_train_forward(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, int finalize, void* stream) {
     if (int rc = train_check(f, p, t, "train_forward")) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d, M = N * S;
-    const TrainWs w = train_ws(f, t);
-    // A1
-    const float* jitter = t->perturb ? t->rand : nullptr;
-    const uint64_t* jitter_rng = (t->perturb && t->rand == nullptr) ? t->rng : nullptr;
-    // A1 (+ the smoothness lattice: its points go straight to the FRONT of the backward's scatter list, features level-major)
-    TvArgs tva = tv_args(t);
-    tva.cap = list_cap(M + w.n3);
-    const BwdWs bw = bwd_ws(f, w.bwd, list_cap(M + w.n3));
+    const TrainCtx c = train_ctx(f, t);
+    const uint32_t N = c.N, S = c.S;
+    const TrainWs& w = c.w;
     // (the smoothness term is left to the backward: the single-process deferred tail, or the data-parallel SUMS_TV_LATER form)
     const bool deferred_ = (finalize == NARUTO_TRAIN_FWD_DEFER_TAIL || finalize == NARUTO_TRAIN_FWD_SUMS_TV_LATER) && tail_rides_in_backward(t);
-    WalkExtra wx{};
-    wx.w_img = fresh_fwd_image(f, t);
-    note_tv_left(t->workspace, finalize == NARUTO_TRAIN_FWD_SUMS_TV_LATER && tv_moved(f, t, deferred_));
-    if (tv_moved(f, t, deferred_)) {
-        wx.on = 1u;
-        wx.tv_groups = tv_tail_groups();
-        wx.sa = SampleArgs{N, t->target_d, t->near_, t->far_, t->n_samples_d, t->n_range_d, t->range_d, jitter, jitter_rng, t->z_vals, (N + 3u) / 4u};
-        wx.rand6 = t->rand6; wx.rng = t->rng; wx.x_out = bw.x_soa;
-    } else if (t->smooth_points != 0) {
-        SampleArgs sa{N, t->target_d, t->near_, t->far_, t->n_samples_d, t->n_range_d, t->range_d, jitter, jitter_rng, t->z_vals, (N + 3u) / 4u};
+    const TrainFwdPlan pl = train_fwd_plan(f, t, true, deferred_);
+    const WalkExtra wx = walk_extra(f, t, c, pl);
+    note_tv_left(t->workspace, finalize == NARUTO_TRAIN_FWD_SUMS_TV_LATER && pl.tv_moved);
+    // A1 (+ the smoothness lattice: its points go straight to the FRONT of the backward's scatter list, features level-major); with the term moved
+    // the walk samples the depths itself and its tail workgroups encode the lattice (walk_extra)
+    SampleArgs sa = c.sample_args(t);
+    if (!pl.tv_moved && t->smooth_points != 0) {
         static const int dbg_roles = env_int("NARUTO_DEBUG_SAMPLE_ROLES", 3);   // profiling knob: 1 rays, 2 lattice
         if (dbg_roles == 2) sa.n_rays = 0;
         hipLaunchKernelGGL(k_sample_encode, dim3(sa.n_ray_blocks + (dbg_roles == 1 ? 0u : tv_encode_blocks(w.n3))), dim3(256), (size_t)4u * 2u * S * sizeof(float), st, sa, f->lt,
-                           f->bt, tva, t->rand6, t->rng, reinterpret_cast<const float2*>(p->table), bw.x_soa, w.tv_feat);
+                           f->bt, c.tva, t->rand6, t->rng, reinterpret_cast<const float2*>(p->table), c.bw.x_soa, w.tv_feat);
         if (int rc = check_launch("sample_encode")) return rc;
-    } else {
-        hipLaunchKernelGGL(k_sample_z, dim3(N), dim3(64), 0, st, N, t->target_d, t->near_, t->far_, t->n_samples_d, t->n_range_d, t->range_d, jitter, jitter_rng,
-                           t->z_vals);
+    } else if (!pl.tv_moved) {
+        hipLaunchKernelGGL(k_sample_z, dim3(N), dim3(64), 0, st, N, sa.target_d, sa.near_, sa.far_, sa.nu, sa.nr, sa.range_d, sa.rand, sa.rng, sa.z_vals);
         if (int rc = check_launch("sample_z")) return rc;
     }
     // A2..A5 and A6..A8 (+ the lattice's TV term): one launch where the forward walks one ray per wave, else two; then the one-workgroup tail
-    LossStageArgs a = loss_stage_args(f, t, w, bw, tva);
+    LossStageArgs a = loss_stage_args(f, t, c);
     const bool deferred = finalize == NARUTO_TRAIN_FWD_DEFER_TAIL && tail_rides_in_backward(t);
     if (int rc = ray_lds_attr()) return rc;
     bool loss_done = false;
-    if (int rc = launch_train_query(f, p, t, st, &a, &loss_done, &wx, deferred_)) return rc;
+    if (int rc = launch_train_query(f, p, t, c, pl, st, a, wx, &loss_done)) return rc;
     if (!loss_done) {
         static const int dbg_ls_roles = env_int("NARUTO_DEBUG_LOSS_STAGE_ROLES", 3);     // profiling knob: 1 rays, 2 lattice
         if (dbg_ls_roles == 1) a.n_tv_blocks = 0;
@@ -1387,9 +1421,9 @@ int naruto_train_forward(const NarutoField* f, const NarutoParams* p, const Naru
         if (int rc = check_launch("loss_stage")) return rc;
     }
     if (deferred) return NARUTO_OK;                          // the tail is a workgroup of the backward's first launch
-    const uint32_t n_rows = loss_done ? loss_rows(f, t, deferred_) : a.n_ray_blocks;      // rows of partial sums the loss stage left
+    const uint32_t n_rows = loss_done ? loss_rows(pl, N) : a.n_ray_blocks;      // rows of partial sums the loss stage left
     // (SUMS_TV_LATER with the term moved: nothing has evaluated it yet -- the tail writes losses[8] = 0, the backward adds the value)
-    LossTailArgs tl = loss_tail_args(t, w, n_rows, wx.on != 0u ? 0u : a.n_tv_blocks, tva.inv_p3,
+    LossTailArgs tl = loss_tail_args(t, w, n_rows, wx.on != 0u ? 0u : a.n_tv_blocks, c.tva.inv_p3,
                                      finalize == 1 || finalize == NARUTO_TRAIN_FWD_DEFER_TAIL);      // (DEFER_TAIL beyond kFusedTailMaxRays rays: the ordinary tail, here)
     if (n_rows > 4u * kTailRows) {          // large batch: fold the per-workgroup rows first
         hipLaunchKernelGGL(k_loss_fold, dim3(kTailRows), dim3(64), 0, st, tl.partials, n_rows, w.fold);
@@ -1421,7 +1455,7 @@ const uint32_t* fwd_image_slots_host() {
 }
 int fwd_image_args(const NarutoField* f, const NarutoParams* p, const void* buf, const char* who) {
     if (f == nullptr || p == nullptr || buf == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL argument", who);
-    if (p->sdf_w0 == nullptr || p->sdf_w1 == nullptr || p->col_w0 == nullptr || p->col_w1 == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL weights", who);
+    if (int rc = check_params(p, who, kParamsSdf | kParamsColour, "NULL weights")) return rc;
     if ((reinterpret_cast<uintptr_t>(buf) & 15u) != 0u) return fail(NARUTO_ERR_INVALID, "%s: the buffer must be 16-byte aligned", who);
     return NARUTO_OK;
 }
@@ -1458,26 +1492,11 @@ int naruto_debug_fwd_timeline(void* device_buffer) {
 int naruto_debug_train_query_fwd(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, void* stream) {
     if (int rc = train_check(f, p, t, "debug_train_query_fwd")) return rc;
     // exactly the launch naruto_train_forward issues for the field query: with the loss stage riding in it where that applies
-    const uint32_t M = t->n_rays * (t->n_samples_d + t->n_range_d);
-    const TrainWs w = train_ws(f, t);
-    TvArgs tva = tv_args(t);
-    tva.cap = list_cap(M + w.n3);
-    const BwdWs bw = bwd_ws(f, w.bwd, list_cap(M + w.n3));
-    const LossStageArgs a = loss_stage_args(f, t, w, bw, tva);
+    const TrainCtx c = train_ctx(f, t);
     // (the five-launch iteration's form of it -- depth sampling in the walk, the lattice encode in its tail workgroups -- where the trainer's
     // iteration takes that form; the jitter is whatever the step's generator state gives: timing only)
-    WalkExtra wx{};
-    wx.w_img = fresh_fwd_image(f, t);
-    const bool deferred = tail_rides_in_backward(t);
-    if (tv_moved(f, t, deferred)) {
-        const float* jitter = t->perturb ? t->rand : nullptr;
-        const uint64_t* jitter_rng = (t->perturb && t->rand == nullptr) ? t->rng : nullptr;
-        wx.on = 1u;
-        wx.tv_groups = tv_tail_groups();
-        wx.sa = SampleArgs{t->n_rays, t->target_d, t->near_, t->far_, t->n_samples_d, t->n_range_d, t->range_d, jitter, jitter_rng, t->z_vals, (t->n_rays + 3u) / 4u};
-        wx.rand6 = t->rand6; wx.rng = t->rng; wx.x_out = bw.x_soa;
-    }
-    return launch_train_query(f, p, t, (hipStream_t)stream, &a, nullptr, &wx, deferred);
+    const TrainFwdPlan pl = train_fwd_plan(f, t, true, tail_rides_in_backward(t));
+    return launch_train_query(f, p, t, c, pl, (hipStream_t)stream, loss_stage_args(f, t, c), walk_extra(f, t, c, pl), nullptr);
 }
 
 // profiling: k_hash_scatter_lds ALONE over the point list the last naruto_train_backward left in the workspace, in the launch shape
@@ -1485,19 +1504,14 @@ int naruto_debug_train_query_fwd(const NarutoField* f, const NarutoParams* p, co
 int naruto_debug_train_scatter(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, void* stream) {
     if (int rc = train_check(f, p, t, "debug_train_scatter")) return rc;
     if (f->bplan.n_levels != 0) return fail(NARUTO_ERR_INVALID, "debug_train_scatter: this field has binned levels (the tiled launch is not its whole scatter)");
-    const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d, M = N * S;
-    const TrainWs w = train_ws(f, t);
-    const uint32_t cap = list_cap(M + w.n3);
-    const BwdWs bw = bwd_ws(f, w.bwd, cap);
-    const uint32_t n_front = t->smooth_points != 0 ? w.n3 : 0u;
-    PointSrc pss{};
-    pss.xsoa = bw.x_soa;
-    pss.M = cap;
-    pss.S = 1;
+    const TrainCtx c = train_ctx(f, t);
+    const uint32_t cap = c.cap;
+    const BwdWs& bw = c.bw;
+    const uint32_t n_front = t->smooth_points != 0 ? c.w.n3 : 0u;
     const uint32_t* cnt = n_front > 0 ? bw.n_total : t->n_active;
     const float* unc_g = f->plan.n_uncert != 0 ? bw.x_soa + 3u * (size_t)cap : nullptr;
     // d_table / d_uncert only select the roles here: without the reduce nothing is written through them
-    return launch_scatter(f, pss, cap, bw.d_feat, (size_t)2, (size_t)2 * (size_t)cap, const_cast<float*>(p->table), bw.scatter_ws, (hipStream_t)stream, cnt, nullptr, 1, false,
+    return launch_scatter(f, list_points(bw.x_soa, cap), cap, bw.d_feat, (size_t)2, (size_t)2 * (size_t)cap, const_cast<float*>(p->table), bw.scatter_ws, (hipStream_t)stream, cnt, nullptr, 1, false,
                           nullptr, unc_g, unc_g != nullptr ? const_cast<float*>(p->uncert_grid) : nullptr, n_front);
 }
 
@@ -1550,27 +1564,27 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
             return fail(NARUTO_ERR_INVALID, "train_backward_poses: pose refinement belongs to the one-piece single-process backward");
         if (int rc = ba_poses_check(bap, t_in, true, "train_backward_poses")) return rc;
     }
+    const hipStream_t st = (hipStream_t)stream;
+    const TrainCtx c = train_ctx(f, t_in);          // (nothing in it reads the loss weights, which the next lines may swap)
+    const TrainWs& w = c.w;
+    const BwdWs& bw = c.bw;
+    const uint32_t N = c.N, S = c.S, M = c.M;
     // loss weights given as separate device scalars: gather them (+ the vector, if any) into the workspace first
     NarutoTrainStep t_local;
     const NarutoTrainStep* t = t_in;
-    {
-        bool parts = false;
-        for (int i = 0; i < 10; ++i) parts = parts || t_in->loss_weight_parts[i] != nullptr;
-        if (parts && (flags & NARUTO_TRAIN_BWD_TABLE_ONLY) == 0u) {
+    bool parts = false;
+    for (int i = 0; i < 10; ++i) parts = parts || t_in->loss_weight_parts[i] != nullptr;
+    if (parts) {
+        if ((flags & NARUTO_TRAIN_BWD_TABLE_ONLY) == 0u) {           // (TABLE_ONLY: gathered by the preceding MLP_ONLY call)
             WeightParts wp{};
             for (int i = 0; i < 10; ++i) wp.part[i] = t_in->loss_weight_parts[i];
             wp.base = t_in->loss_weights;
-            const TrainWs w0 = train_ws(f, t_in);
-            hipLaunchKernelGGL(k_gather_loss_weights, dim3(1), dim3(64), 0, (hipStream_t)stream, wp, w0.w10);
+            hipLaunchKernelGGL(k_gather_loss_weights, dim3(1), dim3(64), 0, st, wp, w.w10);
             if (int rc = check_launch("gather_loss_weights")) return rc;
-            t_local = *t_in;
-            t_local.loss_weights = w0.w10;
-            t = &t_local;
-        } else if (parts) {
-            t_local = *t_in;
-            t_local.loss_weights = train_ws(f, t_in).w10;            // gathered by the preceding MLP_ONLY call
-            t = &t_local;
         }
+        t_local = *t_in;
+        t_local.loss_weights = w.w10;
+        t = &t_local;
     }
     AdamFuse adam{};
     if (opt != nullptr) {
@@ -1588,9 +1602,6 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
     if (g == nullptr || t->loss_weights == nullptr || t->feat_save == nullptr || t->d_raw == nullptr || t->ray_count == nullptr || t->ray_offset == nullptr ||
         t->active_idx == nullptr || t->n_active == nullptr)
         return fail(NARUTO_ERR_INVALID, "train_backward: NULL buffer");
-    const hipStream_t st = (hipStream_t)stream;
-    const uint32_t N = t->n_rays, S = t->n_samples_d + t->n_range_d, M = N * S;
-    const TrainWs w = train_ws(f, t);
     const LossArgs la = train_loss_args(f, t);
     if ((flags & NARUTO_TRAIN_BWD_MLP_ONLY) && (flags & NARUTO_TRAIN_BWD_TABLE_ONLY)) return fail(NARUTO_ERR_INVALID, "train_backward: pick one phase");
     const bool table_only = (flags & NARUTO_TRAIN_BWD_TABLE_ONLY) != 0u;
@@ -1605,7 +1616,9 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
     // the smoothness term moved into this backward only where the FORWARD was told to defer its tail (NARUTO_TRAIN_BWD_DEFERRED_TAIL): with
     // NARUTO_TRAIN_BWD_SUMS_GIVEN (data parallel, the autograd node) the forward ran k_sample_encode, evaluated the term itself and its
     // value is already in losses[8] -- evaluating it here again would count it twice in the total (round-4 advisor finding)
-    const bool moved = (flags & (NARUTO_TRAIN_BWD_DEFERRED_TAIL | NARUTO_TRAIN_BWD_TV_MOVED)) != 0u && deferred && tv_moved(f, t, true);
+    // the plan of this step's forward as the first half of one iteration (`deferred` decides tv_moved and nothing else: the form is any forward's)
+    const TrainFwdPlan pl = train_fwd_plan(f, t, true, true);
+    const bool moved = (flags & (NARUTO_TRAIN_BWD_DEFERRED_TAIL | NARUTO_TRAIN_BWD_TV_MOVED)) != 0u && deferred && pl.tv_moved;
     if ((flags & NARUTO_TRAIN_BWD_TV_MOVED) != 0u && !sums_given && !table_only)
         return fail(NARUTO_ERR_INVALID, "train_backward: NARUTO_TRAIN_BWD_TV_MOVED belongs to NARUTO_TRAIN_BWD_SUMS_GIVEN (a forward with NARUTO_TRAIN_FWD_SUMS_TV_LATER)");
     if (sums_given && !table_only && (flags & NARUTO_TRAIN_BWD_TV_MOVED) == 0u && tv_was_left(t_in->workspace))
@@ -1613,24 +1626,21 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
                                         "backward): pass NARUTO_TRAIN_BWD_TV_MOVED with NARUTO_TRAIN_BWD_SUMS_GIVEN, or the term is dropped");
     if (deferred) {
         const bool smooth_d = t->smooth_points != 0 && (g->table != nullptr || opt != nullptr);
-        const BwdWs bwd = bwd_ws(f, w.bwd, list_cap(M + w.n3));
         FusedBwdArgs fa{};
         fa.n_rays = N; fa.S = S; fa.trunc = f->desc.trunc; fa.sc_factor = f->desc.sc_factor; fa.white_bkgd = f->desc.white_bkgd;
         fa.raw = t->raw; fa.z_vals = t->z_vals; fa.la = la; fa.d_raw = t->d_raw;
         fa.partials = reinterpret_cast<const double*>(w.terms); fa.n_ray_blocks = (N + kRaysPerBlock - 1) / kRaysPerBlock;
         fa.ray_count = t->ray_count; fa.ray_off = t->ray_offset; fa.active_idx = t->active_idx; fa.n_active = t->n_active;
-        fa.n_front = smooth_d ? w.n3 : 0u; fa.n_list = bwd.n_total;
+        fa.n_front = smooth_d ? w.n3 : 0u; fa.n_list = bw.n_total;
         // (the term moved into this launch: the tail cannot see its partial sums -- the last launch of the backward adds the value, TvLate)
         // rows the forward's loss stage left: the plan's, when this backward belongs to a forward that deferred its tail (sums_given: unused)
-        fa.n_rows = (flags & (NARUTO_TRAIN_BWD_DEFERRED_TAIL | NARUTO_TRAIN_BWD_TV_MOVED)) != 0u ? loss_rows(f, t, true) : fa.n_ray_blocks;
-        fa.tail = loss_tail_args(t, w, fa.n_rows, (t->smooth_points != 0 && !moved) ? w.n_tv_blocks : 0u, tv_args(t).inv_p3, 1);
+        fa.n_rows = (flags & (NARUTO_TRAIN_BWD_DEFERRED_TAIL | NARUTO_TRAIN_BWD_TV_MOVED)) != 0u ? loss_rows(pl, N) : fa.n_ray_blocks;
+        fa.tail = loss_tail_args(t, w, fa.n_rows, (t->smooth_points != 0 && !moved) ? w.n_tv_blocks : 0u, c.tva.inv_p3, 1);
         fa.sums_given = sums_given ? 1 : 0;
         // one more workgroup prepares the MLP backward's weight images (the parameters do not change before k_query_bwd reads them)
         fa.w_img = w.w_img; fa.w_bf = f->desc.mlp_mode == NARUTO_MLP_BF16 ? 1 : 0; fa.params = *p;
         if (moved) {
-            TvArgs tva = tv_args(t);
-            tva.cap = list_cap(M + w.n3);
-            fa.tv = tva; fa.tv_feat = w.tv_feat; fa.tv_d_list = bwd.d_feat; fa.tv_partial = w.tv_partial;
+            fa.tv = c.tva; fa.tv_feat = w.tv_feat; fa.tv_d_list = bw.d_feat; fa.tv_partial = w.tv_partial;
             fa.tv_scale_dev = t->loss_weights != nullptr ? t->loss_weights + 8 : nullptr;
             fa.tv_scale_host = t->smooth_grad_scale != 0.0f ? t->smooth_grad_scale : 1.0f;
             fa.tv_n_blocks = w.n_tv_blocks;
@@ -1640,7 +1650,6 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
     }
     const bool smooth = t->smooth_points != 0 && (g->table != nullptr || opt != nullptr);
     const uint32_t n_front = smooth ? w.n3 : 0u;
-    const BwdWs bw = bwd_ws(f, w.bwd, list_cap(M + w.n3));
     if (!table_only && !deferred) {
         if (int rc = loss_bwd_compact(f, t, w, la, n_front, bw.n_total, st)) return rc;
     }
@@ -1659,19 +1668,21 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
         if (int rc2 = assemble_args(opt->next_batch, true, next_args, "train_backward (next_batch)")) return rc2;
         if (next_args.n_global + next_args.n_cur != 0u) next = &next_args;
     }
-    const void* w_img = deferred ? w.w_img : nullptr;            // prepared by k_loss_bwd_fused just above
     TvLate tvl{};
-    const bool late = moved;
-    if (late) { tvl.tv_partial = w.tv_partial; tvl.n_tv_blocks = w.n_tv_blocks; tvl.inv_p3 = tv_args(t).inv_p3; tvl.losses = t->losses; tvl.loss_weights = t->loss_weights; }
-    int rc;
-    const bool feat_sm = train_fwd_plan(f, t, true, false).form == FwdForm::Sorted;      // the layout the forward of this plan left feat_save in
-    if (n_front > 0)
-        rc = query_bwd_impl(f, p, M, &pts, t->feat_save, t->d_raw, nullptr, t->active_idx, t->n_active, nullptr, flags, g, w.bwd, stream, n_front, bw.n_total, ad, w_img,
-                            (late && ad != nullptr) ? &tvl : nullptr, next, feat_sm);
-    else        // no smoothness term: the workspace was sized for cap = M + n3 with n3 = 0
-        rc = query_bwd_impl(f, p, M, &pts, t->feat_save, t->d_raw, nullptr, t->active_idx, t->n_active, nullptr, flags, g, w.bwd, stream, 0u, nullptr, ad, w_img, nullptr, next, feat_sm);
-    if (rc != NARUTO_OK) return rc;
-    if (late && ad == nullptr) {                                 // no optimiser in the backward: the value gets a (tiny) launch of its own
+    if (moved) { tvl.tv_partial = w.tv_partial; tvl.n_tv_blocks = w.n_tv_blocks; tvl.inv_p3 = c.tva.inv_p3; tvl.losses = t->losses; tvl.loss_weights = t->loss_weights; }
+    QueryBwd q{};
+    q.M = M; q.pts = &pts; q.feat_save = t->feat_save; q.d_raw = t->d_raw;
+    q.active_idx = t->active_idx; q.n_active = t->n_active;
+    q.flags = flags; q.g = g; q.workspace = w.bwd; q.stream = st;
+    q.n_front = n_front;            // (0: no smoothness term in this backward -- the list is the samples alone, in a workspace sized for cap = M + n3)
+    q.n_list_dev = n_front > 0 ? bw.n_total : nullptr;
+    q.adam = ad;
+    q.w_img = deferred ? w.w_img : nullptr;                      // prepared by k_loss_bwd_fused just above
+    q.tv_late = (moved && ad != nullptr) ? &tvl : nullptr;
+    q.next = next;
+    q.feat_sample_major = pl.form == FwdForm::Sorted;            // the layout the forward of this plan left feat_save in
+    if (int rc = query_bwd_impl(f, p, q)) return rc;
+    if (moved && ad == nullptr) {                                 // no optimiser in the backward: the value gets a (tiny) launch of its own
         hipLaunchKernelGGL(k_tv_late, dim3(1), dim3(256), 0, st, tvl);
         return check_launch("tv_late");
     }
@@ -1680,8 +1691,7 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
 
 int naruto_render_fwd(const NarutoField* f, const NarutoParams* p, const NarutoRender* r, void* stream) {
     if (f == nullptr || p == nullptr || r == nullptr) return fail(NARUTO_ERR_INVALID, "render_fwd: NULL argument");
-    if (p->table == nullptr || p->uncert_grid == nullptr || p->sdf_w0 == nullptr || p->sdf_w1 == nullptr || p->col_w0 == nullptr || p->col_w1 == nullptr)
-        return fail(NARUTO_ERR_INVALID, "render_fwd: NULL parameter");
+    if (int rc = check_params(p, "render_fwd")) return rc;
     if (r->n_rays == 0) return NARUTO_OK;
     if (r->rays_o == nullptr || r->rays_d == nullptr) return fail(NARUTO_ERR_INVALID, "render_fwd: NULL rays");
     RenderArgs a{};
@@ -2787,6 +2797,31 @@ TrackArgs track_args(const NarutoTrackStep* k, const NarutoTrainStep* t) {
     a.trace_loss = k->trace_loss; a.trace_pose = k->trace_pose; a.trace_d_pose = k->trace_d_pose; a.max_trace = k->max_trace;
     return a;
 }
+
+// The gradient of the iteration's loss with respect to its rays, after the loss backward and the compaction: naruto_query_bwd_points' launches for
+// ray points over the active list, written (not accumulated) into d_rays_o / d_rays_d.  The zero fill is a kernel, so that a captured call stays one
+// chain of kernel nodes.  `workspace`: naruto_track_workspace / naruto_ba_poses_workspace bytes; `who` heads a failed launch's message.
+int launch_ray_point_grads(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, void* workspace, float* d_rays_o, float* d_rays_d, const char* who,
+                           hipStream_t st) {
+    const uint32_t S = t->n_samples_d + t->n_range_d, M = t->n_rays * S;
+    NarutoPoints pts{};
+    pts.rays_o = t->rays_o; pts.rays_d = t->rays_d; pts.z_vals = t->z_vals; pts.n_samples = S;
+    if (int rc = check_points(&pts)) return rc;
+    auto launched = [who](const char* kernel) {
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? NARUTO_OK : fail(NARUTO_ERR_LAUNCH, "%s: %s: %s", who, kernel, hipGetErrorString(e));
+    };
+    float* gp = point_grad_ws(workspace, M).d_x;
+    const uint64_t n_gp = 3u * (uint64_t)M;
+    hipLaunchKernelGGL(k_track_zero, dim3((uint32_t)((n_gp + 255u) / 256u)), dim3(256), 0, st, gp, n_gp);
+    if (int rc = launched("zero")) return rc;
+    hipLaunchKernelGGL(k_query_bwd_points, dim3((M + (uint32_t)kPgThreads - 1u) / (uint32_t)kPgThreads), dim3(kPgThreads), 0, st, f->lt, f->ut, f->bt, make_points(&pts), M,
+                       reinterpret_cast<const float2*>(p->table), p->uncert_grid, p->sdf_w0, p->sdf_w1, p->col_w0, p->col_w1, t->d_raw, nullptr, t->active_idx,
+                       t->n_active, gp, 1, 0);
+    if (int rc = launched("query_bwd_points")) return rc;
+    hipLaunchKernelGGL(k_ray_point_reduce, dim3((t->n_rays + 3u) / 4u), dim3(256), 0, st, t->n_rays, S, gp, t->z_vals, d_rays_o, d_rays_d, 0);
+    return launched("ray_point_reduce");
+}
 }  // namespace
 
 size_t naruto_track_workspace(const NarutoField*, uint32_t n_rays, uint32_t n_samples) {
@@ -2814,26 +2849,11 @@ int naruto_track_backward(const NarutoField* f, const NarutoParams* p, const Nar
     if (t->loss_weights == nullptr || t->d_raw == nullptr || t->ray_count == nullptr || t->ray_offset == nullptr || t->active_idx == nullptr || t->n_active == nullptr)
         return fail(NARUTO_ERR_INVALID, "track_backward: NULL buffer in NarutoTrainStep");
     const hipStream_t st = (hipStream_t)stream;
-    const uint32_t S = t->n_samples_d + t->n_range_d, M = t->n_rays * S;
-    if (M > (1u << 29)) return fail(NARUTO_ERR_INVALID, "track_backward: at most 2^29 samples per iteration (got %u)", M);
-    const TrainWs w = train_ws(f, t);
-    const BwdWs bw = bwd_ws(f, w.bwd, list_cap(M + w.n3));
+    const TrainCtx c = train_ctx(f, t);
+    if (c.M > (1u << 29)) return fail(NARUTO_ERR_INVALID, "track_backward: at most 2^29 samples per iteration (got %u)", c.M);
     if (int rc = ray_lds_attr()) return rc;
-    if (int rc = loss_bwd_compact(f, t, w, train_loss_args(f, t), 0u, bw.n_total, st)) return rc;
-    // naruto_query_bwd_points' launches for ray points over the active list (its zero fill as a kernel)
-    NarutoPoints pts{};
-    pts.rays_o = t->rays_o; pts.rays_d = t->rays_d; pts.z_vals = t->z_vals; pts.n_samples = S;
-    if (int rc = check_points(&pts)) return rc;
-    float* gp = point_grad_ws(k->workspace, M).d_x;
-    const uint64_t n_gp = 3u * (uint64_t)M;
-    hipLaunchKernelGGL(k_track_zero, dim3((uint32_t)((n_gp + 255u) / 256u)), dim3(256), 0, st, gp, n_gp);
-    if (int rc = check_launch("track_zero")) return rc;
-    hipLaunchKernelGGL(k_query_bwd_points, dim3((M + (uint32_t)kPgThreads - 1u) / (uint32_t)kPgThreads), dim3(kPgThreads), 0, st, f->lt, f->ut, f->bt, make_points(&pts), M,
-                       reinterpret_cast<const float2*>(p->table), p->uncert_grid, p->sdf_w0, p->sdf_w1, p->col_w0, p->col_w1, t->d_raw, nullptr, t->active_idx,
-                       t->n_active, gp, 1, 0);
-    if (int rc = check_launch("query_bwd_points")) return rc;
-    hipLaunchKernelGGL(k_ray_point_reduce, dim3((t->n_rays + 3u) / 4u), dim3(256), 0, st, t->n_rays, S, gp, t->z_vals, k->d_rays_o, k->d_rays_d, 0);
-    if (int rc = check_launch("ray_point_reduce")) return rc;
+    if (int rc = loss_bwd_compact(f, t, c.w, train_loss_args(f, t), 0u, c.bw.n_total, st)) return rc;
+    if (int rc = launch_ray_point_grads(f, p, t, k->workspace, k->d_rays_o, k->d_rays_d, "track_backward", st)) return rc;
     hipLaunchKernelGGL(k_track_step, dim3(1), dim3(kTrackStepThreads), 0, st, track_args(k, t));
     return check_launch("track_step");
 }
@@ -2877,23 +2897,9 @@ BAPoseArgs ba_pose_args(const NarutoBAPoses* b, const NarutoTrainStep* t) {
     return a;
 }
 
-// after the loss backward and the compaction: naruto_query_bwd_points' launches for ray points over the active list (its zero fill as a
-// kernel: a captured call stays one chain of kernel nodes), the per-pose sums and the pose step
+// after the loss backward and the compaction: the rays' gradients, the per-pose sums and the pose step
 int ba_poses_launch(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const NarutoBAPoses* b, hipStream_t st) {
-    const uint32_t S = t->n_samples_d + t->n_range_d, M = t->n_rays * S;
-    NarutoPoints pts{};
-    pts.rays_o = t->rays_o; pts.rays_d = t->rays_d; pts.z_vals = t->z_vals; pts.n_samples = S;
-    if (int rc = check_points(&pts)) return rc;
-    float* gp = point_grad_ws(b->workspace, M).d_x;
-    const uint64_t n_gp = 3u * (uint64_t)M;
-    hipLaunchKernelGGL(k_track_zero, dim3((uint32_t)((n_gp + 255u) / 256u)), dim3(256), 0, st, gp, n_gp);
-    if (int rc = check_launch("ba_poses: zero")) return rc;
-    hipLaunchKernelGGL(k_query_bwd_points, dim3((M + (uint32_t)kPgThreads - 1u) / (uint32_t)kPgThreads), dim3(kPgThreads), 0, st, f->lt, f->ut, f->bt, make_points(&pts), M,
-                       reinterpret_cast<const float2*>(p->table), p->uncert_grid, p->sdf_w0, p->sdf_w1, p->col_w0, p->col_w1, t->d_raw, nullptr, t->active_idx,
-                       t->n_active, gp, 1, 0);
-    if (int rc = check_launch("ba_poses: query_bwd_points")) return rc;
-    hipLaunchKernelGGL(k_ray_point_reduce, dim3((t->n_rays + 3u) / 4u), dim3(256), 0, st, t->n_rays, S, gp, t->z_vals, b->d_rays_o, b->d_rays_d, 0);
-    if (int rc = check_launch("ba_poses: ray_point_reduce")) return rc;
+    if (int rc = launch_ray_point_grads(f, p, t, b->workspace, b->d_rays_o, b->d_rays_d, "ba_poses", st)) return rc;
     const BAPoseArgs a = ba_pose_args(b, t);
     hipLaunchKernelGGL(k_ba_pose_accum, dim3(b->max_poses), dim3(kBaPoseThreads), 0, st, a);
     if (int rc = check_launch("ba_pose_accum")) return rc;

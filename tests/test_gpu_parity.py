@@ -1653,9 +1653,10 @@ def test_backward_refuses_a_forward_that_left_the_smoothness_term_unannounced(gp
     N = 64
     rays = syn.random_rays(N, cfg["mapping"]["bound"], seed=19)
     w = torch.tensor([tr["rgb_weight"], tr["depth_weight"], tr["sdf_weight"], tr["fs_weight"], 0.0, tr["uncert_weight"], 0.0, 0.0, 0.1, 0.0])
-    ts = ops.TrainStep(m._handle(), m._params(), torch.zeros_like(m.uncert_grid), N, n_samples_d=tr["n_samples_d"], n_range_d=tr["n_range_d"],
-                       near=cam["near"], far=cam["far"], range_d=tr["range_d"], depth_trunc=cam["depth_trunc"], rgb_missing=tr["rgb_missing"],
-                       perturb=True, loss_weights=w.to(gpu), smooth=(12, 0.1, 0.05), device_rng=True, seed=5)
+    step = lambda: ops.TrainStep(m._handle(), m._params(), torch.zeros_like(m.uncert_grid), N, n_samples_d=tr["n_samples_d"], n_range_d=tr["n_range_d"],
+                                 near=cam["near"], far=cam["far"], range_d=tr["range_d"], depth_trunc=cam["depth_trunc"], rgb_missing=tr["rgb_missing"],
+                                 perturb=True, loss_weights=w.to(gpu), smooth=(12, 0.1, 0.05), device_rng=True, seed=5)
+    ts = step()
     args = [torch.from_numpy(rays[k]).to(gpu).contiguous() for k in ("rays_o", "rays_d", "target_rgb")] + [torch.from_numpy(rays["target_d"]).to(gpu).reshape(-1).contiguous()]
     ts.run(*args)                                           # fills the step's pointers; an ordinary iteration
     lib = _lib.load()
@@ -1670,6 +1671,15 @@ def test_backward_refuses_a_forward_that_left_the_smoothness_term_unannounced(gp
     assert rc != 0 and b"NARUTO_TRAIN_BWD_TV_MOVED" in lib.naruto_last_error()
     assert bwd(_lib.TRAIN_BWD_SUMS_GIVEN | _lib.TRAIN_BWD_TV_MOVED) == 0
     assert fwd(0) == 0 and bwd(_lib.TRAIN_BWD_SUMS_GIVEN) == 0          # a forward that evaluated the term itself: nothing to announce
+    # the record outlives any number of other workspaces' iterations in between (a ring of 16 records once forgot it here)
+    assert fwd(_lib.TRAIN_FWD_SUMS_TV_LATER) == 0
+    others = [step() for _ in range(17)]                    # all alive at once: seventeen further workspace addresses
+    for o in others:
+        o.run(*args)
+    rc = bwd(_lib.TRAIN_BWD_SUMS_GIVEN)
+    assert rc != 0 and b"NARUTO_TRAIN_BWD_TV_MOVED" in lib.naruto_last_error()
+    assert bwd(_lib.TRAIN_BWD_SUMS_GIVEN | _lib.TRAIN_BWD_TV_MOVED) == 0
+    assert fwd(0) == 0 and bwd(_lib.TRAIN_BWD_SUMS_GIVEN) == 0
     torch.cuda.synchronize()
 
 
