@@ -44,8 +44,6 @@ re-captured when the switch changes, not when P grows."""
 
 from __future__ import annotations
 
-import contextlib
-import gc
 import os
 from typing import Dict, Optional
 
@@ -53,27 +51,9 @@ import torch
 
 from . import _lib
 from .active_ray_sampler import ActiveRaySamplerHIP
+from .capture import no_collection, parked, preserved, release_parked
 from .keyframe_store import KeyFrameStoreHIP
-from .trainer import MappingTrainer
-
-
-# graphs a FusedBA had to drop while somebody's stream capture was under way (its finaliser ran inside the capture: destroying a graph
-# there ends the capture with an error); released by the next prepare() outside a capture
-_PARKED_GRAPHS = []
-
-
-@contextlib.contextmanager
-def _no_collection():
-    """Around a stream capture: the garbage there is is collected first, and the cyclic collector rests until the capture has ended --
-    a finaliser that frees graphs or device memory (a dropped FusedBA / MappingTrainer) must not run inside it."""
-    gc.collect()
-    was = gc.isenabled()
-    gc.disable()
-    try:
-        yield
-    finally:
-        if was:
-            gc.enable()
+from .trainer import MappingTrainer, unpack_rays
 
 
 class FusedBA:
@@ -95,12 +75,14 @@ class FusedBA:
         # iteration counter that keys the draw has been advanced -- so only the FIRST iteration of a global_BA call launches k_assemble_rays
         # itself.  Same batches, same trajectory (tests: the graph twin prefetches, the eager twin does not).
         self.prefetch = (os.environ.get("NARUTO_BA_PREFETCH", "1") != "0") if prefetch is None else bool(prefetch)
-        self._armed = None            # the TrainStep whose finishing launch draws the next batch (it holds the struct and its keep-alives)
         # ... and with active rays that assembly also looks the candidates' keys up (NarutoRayBatch.keys_out): the selection in front of the
         # next forward starts from the keys (naruto_active_ray_select_keyed) instead of two dependent trips to memory per candidate.
         # NARUTO_BA_KEYED_SELECT=0 switches it off.
         self.keyed = sampler is not None and os.environ.get("NARUTO_BA_KEYED_SELECT", "1") != "0"
         self._keys = None
+        # the TrainStep this object last hung its riders on (TrainStep.attach: the next-batch draw, the pose refinement); the step holds
+        # them and knows whose they are
+        self._armed = None
         # CALL GRAPH (round 5; NARUTO_BA_CALL_GRAPH=0 switches it off): the mapping.iters iterations of a global_BA call recorded as ONE graph
         # next to the per-iteration graphs -- a call of the configured length is one graph launch
         self.call_graph = use_graph and os.environ.get("NARUTO_BA_CALL_GRAPH", "1") != "0"
@@ -130,7 +112,6 @@ class FusedBA:
         self._pose = None             # the per-pose device buffers (allocated on first use)
         self._bap = None              # the NarutoBAPoses of the current shape
         self._pose_on = False         # this call refines poses
-        self._pose_ts = None          # the TrainStep whose backward carries self._bap
         self._n_poses = 0
         self._init_c2w = None
 
@@ -143,57 +124,76 @@ class FusedBA:
         n_train = self.sampler.n_out(n_cur) if self.active else self.sample_num + n_cur
         return n_cur, n_train
 
-    def _later_prologue(self, n_cur: int):
-        """With prefetch: what an iteration that finds its batch assembled still has to launch (the selection), or None."""
-        if not self.active:
-            return None
-        sampler = self.sampler
-
-        def prologue(rays_o, rays_d, target_rgb, target_d):
-            # (the candidates' keys were looked up by the assembly that rode in the previous iteration's finishing launch)
-            sampler.sample_rays(*self._stage, n_cur, None, self.bbox, out=(rays_o, rays_d, target_rgb, target_d), workspace=self._ws,
-                                keys=self._keys if self._keyed(n_cur) else None, src_rows=self._src_rows())
-        return prologue
-
     def _keyed(self, n_cur: int) -> bool:
         return self.keyed and self.sample_num + n_cur - self.sampler.n_out(n_cur) <= 8192
 
-    def _arm_prefetch(self, n_cur: int, bufs, train_step):
-        """Point the fused optimiser's next_batch at the draw of the NEXT iteration (into the stage when active rays select from it, else
-        straight into the iteration's own input buffers)."""
-        out = self._stage if self.active else bufs
-        keys = self.sampler.key_lookup(self.sample_num + n_cur, n_cur, self.bbox, self._keys) if (self.active and self._keyed(n_cur)) else None
-        b, keep = self.store.next_batch_struct(self.sample_num, self.current, self.poses, self.min_pixels_cur, out, filter_depth=self.filter_depth,
-                                               rng=self.trainer.iter_state, dyn=self.dyn, n_cur=n_cur, n_cur_pop=self._n_cur_pop, keys=keys,
-                                               ids_out=self._ids())
-        assert train_step.opt is not None, "prefetch needs the optimiser in the backward (MappingTrainer(fused_adam=True))"
-        import ctypes as C
-        self._disarm_prefetch()
-        # the struct and everything it points into live ON the TrainStep whose backward reads them (the trainer's cache and a captured graph's
-        # _static['ts'] outlive this object): the host pointer in opt.next_batch can never dangle
-        train_step._next_batch_keep = (b, keep)
-        train_step.opt.next_batch = C.cast(C.pointer(b), C.c_void_p)
-        self._armed = train_step
+    def _assemble(self, out, n_cur: int, keyed: bool = False, call=None, frame_only: bool = False):
+        """The batch draw into ``out``, its argument list stated once: launched (``assemble_batch``) or, with
+        ``call=self.store.next_batch_struct``, described for the fused optimiser's next_batch.  ``keyed``: the assembly looks the
+        candidates' keys up while the rows are in registers (NarutoRayBatch.keys_out).  ``frame_only``: first-frame mapping -- no stored
+        ray, every pixel of the frame a candidate."""
+        sample_num, filter_depth = (0, False) if frame_only else (self.sample_num, self.filter_depth)
+        keys = self.sampler.key_lookup(self.sample_num + n_cur, n_cur, self.bbox, self._keys) if keyed else None
+        return (call or self.store.assemble_batch)(sample_num, self.current, self.poses, self.min_pixels_cur, out=out, filter_depth=filter_depth,
+                                                   rng=self.trainer.iter_state, dyn=self.dyn, n_cur=n_cur, n_cur_pop=self._n_cur_pop, keys=keys,
+                                                   ids_out=self._ids())
 
-    def _disarm_prefetch(self):
-        """Take the next-batch draw off the TrainStep it rides on: its backward no longer assembles anything (and no longer overwrites the stage /
-        ray buffers of this object).  Called on re-arm, on close() and when this object is dropped."""
-        ts = getattr(self, "_armed", None)
-        self._armed = None
-        if ts is not None and getattr(ts, "opt", None) is not None:
-            ts.opt.next_batch = None
-            ts._next_batch_keep = None
+    def _select(self, bufs, n_cur: int, keyed: bool):
+        """The active ray selection from the stage into ``bufs`` (``keyed``: starting from the keys the assembly looked up)."""
+        self.sampler.sample_rays(*self._stage, n_cur, None, self.bbox, out=bufs, workspace=self._ws, keys=self._keys if keyed else None,
+                                 src_rows=self._src_rows())
+
+    def _prologue(self, n_cur: int):
+        def prologue(*bufs):
+            if not self.active:
+                self._assemble(bufs, n_cur)
+            elif self.one_launch_prologue and self.sample_num + n_cur - self.sampler.n_out(n_cur) <= 8192:
+                # assembly + selection in one launch (naruto_assemble_select): the oversampled batch is never written
+                assert not self._pose_on
+                self.store.assemble_select(self.sampler, self.sample_num, self.current, self.poses, self.min_pixels_cur, self.bbox, out=bufs,
+                                           filter_depth=self.filter_depth, rng=self.trainer.iter_state, dyn=self.dyn, n_cur=n_cur, n_cur_pop=self._n_cur_pop)
+            else:
+                keyed = self._keyed(n_cur)
+                self._assemble(self._stage, n_cur, keyed)
+                self._select(bufs, n_cur, keyed)
+        return prologue
+
+    def _later_prologue(self, n_cur: int):
+        """With prefetch: what an iteration that finds its batch assembled still has to launch (the selection; the candidates' keys were
+        looked up by the assembly that rode in the previous iteration's finishing launch), or None."""
+        return (lambda *bufs: self._select(bufs, n_cur, self._keyed(n_cur))) if self.active else None
+
+    def _attach(self, train_step, next_batch=None):
+        """This object's riders onto ``train_step`` -- the pose refinement while a call refines poses, ``next_batch`` -- and off the step
+        they rode on before."""
+        if self._armed is not None and self._armed is not train_step:
+            self._armed.detach(self)
+        ba_poses = self._bap if self._pose_on else None
+        train_step.attach(self, next_batch=next_batch, ba_poses=ba_poses)
+        self._armed = train_step if (next_batch is not None or ba_poses is not None) else None
+
+    def _arm(self, n_cur: int, bufs, train_step):
+        """``_attach`` with the draw of the NEXT iteration as the fused optimiser's next_batch when this object prefetches (into the stage
+        when active rays select from it, else straight into the iteration's own input buffers).  The struct and everything it points
+        into live ON the TrainStep whose backward reads them (the trainer's cache and a captured graph's _static['ts'] outlive this
+        object): the host pointer in opt.next_batch can never dangle."""
+        self._attach(train_step, self._assemble(self._stage if self.active else bufs, n_cur, self.active and self._keyed(n_cur),
+                                                call=self.store.next_batch_struct) if self.prefetch else None)
+
+    def _detach(self):
+        """Take this object's riders off the TrainStep they ride on: its backward no longer assembles anything (and no longer overwrites
+        the stage / ray buffers of this object) nor refines poses.  Somebody else's riders on that step stay."""
+        ts, self._armed = getattr(self, "_armed", None), None
+        return ts is not None and ts.detach(self)
 
     def close(self):
-        """Detach from the trainer: the TrainStep this object armed keeps working as a plain training step (trainer.step, first_frame_mapping).
-        A graph captured with the prefetch inside is dropped (its finishing launch would go on drawing batches)."""
-        armed = getattr(self, "_armed", None)
-        pose_ts = getattr(self, "_pose_ts", None)
+        """Detach from the trainer: the TrainStep this object rode on keeps working as a plain training step (trainer.step,
+        first_frame_mapping).  Graphs captured with this object's riders inside are dropped (their finishing launch would go on drawing
+        batches) -- not the graphs another FusedBA has captured on the same TrainStep since."""
         st = getattr(self.trainer, "_static", None)
-        if self.use_graph and st is not None and ((armed is not None and st.get('ts') is armed) or (pose_ts is not None and st.get('ts') is pose_ts)):
+        captured = getattr(self, "_armed", None) is not None and st is not None and st.get('ts') is self._armed
+        if self._detach() and captured and self.use_graph:
             self._drop_graphs()
-        self._disarm_prefetch()
-        self._detach_poses()
         self._shape = None
 
     def _drop_graphs(self):
@@ -201,7 +201,7 @@ class FusedBA:
         finaliser can run in somebody else's -- the graph objects are parked instead of destroyed."""
         tr = self.trainer
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            _PARKED_GRAPHS.append((tr._graphs, getattr(tr, "_static", None)))
+            parked((tr._graphs, getattr(tr, "_static", None)))
         tr._graphs = None
 
     def __del__(self):
@@ -209,33 +209,6 @@ class FusedBA:
             self.close()
         except Exception:
             pass
-
-    def _prologue(self, n_cur: int):
-        store, sampler = self.store, self.sampler
-        rng = self.trainer.iter_state
-
-        def prologue(rays_o, rays_d, target_rgb, target_d):
-            kw = dict(filter_depth=self.filter_depth, rng=rng, dyn=self.dyn, n_cur=n_cur, n_cur_pop=self._n_cur_pop)
-            if self._pose_on:
-                kw["ids_out"] = self._ids()
-            if not self.active:
-                store.assemble_batch(self.sample_num, self.current, self.poses, self.min_pixels_cur, out=(rays_o, rays_d, target_rgb, target_d), **kw)
-                return
-            if self.one_launch_prologue and self.sample_num + n_cur - sampler.n_out(n_cur) <= 8192:
-                # assembly + selection in one launch (naruto_assemble_select): the oversampled batch is never written
-                assert not self._pose_on
-                store.assemble_select(sampler, self.sample_num, self.current, self.poses, self.min_pixels_cur, self.bbox,
-                                      out=(rays_o, rays_d, target_rgb, target_d), **kw)
-                return
-            if self._keyed(n_cur):         # the assembly looks the candidates' keys up while the rows are in registers (NarutoRayBatch.keys_out)
-                store.assemble_batch(self.sample_num, self.current, self.poses, self.min_pixels_cur, out=self._stage,
-                                     keys=sampler.key_lookup(self.sample_num + n_cur, n_cur, self.bbox, self._keys), **kw)
-                sampler.sample_rays(*self._stage, n_cur, None, self.bbox, out=(rays_o, rays_d, target_rgb, target_d), workspace=self._ws, keys=self._keys,
-                                    src_rows=self._src_rows())
-                return
-            store.assemble_batch(self.sample_num, self.current, self.poses, self.min_pixels_cur, out=self._stage, **kw)
-            sampler.sample_rays(*self._stage, n_cur, None, self.bbox, out=(rays_o, rays_d, target_rgb, target_d), workspace=self._ws, src_rows=self._src_rows())
-        return prologue
 
     # --------------------------------------------------------------------------------------------- pose refinement
     def _ids(self):
@@ -297,22 +270,6 @@ class FusedBA:
         b.workspace = pb["ws"].data_ptr()
         self._bap = b
 
-    def _attach_poses(self, train_step):
-        """Hang the pose refinement on the TrainStep this object's iterations run on (or take it off: a plain call)."""
-        old = self._pose_ts
-        if old is not None and old is not train_step:
-            old.ba_poses = None
-        want = self._bap if self._pose_on else None
-        if train_step.ba_poses is not want:
-            train_step.ba_poses = want
-        self._pose_ts = train_step if want is not None else None
-
-    def _detach_poses(self):
-        ts = getattr(self, "_pose_ts", None)
-        self._pose_ts = None
-        if ts is not None:
-            ts.ba_poses = None
-
     def refined_poses(self) -> torch.Tensor:
         """The P poses of the last ``prepare`` / ``global_BA`` as they stand now, [P,4,4] float32 on the device: refined where the call
         optimised them, the caller's bits otherwise.  The caller writes them back to ``est_c2w_data`` (coslam.py:401-407)."""
@@ -341,8 +298,7 @@ class FusedBA:
         ``pose_init_on_device``: the (omega, t) of the P poses come from ``naruto_pose_log`` over ``self.poses[:P]`` on the device instead
         of the host conversion -- same branches and formulas, no wait for the host (the run loop's tracked frames)."""
         dev = self.device
-        if _PARKED_GRAPHS and not torch.cuda.is_current_stream_capturing():
-            del _PARKED_GRAPHS[:]
+        release_parked()
         want_poses = self.optimize_poses if optimize_poses is None else bool(optimize_poses)
         if want_poses:
             self._check_pose_refinement()
@@ -395,7 +351,7 @@ class FusedBA:
             self._vol_ptr = vol.data_ptr()
         n_cur, n_train = self.sizes(n_kf, n_valid)
         if self._shape != (n_cur, n_train, smooth, pose_on) or (vol_moved and (self.use_graph or self.keyed)):
-            self._detach_poses()
+            self._detach()
             self._pose_on = pose_on
             if pose_on:
                 self._build_bap(n_cur, n_train)
@@ -405,28 +361,9 @@ class FusedBA:
                 self._stage = (torch.empty(n_stage, 3, **f32), torch.empty(n_stage, 3, **f32), torch.empty(n_stage, 3, **f32), torch.empty(n_stage, 1, **f32))
                 self._ws = _lib.workspace(4 * self.sampler.workspace_elems(n_stage), dev, torch.int32)
                 self._keys = torch.zeros(n_stage, dtype=torch.int32, device=dev)
-            self._pro = self._prologue(n_cur)
-            self._pro_later = self._later_prologue(n_cur) if self.prefetch else self._pro
-            if self.use_graph:
-                chain = [(i + 1) % 5 == 0 for i in range(int(self.config['mapping']['iters']))] if self.call_graph else None
-                with _no_collection():
-                    if self.prefetch:
-                        self.trainer.capture(n_train, smooth=smooth, prologue=self._pro_later, first_prologue=self._pro, chain=chain,
-                                             on_buffers=lambda ro, rd, tc, td, ts: (self._arm_prefetch(n_cur, (ro, rd, tc, td), ts), self._attach_poses(ts)))
-                    else:
-                        self.trainer.capture(n_train, smooth=smooth, prologue=self._pro, chain=chain,
-                                             on_buffers=lambda ro, rd, tc, td, ts: self._attach_poses(ts))
-            else:
-                f = torch.zeros(n_train * 10, **f32)
-                from .trainer import unpack_rays
-                self._eager_bufs = unpack_rays(f, n_train)
-                self.trainer._graphs = None
-                self._disarm_prefetch()
-                tr_cfg = self.config['training']
-                ts0 = self.trainer._train_step(n_train, bool(smooth and tr_cfg['smooth_weight'] > 0))
-                if self.prefetch:
-                    self._arm_prefetch(n_cur, self._eager_bufs, ts0)
-                self._attach_poses(ts0)
+            pro = self._prologue(n_cur)
+            chain = [(i + 1) % 5 == 0 for i in range(int(self.config['mapping']['iters']))] if self.call_graph else None
+            self._drive(n_train, smooth, pro, self._later_prologue(n_cur) if self.prefetch else pro, lambda bufs, ts: self._arm(n_cur, bufs, ts), chain)
             self._shape = (n_cur, n_train, smooth, pose_on)
         if pose_on:
             # the call's reset: (omega, t) <- the upload, moments / sums / counts zeroed, the parameter poses' matrices from R(omega) -- after
@@ -438,31 +375,57 @@ class FusedBA:
             self._init_c2w = self.poses[:P].clone()
         return n_cur, n_train
 
-    def iteration(self, i: int, smooth: bool = True):
-        """Iteration ``i`` (0-based) of the current ``global_BA`` call: the uncertainty grid's Adam steps after iterations 5, 10, ...
-        (coslam.py:397-399)."""
+    def _drive(self, n_train: int, smooth: bool, first_prologue, later_prologue, arm, chain=None):
+        """Set the trainer up for this object's iterations of ``n_train`` rays.  Graph mode: capture them, ``later_prologue`` in front of
+        every iteration and, with prefetch, ``first_prologue`` in front of a call's first (the later ones find their batch drawn by the
+        preceding iteration's last launch; without prefetch the two are the same), ``chain`` as ``MappingTrainer.capture`` takes it.
+        Eager mode: the iterations' own ray buffers.  Either way ``arm(bufs, train_step)`` hangs this object's riders on the step."""
+        self._pro, self._pro_later, self._driven = first_prologue, later_prologue, (n_train, smooth, arm, chain)
         tr = self.trainer
         if self.use_graph:
+            with no_collection():
+                tr.capture(n_train, smooth=smooth, prologue=later_prologue, first_prologue=first_prologue if self.prefetch else None, chain=chain,
+                           on_buffers=lambda *a: arm(a[:4], a[4]))
+        else:
+            self._eager_bufs = unpack_rays(torch.zeros(n_train * 10, dtype=torch.float32, device=self.device), n_train)
+            tr._graphs = None
+            arm(self._eager_bufs, tr.train_step_for(n_train, smooth))
+
+    def _iterate(self, i: int, smooth: bool, uncert_step: bool):
+        tr = self.trainer
+        n_train, _, arm, chain = self._driven
+        if self.use_graph:
+            dropped = tr.ray_buffers() is None
+            if dropped:
+                # somebody took the trainer's graphs away (another FusedBA on the same trainer, trainer._graphs = None): capture again,
+                # the poses being refined put back like the rest of the training state, and assemble this iteration's batch here -- nothing
+                # prefetched it (the draw is keyed by the iteration counter: assembling twice is idempotent)
+                pose_state = [self.poses] + [v for v in self._pose.values() if torch.is_tensor(v)] if self._pose_on else []
+                with preserved(pose_state):
+                    self._drive(n_train, smooth, self._pro, self._pro_later, arm, chain)
             bufs = tr.ray_buffers()
-            return tr.step(*bufs, smooth=smooth, uncert_step=(i + 1) % 5 == 0, first=(i == 0))           # the replay starts with the prologue's launches
+            if dropped:
+                self._pro(*bufs)
+            return tr.step(*bufs, smooth=smooth, uncert_step=uncert_step, first=(i == 0))           # the replay starts with the prologue's launches
         bufs = self._eager_bufs
         full = i == 0 or not self.prefetch
-        if self._pose_on or self._pose_ts is not None:
-            tr_cfg = self.config['training']
-            self._attach_poses(tr._train_step(bufs[0].shape[0], bool(smooth and tr_cfg['smooth_weight'] > 0)))
-        if self.prefetch:
-            # the TrainStep this iteration WILL run on (the trainer's cache is keyed on (n_rays, smooth, n_rays_total) and evicts): if it is not
-            # the one whose finishing launch draws the batches, nothing drew this iteration's batch and nothing would draw the next one --
-            # arm it and assemble this batch with the full prologue (the draw is keyed by the iteration counter: assembling twice is idempotent)
-            tr_cfg = self.config['training']
-            ts = tr._train_step(bufs[0].shape[0], bool(smooth and tr_cfg['smooth_weight'] > 0))
-            if ts is not self._armed or ts.opt is None or not ts.opt.next_batch:
-                self._arm_prefetch(self._shape[0], bufs, ts)
-                full = True
+        # the TrainStep this iteration WILL run on (the trainer's cache is keyed on (n_rays, smooth, n_rays_total) and evicts, and another
+        # FusedBA may have taken it over): if this object's riders are not on it, nothing drew this iteration's batch and nothing would draw
+        # the next one -- arm it and assemble this batch with the full prologue
+        ts = tr.train_step_for(n_train, smooth)
+        drawn, refined = ts.riders_of(self)
+        if (self.prefetch and drawn is None) or refined is not (self._bap if self._pose_on else None):
+            arm(bufs, ts)
+            full = True
         pro = self._pro if full else self._pro_later
         if pro is not None:
             pro(*bufs)
-        return tr.step(*bufs, smooth=smooth, uncert_step=(i + 1) % 5 == 0)
+        return tr.step(*bufs, smooth=smooth, uncert_step=uncert_step)
+
+    def iteration(self, i: int, smooth: bool = True):
+        """Iteration ``i`` (0-based) of the current ``global_BA`` call: the uncertainty grid's Adam steps after iterations 5, 10, ...
+        (coslam.py:397-399)."""
+        return self._iterate(i, smooth, (i + 1) % 5 == 0)
 
     def global_BA(self, current_rays: Optional[torch.Tensor], poses_all: torch.Tensor, n_iters: Optional[int] = None, uncert_vol=None, smooth: bool = True,
                   optimize_poses: Optional[bool] = None, n_valid: Optional[int] = None, pose_init_on_device: bool = False):
@@ -487,61 +450,34 @@ class FusedBA:
         n = int(mp['sample'])
         n_pix = self.current.shape[0]
         assert n <= n_pix, "mapping.sample exceeds the frame's pixel count"
-        if _PARKED_GRAPHS and not torch.cuda.is_current_stream_capturing():
-            del _PARKED_GRAPHS[:]
-        self._detach_poses()
+        release_parked()
+        self._detach()
         self._pose_on = False
         self._shape = None                     # the graphs below replace a global_BA call's
         self.poses[:1].copy_(pose.to(dev, torch.float32).reshape(1, 4, 4), non_blocking=True)
         self._n_poses = 1
         self.dyn.copy_(torch.tensor([0, 1, n_pix], dtype=torch.int64), non_blocking=False)
         self._n_cur_pop = n_pix
-        store, rng = self.store, tr.iter_state
-        kw = dict(filter_depth=False, rng=rng, dyn=self.dyn, n_cur=n, n_cur_pop=n_pix)
 
-        def prologue(rays_o, rays_d, target_rgb, target_d):
-            store.assemble_batch(0, self.current, self.poses, 0, out=(rays_o, rays_d, target_rgb, target_d), **kw)
+        def prologue(*bufs):
+            self._assemble(bufs, n, frame_only=True)
 
         def arm(bufs, ts):
-            b, keep = store.next_batch_struct(0, self.current, self.poses, 0, bufs, **kw)
-            assert ts.opt is not None, "prefetch needs the optimiser in the backward (MappingTrainer(fused_adam=True))"
-            import ctypes as C
-            self._disarm_prefetch()
-            ts._next_batch_keep = (b, keep)
-            ts.opt.next_batch = C.cast(C.pointer(b), C.c_void_p)
-            self._armed = ts
+            self._attach(ts, self._assemble(bufs, n, call=self.store.next_batch_struct, frame_only=True) if self.prefetch else None)
 
         with torch.no_grad():
             tr.model.uncert_grid.grad.zero_()
+        self._drive(n, False, prologue, None if self.prefetch else prologue, arm)
         out = None
-        if self.use_graph:
-            with _no_collection():
-                if self.prefetch:
-                    tr.capture(n, smooth=False, prologue=None, first_prologue=prologue, on_buffers=lambda ro, rd, tc, td, ts: arm((ro, rd, tc, td), ts))
-                else:
-                    tr.capture(n, smooth=False, prologue=prologue)
-            bufs = tr.ray_buffers()
-            for i in range(n_iters):
-                out = tr.step(*bufs, smooth=False, uncert_step=False, first=(i == 0))
-        else:
-            f = torch.zeros(n * 10, dtype=torch.float32, device=dev)
-            from .trainer import unpack_rays
-            bufs = unpack_rays(f, n)
-            tr._graphs = None
-            self._disarm_prefetch()
-            if self.prefetch:
-                arm(bufs, tr._train_step(n, False))
-            for i in range(n_iters):
-                if i == 0 or not self.prefetch:
-                    prologue(*bufs)
-                out = tr.step(*bufs, smooth=False, uncert_step=False)
+        for i in range(n_iters):
+            out = self._iterate(i, False, False)
         with torch.no_grad():
             tr.uncert_optim.step()
         # the finishing launch of the last iteration drew one more batch into buffers nobody reads; take the draw off the training step
         # so that a plain trainer.step on it afterwards assembles nothing
         if self.use_graph:
             self._drop_graphs()
-        self._disarm_prefetch()
+        self._detach()
         return out
 
     def call_iterations(self, n_iters: Optional[int] = None, smooth: bool = True):

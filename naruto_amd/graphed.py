@@ -26,6 +26,7 @@ class GraphedIteration:
     static buffers, ``ret`` / ``loss`` are the graphs' static outputs (overwritten by the next replay)."""
 
     def __init__(self, caller, n_rays: int, warmup: int = 3):
+        from .capture import preserved, warm_up
         from .trainer import FusedAdam
         mp = caller.config['mapping']
         # the two recorded variants are "i + 1 not a multiple of 5" and "a multiple of 5" with the mapping optimiser stepping in BOTH: any other
@@ -44,47 +45,28 @@ class GraphedIteration:
         self.target_d = torch.ones(n_rays, 1, **f32)
         self.rays_d[:, 2] = 1.0
         params = list(m.parameters())
-        opts = (caller.map_optimizer, caller.uncert_optim)
-        snap_p = [p.detach().clone() for p in params]
-        snap_o = [(o.step_dev.clone(), [(s_['exp_avg'].clone(), s_['exp_avg_sq'].clone(), s_['lag']) for s_ in o.state.values()], o._n_steps) for o in opts]
-        rng = None if m._rng_state is None else m._rng_state.clone()
+        had_rng = m._rng_state is not None
         args = (self.rays_o, self.rays_d, self.target_s, self.target_d)
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for k in range(warmup):
-                caller.ba_iteration(4 if k == warmup - 1 else 0, *args)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
-        if rng is None and m._rng_state is not None:
-            rng = m._rng_state.clone()
-            rng[1] = 0
         self.graphs, self.out, pool = [], [], None
-        # Inside a capture nothing may depend on host-side state that changes between replays: every .grad has to be a PERSISTENT tensor
-        # that autograd adds into and the optimiser zeroes in place (FusedAdam.zero_grad does so while a stream is capturing) -- the
-        # uncertainty grid's gradient really accumulates over five replays (coslam.py:397-399).
-        for p in params:
-            p.grad = torch.zeros_like(p)
-        for variant in (0, 4):                       # iteration index with (i + 1) % 5 != 0 / == 0
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
-                ret, loss = caller.ba_iteration(variant, *args)
-            pool = g.pool()
-            self.graphs.append(g)
-            self.out.append((ret, loss))
+        with preserved(params + ([m._rng_state] if had_rng else []), (caller.map_optimizer, caller.uncert_optim)):
+            warm_up(dev, lambda k: caller.ba_iteration(4 if k == warmup - 1 else 0, *args), warmup)
+            # Inside a capture nothing may depend on host-side state that changes between replays: every .grad has to be a PERSISTENT
+            # tensor that autograd adds into and the optimiser zeroes in place (FusedAdam.zero_grad does so while a stream is
+            # capturing) -- the uncertainty grid's gradient really accumulates over five replays (coslam.py:397-399).
+            for p in params:
+                p.grad = torch.zeros_like(p)
+            for variant in (0, 4):                       # iteration index with (i + 1) % 5 != 0 / == 0
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=pool):
+                    ret, loss = caller.ba_iteration(variant, *args)
+                pool = g.pool()
+                self.graphs.append(g)
+                self.out.append((ret, loss))
         with torch.no_grad():
-            for p, q in zip(params, snap_p):
-                p.copy_(q)
+            for p in params:
                 p.grad.zero_()
-            for o, (sd, mv, ns) in zip(opts, snap_o):
-                o.step_dev.copy_(sd)
-                o._n_steps = ns
-                for s_, (m0, v0, lag) in zip(o.state.values(), mv):
-                    s_['exp_avg'].copy_(m0)
-                    s_['exp_avg_sq'].copy_(v0)
-                    s_['lag'] = lag
-            if rng is not None:
-                m._rng_state.copy_(rng)
+            if not had_rng and m._rng_state is not None:
+                m._rng_state[1] = 0                  # the model's rng word was created during the warm-up: its seed, counter 0
 
     def __call__(self, i: int, rays_o, rays_d, target_s, target_d):
         self.rays_o.copy_(rays_o, non_blocking=True)

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
@@ -827,7 +828,39 @@ class TrainStep:
         self.opt = None                      # NarutoFusedAdam: set by fuse_adam()
         self.fwd_image = None                # the forward's weight image (NarutoTrainStep.fwd_image): allocated by fuse_adam(), exact mode
         self._gs_nograd = None
-        self.ba_poses = None                 # NarutoBAPoses: set by naruto_amd.ba_loop.FusedBA while it refines poses (naruto_train_backward_poses)
+        # RIDERS on the backward, hung on by attach() for one owner at a time (naruto_amd.ba_loop.FusedBA): the next-batch draw
+        # (NarutoFusedAdam.next_batch; the NarutoRayBatch and what it points into are kept alive HERE, on the step whose backward reads
+        # them) and the pose refinement (NarutoBAPoses, naruto_train_backward_poses)
+        self.ba_poses = None
+        self._next_batch_keep = None
+        self._rider_owner = None
+
+    def attach(self, owner, *, next_batch=None, ba_poses=None):
+        """Hang riders on this step's backward on behalf of ``owner`` (held weakly), replacing whatever rode there, whoever's it was:
+        ``next_batch`` = ``KeyFrameStoreHIP.next_batch_struct(...)``'s (struct, keep-alives), ``ba_poses`` a ``NarutoBAPoses``.  With neither
+        the step is a plain training step that nobody owns."""
+        assert next_batch is None or self.opt is not None, "prefetch needs the optimiser in the backward (MappingTrainer(fused_adam=True))"
+        self._rider_owner = weakref.ref(owner) if (next_batch is not None or ba_poses is not None) else None
+        self._next_batch_keep = next_batch
+        if self.opt is not None:
+            self.opt.next_batch = C.cast(C.pointer(next_batch[0]), C.c_void_p) if next_batch is not None else None
+        self.ba_poses = ba_poses
+
+    def _ridden_by(self, owner, or_orphaned: bool) -> bool:
+        ref = self._rider_owner
+        return ref is not None and (ref() is owner or (or_orphaned and ref() is None))
+
+    def detach(self, owner) -> bool:
+        """Take the riders off if they are ``owner``'s -- or nobody's any more: the cyclic collector clears weak references before it
+        runs finalisers, so the owner's own ``__del__`` finds its riders orphaned.  Somebody else's stay.  Returns whether they came off."""
+        mine = self._ridden_by(owner, or_orphaned=True)
+        if mine:
+            self.attach(owner)
+        return mine
+
+    def riders_of(self, owner):
+        """(next-batch keep-alive, ba_poses) as attached by ``owner`` and still in place; (None, None) when the riders are not its."""
+        return (self._next_batch_keep, self.ba_poses) if self._ridden_by(owner, or_orphaned=False) else (None, None)
 
     def fuse_adam(self, entries: Dict[str, tuple], betas, step_dev: torch.Tensor, write_grads: bool = False):
         """Optimiser in the backward (single process): ``entries[name] = (exp_avg, exp_avg_sq, lr, eps, weight_decay)`` for the

@@ -66,7 +66,8 @@ from typing import Dict, Iterator, List, Optional
 import torch
 
 from .active_ray_sampler import ActiveRaySamplerHIP
-from .ba_loop import FusedBA, _no_collection
+from .ba_loop import FusedBA
+from .capture import no_collection
 from .field import _map_lattice, get_map_volumes
 from .keyframe_store import KeyFrameStoreHIP, frame_ingest
 from .mesh import extract_mesh
@@ -219,7 +220,7 @@ class CoSLAMNarutoHIP:
             tr.rgb.copy_(color.to(self.device, torch.float32))
             tr.depth.copy_(depth.to(self.device, torch.float32))
         pose_log(self.est_c2w_data.tensor[0], out=tr.pose_init)
-        with _no_collection():
+        with no_collection():
             tr.capture()
 
     def _track(self, i: int, color: torch.Tensor, depth: torch.Tensor, every: int):

@@ -30,6 +30,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib, ops
+from .capture import preserved, warm_up
 
 # replica_coslam.yaml:29-42
 TRACKING_DEFAULTS = {"iter": 10, "sample": 1024, "lr_rot": 1e-3, "lr_trans": 1e-3, "ignore_edge_W": 20, "ignore_edge_H": 20,
@@ -287,22 +288,14 @@ class TrackerHIP:
         """Record one call (draw, iteration 0's rays, ``iter`` iterations; no parallel branches) as ONE hipGraph.  Later ``track``
         calls without ``rand`` copy their frame and initial pose into the static buffers and replay it.  The warm-up and the capture
         put the random word back."""
-        dev = self.device
-        rng0 = self.rng.clone()
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s), torch.no_grad():
-            for _ in range(warmup):
-                self._run()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g), torch.no_grad():
-            self._launch_prologue()
-            for _ in range(self.iters):
-                self._launch_iteration()
-        torch.cuda.synchronize(dev)
-        self.rng.copy_(rng0)
+        with preserved([self.rng]), torch.no_grad():
+            warm_up(self.device, lambda _: self._run(), warmup)
+            with torch.cuda.graph(g):
+                self._launch_prologue()
+                for _ in range(self.iters):
+                    self._launch_iteration()
+            torch.cuda.synchronize(self.device)
         self._graph = g
         return g
 

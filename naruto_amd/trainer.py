@@ -12,12 +12,14 @@ Ray assembly (keyframe database, active ray sampler) stays with the caller, as i
 
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
 import torch.optim as optim
 
 from . import parallel
+from .capture import preserved, warm_up
 from .field import NarutoFieldHIP
 
 
@@ -47,6 +49,11 @@ def smoothness(model: NarutoFieldHIP, config: Dict, sample_points: int = 256, vo
     return ops.smoothness(model._handle(), model.embed_fn.params, sample_points, voxel_size, margin, r)
 
 
+def wants_smoothness(config: Dict, smooth: bool) -> bool:
+    """Whether an iteration asked to ``smooth`` carries the smoothness term (coslam.py:166)."""
+    return bool(smooth and config['training']['smooth_weight'] > 0)
+
+
 def get_loss_from_ret(model: NarutoFieldHIP, config: Dict, ret: Dict, rgb=True, sdf=True, depth=True, fs=True, uncert=True,
                       smooth=False) -> torch.Tensor:
     """coslam.py:154-174."""
@@ -60,7 +67,7 @@ def get_loss_from_ret(model: NarutoFieldHIP, config: Dict, ret: Dict, rgb=True, 
         loss = loss + tr['sdf_weight'] * ret["sdf_loss"]
     if fs:
         loss = loss + tr['fs_weight'] * ret["fs_loss"]
-    if smooth and tr['smooth_weight'] > 0:
+    if wants_smoothness(config, smooth):
         loss = loss + tr['smooth_weight'] * smoothness(model, config, tr['smooth_pts'], tr['smooth_vox'], margin=tr['smooth_margin'])
     if uncert and (config['decoder']['pred_uncert'] or config['decoder']['uncert_grid']):
         loss = loss + tr['uncert_weight'] * ret['uncert_loss']
@@ -359,33 +366,47 @@ class MappingTrainer:
             self._train_steps[key] = ts
         return ts
 
+    def train_step_for(self, n_rays: int, smooth: bool):
+        """The TrainStep an iteration of ``n_rays`` rays asked to ``smooth`` runs on."""
+        return self._train_step(n_rays, wants_smoothness(self.config, smooth))
+
+    @staticmethod
+    def _ret_of(ts) -> Dict:
+        losses = ts.losses
+        return {"rgb": ts.rgb, "depth": ts.depth, "rgb_loss": losses[0], "depth_loss": losses[1], "sdf_loss": losses[2], "fs_loss": losses[3],
+                "psnr": losses[4], "uncert_loss": losses[5], "_losses": losses, "_smooth_loss": losses[8]}
+
+    def _dp_exchange(self, ts, fwd, bwd_mlp, bwd_table):
+        """Data parallel: forward | all-reduce of the loss sums | backward up to the MLP weight gradients | their (20 KB) all-reduce,
+        issued asynchronously so that it runs under the table scatter | scatter | all-reduce (or, sharded, reduce-scatter) of the table
+        gradient.  The three callables are eager launches (``_iteration_direct``) or graph segments (``step``)."""
+        fwd()
+        parallel.allreduce_loss_sums(ts.sums, self.group)
+        bwd_mlp()
+        pending = parallel.all_reduce_sum(ts.grad_bucket_mlp, self.group, async_op=True)
+        bwd_table()
+        if self.table_shard is not None:
+            parallel.reduce_scatter_sum(ts.grad_bucket_table, self.table_shard["p_slice"].grad, self.group)
+        else:
+            parallel.all_reduce_sum(ts.grad_bucket_table, self.group)
+        if pending is not None:
+            pending.wait()
+
     def _iteration_direct(self, rays_o, rays_d, target_rgb, target_d, smooth: bool, uncert_step: bool, check: bool = True):
         """Same iteration as _iteration, without autograd: ops.TrainStep + the fused Adams (9 launches single-process, 14 + two collectives data-parallel)."""
         model = self.model
         model.train()
         if check:
             model.check_asserts()
-        tr = self.config['training']
-        use_smooth = bool(smooth and tr['smooth_weight'] > 0)
-        ts = self._train_step(rays_o.shape[0], use_smooth)
+        ts = self.train_step_for(rays_o.shape[0], smooth)
         with torch.no_grad():
             if self.group is not None and ts.opt is None:
-                # data parallel: forward | all-reduce of the loss sums | backward up to the MLP weight gradients | their (20 KB)
-                # all-reduce, issued asynchronously so that it runs under the table scatter | scatter | all-reduce of the table
-                # gradient | identical Adam steps on every rank
-                ts.run_forward(rays_o, rays_d, target_rgb, target_d.reshape(-1))
-                parallel.allreduce_loss_sums(ts.sums, self.group)
-                ts.run_backward(phase=1)
-                pending = parallel.all_reduce_sum(ts.grad_bucket_mlp, self.group, async_op=True)
-                ts.run_backward(phase=2)
-                if self.table_shard is not None:
-                    parallel.reduce_scatter_sum(ts.grad_bucket_table, self.table_shard["p_slice"].grad, self.group)
-                else:
-                    parallel.all_reduce_sum(ts.grad_bucket_table, self.group)
-                pending.wait()
-                losses = ts.losses
+                # (then identical Adam steps on every rank)
+                self._dp_exchange(ts, lambda: ts.run_forward(rays_o, rays_d, target_rgb, target_d.reshape(-1)),
+                                  lambda: ts.run_backward(phase=1), lambda: ts.run_backward(phase=2))
             else:
-                losses = ts.run(rays_o, rays_d, target_rgb, target_d.reshape(-1))
+                ts.run(rays_o, rays_d, target_rgb, target_d.reshape(-1))
+            losses = ts.losses
             if ts.opt is None:
                 for name, p in model._params().items():
                     p.grad = ts.grads[name]
@@ -400,9 +421,7 @@ class MappingTrainer:
         model.note_min_uncert(losses[6])
         if model.strict_assert:
             model.check_asserts(block=True)
-        ret = {"rgb": ts.rgb, "depth": ts.depth, "rgb_loss": losses[0], "depth_loss": losses[1], "sdf_loss": losses[2], "fs_loss": losses[3],
-               "psnr": losses[4], "uncert_loss": losses[5], "_losses": losses, "_smooth_loss": losses[8]}
-        return ret, losses[9]
+        return self._ret_of(ts), losses[9]
 
     def _table_shard_step(self, adam: bool = True, gather: bool = True):
         """Sharded table optimiser: Adam on this rank's slice (its gradient sits in p_slice.grad after the reduce-scatter), then the
@@ -424,7 +443,7 @@ class MappingTrainer:
         model.train()
         self.map_optimizer.zero_grad(set_to_none=True)
         tr = self.config['training']
-        use_smooth = smooth and tr['smooth_weight'] > 0
+        use_smooth = wants_smoothness(self.config, smooth)
         # one RNG launch per iteration: the depth jitter [N,S] and the six numbers placing the smoothness lattice
         n_rays = rays_o.shape[0]
         n_z = n_rays * (tr['n_samples_d'] + tr['n_range_d']) if tr['perturb'] > 0. else 0
@@ -487,18 +506,8 @@ class MappingTrainer:
                 st['target_d'].copy_(target_d.reshape(st['target_d'].shape), non_blocking=True)
             if st.get('segments') is not None:
                 # data parallel: three graph segments with the collectives as ordinary eager RCCL calls in between
-                seg, ts = st['segments'], st['ts']
-                seg['fwd'].replay()
-                parallel.allreduce_loss_sums(ts.sums, self.group)
-                seg['bwd_mlp'].replay()
-                pending = parallel.all_reduce_sum(ts.grad_bucket_mlp, self.group, async_op=True)      # under the scatter
-                seg['bwd_table'].replay()
-                if self.table_shard is not None:
-                    parallel.reduce_scatter_sum(ts.grad_bucket_table, self.table_shard["p_slice"].grad, self.group)
-                else:
-                    parallel.all_reduce_sum(ts.grad_bucket_table, self.group)
-                if pending is not None:
-                    pending.wait()
+                seg = st['segments']
+                self._dp_exchange(st['ts'], seg['fwd'].replay, seg['bwd_mlp'].replay, seg['bwd_table'].replay)
                 if uncert_step:
                     parallel.allreduce_grads([self.model.uncert_grid], self.group)
                 seg['opt'][1 if uncert_step else 0].replay()
@@ -600,154 +609,94 @@ class MappingTrainer:
         dev = self.device
         self.model.n_rays_total = n_rays_total
         flat = torch.zeros(n_rays * 10, device=dev)
-        st = {'flat': flat, 'smooth': smooth, 'ret': [None, None], 'loss': [None, None]}
-        st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'] = unpack_rays(flat, n_rays)
+        st = {'flat': flat, 'smooth': smooth, 'ret': [None, None], 'loss': [None, None], 'chain': None}
+        bufs = st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'] = unpack_rays(flat, n_rays)
         st['rays_d'][:, 2] = 1.0
         st['target_d'].fill_(1.0)
-        # snapshot: the warm-up / capture iterations below must not change the training state -- parameters, both optimisers'
-        # moments and step counts, the accumulated uncertainty-grid gradient and the iteration counter are all put back
-        params = self.parameters()
-        snap = [p.detach().clone() for p in params]
-        iter_snap = self.iter_state.clone() if self.direct else None
-        ugrad_snap = self.model.uncert_grid.grad.detach().clone()
-        opt_snap = []
-        opts_all = (self.map_optimizer, self.uncert_optim) + ((self.table_optimizer,) if self.table_shard is not None else ())
-        for opt in opts_all:
-            if isinstance(opt, FusedAdam):
-                opt_snap.append((opt.step_dev.clone(), [(st_['exp_avg'].clone(), st_['exp_avg_sq'].clone()) for st_ in opt.state.values()]))
-            else:
-                import copy
-                opt_snap.append(copy.deepcopy(opt.state_dict()))
-        if on_buffers is not None:
-            tr_cfg0 = self.config['training']
-            on_buffers(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'], self._train_step(n_rays, bool(smooth and tr_cfg0['smooth_weight'] > 0)))
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for i in range(warmup):
-                if first_prologue is not None and i == 0:
-                    first_prologue(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'])
-                elif prologue is not None:
-                    prologue(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'])
-                self._iteration(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'], smooth, i == warmup - 1, check=False)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
-        graphs = []
-        pool = None
-        import os
         segmented = self.group is not None and self.direct and os.environ.get("NARUTO_GRAPH_DIST", "segmented") != "whole"
+        assert prologue is None or not segmented, "a captured prologue belongs to the single-process graph"
         # with a process group its watchdog thread polls events while this thread captures: only this thread's calls may end the capture
         cap_mode = "thread_local" if self.group is not None else "global"
-        assert prologue is None or not segmented, "a captured prologue belongs to the single-process graph"
-        if segmented:
-            # Data parallel: forward | backward | optimiser as three graph segments; the two all-reduces (loss sums, flat
-            # gradient) run between them as eager RCCL calls on the same stream.  (Capturing the collectives inside one graph
-            # also works -- NARUTO_GRAPH_DIST=whole, 0.47 ms at world size 1 -- but a multi-rank capture cannot be
-            # exercised on the single-GPU test boxes, so the default does not depend on it.)
-            tr_cfg = self.config['training']
-            ts = self._train_step(n_rays, bool(smooth and tr_cfg['smooth_weight'] > 0))
-            args = (st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'].reshape(-1))
-            seg = {'opt': [None, None]}
+        # the graphs hold the ADDRESSES of this TrainStep's buffers: st['ts'] keeps it alive with them, whatever the LRU cache evicts
+        ts = self.train_step_for(n_rays, smooth) if (self.direct or on_buffers is not None) else None
+        if self.direct:
+            st['ts'] = ts
+        graphs, pool = [], None
+
+        def record(body):
+            """``body()`` recorded into one more graph on the shared pool -> (graph, what body returned)."""
+            nonlocal pool
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode), torch.no_grad():
-                ts.run_forward(*args)
+            with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode):
+                out = body()
             pool = g.pool()
-            seg['fwd'] = g
-            # the backward as TWO segments split at the MLP / table boundary (as the eager path does): the 20 KB bucket of MLP weight
-            # gradients is complete after the first and is all-reduced asynchronously WHILE the second -- the table scatter, the longest
-            # kernel of the step -- replays; the table bucket follows it.  Same kernels in the same order as the one-piece backward:
-            # same bits (tests/test_gpu_parity.py::test_two_rank_data_parallel_training compares against the single-process trajectory).
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode), torch.no_grad():
-                ts.run_backward(phase=1)
-            seg['bwd_mlp'] = g
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode), torch.no_grad():
-                ts.run_backward(phase=2)
-            seg['bwd_table'] = g
-            for name, p in self.model._params().items():
-                p.grad = ts.grads[name]
-            for variant in (False, True):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode), torch.no_grad():
+            return g, out
+
+        def iterations(prologues, uncert_steps, image=None):
+            """A body of len(uncert_steps) iterations back to back, each behind its prologue (None: none)."""
+            def body():
+                out = None
+                for i, (pro, u) in enumerate(zip(prologues, uncert_steps)):
+                    if pro is not None:
+                        pro(*bufs)
+                    if image is not None:
+                        image.fwd_image_fresh(i > 0)          # the launch in front of this forward is iteration i - 1's fused-Adam finish
+                    out = self._iteration(*bufs, smooth, bool(u), check=False)
+                return out
+            return body
+
+        def prologues(n):
+            return [first_prologue if first_prologue is not None else prologue] + [prologue] * (n - 1)
+
+        # the warm-up / capture iterations below must not change the training state -- parameters, both optimisers' moments and step
+        # counts, the accumulated uncertainty-grid gradient and the iteration counter are all put back
+        opts = (self.map_optimizer, self.uncert_optim) + ((self.table_optimizer,) if self.table_shard is not None else ())
+        with preserved(self.parameters() + [self.model.uncert_grid.grad] + ([self.iter_state] if self.direct else []), opts):
+            if on_buffers is not None:
+                on_buffers(*bufs, ts)
+            warm_up(dev, lambda i: iterations(prologues(warmup)[i:i + 1], [i == warmup - 1])(), warmup)
+            if segmented:
+                # Data parallel: forward | backward | optimiser as graph segments; the collectives run between them as eager RCCL
+                # calls on the same stream (_dp_exchange).  (Capturing the collectives inside one graph also works --
+                # NARUTO_GRAPH_DIST=whole, 0.47 ms at world size 1 -- but a multi-rank capture cannot be exercised on the
+                # single-GPU test boxes, so the default does not depend on it.)  The backward is TWO segments split at the MLP / table
+                # boundary, as the eager path does.  Same kernels in the same order as the one-piece backward: same bits
+                # (tests/test_gpu_parity.py::test_two_rank_data_parallel_training compares against the single-process trajectory).
+                args = bufs[:3] + (st['target_d'].reshape(-1),)
+
+                def optimisers(uncert):
                     self.map_optimizer.step()
                     self._table_shard_step(gather=False)
-                    if variant:
+                    if uncert:
                         self.uncert_optim.step(zero_grad=True)
-                seg['opt'][1 if variant else 0] = g
-            losses = ts.losses
-            self.model._pending_min_uncert = losses[6]
-            st['segments'], st['ts'] = seg, ts
-            st['ret'][0] = {"rgb": ts.rgb, "depth": ts.depth, "rgb_loss": losses[0], "depth_loss": losses[1], "sdf_loss": losses[2],
-                            "fs_loss": losses[3], "psnr": losses[4], "uncert_loss": losses[5], "_losses": losses, "_smooth_loss": losses[8]}
-            st['loss'][0] = losses[9]
-            graphs = [seg['fwd']]
-        for variant in (() if segmented else (False, True)):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode):
-                if prologue is not None:
-                    prologue(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'])
-                ret, loss = self._iteration(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'], smooth, variant, check=False)
-            pool = g.pool()
-            st['ret'][1 if variant else 0] = ret
-            st['loss'][1 if variant else 0] = loss
-            graphs.append(g)
-        if first_prologue is not None and not segmented:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode):
-                first_prologue(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'])
-                ret, loss = self._iteration(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'], smooth, False, check=False)
-            st['ret'].append(ret)
-            st['loss'].append(loss)
-            graphs.append(g)
-        st['chain'] = None
-        if chain and not segmented:
-            g = torch.cuda.CUDAGraph()
-            if fwd_image is None:
-                fwd_image = os.environ.get("NARUTO_FWD_WEIGHT_IMAGE", "1") != "0"
-            ts_img = self._train_step(n_rays, bool(smooth and self.config['training']['smooth_weight'] > 0)) if (fwd_image and self.direct) else None
-            try:
-                with torch.cuda.graph(g, pool=pool, capture_error_mode=cap_mode):
-                    for i, u in enumerate(chain):
-                        pro = first_prologue if (i == 0 and first_prologue is not None) else prologue
-                        if pro is not None:
-                            pro(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'])
+                with torch.no_grad():
+                    seg = {'fwd': record(lambda: ts.run_forward(*args))[0], 'bwd_mlp': record(lambda: ts.run_backward(phase=1))[0],
+                           'bwd_table': record(lambda: ts.run_backward(phase=2))[0]}
+                    for name, p in self.model._params().items():
+                        p.grad = ts.grads[name]
+                    seg['opt'] = [record(lambda: optimisers(uncert))[0] for uncert in (False, True)]
+                self.model._pending_min_uncert = ts.losses[6]
+                st['segments'] = seg
+                st['ret'][0], st['loss'][0] = self._ret_of(ts), ts.losses[9]
+                graphs = [seg['fwd']]
+            else:
+                for uncert in (False, True):
+                    g, (st['ret'][uncert], st['loss'][uncert]) = record(iterations([prologue], [uncert]))
+                    graphs.append(g)
+                if first_prologue is not None:
+                    g, (ret, loss) = record(iterations([first_prologue], [False]))
+                    st['ret'].append(ret)
+                    st['loss'].append(loss)
+                    graphs.append(g)
+                if chain:
+                    if fwd_image is None:
+                        fwd_image = os.environ.get("NARUTO_FWD_WEIGHT_IMAGE", "1") != "0"
+                    ts_img = ts if (fwd_image and self.direct) else None
+                    try:
+                        g, (ret, loss) = record(iterations(prologues(len(chain)), chain, ts_img))
+                    finally:
                         if ts_img is not None:
-                            ts_img.fwd_image_fresh(i > 0)          # the launch in front of this forward is iteration i - 1's fused-Adam finish
-                        ret, loss = self._iteration(st['rays_o'], st['rays_d'], st['target_rgb'], st['target_d'], smooth, bool(u), check=False)
-            finally:
-                if ts_img is not None:
-                    ts_img.fwd_image_fresh(False)
-            st['chain'] = (g, ret, loss, len(chain))
-            st['chain_fwd_image'] = bool(ts_img is not None and ts_img.fwd_image is not None and ts_img.opt is not None)
-        if self.direct and not segmented:
-            # the graphs hold the ADDRESSES of this TrainStep's buffers: keep it alive with them, whatever the LRU cache below evicts
-            tr_cfg = self.config['training']
-            st['ts'] = self._train_step(n_rays, bool(smooth and tr_cfg['smooth_weight'] > 0))
-        # restore parameters and optimiser state to "before capture"
-        with torch.no_grad():
-            for p, q in zip(params, snap):
-                p.copy_(q)
-            if iter_snap is not None:
-                self.iter_state.copy_(iter_snap)
-            self.model.uncert_grid.grad.copy_(ugrad_snap)
-            for opt, sn in zip(opts_all, opt_snap):
-                if isinstance(opt, FusedAdam):
-                    opt.step_dev.copy_(sn[0])
-                    for st_, (m0, v0) in zip(opt.state.values(), sn[1]):
-                        st_['exp_avg'].copy_(m0)
-                        st_['exp_avg_sq'].copy_(v0)
-                else:
-                    # torch.optim.Adam creates its state lazily: a fresh optimiser has none before capture.  The captured graphs
-                    # hold the state tensors' ADDRESSES, so restore by value into the existing tensors.
-                    had = sn['state']
-                    index = {id(q): i for i, q in enumerate(q for gp in opt.param_groups for q in gp['params'])}
-                    for p_, stt in opt.state.items():
-                        idx = index[id(p_)]
-                        for k, val in stt.items():
-                            if torch.is_tensor(val):
-                                if idx in had and k in had[idx]:
-                                    val.copy_(had[idx][k])
-                                else:
-                                    val.zero_()
+                            ts_img.fwd_image_fresh(False)
+                    st['chain'] = (g, ret, loss, len(chain))
+                    st['chain_fwd_image'] = bool(ts_img is not None and ts_img.fwd_image is not None and ts_img.opt is not None)
         self._graphs, self._static = graphs, st

@@ -2926,6 +2926,60 @@ def test_fused_ba_prefetch_survives_eviction_and_close(gpu, active):
     assert tr_a._train_step(n_train, True) is ts
 
 
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_a_stale_fused_ba_does_not_disarm_the_live_one(gpu, use_graph):
+    """The trainer's cache hands the SAME TrainStep to a second FusedBA on the same trainer.  What rides on its backward belongs to the
+    object that attached it last (ops.TrainStep.attach): close() of the first object, or the finaliser of any other, neither disarms the
+    second one's prefetch nor drops the graphs it captured -- the trajectory is that of a trainer that only ever had one FusedBA, bit for bit.
+    And when the graphs ARE taken away (trainer._graphs = None), the next iteration captures again instead of failing."""
+    import gc
+    from naruto_amd import trainer
+    from naruto_amd.ba_loop import FusedBA
+    cfg = H.office_cfg(12, perturb=1.0)
+    cfg["mapping"].update(sample=256, min_pixels_cur=40, filter_depth=True, keyframe_every=5)
+    bound = torch.tensor(cfg["mapping"]["bound"])
+    twins = []
+    for _ in range(2):
+        torch.manual_seed(37)
+        tr = trainer.MappingTrainer(cfg, bound, gpu, fused_adam=True)
+        store, current, poses, _ = _ba_scene(cfg, gpu, n_kf=8)
+        twins.append((tr, store))
+    (tr_a, store_a), (tr_b, store_b) = twins
+    tr_b.model.load_state_dict(tr_a.model.state_dict())
+    tr_b.iter_state.copy_(tr_a.iter_state)
+
+    def make(tr, store):
+        ba = FusedBA(tr, store, None, max_poses=64, use_graph=use_graph)
+        assert ba.prepare(current, poses) == (40, 296)
+        return ba
+    stale = make(tr_a, store_a)
+    live = make(tr_a, store_a)
+    only = make(tr_b, store_b)
+    ts = tr_a._train_step(296, True)
+    assert ts.opt.next_batch, "the prefetch rides on the TrainStep both objects were handed"
+    losses = {"a": [float(live.iteration(i)[1]) for i in range(2)]}
+    graphs = tr_a._graphs
+    assert (graphs is not None) == use_graph
+    stale.close()
+    third = FusedBA(tr_a, store_a, None, max_poses=64, use_graph=use_graph)
+    del third
+    gc.collect()
+    assert tr_a._graphs is graphs, "a stale close() dropped the live object's graphs"
+    assert ts.opt.next_batch, "a stale close() disarmed the live object's prefetch"
+    assert ts.riders_of(live)[0] is ts._next_batch_keep is not None and ts.riders_of(stale) == (None, None)
+    losses["a"] += [float(live.iteration(i)[1]) for i in range(2, 6)]
+    losses["b"] = [float(only.iteration(i)[1]) for i in range(6)]
+    if use_graph:
+        tr_a._graphs = None                      # (what another driver of the same trainer does): iteration 6 captures again
+        losses["a"].append(float(live.iteration(6)[1]))
+        losses["b"].append(float(only.iteration(6)[1]))
+        assert tr_a._graphs is not None
+    assert losses["a"] == losses["b"], losses
+    assert len(set(losses["a"])) == len(losses["a"]), "every iteration draws another batch"
+    for (n, p), (_, q) in zip(tr_a.model.named_parameters(), tr_b.model.named_parameters()):
+        assert torch.equal(p, q), f"parameter {n}: a trainer with a stale FusedBA != a trainer with one"
+
+
 def test_active_ray_keys_looked_up_by_the_assembly(gpu):
     """NarutoRayBatch.keys_out + naruto_active_ray_select_keyed (round 5): the candidates' keys looked up by the batch assembly, while the
     rows are in registers, and the selection started from them -- the same selected batch, bit for bit, as assembly | selection with its
