@@ -543,6 +543,46 @@ int naruto_nn_scan(uint64_t n_targets, const float* targets, uint64_t n_queries,
 size_t naruto_dist_reduce_workspace(uint64_t n);
 int naruto_dist_reduce(uint64_t n, const double* dist, double threshold, void* workspace, double* out, void* stream);
 
+/* Rigid alignment of a source cloud to a target cloud: the loop of point-to-point ICP (Open3D's registration_icp, defaults), which the
+ * reference's protocol runs on the mesh vertices before the metrics above (src/evaluation/eval_recon.py:80-85 -> neural_slam_eval's
+ * get_align_transformation, third-party code outside the reference tree: PARITY UNPINNED; the contract is restated in
+ * naruto_amd/evaluation.py).  One iteration = naruto_icp_transform -> naruto_nn_grid_query -> naruto_icp_accumulate -> naruto_icp_step
+ * on one stream; nothing synchronises, allocates or uses float atomics; every buffer is the caller's.
+ *
+ * state: DEVICE float64 [NARUTO_ICP_STATE_DOUBLES]:  [0..15] T (row-major [4,4], cumulative), [16] fitness, [17] inlier_rmse,
+ *   [18], [19] the previous evaluation's, [20] iteration (updates applied), [21] status (NARUTO_ICP_*), [22] s2 / s1 of the last
+ *   cross-covariance, [23] 0.  The caller writes the initial T and zeros; naruto_icp_step maintains the rest.
+ * naruto_icp_transform: out[i] = T points[i], i < n.  points / out are float32 [n,3], or float64 [n,3] both when points_f64; T = 16
+ *   DEVICE doubles (the head of a state block).  fp64 arithmetic, out_a = ((T[a][0]*x + T[a][1]*y) + T[a][2]*z) + T[a][3], every product
+ *   and sum rounded (no contraction), then rounded once to the output type: the order is part of the ABI.
+ * naruto_icp_accumulate: sums (DEVICE float64 [NARUTO_ICP_SUMS]) over the inliers i < n -- dist[i] <= max_distance and
+ *   0 <= index[i] < n_targets -- of: 1, dist^2, p [3], q [3], p q^T [9, row-major], with p = points[i] - origin (the TRANSFORMED source
+ *   points, float32 [n,3]) and q = targets[index[i]] - origin (targets float32 [n_targets,3] in original order; index / dist as
+ *   naruto_nn_grid_query wrote them).  origin: HOST float64 [3], e.g. the target box's centre, so that the centred covariance does not
+ *   cancel.  Two stages in a fixed order that depends on n alone: bitwise reproducible.  workspace:
+ *   naruto_icp_accumulate_workspace of n, in bytes.
+ * naruto_icp_step (one thread): fitness = count / n_source, inlier_rmse = sqrt(sum dist^2 / count) (0 without inliers) into the state; from
+ *   the second evaluation on, status = CONVERGED when |fitness - previous| < relative_fitness and |rmse - previous| < relative_rmse;
+ *   else status = MAX_ITERATION when `iteration` has reached max_iteration; else dT from the sums -- centroids, H = sum p q^T -
+ *   (sum p)(sum q)^T / count = U S V^T (one-sided Jacobi), R = V diag(1, 1, det(V U^T)) U^T, t = mean q - R mean p (Kabsch with the
+ *   determinant correction, no scale) -- and T = dT @ T, iteration += 1; or status = DEGENERATE with T unchanged when count < 3 or
+ *   s2 <= 1e-10 s1.  A state whose status is not RUNNING is left as it is.
+ * naruto_debug_icp_solve is the solver on the host (host arrays, nothing launched): sums [17], origin [3] (NULL = 0) -> dT [16],
+ *   *status = NARUTO_ICP_RUNNING or NARUTO_ICP_DEGENERATE (dT = identity). */
+#define NARUTO_ICP_SUMS 17
+#define NARUTO_ICP_STATE_DOUBLES 24
+#define NARUTO_ICP_RUNNING 0
+#define NARUTO_ICP_CONVERGED 1
+#define NARUTO_ICP_DEGENERATE 2
+#define NARUTO_ICP_MAX_ITERATION 3
+int naruto_icp_transform(uint64_t n, const void* points, int points_f64, const double* T, void* out, void* stream);
+size_t naruto_icp_accumulate_workspace(uint64_t n);
+int naruto_icp_accumulate(uint64_t n, const float* points, uint64_t n_targets, const float* targets, const int32_t* index,
+                          const double* dist, double max_distance, const double* origin, void* workspace, double* sums, void* stream);
+int naruto_icp_step(const double* sums, uint64_t n_source, const double* origin, uint32_t max_iteration, double relative_fitness,
+                    double relative_rmse, double* state, void* stream);
+int naruto_debug_icp_solve(const double* sums, const double* origin, double* dT, int32_t* status);
+
 /* The planner's local RRT (reference src/planner/rrt.py and src/planner/rrt_naruto.py: class RRTNaruto, the
  * local_planner_method of every shipped config), on the volumes of naruto_map_volumes.  Unit: voxel.
  *

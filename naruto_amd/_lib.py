@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_sim.hip", "naruto_frame.hip", "naruto_posechain.hip", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_sim.hip", "naruto_frame.hip", "naruto_posechain.hip", "naruto_icp.hip", "naruto_icp.h", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -135,6 +135,11 @@ class NarutoCullCam(C.Structure):
     _fields_ = [("H", C.c_uint32), ("W", C.c_uint32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
                 ("near_", C.c_float), ("far_", C.c_float)]
 
+
+ICP_SUMS = 17                            # count, sum d^2, sum p [3], sum q [3], sum p q^T [9]
+ICP_STATE_DOUBLES = 24                   # T [16], fitness, inlier_rmse, previous fitness, previous rmse, iteration, status, s2 / s1, 0
+ICP_RUNNING, ICP_CONVERGED, ICP_DEGENERATE, ICP_MAX_ITERATION = range(4)
+ICP_STATUS = ("running", "converged", "degenerate", "max_iteration")
 
 SIM_KEEP_INF = 1
 
@@ -257,6 +262,11 @@ SIGNATURES = {
     "naruto_nn_scan": (_I, [_U64, _V, _U64, _V, _V, _V, _V]),
     "naruto_dist_reduce_workspace": (C.c_size_t, [_U64]),
     "naruto_dist_reduce": (_I, [_U64, _V, C.c_double, _V, _V, _V]),
+    "naruto_icp_transform": (_I, [_U64, _V, _I, _V, _V, _V]),
+    "naruto_icp_accumulate_workspace": (C.c_size_t, [_U64]),
+    "naruto_icp_accumulate": (_I, [_U64, _V, _U64, _V, _V, _V, C.c_double, C.POINTER(C.c_double), _V, _V, _V]),
+    "naruto_icp_step": (_I, [_V, _U64, C.POINTER(C.c_double), _U32, C.c_double, C.c_double, _V, _V]),
+    "naruto_debug_icp_solve": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "naruto_render_depth_workspace": (C.c_size_t, [_U64, _U64, _U32]),
     "naruto_render_depth": (_I, [C.POINTER(NarutoCullCam), _U64, _V, _U64, _V, _V, _U32, _V, _U32, _V, _V, _V]),
     "naruto_observed_vertices": (_I, [C.POINTER(NarutoCullCam), _U64, _V, _U32, _V, _V, _F, _V, _V]),

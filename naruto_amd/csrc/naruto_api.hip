@@ -30,6 +30,7 @@
 #include "naruto_sim.hip"
 #include "naruto_frame.hip"
 #include "naruto_posechain.hip"
+#include "naruto_icp.hip"
 
 using namespace naruto;
 
@@ -2317,6 +2318,65 @@ int naruto_dist_reduce(uint64_t n, const double* dist, double threshold, void* w
     return check_launch("dist_finish");
 }
 
+// ---- rigid alignment (naruto_icp.hip) -----------------------------------------------------------------------------------
+namespace {
+struct IcpWs { double* part; uint32_t parts; size_t total; };
+IcpWs icp_ws(uint64_t n, void* workspace) {
+    const uint32_t parts = (uint32_t)((n + kIcpThreads * kIcpPer - 1u) / (kIcpThreads * kIcpPer));
+    Carve c(workspace);
+    return {c.take<double>((size_t)parts * kIcpSums * sizeof(double)), parts, c.size()};
+}
+int icp_origin(const double* origin, const char* who, IcpOrigin* out) {
+    if (origin == nullptr) return fail(NARUTO_ERR_INVALID, "%s: NULL origin", who);
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) return fail(NARUTO_ERR_INVALID, "%s: non-finite origin", who);
+    *out = IcpOrigin{origin[0], origin[1], origin[2]};
+    return NARUTO_OK;
+}
+}  // namespace
+
+int naruto_icp_transform(uint64_t n, const void* points, int points_f64, const double* T, void* out, void* stream) {
+    if (n == 0) return fail(NARUTO_ERR_INVALID, "icp_transform: zero points");
+    if (n > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "icp_transform: counts beyond int32");
+    if (points == nullptr || T == nullptr || out == nullptr) return fail(NARUTO_ERR_INVALID, "icp_transform: NULL argument");
+    const dim3 grid((uint32_t)((n + kIcpThreads - 1u) / kIcpThreads)), block(kIcpThreads);
+    if (points_f64) hipLaunchKernelGGL(k_icp_transform<true>, grid, block, 0, (hipStream_t)stream, (uint32_t)n, points, T, out);
+    else hipLaunchKernelGGL(k_icp_transform<false>, grid, block, 0, (hipStream_t)stream, (uint32_t)n, points, T, out);
+    return check_launch("icp_transform");
+}
+
+size_t naruto_icp_accumulate_workspace(uint64_t n) {
+    return (n == 0 || n > kReconMaxCount) ? 0 : icp_ws(n, nullptr).total;
+}
+
+int naruto_icp_accumulate(uint64_t n, const float* points, uint64_t n_targets, const float* targets, const int32_t* index, const double* dist,
+                          double max_distance, const double* origin, void* workspace, double* sums, void* stream) {
+    if (n == 0 || n_targets == 0) return fail(NARUTO_ERR_INVALID, "icp_accumulate: zero points");
+    if (n > kReconMaxCount || n_targets > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "icp_accumulate: counts beyond int32");
+    if (std::isnan(max_distance) || max_distance < 0.0) return fail(NARUTO_ERR_INVALID, "icp_accumulate: the correspondence distance must be a number >= 0");
+    IcpOrigin o;
+    if (int rc = icp_origin(origin, "icp_accumulate", &o)) return rc;
+    if (points == nullptr || targets == nullptr || index == nullptr || dist == nullptr || workspace == nullptr || sums == nullptr)
+        return fail(NARUTO_ERR_INVALID, "icp_accumulate: NULL argument");
+    const IcpWs w = icp_ws(n, workspace);
+    hipLaunchKernelGGL(k_icp_accumulate, dim3(w.parts), dim3(kIcpThreads), 0, (hipStream_t)stream, (uint32_t)n, points, (uint32_t)n_targets, targets, index, dist,
+                       max_distance, o, w.part);
+    if (int rc = check_launch("icp_accumulate")) return rc;
+    hipLaunchKernelGGL(k_icp_accumulate_finish, dim3(1), dim3(kIcpThreads), 0, (hipStream_t)stream, w.parts, w.part, sums);
+    return check_launch("icp_accumulate_finish");
+}
+
+int naruto_icp_step(const double* sums, uint64_t n_source, const double* origin, uint32_t max_iteration, double relative_fitness, double relative_rmse,
+                    double* state, void* stream) {
+    if (n_source == 0) return fail(NARUTO_ERR_INVALID, "icp_step: zero points");
+    if (n_source > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "icp_step: counts beyond int32");
+    if (std::isnan(relative_fitness) || std::isnan(relative_rmse)) return fail(NARUTO_ERR_INVALID, "icp_step: a convergence criterion is not a number");
+    IcpOrigin o;
+    if (int rc = icp_origin(origin, "icp_step", &o)) return rc;
+    if (sums == nullptr || state == nullptr) return fail(NARUTO_ERR_INVALID, "icp_step: NULL argument");
+    hipLaunchKernelGGL(k_icp_step, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, (double)n_source, o, (double)max_iteration, relative_fitness, relative_rmse, state);
+    return check_launch("icp_step");
+}
+
 // ---- mesh culling (naruto_cull.hip) -------------------------------------------------------------------------------------
 namespace {
 constexpr uint32_t kCullLargeGrid = 2048;                     // workgroups of the large route: 8 per CU, grid-stride over the chunks
@@ -2975,6 +3035,14 @@ int naruto_debug_rodrigues(const double* w, const double* G, double* R, double* 
 int naruto_debug_pose_log(uint32_t P, const float* c2w, float* pose6) {
     if (c2w == nullptr || pose6 == nullptr) return fail(NARUTO_ERR_INVALID, "debug_pose_log: NULL argument");
     for (uint32_t p = 0; p < P; ++p) pose_log(c2w + 16 * (size_t)p, pose6 + 6 * (size_t)p);
+    return NARUTO_OK;
+}
+
+int naruto_debug_icp_solve(const double* sums, const double* origin, double* dT, int32_t* status) {
+    if (sums == nullptr || dT == nullptr || status == nullptr) return fail(NARUTO_ERR_INVALID, "debug_icp_solve: NULL argument");
+    const double zero[3] = {0.0, 0.0, 0.0};
+    double ratio;
+    *status = icp_solve(sums, origin != nullptr ? origin : zero, dT, ratio);
     return NARUTO_OK;
 }
 

@@ -24,19 +24,45 @@ units of the truncation distance, so the metric value is mean * training.trunc *
 the same number for its trunc of 0.1 m and a quirk for any other (tests/accuracy_study.py uses the same conversion).
 
 Mesh culling, the step the protocol runs before these metrics (cull_mesh.py --remove_occlusion from the estimated poses), is
-``naruto_amd.culling``; ``evaluate_field(cull_poses=..., cull_cam=...)`` runs it on the device between extraction and sampling.  Mesh
-alignment stays with the caller.
+``naruto_amd.culling``; ``evaluate_field(cull_poses=..., cull_cam=...)`` runs it on the device between extraction and sampling.
+
+Mesh alignment, the protocol's other step before the metrics (eval_recon.py:80-85: ``get_align_transformation(rec_mesh, gt_mesh)``, applied
+to the reconstruction), is ``icp`` / ``get_align_transformation`` here and ``align=True`` on the three metric entry points.  A tracked run's
+mesh lives in the frame of the ESTIMATED trajectory; without the alignment Accuracy and Completion mix reconstruction error with drift
+(the trajectory gets the same treatment before its error is reported: ``ate``).  ``get_align_transformation`` is neural_slam_eval's too,
+so this is PARITY UNPINNED as well; the contract follows the published algorithm (Open3D's ``registration_icp``, point-to-point, defaults):
+
+  * source = the reconstructed mesh's VERTICES, target = the ground-truth mesh's VERTICES; the initial transformation is the identity;
+  * ``max_correspondence_distance`` 0.1 m; ``max_iteration`` 30; ``relative_fitness`` = ``relative_rmse`` = 1e-6;
+  * a source point is an inlier iff its nearest target is at distance <= max_correspondence_distance (the fp64 distance of the query
+    above; ties go to the lowest original index); ``fitness`` = inliers / source points, ``inlier_rmse`` = sqrt(mean squared inlier
+    distance), 0 without inliers;
+  * point-to-point estimation, no scale: Kabsch with the determinant correction, ``ate``'s formula, on the inlier pairs (transformed
+    source point, its target);
+  * the loop: evaluate the correspondences at T; then up to max_iteration times: dT from the current inlier pairs, T = dT @ T,
+    re-evaluate, and stop as ``converged`` when |fitness - previous| < relative_fitness and |rmse - previous| < relative_rmse;
+  * it stops early, unconverged, with T unchanged and status ``degenerate``, when there are fewer than 3 inliers or the second singular
+    value of the cross-covariance is <= 1e-10 x the first (collinear pairs: the rotation is not determined);
+  * every evaluation transforms the ORIGINAL source points by the cumulative fp64 T and rounds once to float32, in the order
+    ((r0*x + r1*y) + r2*z) + t with products and sums rounded (no contraction): tests/icp_spec.py makes the same bits in numpy, and
+    nothing drifts across iterations.
+
+It runs in csrc/naruto_icp.hip (transform, 17 fp64 sums in a fixed order, a one-thread Kabsch / convergence step) around the query above;
+per iteration the host reads eight doubles to learn whether to go on.
 
 Command line, with the arguments of the reference's eval_recon.py::
 
-    python -m naruto_amd.evaluation --rec_mesh A.ply --gt_mesh B.ply --result_txt out.txt
+    python -m naruto_amd.evaluation --rec_mesh A.ply --gt_mesh B.ply --result_txt out.txt [--icp_align]
+
+``--icp_align`` is the reference's ``--align`` step; ``--align`` itself still raises NotImplementedError (its behaviour is pinned).
 """
 
 from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -136,6 +162,7 @@ class PointGridHIP:
         box = torch.stack([self.target.amin(0), self.target.amax(0)]).cpu().double().numpy()                # six numbers
         if not np.isfinite(box).all():
             raise ValueError("PointGridHIP: non-finite coordinates in the target cloud")
+        self.box = box                       # float64 [2,3]: the cloud's lower and upper corner
         lib = _lib.load()
         self.grid = _lib.NarutoNnGrid()
         check(lib.naruto_nn_grid_plan(n, (C.c_double * 3)(*box[0]), (C.c_double * 3)(*box[1]), 0.0 if cell is None else float(cell), int(max_cells or 0),
@@ -217,6 +244,97 @@ def reduce_distances(dist: torch.Tensor, threshold: float) -> torch.Tensor:
     return out
 
 
+@dataclass
+class IcpResult:
+    """``transformation``: float64 [4,4] taking source coordinates to target coordinates; ``fitness`` / ``inlier_rmse``: of the last
+    evaluation (the one at ``transformation``); ``iterations``: updates applied; ``status``: converged | max_iteration | degenerate;
+    ``history``: (fitness, inlier_rmse) of every evaluation, the one at the initial transformation first."""
+    transformation: np.ndarray
+    fitness: float
+    inlier_rmse: float
+    iterations: int
+    converged: bool
+    status: str
+    history: List[Tuple[float, float]]
+
+
+def transform_points(points: torch.Tensor, transformation) -> torch.Tensor:
+    """``points`` (device float32 or float64 [N,3]) moved by ``transformation`` ([4,4], or a device float64 tensor of >= 16 elements) in
+    fp64, the points' own dtype out (naruto_icp_transform: the operation order is part of the ABI)."""
+    if points.dtype not in (torch.float32, torch.float64):
+        raise ValueError("transform_points: float32 or float64 points")
+    p = points.reshape(-1, 3).contiguous()
+    if isinstance(transformation, torch.Tensor) and transformation.is_cuda:
+        T = transformation.to(torch.float64).contiguous()
+    else:
+        T = torch.from_numpy(np.ascontiguousarray(np.asarray(transformation, dtype=np.float64).reshape(16))).to(p.device)
+    if T.numel() < 16:
+        raise ValueError("transform_points: a [4,4] transformation")
+    out = torch.empty_like(p)
+    if len(p):
+        with torch.cuda.device(p.device):
+            check(_lib.load().naruto_icp_transform(len(p), p.data_ptr(), int(p.dtype == torch.float64), T.data_ptr(), out.data_ptr(), _stream()), "naruto_icp_transform")
+    return out
+
+
+def icp(source, target, max_correspondence_distance: float = 0.1, max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6,
+        init=None) -> IcpResult:
+    """Point-to-point ICP of the cloud ``source`` ([N,3]) onto ``target`` ([M,3], or a ready ``PointGridHIP``): the module docstring's
+    contract.  The target is binned once; per iteration the device runs transform -> nearest neighbour -> 17 sums -> Kabsch and the
+    convergence test, and the host reads eight doubles.  ``init``: the initial [4,4] (identity)."""
+    grid = target if isinstance(target, PointGridHIP) else PointGridHIP(target)
+    src = _cloud(source, grid.device)
+    n = len(src)
+    if n == 0:
+        raise ValueError("icp: an empty source cloud")
+    if not (max_correspondence_distance >= 0.0):
+        raise ValueError(f"icp: max_correspondence_distance {max_correspondence_distance}")
+    if int(max_iteration) < 0 or math.isnan(relative_fitness) or math.isnan(relative_rmse):
+        raise ValueError("icp: max_iteration >= 0 and numbers for the convergence criteria")
+    host = np.zeros(_lib.ICP_STATE_DOUBLES, dtype=np.float64)
+    host[:16] = (np.eye(4) if init is None else np.asarray(init, dtype=np.float64)).reshape(16)
+    if not np.isfinite(host).all():
+        raise ValueError("icp: a non-finite initial transformation")
+    lib = _lib.load()
+    dev = grid.device
+    state = torch.from_numpy(host).to(dev)
+    origin = (C.c_double * 3)(*(0.5 * (grid.box[0] + grid.box[1])))
+    moved = torch.empty_like(src)
+    sums = torch.empty(_lib.ICP_SUMS, dtype=torch.float64, device=dev)
+    ws = _lib.workspace(lib.naruto_icp_accumulate_workspace(n), dev, torch.float64)
+    history: List[Tuple[float, float]] = []
+    with torch.cuda.device(dev):
+        for _ in range(int(max_iteration) + 1):
+            check(lib.naruto_icp_transform(n, src.data_ptr(), 0, state.data_ptr(), moved.data_ptr(), _stream()), "naruto_icp_transform")
+            dist, index = grid.query(moved)
+            check(lib.naruto_icp_accumulate(n, moved.data_ptr(), len(grid.target), grid.target.data_ptr(), index.data_ptr(), dist.data_ptr(),
+                                            float(max_correspondence_distance), origin, ws.data_ptr(), sums.data_ptr(), _stream()), "naruto_icp_accumulate")
+            check(lib.naruto_icp_step(sums.data_ptr(), n, origin, int(max_iteration), float(relative_fitness), float(relative_rmse), state.data_ptr(), _stream()),
+                  "naruto_icp_step")
+            row = state[16:24].cpu().numpy()                     # the one read of the iteration: fitness, rmse, previous two, iteration, status, ...
+            history.append((float(row[0]), float(row[1])))
+            if int(row[5]) != _lib.ICP_RUNNING:
+                break
+    final = state.cpu().numpy()
+    status = int(final[21])
+    if status == _lib.ICP_RUNNING:
+        raise _lib.NarutoError("icp: the device loop did not stop")
+    return IcpResult(final[:16].reshape(4, 4).copy(), float(final[16]), float(final[17]), int(final[20]), status == _lib.ICP_CONVERGED, _lib.ICP_STATUS[status],
+                     history)
+
+
+def _mesh_vertices(mesh):
+    if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
+        mesh = M.load_ply(mesh)
+    return mesh.vertices if isinstance(mesh, M.Mesh) else mesh[0]
+
+
+def get_align_transformation(rec_mesh, gt_mesh) -> np.ndarray:
+    """The reference's name (eval_recon.py:83): the float64 [4,4] that moves ``rec_mesh`` onto ``gt_mesh``, ``icp`` of the vertices with
+    the defaults.  Either mesh is a ``.ply`` path, a ``naruto_amd.mesh.Mesh`` or a (vertices, faces) tuple."""
+    return icp(_mesh_vertices(rec_mesh), _mesh_vertices(gt_mesh)).transformation
+
+
 def empty_reconstruction_metrics() -> Dict[str, float]:
     """A reconstruction without faces: nothing to be accurate about, nothing completed."""
     return {"accuracy_cm": float("nan"), "completion_cm": float("inf"), "completion_ratio_pct": 0.0}
@@ -244,6 +362,15 @@ class ReconEvaluatorHIP:
         self.device = v.device
         self.gt_points, _ = sample_surface(v, f, self.n_samples, self.seed)
         self.gt_grid = PointGridHIP(self.gt_points, **grid_args)
+        self._gt_vertices, self._gt_vertex_grid = v, None       # the alignment target: binned once, at the first align=True
+
+    def align_vertices(self, vertices: torch.Tensor) -> Tuple[torch.Tensor, IcpResult]:
+        """The reconstruction's vertices moved onto the ground truth's (``icp`` of vertices onto vertices, the defaults): fp64
+        arithmetic, the vertices' own dtype out."""
+        if self._gt_vertex_grid is None:
+            self._gt_vertex_grid = PointGridHIP(self._gt_vertices, **self.grid_args)
+        result = icp(vertices, self._gt_vertex_grid)
+        return transform_points(vertices, result.transformation), result
 
     def _metrics_device(self, vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
         rec_points, _ = sample_surface(vertices, faces, self.n_samples, self.seed + 1)
@@ -254,23 +381,32 @@ class ReconEvaluatorHIP:
         comp = reduce_distances(d_gt, self.threshold)
         return torch.stack([acc[0] * 100.0, comp[0] * 100.0, comp[1] / float(len(d_gt)) * 100.0])
 
-    def evaluate_mesh(self, vertices, faces=None) -> Dict[str, float]:
+    def evaluate_mesh(self, vertices, faces=None, align: bool = False) -> Dict[str, float]:
+        """``align``: move the reconstruction onto the ground truth first (``icp`` of its vertices onto the ground truth's); the result
+        then carries ``align_fitness`` / ``align_inlier_rmse``.  Without it, launches and results are unchanged."""
         mesh = vertices if faces is None else (vertices, faces)
         if _n_faces(mesh) == 0:
             return empty_reconstruction_metrics()
         v, f = _mesh_tensors(mesh, self.device)
         if len(f) == 0:
             return empty_reconstruction_metrics()
+        aligned = None
+        if align:
+            v, aligned = self.align_vertices(v)
         acc, comp, ratio = (float(x) for x in self._metrics_device(v, f).cpu())
-        return {"accuracy_cm": acc, "completion_cm": comp, "completion_ratio_pct": ratio}
+        out = {"accuracy_cm": acc, "completion_cm": comp, "completion_ratio_pct": ratio}
+        if aligned is not None:
+            out["align_fitness"], out["align_inlier_rmse"] = aligned.fitness, aligned.inlier_rmse
+        return out
 
     @torch.no_grad()
     def evaluate_field(self, model, config, bounding_box: torch.Tensor, voxel_size: float, marching_cube_bound=None, cull_poses=None, cull_cam=None,
-                       **cull_args) -> Dict[str, float]:
+                       align: bool = False, **cull_args) -> Dict[str, float]:
         """field -> SDF lattice -> marching cubes -> metric vertices (as ``mesh.extract_mesh``) -> samples -> both queries, plus ``mad_cm``;
         no mesh or cloud goes to the host, one copy of four numbers ends the call.  With ``cull_poses`` ([P,4,4], metric frame) and
         ``cull_cam`` (config["cam"]) the extracted mesh is culled on the device first (``culling.cull_mesh``; ``cull_args`` are its keyword
-        arguments), at the price of one more copy of two numbers; without them the launches are unchanged."""
+        arguments), at the price of one more copy of two numbers; without them the launches are unchanged.  ``align``: the (culled)
+        mesh is moved onto the ground truth by ``icp`` before sampling, as in ``evaluate_mesh``; ``mad_cm`` does not depend on it."""
         vertices, triangles = M.extract_surface(model.query_sdf, config, bounding_box, marching_cube_bound, voxel_size=voxel_size)
         if cull_poses is not None and len(triangles) > 0:
             if cull_cam is None:
@@ -287,19 +423,29 @@ class ReconEvaluatorHIP:
             out = empty_reconstruction_metrics()
             out["mad_cm"] = float(mad.cpu())
             return out
+        aligned = None
+        if align:
+            v, triangles = _mesh_tensors((vertices, triangles), self.device)
+            vertices, aligned = self.align_vertices(v)
         acc, comp, ratio, mad = (float(x) for x in torch.cat([self._metrics_device(vertices, triangles), mad[None]]).cpu())
-        return {"accuracy_cm": acc, "completion_cm": comp, "completion_ratio_pct": ratio, "mad_cm": mad}
+        out = {"accuracy_cm": acc, "completion_cm": comp, "completion_ratio_pct": ratio, "mad_cm": mad}
+        if aligned is not None:
+            out["align_fitness"], out["align_inlier_rmse"] = aligned.fitness, aligned.inlier_rmse
+        return out
 
 
-def calc_3d_mesh_metric(mesh_gt, mesh_rec, n_samples: int = 200000, threshold: float = 0.05, seed: int = 0) -> Dict[str, float]:
+def calc_3d_mesh_metric(mesh_gt, mesh_rec, n_samples: int = 200000, threshold: float = 0.05, seed: int = 0, align: bool = False) -> Dict[str, float]:
     """Accuracy / Completion / Completion ratio of ``mesh_rec`` against ``mesh_gt`` (module docstring).  Either mesh is a
-    ``naruto_amd.mesh.Mesh``, a (vertices, faces) tuple of numpy arrays or device tensors, or the path of a ``.ply`` file."""
+    ``naruto_amd.mesh.Mesh``, a (vertices, faces) tuple of numpy arrays or device tensors, or the path of a ``.ply`` file.  ``align``:
+    ``mesh_rec`` is first moved onto ``mesh_gt`` (``ReconEvaluatorHIP.evaluate_mesh``)."""
     load = lambda m: M.load_ply(m) if isinstance(m, (str, bytes)) or hasattr(m, "__fspath__") else m      # noqa: E731
     mesh_gt, mesh_rec = load(mesh_gt), load(mesh_rec)
     if _n_faces(mesh_gt) == 0:
         raise ValueError("calc_3d_mesh_metric: the ground-truth mesh has no faces")
     if _n_faces(mesh_rec) == 0:
         return empty_reconstruction_metrics()
+    if align:
+        return ReconEvaluatorHIP(mesh_gt, n_samples, threshold, seed).evaluate_mesh(mesh_rec, align=True)
     return ReconEvaluatorHIP(mesh_gt, n_samples, threshold, seed).evaluate_mesh(mesh_rec)
 
 
@@ -361,15 +507,18 @@ def main(argv=None) -> Dict[str, float]:
     parser = argparse.ArgumentParser(prog="python -m naruto_amd.evaluation", description="Arguments to evaluate the reconstruction.")
     parser.add_argument("--rec_mesh", type=str, required=True, help="reconstructed mesh file path (.ply)")
     parser.add_argument("--gt_mesh", type=str, required=True, help="ground truth mesh file path (.ply)")
-    parser.add_argument("--align", action="store_true", help="Align meshes (not available: raises NotImplementedError)")
+    parser.add_argument("--align", action="store_true", help="not available: raises NotImplementedError, as it always has here; use --icp_align")
+    parser.add_argument("--icp_align", action="store_true",
+                        help="align the reconstructed mesh to the ground truth first (point-to-point ICP of the vertices on the device: the reference's --align step)")
     parser.add_argument("--result_txt", type=str, help="result txt")
     args = parser.parse_args(argv)
     if args.align:
-        raise NotImplementedError("--align: the reference's get_align_transformation is third-party code outside its tree; align the meshes before calling")
+        raise NotImplementedError("--align: the reference's get_align_transformation is third-party code outside its tree; --icp_align runs this library's "
+                                  "restatement of it (point-to-point ICP of the vertices)")
     for path in (args.rec_mesh, args.gt_mesh):
         if not path.lower().endswith(".ply"):
             raise ValueError(f"{path}: only .ply meshes are read (.obj scenes are not)")
-    result = calc_3d_mesh_metric(args.gt_mesh, args.rec_mesh)
+    result = calc_3d_mesh_metric(args.gt_mesh, args.rec_mesh, align=True) if args.icp_align else calc_3d_mesh_metric(args.gt_mesh, args.rec_mesh)
     print(result)
     if args.result_txt:
         update_results_file(result, args.result_txt)
