@@ -740,6 +740,16 @@ typedef struct NarutoFusedAdam {
      * (nothing of this iteration reads the ray buffers any more by then; a device-side rng is read AFTER this iteration's forward
      * advanced it, i.e. it keys the next iteration's draw).  NULL: off. */
     const struct NarutoRayBatch* next_batch;
+    /* optional: the uncertainty grid's own optimiser (a separate Adam that steps every fifth iteration on the gradient accumulated in
+     * g->uncert_grid) rides in the launch that finishes the gradients.  uncert_step != 0: the thread that adds voxel v's partial sums into the
+     * accumulated gradient applies naruto_adam_multi's step to p->uncert_grid[v] and zeroes the gradient (NARUTO_ADAM_ADVANCE |
+     * NARUTO_ADAM_ZERO_GRAD: uncert_step_dev = {completed steps, ticket word}, advanced by the last of the grid's workgroups; uncert_step_lag as
+     * NarutoAdamSeg.step_lag).  Same arithmetic in the same order as the separate launch.  Needs a grid whose gradient goes through the scatter
+     * (up to 2^20 voxels); uncert_step == 0: the gradient is accumulated and nothing else, the fields below are not read. */
+    uint32_t uncert_step, uncert_step_lag;
+    float* uncert_exp_avg; float* uncert_exp_avg_sq;
+    int32_t* uncert_step_dev;
+    float uncert_lr, uncert_eps, uncert_weight_decay, uncert_beta1, uncert_beta2;
 } NarutoFusedAdam;
 size_t naruto_train_workspace(const NarutoField* f, const NarutoTrainStep* t);
 int naruto_train_forward(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, int finalize, void* stream);
@@ -765,6 +775,14 @@ int naruto_debug_train_query_fwd(const NarutoField* f, const NarutoParams* p, co
 /* profiling: a device buffer of 16 x (ray workgroups) uint64 into which the packed training forward (k_query_fwd_loss_packed) stamps the
  * shader clock at the start and behind each step of every workgroup's first chunk (tools/fwd_timeline.py); NULL switches it off. */
 int naruto_debug_fwd_timeline(void* device_buffer);
+/* profiling: a device buffer of 16 x (4 x workgroups of the fp32 MLP backward, at most one workgroup per compute unit) uint64.  While it is set
+ * the backward launches the stamped build of k_query_bwd: every wave leaves the 100 MHz clock summed per phase of its tile loop and four stamps
+ * of the kernel's own (tools/bwd_timeline.py); the gradients are the product kernel's.  NULL switches it off. */
+int naruto_debug_bwd_timeline(void* device_buffer);
+/* naruto_query_bwd / naruto_train_backward: the workspace must be 16-byte aligned (the fp32 MLP backward writes its per-workgroup weight-gradient
+ * partials with 16-byte stores); NARUTO_ERR_INVALID otherwise. */
+/* bytes of dynamic LDS the launcher reserves for the fp32 MLP backward (k_query_bwd) and passes to every launch of it */
+size_t naruto_debug_query_bwd_lds_bytes(void);
 /* profiling (bench.py's roofline): k_hash_scatter_lds alone, over the point list the preceding naruto_train_backward left in the
  * workspace, in the launch shape of the iteration; writes the scatter's partial tables only (no gradient, no parameter). */
 int naruto_debug_train_scatter(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, void* stream);

@@ -74,7 +74,10 @@ class NarutoRayBatch(C.Structure):
 class NarutoFusedAdam(C.Structure):
     _fields_ = [("param", C.c_void_p * 5), ("exp_avg", C.c_void_p * 5), ("exp_avg_sq", C.c_void_p * 5),
                 ("lr", C.c_float * 5), ("eps", C.c_float * 5), ("weight_decay", C.c_float * 5),
-                ("beta1", C.c_float), ("beta2", C.c_float), ("step_dev", C.c_void_p), ("next_batch", C.c_void_p)]
+                ("beta1", C.c_float), ("beta2", C.c_float), ("step_dev", C.c_void_p), ("next_batch", C.c_void_p),
+                ("uncert_step", C.c_uint32), ("uncert_step_lag", C.c_uint32), ("uncert_exp_avg", C.c_void_p), ("uncert_exp_avg_sq", C.c_void_p),
+                ("uncert_step_dev", C.c_void_p), ("uncert_lr", C.c_float), ("uncert_eps", C.c_float), ("uncert_weight_decay", C.c_float),
+                ("uncert_beta1", C.c_float), ("uncert_beta2", C.c_float)]
 
 
 class NarutoTrainStep(C.Structure):
@@ -289,6 +292,8 @@ SIGNATURES = {
     "naruto_decoder_fwd": (_I, [_V, C.POINTER(NarutoParams), C.c_uint32, C.c_int, _V, _V, _V, _V]),
     "naruto_debug_train_query_fwd": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), _V]),
     "naruto_debug_fwd_timeline": (_I, [_V]),
+    "naruto_debug_bwd_timeline": (_I, [_V]),
+    "naruto_debug_query_bwd_lds_bytes": (C.c_size_t, []),
     "naruto_fwd_image_bytes": (C.c_size_t, [C.POINTER(C.c_size_t), C.POINTER(_U32)]),
     "naruto_fwd_image_init": (_I, [_V, C.POINTER(NarutoParams), _V, _V]),
     "naruto_debug_fwd_image": (_I, [_V, C.POINTER(NarutoParams), _V, _V]),

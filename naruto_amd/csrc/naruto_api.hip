@@ -51,6 +51,7 @@ namespace {
 
 thread_local char g_err[512] = "";
 unsigned long long* g_fwd_timeline = nullptr;       // profiling: naruto_debug_fwd_timeline
+unsigned long long* g_bwd_timeline = nullptr;       // profiling: naruto_debug_bwd_timeline
 
 int fail(int code, const char* fmt, ...) {
     va_list ap;
@@ -774,6 +775,7 @@ struct QueryBwd {
     uint32_t n_front;
     const uint32_t* n_list_dev;
     const AdamFuse* adam;           // the optimiser steps in the launch that finishes the gradients
+    const UncertAdam* unc_adam;     // ... and, on its stepping iterations, the uncertainty grid's own (needs adam; p is filled in here)
     const void* w_img;              // the MLP backward's weight images, prepared by k_loss_bwd_fused
     const TvLate* tv_late;          // the moved smoothness term's value lands in the losses with that launch (needs adam)
     const AssembleArgs* next;       // ... which also assembles the next iteration's ray batch (needs adam)
@@ -795,6 +797,7 @@ int query_bwd_impl(const NarutoField* f, const NarutoParams* p, const QueryBwd& 
     if (M == 0) return NARUTO_OK;
     if (int rc = check_points(q.pts)) return rc;
     const BwdWs w = bwd_ws(f, q.workspace, cap);
+    if ((reinterpret_cast<uintptr_t>(w.partials) & 15u) != 0u) return fail(NARUTO_ERR_INVALID, "query_bwd: the workspace must be 16-byte aligned");
     const bool bf = f->desc.mlp_mode == NARUTO_MLP_BF16;
     const uint32_t n_tiles = bf ? (M + 63u) / 64u : (M + 31u) / 32u;
     const uint32_t waves = bf ? 4u : (uint32_t)kBwdWaves;
@@ -806,7 +809,7 @@ int query_bwd_impl(const NarutoField* f, const NarutoParams* p, const QueryBwd& 
     if (blocks > max_blocks) blocks = max_blocks;
     const PointSrc ps = make_points(q.pts);
     static bool attr_set = false;
-    if (int rc = reserve_lds(attr_set, {lds_use(k_query_bwd, sizeof(BwdLds)), lds_use(k_query_bwd_bf, kBwdBfLdsBytes)}, "query_bwd: cannot reserve %zu bytes of LDS", sizeof(BwdLds)))
+    if (int rc = reserve_lds(attr_set, {lds_use(k_query_bwd, sizeof(BwdLds)), lds_use(k_query_bwd_timeline, sizeof(BwdLds)), lds_use(k_query_bwd_bf, kBwdBfLdsBytes)}, "query_bwd: cannot reserve %zu bytes of LDS", sizeof(BwdLds)))
         return rc;
     // the uncertainty grid's gradient: through the scatter (row 3 of the point list) unless the grid is too large for that
     const bool unc_scatter = g->uncert_grid != nullptr && f->plan.n_uncert != 0;
@@ -820,6 +823,10 @@ int query_bwd_impl(const NarutoField* f, const NarutoParams* p, const QueryBwd& 
     else if (bf)
         hipLaunchKernelGGL(k_query_bwd_bf, dim3(blocks), dim3(256), kBwdBfLdsBytes, st, f->lt, f->ut, f->bt, *p, ps, M, cap, q.feat_save, q.d_raw,
                            q.d_geo, w.d_feat, x_list, g->uncert_grid, w.partials, q.active_idx, q.n_active, n_front, unc_atomic, q.w_img, feat_M, feat_mul);
+    else if (g_bwd_timeline != nullptr)         // profiling build of the same kernel: a row of kBwdTlSlots stamps per wave
+        hipLaunchKernelGGL(k_query_bwd_timeline, dim3(blocks), dim3(64 * kBwdWaves), sizeof(BwdLds), st, f->lt, f->ut, f->bt, *p, ps, M, cap, q.feat_save, q.d_raw,
+                           q.d_geo, w.d_feat, x_list, g->uncert_grid, w.partials, q.active_idx, q.n_active, n_front, unc_atomic, q.w_img, feat_M, feat_mul,
+                           g_bwd_timeline);
     else
         hipLaunchKernelGGL(k_query_bwd, dim3(blocks), dim3(64 * kBwdWaves), sizeof(BwdLds), st, f->lt, f->ut, f->bt, *p, ps, M, cap, q.feat_save, q.d_raw,
                            q.d_geo, w.d_feat, x_list, g->uncert_grid, w.partials, q.active_idx, q.n_active, n_front, unc_atomic, q.w_img, feat_M, feat_mul);
@@ -839,6 +846,13 @@ int query_bwd_impl(const NarutoField* f, const NarutoParams* p, const QueryBwd& 
         if (unc_scatter) {
             ur.d_uncert = d_unc; ur.partial = scatter_ws(f, w.scatter_ws, Ml).unc_partial; ur.n_voxels = f->plan.uncert_voxels; ur.n_splits = uncert_splits(f, Ml);
             ur.voxels_pad = uncert_pad(f);
+        }
+        if (q.unc_adam != nullptr && q.unc_adam->on) {
+            if (!unc_scatter || p->uncert_grid == nullptr)
+                return fail(NARUTO_ERR_INVALID, "query_bwd: the uncertainty grid's step rides in the finishing launch only where its gradient goes through the scatter");
+            ur.adam = *q.unc_adam;
+            ur.adam.p = const_cast<float*>(p->uncert_grid);          // (NarutoParams is read-only to a backward; the fused optimisers step in place)
+            ur.adam.n_blocks = (ur.n_voxels + 255u) / 256u;
         }
         const uint32_t n_unc_blocks = unc_scatter ? (ur.n_voxels + 255u) / 256u : 0u;
         const TvLate tvl = q.tv_late != nullptr ? *q.tv_late : TvLate{};
@@ -1490,6 +1504,16 @@ int naruto_debug_fwd_timeline(void* device_buffer) {
     return NARUTO_OK;
 }
 
+// profiling: device buffer of kBwdTlSlots x 4 waves x kBwdMaxBlocks uint64; while it is set the fp32 MLP backward launches k_query_bwd_timeline,
+// the stamped build of k_query_bwd (NULL: off, the product kernel) -- tools/bwd_timeline.py
+int naruto_debug_bwd_timeline(void* device_buffer) {
+    g_bwd_timeline = static_cast<unsigned long long*>(device_buffer);
+    return NARUTO_OK;
+}
+
+// the dynamic LDS the launcher reserves for k_query_bwd and passes to its launches (the kernel has no static LDS): weight images + per-wave stages
+size_t naruto_debug_query_bwd_lds_bytes(void) { return sizeof(BwdLds); }
+
 int naruto_debug_train_query_fwd(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, void* stream) {
     if (int rc = train_check(f, p, t, "debug_train_query_fwd")) return rc;
     // exactly the launch naruto_train_forward issues for the field query: with the loss stage riding in it where that applies
@@ -1600,6 +1624,14 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
         // the finishing launch keeps the forward's weight image in step with the weights it updates (exact mode; whoever reads it decides per forward)
         if (f->desc.mlp_mode != NARUTO_MLP_BF16) adam.fwd_img = t_in->fwd_image;
     }
+    UncertAdam unc_adam{};
+    if (opt != nullptr && opt->uncert_step != 0u) {
+        if (opt->uncert_exp_avg == nullptr || opt->uncert_exp_avg_sq == nullptr || opt->uncert_step_dev == nullptr)
+            return fail(NARUTO_ERR_INVALID, "train_backward: NarutoFusedAdam.uncert_step needs the grid's moments and step word");
+        unc_adam.on = 1; unc_adam.m = opt->uncert_exp_avg; unc_adam.v = opt->uncert_exp_avg_sq; unc_adam.step_dev = opt->uncert_step_dev;
+        unc_adam.lag = opt->uncert_step_lag; unc_adam.lr = opt->uncert_lr; unc_adam.eps = opt->uncert_eps; unc_adam.wd = opt->uncert_weight_decay;
+        unc_adam.b1 = opt->uncert_beta1; unc_adam.b2 = opt->uncert_beta2;
+    }
     if (g == nullptr || t->loss_weights == nullptr || t->feat_save == nullptr || t->d_raw == nullptr || t->ray_count == nullptr || t->ray_offset == nullptr ||
         t->active_idx == nullptr || t->n_active == nullptr)
         return fail(NARUTO_ERR_INVALID, "train_backward: NULL buffer");
@@ -1678,6 +1710,7 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
     q.n_front = n_front;            // (0: no smoothness term in this backward -- the list is the samples alone, in a workspace sized for cap = M + n3)
     q.n_list_dev = n_front > 0 ? bw.n_total : nullptr;
     q.adam = ad;
+    q.unc_adam = unc_adam.on ? &unc_adam : nullptr;
     q.w_img = deferred ? w.w_img : nullptr;                      // prepared by k_loss_bwd_fused just above
     q.tv_late = (moved && ad != nullptr) ? &tvl : nullptr;
     q.next = next;

@@ -556,6 +556,20 @@ __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
 #endif
 }
 
+// mfma16x4: D[i][j] += sum_k A[i][k] B[k][j], 16x16x4 fp32 (v_mfma_f32_16x16x4_f32: the same multiply-add rate as the 32x32x2 form, half its
+//   cycles per instruction -- for products with a 16-wide side, which the 32x32 form pads to 32).
+//     A operand: lane l holds A[i = l&15][k = l>>4];  B operand: lane l holds B[k = l>>4][j = l&15];
+//     C/D: lane l, reg r holds D[row = 4*(l>>4) + r][col = l&15].
+__device__ __forceinline__ f32x4 mfma16x4(float a, float b, f32x4 c) {
+#ifdef NARUTO_ABLATE_MFMA
+    asm volatile("" ::"v"(a), "v"(b));
+    c[0] += a * b;
+    return c;
+#else
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+#endif
+}
+
 __device__ __forceinline__ void swap32(float& a, float& b) {
     auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
     a = __uint_as_float(r[0]);

@@ -1871,17 +1871,63 @@ __global__ __launch_bounds__(kScatterThreads) void k_hash_scatter_lds(LevelTab l
 
 // the uncertainty grid's share of a reduction launch: d_uncert[v] += sum over splits of the partial images (always accumulated: the
 // grid's optimiser steps every 5th iteration, its gradient adds up in between -- reference coslam.py:397-399)
+// ... and, on a stepping iteration of the fused optimiser, the grid's own Adam step (NarutoFusedAdam.uncert_step): the thread that owns voxel v adds
+// the partial sums, applies k_adam_multi's arithmetic (NARUTO_ADAM_ADVANCE | NARUTO_ADAM_ZERO_GRAD) and zeroes the accumulated gradient -- the
+// separate launch's read of what this thread would just have stored, its pass over the grid and its launch boundary go away.
+struct UncertAdam {
+    int on;                     // 0: accumulate only
+    float* p; float* m; float* v;
+    int32_t* step_dev;          // {completed steps, ticket}: the last of the grid's n_blocks workgroups to retire stores the new count
+    uint32_t lag, n_blocks;
+    float lr, eps, wd, b1, b2;
+};
 struct UncertReduce {
     float* d_uncert;            // NULL: nothing to do
     const float* partial;       // [n_splits][voxels_pad]
     uint32_t n_voxels, n_splits, voxels_pad;
+    UncertAdam adam;
 };
 __device__ __forceinline__ void uncert_reduce_body(const UncertReduce& u, uint32_t block) {
-    const uint32_t v = block * 256u + threadIdx.x;
-    if (u.d_uncert == nullptr || v >= u.n_voxels) return;
-    float s = 0.0f;
-    for (uint32_t k = 0; k < u.n_splits; ++k) s += u.partial[(size_t)k * u.voxels_pad + v];
-    u.d_uncert[v] += s;
+    const uint32_t i = block * 256u + threadIdx.x;
+    if (u.d_uncert == nullptr) return;
+    const UncertAdam& a = u.adam;
+    if (!a.on) {
+        if (i >= u.n_voxels) return;
+        float s = 0.0f;
+        for (uint32_t k = 0; k < u.n_splits; ++k) s += u.partial[(size_t)k * u.voxels_pad + i];
+        u.d_uncert[i] += s;
+        return;
+    }
+    const int32_t t_int = __hip_atomic_load(a.step_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+    if (i < u.n_voxels) {
+        float s = 0.0f;
+        for (uint32_t k = 0; k < u.n_splits; ++k) s += u.partial[(size_t)k * u.voxels_pad + i];
+        const float t = (float)(t_int - (int32_t)a.lag);
+        const float bc1 = 1.0f - powf(a.b1, t), bc2_sqrt = sqrtf(1.0f - powf(a.b2, t));
+        const float step_size = a.lr / bc1, eps = a.eps, wd = a.wd, b1 = a.b1, b2 = a.b2;
+        float* __restrict__ p = a.p;
+        float* __restrict__ m = a.m;
+        float* __restrict__ v = a.v;
+        float gi = u.d_uncert[i] + s;
+        const float pi = p[i];
+        if (wd != 0.0f) gi = fmaf(wd, pi, gi);
+        const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
+        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+        u.d_uncert[i] = 0.0f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t* ticket = reinterpret_cast<uint32_t*>(a.step_dev + 1);
+        // relaxed, as in k_adam_multi: the ticket counts retirements (every workgroup read the old count before it got here); the next launch reads the new one
+        const uint32_t k = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == a.n_blocks - 1u) {
+            __hip_atomic_store(a.step_dev, t_int, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 // d_table += sum over the level's splits of partial[split], for the entry ranges of the LDS-tiled levels
@@ -2065,8 +2111,8 @@ __global__ __launch_bounds__(256) void k_append_points(uint32_t E, const float* 
 constexpr int kStageLd = 97;   // row stride (floats) of the per-wave [32][96] input stage: odd => conflict-free
 constexpr int kGradLd = 33;    // row stride of the per-wave [32][32] stages
 // per-block dW image, 32x32 tiles (row = output unit of the layer, col = input column):
-//   0..2 dW(sdf_w0): stage cols 0..31 | 32..63 | 64..95   (80 real columns, 80..95 discarded)
-//   3    dW(sdf_w1): rows < 16 valid
+//   0..2 dW(sdf_w0): stage cols 0..31 | 32..63 | 64..95   (80 real columns: columns 16..31 of tile 2 are zeros)
+//   3    dW(sdf_w1): rows < 16 valid (the rest zeros)
 //   4..5 dW(col_w0): stage cols 32..63 (OneBlob 0..31) | 64..95 (OneBlob 32..47 ++ sdf-net outputs 0..15)
 //   6    dW(col_w1): rows < 3 valid
 constexpr int kAccTiles = 7;
@@ -2084,6 +2130,25 @@ __device__ __forceinline__ void block_sum_quarter(float* __restrict__ acc, const
         const float v = (*tiles[T])[R];
         *a = first ? v : *a + v;
     });
+}
+// the same rotation for tiles that are not all 32x32 register tiles: entry(constant K = 16 * tile + register, first) adds (first pass: writes) what
+// this lane holds of that pair -- k_query_bwd, whose 16-wide tiles are 16x16 blocks
+template <int G, class F>
+__device__ __forceinline__ void block_sum_quarter_of(bool first, F& entry) {
+    constexpr int kPer = kAccTiles * 16 / 4;
+    static_for<G * kPer, (G + 1) * kPer>([&](auto kc) { entry(kc, first); });
+}
+template <class F>
+__device__ __forceinline__ void block_sum_rotate(int wave, F entry) {
+    for (int p = 0; p < 4; ++p) {
+        switch ((wave + p) & 3) {
+            case 0: block_sum_quarter_of<0>(p == 0, entry); break;
+            case 1: block_sum_quarter_of<1>(p == 0, entry); break;
+            case 2: block_sum_quarter_of<2>(p == 0, entry); break;
+            default: block_sum_quarter_of<3>(p == 0, entry); break;
+        }
+        __syncthreads();
+    }
 }
 __device__ __forceinline__ void block_sum_tiles(float* __restrict__ acc, const f32x16* const (&tiles)[kAccTiles], int wave, int hh, int j) {
     for (int p = 0; p < 4; ++p) {
@@ -2157,57 +2222,99 @@ __device__ __forceinline__ void fetch_weight_image(void* __restrict__ lds, const
     uint4* __restrict__ dst = reinterpret_cast<uint4*>(lds);
     for (uint32_t i = (uint32_t)tid; i < (uint32_t)(bytes / 16u); i += (uint32_t)NT) dst[i] = src[i];
 }
+// The same copy for a size known at compile time, in two halves: every 16-byte load is issued before anything waits (the loop above waits for each
+// load before it issues the next: nine trips to L2 in a row), and the pieces go to LDS later, so that the caller can put its own dependent trips
+// to memory between the two -- k_query_bwd's count -> list entry -> first tile's inputs, tools/bwd_timeline.py.
+template <int NT, size_t BYTES>
+struct WeightImageCopy {
+    static constexpr uint32_t n = (uint32_t)(BYTES / 16u), kTrips = (n + (uint32_t)NT - 1u) / (uint32_t)NT;
+};
+template <int NT, size_t BYTES, class Pieces>
+__device__ __forceinline__ void weight_image_load(Pieces& v, const void* __restrict__ img, int tid) {
+    constexpr uint32_t n = WeightImageCopy<NT, BYTES>::n;
+    const u32x4_t* __restrict__ src = reinterpret_cast<const u32x4_t*>(img);
+    static_for<0, (int)WeightImageCopy<NT, BYTES>::kTrips>([&](auto kc) {
+        constexpr uint32_t k = decltype(kc)::value;
+        const uint32_t i = (uint32_t)tid + k * (uint32_t)NT;
+        v[k] = src[i < n ? i : n - 1u];                 // (the last trip is partial: its idle lanes reload the last piece and store nothing)
+    });
+}
+template <int NT, size_t BYTES, class Pieces>
+__device__ __forceinline__ void weight_image_store(void* __restrict__ lds, const Pieces& v, int tid) {
+    constexpr uint32_t n = WeightImageCopy<NT, BYTES>::n;
+    u32x4_t* __restrict__ dst = reinterpret_cast<u32x4_t*>(lds);
+    static_for<0, (int)WeightImageCopy<NT, BYTES>::kTrips>([&](auto kc) {
+        constexpr uint32_t k = decltype(kc)::value;
+        const uint32_t i = (uint32_t)tid + k * (uint32_t)NT;
+        if (i < n) dst[i] = v[k];
+    });
+}
 __device__ __forceinline__ void stage_ctile(float* __restrict__ buf, int ld, int col0, const f32x16& t, int j, int hh) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) buf[j * ld + col0 + crow(r, hh)] = t[r];
 }
 
-// one 32x32 dW tile over this wave's 32 points: D[i][c] += sum_pt G[pt][i] * X[pt][c0 + c].  The tile lives in
+// dW tiles over this wave's 32 points: D[i][c] += sum_pt G[pt][i] * X[pt][c0 + c].  A tile lives in
 // this wave's registers for the whole kernel (ds_add_f32 is ~25x too slow on gfx950 to accumulate in LDS).
 // Operands are read kWgradBatch K-pairs at a time (one lgkmcnt wait per batch, then the dependent MFMAs back to back):
 // large batches hide the LDS round trip when a SIMD holds a single wave, small ones keep the kernel inside the 256
 // registers that two waves per SIMD leave to each.
 constexpr int kWgradBatch = kBwdWaves > 4 ? 4 : 16;
 
-__device__ __forceinline__ void wgrad_tile(const float* __restrict__ gbuf, int gld, const float* __restrict__ xbuf, int xld, int c0,
-                                           f32x16& d, int lane) {
-    const int i = lane & 31, kk = lane >> 5;
+// A dW tile with a 16-wide side runs on the 16x16x4 form: the 32x32 instruction would spend half of its cycles on padding.  The K index stays the
+// point index (four points per instruction: lane l reads point 4u + (l >> 4)), operands straight from the same stages; each 16x16 block of the
+// tile is a chain of eight instructions per 32 points, and a tile's two blocks alternate so that no instruction waits for its predecessor.
+// dW(sdf_w1): D[o][c] += sum_pt G[pt][o] * X[pt][c], o < 16 (rows >= 16 of d_out are exact zeros), c < 32; d[b] = columns 16b .. 16b+15
+__device__ __forceinline__ void wgrad_rows16(const float* __restrict__ gbuf, int gld, const float* __restrict__ xbuf, int xld, f32x4 (&d)[2], int lane) {
+    const int c = lane & 15, q = lane >> 4;
+    float gv[8], x0[8], x1[8];
 #pragma unroll
-    for (int t0 = 0; t0 < 16; t0 += kWgradBatch) {
-        float gv[kWgradBatch], xv[kWgradBatch];
+    for (int u = 0; u < 8; ++u) {
+        const int pt = 4 * u + q;
+        gv[u] = gbuf[pt * gld + c];
+        x0[u] = xbuf[pt * xld + c];
+        x1[u] = xbuf[pt * xld + 16 + c];
+    }
 #pragma unroll
-        for (int t = 0; t < kWgradBatch; ++t) {
-            const int pt = 2 * (t0 + t) + kk;
-            gv[t] = gbuf[pt * gld + i];
-            xv[t] = xbuf[pt * xld + c0 + i];
-        }
-#pragma unroll
-        for (int t = 0; t < kWgradBatch; ++t) d = mfma32(gv[t], xv[t], d);
+    for (int u = 0; u < 8; ++u) {
+        d[0] = mfma16x4(gv[u], x0[u], d[0]);
+        d[1] = mfma16x4(gv[u], x1[u], d[1]);
     }
 }
 
-// three tiles sharing the G operand (dW of one layer, 96 input columns): G is read once, the three accumulators
-// are independent so consecutive MFMAs never wait on each other
-__device__ __forceinline__ void wgrad_tile3(const float* __restrict__ gbuf, int gld, const float* __restrict__ xbuf, int xld, f32x16& d0,
-                                            f32x16& d1, f32x16& d2, int lane) {
-    const int i = lane & 31, kk = lane >> 5;
+// dW of sdf layer 0 (80 input columns): two 32x32 tiles (stage columns 0..31 | 32..63) sharing the G operand, and the 16 columns 64..79 as two
+// 16x16 blocks dh[b] = rows 16b .. 16b+15 (stage columns 80..95 are the colour layer's inputs: no accumulator).  All four accumulators are
+// independent, so consecutive MFMAs never wait on each other.
+__device__ __forceinline__ void wgrad_tile2_cols16(const float* __restrict__ gbuf, int gld, const float* __restrict__ xbuf, int xld, f32x16& d0,
+                                                   f32x16& d1, f32x4 (&dh)[2], int lane) {
+    const int i = lane & 31, kk = lane >> 5, c = lane & 15, q = lane >> 4;
     constexpr int B = kWgradBatch > 8 ? 8 : kWgradBatch;
+    static_assert(B % 2 == 0, "a batch of K pairs holds whole K quads");
 #pragma unroll
     for (int t0 = 0; t0 < 16; t0 += B) {
-        float gv[B], x0[B], x1[B], x2[B];
+        float gv[B], x0[B], x1[B], a0[B / 2], a1[B / 2], xh[B / 2];
 #pragma unroll
         for (int t = 0; t < B; ++t) {
             const int pt = 2 * (t0 + t) + kk;
             gv[t] = gbuf[pt * gld + i];
             x0[t] = xbuf[pt * xld + i];
             x1[t] = xbuf[pt * xld + 32 + i];
-            x2[t] = xbuf[pt * xld + 64 + i];
+        }
+#pragma unroll
+        for (int u = 0; u < B / 2; ++u) {
+            const int pt = 4 * (t0 / 2 + u) + q;
+            a0[u] = gbuf[pt * gld + c];
+            a1[u] = gbuf[pt * gld + 16 + c];
+            xh[u] = xbuf[pt * xld + 64 + c];
         }
 #pragma unroll
         for (int t = 0; t < B; ++t) {
             d0 = mfma32(gv[t], x0[t], d0);
             d1 = mfma32(gv[t], x1[t], d1);
-            d2 = mfma32(gv[t], x2[t], d2);
+            if (t & 1) {
+                dh[0] = mfma16x4(a0[t >> 1], xh[t >> 1], dh[0]);
+                dh[1] = mfma16x4(a1[t >> 1], xh[t >> 1], dh[1]);
+            }
         }
     }
 }
@@ -2233,12 +2340,20 @@ __device__ __forceinline__ void wgrad_tile2(const float* __restrict__ gbuf, int 
     }
 }
 
-__global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, uint32_t cap,
-                                                   const float* __restrict__ feat_save, const float* __restrict__ d_raw,
-                                                   const float* __restrict__ d_geo, float* __restrict__ d_feat, float* __restrict__ x_out,
-                                                   float* __restrict__ d_uncert_grid, float* __restrict__ partials,
-                                                   const uint32_t* __restrict__ active_idx, const uint32_t* __restrict__ n_active, uint32_t list_off, int unc_atomic,
-                                                   const void* __restrict__ w_img, uint32_t feat_M, uint32_t feat_mul) {
+// Per-phase timeline of the tile loop (profiling build only: TL = true is k_query_bwd_timeline behind naruto_debug_bwd_timeline; the product kernel
+// holds no stamp).  Every WAVE owns a row of kBwdTlSlots counters of the 100 MHz clock: 0..6 = time summed over its tiles from one stamp to the next
+// -- 0 inputs ready, 1 layer-0 recompute, 2 OneBlob + colour recompute, 3 colour backward + dW(col_w0), 4 dW(sdf_w1), 5 dW(sdf_w0), 6 dgrad to
+// features + stores -- 7 = tiles, 8 start, 9 weight image in LDS, 10 epilogue start, 11 end (tools/bwd_timeline.py).  A stamp drains the wave's LDS
+// traffic and fences the scheduler, so the build forbids overlaps across phase boundaries that the product kernel has: read its shares, not its length.
+constexpr int kBwdTlSlots = 16;
+
+template <bool TL>
+__device__ __forceinline__ void query_bwd_body(LevelTab lt, UncertTab ut, BoxTab bt, const NarutoParams& p, PointSrc ps, uint32_t M, uint32_t cap,
+                                               const float* __restrict__ feat_save, const float* __restrict__ d_raw,
+                                               const float* __restrict__ d_geo, float* __restrict__ d_feat, float* __restrict__ x_out,
+                                               float* __restrict__ d_uncert_grid, float* __restrict__ partials,
+                                               const uint32_t* __restrict__ active_idx, const uint32_t* __restrict__ n_active, uint32_t list_off, int unc_atomic,
+                                               const void* __restrict__ w_img, uint32_t feat_M, uint32_t feat_mul, unsigned long long* __restrict__ timeline) {
     // feat_save[(T * feat_M + m * feat_mul) * 2 + f]: level-major (feat_M = M, feat_mul = 1) or, behind the Morton-ordered forward of the large
     // tables (naruto_sorted.hip), sample-major (feat_M = 1, feat_mul = 16)
     // list_off: position of this launch's first point in the scatter's point list (the smoothness lattice sits in front)
@@ -2247,13 +2362,39 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
     BwdLds& L = *reinterpret_cast<BwdLds*>(smem_raw);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int hh = lane >> 5, j = lane & 31;
+    unsigned long long tl_sum[7] = {0, 0, 0, 0, 0, 0, 0}, tl_prev = 0, tl_tiles = 0;
+    auto tl_now = [&]() -> unsigned long long {
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned long long t = (unsigned long long)wall_clock64();
+        __builtin_amdgcn_sched_barrier(0);
+        return t;
+    };
+    auto tl_mark = [&](int k) {          // once per kernel
+        if constexpr (TL) {
+            const unsigned long long t = tl_now();
+            if (timeline != nullptr && lane == 0) timeline[((size_t)blockIdx.x * kBwdWaves + wave) * kBwdTlSlots + k] = t;
+        }
+    };
+    auto tl_phase = [&](int k) {         // once per tile and phase: the time since the previous stamp belongs to phase k
+        if constexpr (TL) {
+            const unsigned long long t = tl_now();
+            tl_sum[k] += t - tl_prev;
+            tl_prev = t;
+        }
+    };
+    tl_mark(8);
+    // the weight images set out first: they arrive while the first tile's three dependent trips to memory (count -> list entry -> inputs) are under way
+    u32x4_t w_copy[WeightImageCopy<64 * kBwdWaves, kBwdImageBytes>::kTrips];          // (a native vector type: the pieces stay in registers)
+    if (w_img != nullptr) weight_image_load<64 * kBwdWaves, kBwdImageBytes>(w_copy, w_img, threadIdx.x);
     // M_eff points are processed: all M, or the compacted list of points whose cotangent is not identically 0
     const uint32_t M_eff = n_active != nullptr ? n_active[0] : M;
     const uint32_t n_tiles = (M_eff + 31u) / 32u;
     float* __restrict__ xs = L.xs[wave];
     float* __restrict__ ga = L.ga[wave];
     float* __restrict__ gb = L.gb[wave];
-    f32x16 dW0a = zero16(), dW0b = zero16(), dW0c = zero16(), dW1 = zero16(), dWc0a = zero16(), dWc0b = zero16();
+    f32x16 dW0a = zero16(), dW0b = zero16(), dWc0a = zero16(), dWc0b = zero16();
+    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 dW0c[2] = {zero4, zero4}, dW1[2] = {zero4, zero4};      // the 16-wide tiles 2 and 3 as 16x16 blocks: wgrad_tile2_cols16, wgrad_rows16
     float pc1[3][16];               // dW(col_w1): this lane's partial sums  d_rgb[q] * relu(c)[unit crow(r, hh)]  over its points
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
@@ -2304,11 +2445,12 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
         nxt = load_tile(tile, load_index(tile));
         m_ahead = load_index(min(tile + tile_stride, last_tile));
     }
-    // the weight images arrive while the first tile's three dependent trips to memory (count -> list entry -> inputs) are under way
-    if (w_img != nullptr) fetch_weight_image<64 * kBwdWaves>(smem_raw, w_img, kBwdImageBytes, threadIdx.x);
+    if (w_img != nullptr) weight_image_store<64 * kBwdWaves, kBwdImageBytes>(smem_raw, w_copy, threadIdx.x);
     else stage_bwd_weights<64 * kBwdWaves>(L, p, threadIdx.x);
     __syncthreads();
+    tl_mark(9);
     for (; tile < n_tiles; tile += tile_stride) {
+        if constexpr (TL) tl_prev = tl_now();
         TileIn cur;
         if constexpr (kPrefetch) {
             cur = nxt;
@@ -2344,6 +2486,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
             for (int c = 0; c < 8; ++c)
                 if (ui[c] >= 0) unsafeAtomicAdd(d_uncert_grid + ui[c], uw[c] * g_unc);
         }
+        tl_phase(0);
         // ---- recompute the forward from the saved hash features; stage layer-0 inputs [point][0..79]
         f32x16 h = zero16(), c = zero16();
         static_for<0, kLevels>([&](auto tc) {
@@ -2352,6 +2495,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
             xs[j * kStageLd + 2 * T + hh] = b;            // (padding points: finite inputs of the last valid point x exact-zero cotangents = 0 in every dW sum)
             h = mfma32(L.f.s0[T * 64 + lane], b, h);
         });
+        tl_phase(1);
         const bool blob_fast = __all(oneblob_sparse_ok(x) && oneblob_sparse_ok(y) && oneblob_sparse_ok(z));
         // (zero K pairs skipped as in the forward: a product with an exact 0.0f adds nothing; the stage still gets every column)
         float eb[3][kBins];
@@ -2388,6 +2532,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
         // sdf-net outputs -> stage columns 80..95 (colour layer-0 inputs); padding points -> 0
 #pragma unroll
         for (int r = 0; r < 8; ++r) xs[j * kStageLd + 80 + crow(r, hh)] = o[r];
+        tl_phase(2);
 
         // ---- colour layer 1 backward (VALU): d_c = relu'(c) * (col_w1^T . d_rgb)
         f32x16 dcv, cact;
@@ -2425,6 +2570,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
             }
         }
         if (hh == 0) dov[0] += g_sdf;             // row 0 is the sdf: its direct cotangent
+        tl_phase(3);
         // ---- dW(sdf_w1)[o][i] = sum_pt d_out[o] * relu(h)[i]   (tile 3; rows >= 16 of d_out are exact zeros)
         {
             f32x16 hact;
@@ -2432,10 +2578,12 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
             for (int r = 0; r < 16; ++r) hact[r] = fmaxf(h[r], 0.0f);
             wave_lds_sync();
             stage_ctile(gb, kGradLd, 0, hact, j, hh);
-            stage_ctile(ga, kGradLd, 0, dov, j, hh);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) ga[j * kGradLd + crow(r, hh)] = dov[r];          // rows 0..15: registers 0..7 of both halves
             wave_lds_sync();
-            wgrad_tile(ga, kGradLd, gb, kGradLd, 0, dW1, lane);
+            wgrad_rows16(ga, kGradLd, gb, kGradLd, dW1, lane);
         }
+        tl_phase(4);
         // ---- dgrad sdf layer 1 -> hidden, masked by ReLU
         f32x16 dh = zero16();
         static_for<0, 8>([&](auto rc) {
@@ -2444,12 +2592,13 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
         });
 #pragma unroll
         for (int r = 0; r < 16; ++r) dh[r] = h[r] > 0.0f ? dh[r] : 0.0f;
-        // ---- dW(sdf_w0) = d_h^T . [feat32 | OneBlob48 | (16 discarded)]   (tiles 0..2)
+        // ---- dW(sdf_w0) = d_h^T . [feat32 | OneBlob48]   (tiles 0, 1 and the 16 columns of tile 2)
         wave_lds_sync();
         stage_ctile(ga, kGradLd, 0, dh, j, hh);
         wave_lds_sync();
-        wgrad_tile3(ga, kGradLd, xs, kStageLd, dW0a, dW0b, dW0c, lane);
+        wgrad_tile2_cols16(ga, kGradLd, xs, kStageLd, dW0a, dW0b, dW0c, lane);
         wave_lds_sync();
+        tl_phase(5);
         // ---- dgrad sdf layer 0 -> hash features
         f32x16 df = zero16();
         static_for<0, 16>([&](auto tc) {
@@ -2468,7 +2617,10 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
                 }
             }
         }
+        tl_phase(6);
+        ++tl_tiles;
     }
+    tl_mark(10);
     // block-level sum of the four waves' register tiles through the LDS image, then one coalesced write of the partial
     static_assert(sizeof(L.xs) >= kAccFloats * sizeof(float), "the dW image must fit the xs stages");
     float* __restrict__ acc = &L.xs[0][0];
@@ -2498,12 +2650,73 @@ __global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, Uncer
         }
     }
     {
-        static_assert(kBwdWaves == 4, "block_sum_tiles rotates four waves");
-        const f32x16* const tiles[kAccTiles] = {&dW0a, &dW0b, &dW0c, &dW1, &dWc0a, &dWc0b, &dWc1};
-        block_sum_tiles(acc, tiles, wave, hh, j);
+        static_assert(kBwdWaves == 4, "block_sum_rotate rotates four waves");
+        const f32x16* const full[kAccTiles] = {&dW0a, &dW0b, nullptr, nullptr, &dWc0a, &dWc0b, &dWc1};
+        block_sum_rotate(wave, [&](auto kc, bool first) {
+            constexpr int K = decltype(kc)::value, T = K / 16, R = K % 16;
+            if constexpr (T == 2 || T == 3) {
+                // the 16-wide tiles: "registers" 0..7 are the four registers of the two 16x16 blocks, 8..15 stand for the half of the image tile that
+                // nobody accumulates (tile 2: columns 16..31, tile 3: rows 16..31), zeroed once -- the partial is written and reduced as whole tiles
+                if constexpr (R < 8) {
+                    constexpr int B = R / 4, r = R % 4;
+                    const int q = lane >> 4, c = lane & 15;
+                    const int row = T == 2 ? 16 * B + 4 * q + r : 4 * q + r, col = T == 2 ? c : 16 * B + c;
+                    float* a = &acc[T * 1024 + row * 32 + col];
+                    const float v = T == 2 ? dW0c[B][r] : dW1[B][r];
+                    *a = first ? v : *a + v;
+                } else if (first) {
+                    const int e = (R - 8) * 64 + lane;
+                    const int row = T == 2 ? e >> 4 : 16 + (e >> 5), col = T == 2 ? 16 + (e & 15) : e & 31;
+                    acc[T * 1024 + row * 32 + col] = 0.0f;
+                }
+            } else {
+                float* a = &acc[T * 1024 + crow(R, hh) * 32 + j];
+                const float v = (*full[T])[R];
+                *a = first ? v : *a + v;
+            }
+        });
     }
-    float* __restrict__ out = partials + (size_t)blockIdx.x * kAccFloats;
-    for (int e = threadIdx.x; e < kAccFloats; e += blockDim.x) out[e] = acc[e];
+    // 16 bytes per lane and trip, all of a lane's LDS reads in flight before its first store (as a loop over blockDim.x this was 28 rounds of one
+    // LDS read, its wait and a 4-byte store, behind a load of the launch's block size)
+    {
+        constexpr int kNT = 64 * kBwdWaves, kTrips = kAccFloats / (4 * kNT);
+        static_assert(kAccFloats % (4 * kNT) == 0, "the partial is written in whole 16-byte trips of the workgroup");
+        const float4* __restrict__ a4 = reinterpret_cast<const float4*>(acc);
+        float4* __restrict__ o4 = reinterpret_cast<float4*>(partials + (size_t)blockIdx.x * kAccFloats);        // 16-byte aligned: query_bwd_impl checks
+        float4 v[kTrips];
+#pragma unroll
+        for (int k = 0; k < kTrips; ++k) v[k] = a4[threadIdx.x + k * kNT];
+#pragma unroll
+        for (int k = 0; k < kTrips; ++k) o4[threadIdx.x + k * kNT] = v[k];
+    }
+    if constexpr (TL) {
+        tl_mark(11);
+        if (timeline != nullptr && lane == 0) {
+            unsigned long long* __restrict__ row = timeline + ((size_t)blockIdx.x * kBwdWaves + wave) * kBwdTlSlots;
+#pragma unroll
+            for (int k = 0; k < 7; ++k) row[k] = tl_sum[k];
+            row[7] = tl_tiles;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, uint32_t cap,
+                                                   const float* __restrict__ feat_save, const float* __restrict__ d_raw,
+                                                   const float* __restrict__ d_geo, float* __restrict__ d_feat, float* __restrict__ x_out,
+                                                   float* __restrict__ d_uncert_grid, float* __restrict__ partials,
+                                                   const uint32_t* __restrict__ active_idx, const uint32_t* __restrict__ n_active, uint32_t list_off, int unc_atomic,
+                                                   const void* __restrict__ w_img, uint32_t feat_M, uint32_t feat_mul) {
+    query_bwd_body<false>(lt, ut, bt, p, ps, M, cap, feat_save, d_raw, d_geo, d_feat, x_out, d_uncert_grid, partials, active_idx, n_active, list_off, unc_atomic,
+                          w_img, feat_M, feat_mul, nullptr);
+}
+__global__ __launch_bounds__(64 * kBwdWaves) void k_query_bwd_timeline(LevelTab lt, UncertTab ut, BoxTab bt, NarutoParams p, PointSrc ps, uint32_t M, uint32_t cap,
+                                                   const float* __restrict__ feat_save, const float* __restrict__ d_raw,
+                                                   const float* __restrict__ d_geo, float* __restrict__ d_feat, float* __restrict__ x_out,
+                                                   float* __restrict__ d_uncert_grid, float* __restrict__ partials,
+                                                   const uint32_t* __restrict__ active_idx, const uint32_t* __restrict__ n_active, uint32_t list_off, int unc_atomic,
+                                                   const void* __restrict__ w_img, uint32_t feat_M, uint32_t feat_mul, unsigned long long* __restrict__ timeline) {
+    query_bwd_body<true>(lt, ut, bt, p, ps, M, cap, feat_save, d_raw, d_geo, d_feat, x_out, d_uncert_grid, partials, active_idx, n_active, list_off, unc_atomic,
+                         w_img, feat_M, feat_mul, timeline);
 }
 
 // ------------------------------------------------------------------------------------------------

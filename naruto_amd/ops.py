@@ -898,6 +898,28 @@ class TrainStep:
                 check(lib.naruto_fwd_image_init(self.handle.ptr, C.byref(self.ps), _p(self.fwd_image), _stream()), "naruto_fwd_image_init")
             self.t.fwd_image = _p(self.fwd_image)
 
+    def fuse_uncert_adam(self, exp_avg, exp_avg_sq, step_dev: torch.Tensor, lr, eps, weight_decay, betas, lag: int = 0):
+        """The uncertainty grid's own Adam, to ride in the launch that finishes the gradients on the iterations ``uncert_step_rides(True)``
+        marks (after ``fuse_adam``): its moments, its {completed steps, ticket} device word and its hyper-parameters."""
+        assert self.opt is not None, "fuse_uncert_adam comes after fuse_adam"
+        grid = self.params["uncert_grid"]
+        for t_ in (exp_avg, exp_avg_sq):
+            assert t_.is_cuda and t_.dtype == torch.float32 and t_.is_contiguous() and t_.numel() == grid.numel()
+        assert step_dev.dtype == torch.int32 and step_dev.is_cuda and step_dev.numel() >= 2
+        o = self.opt
+        o.uncert_exp_avg, o.uncert_exp_avg_sq, o.uncert_step_dev = exp_avg.data_ptr(), exp_avg_sq.data_ptr(), step_dev.data_ptr()
+        o.uncert_lr, o.uncert_eps, o.uncert_weight_decay = float(lr), float(eps), float(weight_decay)
+        o.uncert_beta1, o.uncert_beta2, o.uncert_step_lag, o.uncert_step = float(betas[0]), float(betas[1]), int(lag), 0
+        self._opt_keep += [exp_avg, exp_avg_sq, step_dev]
+        self.uncert_adam_fused = True
+
+    def uncert_step_rides(self, on: bool) -> bool:
+        """Whether the backwards issued from now on also step the uncertainty grid (and zero its accumulated gradient).  Returns whether they will."""
+        ok = bool(on) and self.opt is not None and getattr(self, "uncert_adam_fused", False)
+        if self.opt is not None:
+            self.opt.uncert_step = 1 if ok else 0
+        return ok
+
     def fwd_image_fresh(self, fresh: bool) -> bool:
         """The caller's statement for the forwards issued from now on: the weight image matches the MLP weights, i.e. the last thing that changed
         them was this step's own fused-Adam backward.  Returns whether a forward will use it (False: no image -- bf16 mode, no fused optimiser)."""

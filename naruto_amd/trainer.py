@@ -312,6 +312,7 @@ class MappingTrainer:
         self.fuse_optimizer = bool(fused_adam)          # single process: apply the mapping Adam inside the backward
         self._train_steps = {}
         self.max_cached_steps = 2
+        self.uncert_in_finish = True    # the grid's Adam step in the backward's finishing launch (capture(uncert_in_finish=...))
         self.assert_every = 8           # graph replay: deferred ``uncert_map.min() > 0`` check every this many iterations
         if self.direct:
             # {seed, iteration counter}: the kernels' own random numbers are keyed by it, the forward advances the counter,
@@ -363,6 +364,12 @@ class MappingTrainer:
                 betas = self.map_optimizer.param_groups[0]['betas']
                 assert all(tuple(gp['betas']) == tuple(betas) for gp in self.map_optimizer.param_groups)
                 ts.fuse_adam(entries, betas, self.map_optimizer.external_step)
+                uo = self.uncert_optim
+                if isinstance(uo, FusedAdam) and uo.external_step is None and m.uncert_grid.numel() <= (1 << 20):
+                    # ... and on its stepping iterations the uncertainty grid's own Adam too (``uncert_in_finish``; larger grids keep float atomics)
+                    gp = uo.param_groups[0]
+                    mm, vv = uo.moments(m.uncert_grid)
+                    ts.fuse_uncert_adam(mm, vv, uo.step_dev, gp['lr'], gp['eps'], gp['weight_decay'], gp['betas'], uo.state[m.uncert_grid]['lag'])
             self._train_steps[key] = ts
         return ts
 
@@ -399,13 +406,19 @@ class MappingTrainer:
         if check:
             model.check_asserts()
         ts = self.train_step_for(rays_o.shape[0], smooth)
+        rides = False
         with torch.no_grad():
             if self.group is not None and ts.opt is None:
                 # (then identical Adam steps on every rank)
                 self._dp_exchange(ts, lambda: ts.run_forward(rays_o, rays_d, target_rgb, target_d.reshape(-1)),
                                   lambda: ts.run_backward(phase=1), lambda: ts.run_backward(phase=2))
             else:
-                ts.run(rays_o, rays_d, target_rgb, target_d.reshape(-1))
+                # the grid's Adam step rides in the backward's finishing launch where the fused optimiser does (no sixth launch on stepping iterations)
+                rides = ts.uncert_step_rides(uncert_step and self.uncert_in_finish)
+                try:
+                    ts.run(rays_o, rays_d, target_rgb, target_d.reshape(-1))
+                finally:
+                    ts.uncert_step_rides(False)
             losses = ts.losses
             if ts.opt is None:
                 for name, p in model._params().items():
@@ -414,7 +427,9 @@ class MappingTrainer:
                 self._table_shard_step()
             else:
                 model.uncert_grid.grad = ts.grads["uncert_grid"]          # table / weight gradients are consumed inside the backward
-            if uncert_step:
+            if uncert_step and rides:
+                self.uncert_optim._n_steps += 1                # host mirror of the steps issued, as FusedAdam.step keeps it
+            elif uncert_step:
                 if self.group is not None:
                     parallel.allreduce_grads([model.uncert_grid], self.group)
                 self.uncert_optim.step(zero_grad=True)
@@ -591,7 +606,7 @@ class MappingTrainer:
         return out
 
     def capture(self, n_rays: int, smooth: bool = False, n_rays_total: int = 0, warmup: int = 3, prologue=None, first_prologue=None, on_buffers=None, chain=None,
-                fwd_image: Optional[bool] = None):
+                fwd_image: Optional[bool] = None, uncert_in_finish: Optional[bool] = None):
         """Record the iteration into hipGraphs (static shapes: n_rays rays per call).
         ``prologue(rays_o, rays_d, target_rgb, target_d)``: launches recorded IN FRONT of the iteration inside the same graphs -- the
         ray assembly / active ray selection that fill the iteration's input buffers (naruto_amd.ba_loop.FusedBA); single process.
@@ -605,7 +620,12 @@ class MappingTrainer:
         ``fwd_image``: iterations 1 ... of the chain read the MLP weights from the image the preceding iteration's finishing launch left (ops.TrainStep.
         fwd_image_fresh) instead of staging them in every workgroup -- inside the chain nothing else can have changed the weights.  Iteration 0 and
         the per-iteration graphs never do: their predecessor is unknown (a load_state_dict, another optimiser, a copy into the weights).  Default
-        (None): on, unless the environment says NARUTO_FWD_WEIGHT_IMAGE=0 at capture time; single process, fused Adam, exact mode only."""
+        (None): on, unless the environment says NARUTO_FWD_WEIGHT_IMAGE=0 at capture time; single process, fused Adam, exact mode only.
+        ``uncert_in_finish``: whether the uncertainty grid's Adam step rides in the backward's finishing launch on stepping iterations (where the
+        fused optimiser rides there) or keeps its own launch; sets ``self.uncert_in_finish`` for this and later iterations (None: as it is, on
+        by default).  Same bits either way."""
+        if uncert_in_finish is not None:
+            self.uncert_in_finish = bool(uncert_in_finish)
         dev = self.device
         self.model.n_rays_total = n_rays_total
         flat = torch.zeros(n_rays * 10, device=dev)
