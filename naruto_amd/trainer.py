@@ -202,7 +202,8 @@ class FusedAdam(optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, zero_grad: bool = False):
-        """``zero_grad``: zero the gradients inside the same launch, once consumed."""
+        """``zero_grad``: zero the gradients inside the same launch, once consumed (a ``.grad`` that is not contiguous fp32 is stepped from
+        a copy; the caller's tensor is then zeroed by a fill of its own behind the launch)."""
         from . import ops
         loss = None
         if closure is not None:
@@ -211,9 +212,9 @@ class FusedAdam(optim.Optimizer):
         plan = getattr(self, "_plan_cache", None)
         if plan is None or self._plan_key != tuple(p.data_ptr() for g in self.param_groups for p in g['params']):
             plan = self._plan()
-        launches, skipped = [], []
+        launches, skipped, copied = [], [], []
         for betas, chunk, segs in plan:
-            keep, n = [], 0
+            n = 0
             for p, g in chunk:
                 grad = p.grad
                 if grad is None:
@@ -221,7 +222,7 @@ class FusedAdam(optim.Optimizer):
                     continue
                 if not grad.is_contiguous() or grad.dtype != torch.float32:
                     grad = grad.contiguous().float()
-                    keep.append(grad)
+                    copied.append((p.grad, grad))             # the kernel reads (and, with zero_grad, zeroes) the copy: kept until the launches are issued
                 sg = segs[n]
                 if sg.param != p.data_ptr():                  # a tensor without gradient before this one: re-pack (and re-plan next time)
                     m, v = self.moments(p)
@@ -239,15 +240,17 @@ class FusedAdam(optim.Optimizer):
         if self.external_step is not None:
             for betas, segs, n, dev in launches:
                 ops.adam_multi_segs(segs, n, dev, betas=betas, step_dev=self.external_step, zero_grad=zero_grad)
-            return loss
-        if len(launches) == 1:
+        elif len(launches) == 1:
             # the common case: the kernel itself advances the device-side step count (no "step += 1" launch)
             betas, segs, n, dev = launches[0]
             ops.adam_multi_segs(segs, n, dev, betas=betas, step_dev=self.step_dev, advance=True, zero_grad=zero_grad)
-            return loss
-        self.step_dev[:1].add_(1)
-        for betas, segs, n, dev in launches:
-            ops.adam_multi_segs(segs, n, dev, betas=betas, step_dev=self.step_dev, zero_grad=zero_grad)
+        else:
+            self.step_dev[:1].add_(1)
+            for betas, segs, n, dev in launches:
+                ops.adam_multi_segs(segs, n, dev, betas=betas, step_dev=self.step_dev, zero_grad=zero_grad)
+        if zero_grad:
+            for orig, _ in copied:
+                orig.zero_()                               # the kernel zeroed its contiguous fp32 copy, not the caller's tensor
         return loss
 
 
