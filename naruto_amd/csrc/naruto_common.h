@@ -529,6 +529,38 @@ __device__ __forceinline__ void oneblob16_sparse(float x, float (&e)[kBins], uin
     pairs = (1u << (bm >> 1)) | (1u << (b0 >> 1)) | (1u << (bp >> 1));
 }
 
+// The closed form without the placement, for a caller that puts the three bins where they go itself (k_query_bwd stores them to its LDS stage by
+// address instead of selecting them into sixteen registers): bins bm, b0, bp hold p, mid, hi, every other bin is an exact 0.0f.
+// oneblob16_sparse leaves it to the compiler which of its products fuse with the sums behind them, and the answer depends on the code around it:
+// inside k_query_bwd it had always compiled to  yw = fma(-16, floor(y / 16), y)  and
+//   C'(u) = clamp(fma(15/16 u, fma(u^2, -2/3, 1) + round(1/5 u^4), 1/2))
+// (the 1/5 u^4 product paired with 15/16 u in one packed multiply, so the sum behind it stayed an add), while around the stores of this form the
+// same source fused that add as well -- one rounding less, weights that differ in the last bit, a training run that drifts.  So the roundings are
+// spelled out here: contraction off, the two fused steps written as fmaf.  Same bits as that kernel ever produced, whatever surrounds the call.
+__device__ __forceinline__ float oneblob_cq_pinned(float u) {
+#pragma clang fp contract(off)
+    const float u2 = u * u;
+    const float u4 = u2 * u2;
+    const float s = __builtin_fmaf(u2, -(2.0f / 3.0f), 1.0f) + (1.0f / 5.0f) * u4;
+    const float p = __builtin_fmaf((15.0f / 16.0f) * u, s, 0.5f);
+    return fminf(fmaxf(p, 0.0f), 1.0f);
+}
+__device__ __forceinline__ void oneblob16_sparse_bins(float x, int& bm, int& b0, int& bp, float& p, float& mid, float& hi, uint32_t& pairs) {
+#pragma clang fp contract(off)
+    const float y = x * 16.0f;
+    const float yw = __builtin_fmaf(-16.0f, floorf(y * 0.0625f), y);
+    const float fb = floorf(yw);
+    const float f = yw - fb;
+    b0 = ((int)fb) & 15;
+    bm = (b0 + 15) & 15;
+    bp = (b0 + 1) & 15;
+    p = oneblob_cq_pinned(-f);
+    const float q = oneblob_cq_pinned(1.0f - f);
+    mid = q - p;
+    hi = 1.0f - q;
+    pairs = (1u << (bm >> 1)) | (1u << (b0 >> 1)) | (1u << (bp >> 1));
+}
+
 // wave-uniform choice: the closed form when every lane's coordinate allows it, the dense form otherwise
 __device__ __forceinline__ void oneblob16_auto(float x, bool all_sparse_ok, float (&e)[kBins], uint32_t& pairs) {
     if (all_sparse_ok) oneblob16_sparse(x, e, pairs);

@@ -2179,6 +2179,7 @@ struct BwdLds {
     float xs[kBwdWaves][32 * kStageLd];   // per wave: layer inputs  [point][feat32 | oneblob48 | sdf-net out16]
     float ga[kBwdWaves][32 * kGradLd];    // per wave: "G" operand stage [point][32]
     float gb[kBwdWaves][32 * kGradLd];    // per wave: activation stage  [point][32]
+    float dump[kBwdWaves][64];            // per lane: where a OneBlob bin of the other lane's parity is stored instead of branching (never read)
     // the block-level dW image (kAccFloats floats) reuses the xs stages once the tile loop is over
 };
 
@@ -2498,28 +2499,61 @@ __device__ __forceinline__ void query_bwd_body(LevelTab lt, UncertTab ut, BoxTab
         tl_phase(1);
         const bool blob_fast = __all(oneblob_sparse_ok(x) && oneblob_sparse_ok(y) && oneblob_sparse_ok(z));
         // (zero K pairs skipped as in the forward: a product with an exact 0.0f adds nothing; the stage still gets every column)
-        float eb[3][kBins];
-        uint32_t pairs = 0;
-        static_for<0, 3>([&](auto dc) {
-            constexpr int D = decltype(dc)::value;
-            uint32_t pd;
-            oneblob16_auto(D == 0 ? x : (D == 1 ? y : z), blob_fast, eb[D], pd);
-            pairs |= pd << (8 * D);
-        });
-        pairs = blob_fast ? wave_or_u32(pairs) : 0xFFFFFFu;
-        static_for<0, 3>([&](auto dc) {
-            constexpr int D = decltype(dc)::value;
-            static_for<0, 8>([&](auto qc) {
-                constexpr int Q = decltype(qc)::value;
-                constexpr int P = D * 8 + Q;
-                const float b = hh ? eb[D][2 * Q + 1] : eb[D][2 * Q];
-                xs[j * kStageLd + kFeat + 2 * P + hh] = b;
+        if (blob_fast) {
+            // Closed form, through the stage: lanes j and j + 32 hold the same point and each needs the bins of its own parity only -- its 24 stage
+            // slots (columns kFeat + 2P + hh).  They are written as zeros, then the coordinate's three non-zero bins go to the stage BY ADDRESS: a bin
+            // of this lane's parity to its slot, a bin of the other parity (the other lane stores that one) to the lane's dump word behind the
+            // stages -- an address select, no branch.  An active pair's B operand is the lane's own slot read back: LDS executes a wave's accesses
+            // in order, so the read needs no hand-off, and it waits under the preceding pair's matrix instructions.  Same values in the same slots
+            // and the same pairs word as selecting sixteen bins per coordinate into registers (oneblob16_sparse) on both lanes did here:
+            // oneblob16_sparse_bins spells out the roundings that form had in this kernel.
+            const int row = j * kStageLd + kFeat + hh;
+            const int dump = (int)(&L.dump[wave][lane] - xs);
+#pragma unroll
+            for (int P = 0; P < 24; ++P) xs[row + 2 * P] = 0.0f;
+            uint32_t pairs = 0;
+            static_for<0, 3>([&](auto dc) {
+                constexpr int D = decltype(dc)::value;
+                int bm, b0, bp;
+                float vp, vmid, vhi;
+                uint32_t pd;
+                oneblob16_sparse_bins(D == 0 ? x : (D == 1 ? y : z), bm, b0, bp, vp, vmid, vhi, pd);
+                pairs |= pd << (8 * D);
+                const int col = j * kStageLd + kFeat + 16 * D;
+                // bm and bp have the same parity, b0 the other
+                const bool mine0 = (b0 & 1) == hh;
+                xs[mine0 ? dump : col + bm] = vp;
+                xs[mine0 ? col + b0 : dump] = vmid;
+                xs[mine0 ? dump : col + bp] = vhi;
+            });
+            pairs = wave_or_u32(pairs);
+            static_for<0, 24>([&](auto pc) {
+                constexpr int P = decltype(pc)::value;
                 if ((pairs >> P) & 1u) {
+                    const float b = xs[row + 2 * P];
                     h = mfma32(L.f.s0[(16 + P) * 64 + lane], b, h);
                     c = mfma32(L.f.c0p[P * 64 + lane], b, c);
                 }
             });
-        });
+        } else {
+            // a coordinate outside the closed form's range: the dense form, every pair
+            float eb[3][kBins];
+            static_for<0, 3>([&](auto dc) {
+                constexpr int D = decltype(dc)::value;
+                oneblob16(D == 0 ? x : (D == 1 ? y : z), eb[D]);
+            });
+            static_for<0, 3>([&](auto dc) {
+                constexpr int D = decltype(dc)::value;
+                static_for<0, 8>([&](auto qc) {
+                    constexpr int Q = decltype(qc)::value;
+                    constexpr int P = D * 8 + Q;
+                    const float b = hh ? eb[D][2 * Q + 1] : eb[D][2 * Q];
+                    xs[j * kStageLd + kFeat + 2 * P + hh] = b;
+                    h = mfma32(L.f.s0[(16 + P) * 64 + lane], b, h);
+                    c = mfma32(L.f.c0p[P * 64 + lane], b, c);
+                });
+            });
+        }
         f32x16 o = zero16();
         static_for<0, 16>([&](auto tc) {
             constexpr int T = decltype(tc)::value;
