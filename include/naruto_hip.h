@@ -938,6 +938,36 @@ int naruto_cull_compact(uint64_t n_faces, uint64_t n_vertices, const int32_t* fa
  * addresses of buf [n_words] with values that fall per iteration: the rate of scattered 4-byte integer atomics, without a rasteriser. */
 int naruto_debug_atomic_min_rate(uint64_t n_words, uint32_t n_lanes, uint32_t iters, uint32_t* buf, void* stream);
 
+/* Mesh subdivision: trimesh.remesh.subdivide_to_size, which the protocol's cull_mesh.py runs before the vertex test (third-party code outside
+ * the reference tree: parity unpinned; the contract is restated in naruto_amd/remesh.py and csrc/naruto_subdiv.hip).  One generation splits
+ * 1 -> 4 at the edge midpoints every face that has an edge longer than max_edge and leaves the others; the host repeats it.  All pointers
+ * are device memory; the two prefix sums between the calls are the caller's (INCLUSIVE, int32).
+ *   arithmetic   in the vertices' own type (float32, or float64 with vertices_f64), products and sums rounded, no contraction:
+ *                an edge (a, b) is long iff ((dx*dx + dy*dy) + dz*dz) > max_edge*max_edge, d = v[b] - v[a], max_edge converted to the type
+ *                once; the comparison is strict and false for NaN.  midpoint = (v[lo] + v[hi]) * 0.5; colour = (c[lo] + c[hi] + 1) >> 1
+ *                per RGBA8 channel.
+ *   mark         flags[f] = 1 iff face f has a long edge (a face with an index >= n_vertices is never long)
+ *   edges        rank = prefix sum of flags, n_long = its last element.  The slots of the long faces, ordinal 3 * (rank[f] - 1) + k for
+ *                the edges k = (v0v1), (v1v2), (v2v0), are keyed by their undirected edge in an open-addressing table of table_slots
+ *                cells (>= 6 n_long: at most half full) in the workspace; own[s] (uint8 [3 n_long]) = 1 iff s is the LOWEST ordinal that
+ *                carries its edge.  Integer atomics only (64-bit compare-and-swap, 32-bit minimum): own depends on the mesh alone, not on
+ *                table_slots nor on anything about the launch.  The probe loop is bounded by table_slots.
+ *   emit         mid_rank = prefix sum of own, n_mid = its last element: the midpoints in order of first appearance in the face-major edge
+ *                list.  vertices [n_vertices + n_mid, 3] (and colors RGBA8 [n_vertices + n_mid, 4], optional) hold the existing rows on
+ *                entry; midpoint number j is written to row n_vertices + j.  out_faces [n_faces + 3 n_long, 3]: the faces that are not
+ *                long first, in their order and unchanged, then the children (v0,m0,m2) (m0,v1,m1) (m2,m1,v2) (m0,m1,m2) of every long
+ *                face in the long faces' order, m_k the midpoint of edge k.  The workspace is the one edges filled.
+ *   The workspace's first uint32 is an error word, zeroed by edges: bit 0 = an edge found no cell, bit 1 = flags, rank, mid_rank or the
+ *   counts contradict each other (the lane then writes nothing out of range).  The caller reads it with n_mid.  The workspace query
+ *   returns 0 beyond the supported sizes: n_long in 1 .. (2^31-1)/3, table_slots in 6 n_long .. 2^31. */
+size_t naruto_subdivide_workspace(uint64_t n_long, uint64_t table_slots);
+int naruto_subdivide_mark(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const void* vertices, int vertices_f64, double max_edge, uint8_t* flags,
+                          void* stream);
+int naruto_subdivide_edges(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const uint8_t* flags, const int32_t* rank, uint64_t n_long, uint64_t table_slots,
+                           void* workspace, uint8_t* own, void* stream);
+int naruto_subdivide_emit(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const uint8_t* flags, const int32_t* rank, uint64_t n_long, uint64_t table_slots,
+                          void* workspace, const int32_t* mid_rank, uint64_t n_mid, void* vertices, int vertices_f64, uint8_t* colors, int32_t* out_faces, void* stream);
+
 /* Mesh simulator: a mesh in the place of the reference's HabitatSim (src/simulator/habitat_simulator.py; an external renderer that is not
  * on this stack: parity unpinned; the contract is restated in naruto_amd/simulator.py and csrc/naruto_sim.hip).  Camera and poses as for
  * the culling above.  All pointers are device memory.

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_sim.hip", "naruto_frame.hip", "naruto_posechain.hip", "naruto_icp.hip", "naruto_icp.h", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_subdiv.hip", "naruto_sim.hip", "naruto_frame.hip", "naruto_posechain.hip", "naruto_icp.hip", "naruto_icp.h", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -276,6 +276,10 @@ SIGNATURES = {
     "naruto_cull_faces": (_I, [_U64, _U64, _V, _V, _V, _V, _V, _V]),
     "naruto_cull_compact": (_I, [_U64, _U64, _V, _V, _V, _V, _V, _V, _I, _V, _U64, _U64, _V, _V, _V, _V]),
     "naruto_debug_atomic_min_rate": (_I, [_U64, _U32, _U32, _V, _V]),
+    "naruto_subdivide_workspace": (C.c_size_t, [_U64, _U64]),
+    "naruto_subdivide_mark": (_I, [_U64, _U64, _V, _V, _I, C.c_double, _V, _V]),
+    "naruto_subdivide_edges": (_I, [_U64, _U64, _V, _V, _V, _U64, _U64, _V, _V, _V]),
+    "naruto_subdivide_emit": (_I, [_U64, _U64, _V, _V, _V, _U64, _U64, _V, _V, _U64, _V, _I, _V, _V, _V]),
     "naruto_render_rgbd_workspace": (C.c_size_t, [_U64, _U64, _U32, _U32, _U32]),
     "naruto_render_rgbd": (_I, [C.POINTER(NarutoCullCam), _U64, _V, _U64, _V, _V, _I, _U32, _V, _U32, _U32, _V, _V, _V, _V, _V]),
     "naruto_cube_to_erp": (_I, [_U32, _U32, _U64, _V, _V, _V, _V]),

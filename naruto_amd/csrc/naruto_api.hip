@@ -27,6 +27,7 @@
 #include "naruto_rrt.hip"
 #include "naruto_recon.hip"
 #include "naruto_cull.hip"
+#include "naruto_subdiv.hip"
 #include "naruto_sim.hip"
 #include "naruto_frame.hip"
 #include "naruto_posechain.hip"
@@ -2522,6 +2523,83 @@ int naruto_debug_atomic_min_rate(uint64_t n_words, uint32_t n_lanes, uint32_t it
     if (buf == nullptr) return fail(NARUTO_ERR_INVALID, "debug_atomic_min_rate: NULL argument");
     hipLaunchKernelGGL(k_cull_atomic_probe, dim3((n_lanes + kCullThreads - 1u) / kCullThreads), dim3(kCullThreads), 0, (hipStream_t)stream, (uint32_t)n_words, iters, buf);
     return check_launch("cull_atomic_probe");
+}
+
+// ---- mesh subdivision (naruto_subdiv.hip) ---------------------------------------------------------------------------------
+namespace {
+constexpr uint64_t kSubdivMaxLong = kReconMaxCount / 3u;       // slot ordinals 3 * rank + slot stay below 2^31
+constexpr uint64_t kSubdivMaxTable = 1ull << 31;
+// workspace of one generation: | error word | keys [table] | lowest slot ordinal of the key [table] | table cell of every slot [3 n_long] |
+struct SubdivWs { uint32_t* err; unsigned long long* keys; uint32_t* ord; uint32_t* pos; size_t total; };
+SubdivWs subdiv_ws(uint64_t n_long, uint64_t table_slots, void* workspace) {
+    Carve c(workspace);
+    return {c.take<uint32_t>(4u), c.take<unsigned long long>((size_t)table_slots * 8u), c.take<uint32_t>((size_t)table_slots * 4u), c.take<uint32_t>((size_t)n_long * 12u), c.size()};
+}
+bool subdiv_sizes_ok(uint64_t n_long, uint64_t table_slots) {
+    return n_long != 0 && n_long <= kSubdivMaxLong && table_slots >= 6u * n_long && table_slots <= kSubdivMaxTable;
+}
+}  // namespace
+
+size_t naruto_subdivide_workspace(uint64_t n_long, uint64_t table_slots) {
+    if (!subdiv_sizes_ok(n_long, table_slots)) return 0;
+    return subdiv_ws(n_long, table_slots, nullptr).total;
+}
+
+int naruto_subdivide_mark(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const void* vertices, int vertices_f64, double max_edge, uint8_t* flags, void* stream) {
+    if (n_faces > kReconMaxCount || n_vertices > kReconMaxCount) return fail(NARUTO_ERR_INVALID, "subdivide_mark: counts beyond int32");
+    if (!(max_edge > 0.0) || !std::isfinite(max_edge)) return fail(NARUTO_ERR_INVALID, "subdivide_mark: max_edge must be finite and > 0");
+    if (n_faces == 0) return NARUTO_OK;
+    if (faces == nullptr || vertices == nullptr || flags == nullptr) return fail(NARUTO_ERR_INVALID, "subdivide_mark: NULL argument");
+    const uint32_t nf = (uint32_t)n_faces, nv = (uint32_t)n_vertices;
+    const dim3 grid((nf + kSubdivThreads - 1u) / kSubdivThreads), block(kSubdivThreads);
+    if (vertices_f64) {
+        hipLaunchKernelGGL(k_subdiv_mark<double>, grid, block, 0, (hipStream_t)stream, nf, nv, faces, reinterpret_cast<const double*>(vertices), max_edge * max_edge, flags);
+    } else {
+        const float me = (float)max_edge;                     // converted once; the square is a float32 product
+        hipLaunchKernelGGL(k_subdiv_mark<float>, grid, block, 0, (hipStream_t)stream, nf, nv, faces, reinterpret_cast<const float*>(vertices), me * me, flags);
+    }
+    return check_launch("subdiv_mark");
+}
+
+int naruto_subdivide_edges(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const uint8_t* flags, const int32_t* rank, uint64_t n_long, uint64_t table_slots,
+                           void* workspace, uint8_t* own, void* stream) {
+    if (n_faces == 0 || n_faces > kReconMaxCount || n_vertices == 0 || n_vertices > kReconMaxCount || n_long > n_faces) return fail(NARUTO_ERR_INVALID, "subdivide_edges: counts out of range");
+    if (!subdiv_sizes_ok(n_long, table_slots))
+        return fail(NARUTO_ERR_INVALID, "subdivide_edges: 1 .. (2^31-1)/3 long faces and a table of 6 n_long .. 2^31 cells (got %llu, %llu)", (unsigned long long)n_long, (unsigned long long)table_slots);
+    if (faces == nullptr || flags == nullptr || rank == nullptr || workspace == nullptr || own == nullptr) return fail(NARUTO_ERR_INVALID, "subdivide_edges: NULL argument");
+    const SubdivWs w = subdiv_ws(n_long, table_slots, workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nf = (uint32_t)n_faces, n_slots = (uint32_t)(3u * n_long), ts = (uint32_t)table_slots;           // (2^31 cells: the kernels take the count as uint32)
+    if (hipMemsetAsync(w.err, 0, 4u, st) != hipSuccess) return check_launch("subdivide_edges: memset");
+    // keys, ordinals and cells are contiguous up to the carve's padding: 0xFF bytes are the empty key, the largest ordinal and "no cell"
+    if (hipMemsetAsync(w.keys, 0xFF, (size_t)(reinterpret_cast<char*>(w.pos) - reinterpret_cast<char*>(w.keys)) + (size_t)n_slots * 4u, st) != hipSuccess)
+        return check_launch("subdivide_edges: fill");
+    hipLaunchKernelGGL(k_subdiv_insert, dim3((nf + kSubdivThreads - 1u) / kSubdivThreads), dim3(kSubdivThreads), 0, st, nf, (uint32_t)n_vertices, faces, flags, rank, (uint32_t)n_long, ts,
+                       w.keys, w.ord, w.pos, w.err);
+    if (int rc = check_launch("subdiv_insert")) return rc;
+    hipLaunchKernelGGL(k_subdiv_own, dim3((n_slots + kSubdivThreads - 1u) / kSubdivThreads), dim3(kSubdivThreads), 0, st, n_slots, ts, w.pos, w.ord, own);
+    return check_launch("subdiv_own");
+}
+
+int naruto_subdivide_emit(uint64_t n_faces, uint64_t n_vertices, const int32_t* faces, const uint8_t* flags, const int32_t* rank, uint64_t n_long, uint64_t table_slots,
+                          void* workspace, const int32_t* mid_rank, uint64_t n_mid, void* vertices, int vertices_f64, uint8_t* colors, int32_t* out_faces, void* stream) {
+    if (n_faces == 0 || n_faces > kReconMaxCount || n_vertices == 0 || n_long > n_faces || n_mid == 0 || n_mid > 3u * n_long || n_vertices + n_mid > kReconMaxCount ||
+        n_faces + 3u * n_long > kReconMaxCount)
+        return fail(NARUTO_ERR_INVALID, "subdivide_emit: counts out of range");
+    if (!subdiv_sizes_ok(n_long, table_slots)) return fail(NARUTO_ERR_INVALID, "subdivide_emit: 1 .. (2^31-1)/3 long faces and a table of 6 n_long .. 2^31 cells");
+    if (faces == nullptr || flags == nullptr || rank == nullptr || workspace == nullptr || mid_rank == nullptr || vertices == nullptr || out_faces == nullptr)
+        return fail(NARUTO_ERR_INVALID, "subdivide_emit: NULL argument");
+    const SubdivWs w = subdiv_ws(n_long, table_slots, workspace);
+    const uint32_t nf = (uint32_t)n_faces, nv = (uint32_t)n_vertices, nl = (uint32_t)n_long, ts = (uint32_t)table_slots, nm = (uint32_t)n_mid;
+    const dim3 grid((nf + kSubdivThreads - 1u) / kSubdivThreads), block(kSubdivThreads);
+    uint32_t* col = reinterpret_cast<uint32_t*>(colors);
+    if (vertices_f64)
+        hipLaunchKernelGGL(k_subdiv_emit<double>, grid, block, 0, (hipStream_t)stream, nf, nv, faces, flags, rank, nl, ts, w.pos, w.ord, mid_rank, nm, reinterpret_cast<double*>(vertices), col,
+                           out_faces, w.err);
+    else
+        hipLaunchKernelGGL(k_subdiv_emit<float>, grid, block, 0, (hipStream_t)stream, nf, nv, faces, flags, rank, nl, ts, w.pos, w.ord, mid_rank, nm, reinterpret_cast<float*>(vertices), col,
+                           out_faces, w.err);
+    return check_launch("subdiv_emit");
 }
 
 // ---- mesh simulator (naruto_sim.hip) --------------------------------------------------------------------------------------

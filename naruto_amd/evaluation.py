@@ -24,7 +24,8 @@ units of the truncation distance, so the metric value is mean * training.trunc *
 the same number for its trunc of 0.1 m and a quirk for any other (tests/accuracy_study.py uses the same conversion).
 
 Mesh culling, the step the protocol runs before these metrics (cull_mesh.py --remove_occlusion from the estimated poses), is
-``naruto_amd.culling``; ``evaluate_field(cull_poses=..., cull_cam=...)`` runs it on the device between extraction and sampling.
+``naruto_amd.culling``; ``evaluate_field(cull_poses=..., cull_cam=...)`` runs it on the device between extraction and sampling
+(``max_edge=...``: with the tool's subdivision before it, ``naruto_amd.remesh``).
 
 Mesh alignment, the protocol's other step before the metrics (eval_recon.py:80-85: ``get_align_transformation(rec_mesh, gt_mesh)``, applied
 to the reconstruction), is ``icp`` / ``get_align_transformation`` here and ``align=True`` on the three metric entry points.  A tracked run's
@@ -405,7 +406,8 @@ class ReconEvaluatorHIP:
         """field -> SDF lattice -> marching cubes -> metric vertices (as ``mesh.extract_mesh``) -> samples -> both queries, plus ``mad_cm``;
         no mesh or cloud goes to the host, one copy of four numbers ends the call.  With ``cull_poses`` ([P,4,4], metric frame) and
         ``cull_cam`` (config["cam"]) the extracted mesh is culled on the device first (``culling.cull_mesh``; ``cull_args`` are its keyword
-        arguments), at the price of one more copy of two numbers; without them the launches are unchanged.  ``align``: the (culled)
+        arguments: ``max_edge=0.015`` subdivides the surface before the cull, as the protocol's tool does; off by default), at the price
+        of one more copy of two numbers (two more per generation of subdivision); without them the launches are unchanged.  ``align``: the (culled)
         mesh is moved onto the ground truth by ``icp`` before sampling, as in ``evaluate_mesh``; ``mad_cm`` does not depend on it."""
         vertices, triangles = M.extract_surface(model.query_sdf, config, bounding_box, marching_cube_bound, voxel_size=voxel_size)
         if cull_poses is not None and len(triangles) > 0:
