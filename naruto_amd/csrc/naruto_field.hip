@@ -2839,11 +2839,12 @@ __device__ __forceinline__ void wgrad_u(f32x16& d, const f32x16& gU, const f32x1
 }
 
 // one 32-point tile.  F: the two hash K blocks, Bl: the three OneBlob K blocks (B-operand packs of these points); g_*: the
-// cotangent of raw at this lane's point (both halves hold point j's values); returns df (P form: rows = the 32 hash features).
+// cotangent of raw at this lane's point (both halves hold point j's values), d_geo_pt: its geo cotangent (NULL: none), taken where geo_live
+// (a padding entry's cotangents are all zero); returns df (P form: rows = the 32 hash features).
 // The order of the steps keeps few 16-register tensors alive at a time (the seven dW tiles already take 112 registers): the
 // hidden activations survive as their bf16 packs + a sign mask, the U forms of the layer inputs are rebuilt where they are used.
 __device__ __forceinline__ f32x16 bwd_tile_bf(const BwdLdsBf& L, DwTiles& dw, const u32x4_t (&F)[2], const u32x4_t (&Bl)[3], const float (&g_rgb)[3],
-                                              float g_sdf, const float* __restrict__ d_geo_pt, int lane) {
+                                              float g_sdf, const float* __restrict__ d_geo_pt, bool geo_live, int lane) {
     const int hh = lane >> 5;
     // the weight / selection images are loop invariant: left alone the compiler keeps all 24 of them (96 registers) live across the
     // tile loop.  An opaque copy of the lane index ties every image read to this call.
@@ -2914,7 +2915,7 @@ __device__ __forceinline__ f32x16 bwd_tile_bf(const BwdLdsBf& L, DwTiles& dw, co
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const int row = crow(r, hh);
-            if (row >= 1) dov[r] += d_geo_pt[row - 1];
+            if (row >= 1) dov[r] += geo_live ? d_geo_pt[row - 1] : 0.0f;          // padding entries redo the list's last point: no geo cotangent either
         }
     }
     if (hh == 0) dov[0] += g_sdf;
@@ -3075,7 +3076,7 @@ __global__ __launch_bounds__(256, NARUTO_BWD_BF_MINWAVES) void k_query_bwd_bf(Le
             asm volatile("" :: "v"(F[0][0]), "v"(F[1][3]), "v"(bl[0][0]), "v"(bl[2][3]), "v"(g_rgb[0]), "v"(dg));
             df[0] = g_rgb[1];
 #else
-            const f32x16 df = bwd_tile_bf(L, dw, F, bl, g_rgb, half ? gB[3] : gA[3], dg, lane);
+            const f32x16 df = bwd_tile_bf(L, dw, F, bl, g_rgb, half ? gB[3] : gA[3], dg, it < M_eff, lane);
 #endif
             // reg 4q+e of half hh is feature e + 8q + 4hh  => level (e>>1) + 4q + 2hh, component e&1
             if (it < M_eff) {
