@@ -995,6 +995,40 @@ int naruto_sim_erp(uint32_t n_panoramas, uint32_t face_w, uint64_t n_erp, const 
 /* Measurement aid (tools/time_sim.py): naruto_debug_atomic_min_rate on 8-byte cells, the winner raster's access pattern. */
 int naruto_debug_atomic_min64_rate(uint64_t n_cells, uint32_t n_lanes, uint32_t iters, uint64_t* buf, void* stream);
 
+/* Whole views from the field and their 2D scores (Co-SLAM's render_img is not in the reference tree and the surface search is this library's
+ * own: parity unpinned; the contract is restated in naruto_amd/render.py and csrc/naruto_view.hip).  Camera and poses as for the culling
+ * above; a flat pixel p of n_poses views is pose p / (H W), row (p % (H W)) / W, column p % W.  All pointers are device memory unless noted.
+ *   view rays       rays_o / rays_d [p1 - p0, 3] of the flat pixels [p0, p1): the camera-frame direction ((i - cx)/fx, -(j - cy)/fy, -1), each
+ *                   operation rounded once, rotated as naruto_rays_to_world does it
+ *   view crossing   z_star[n] = z[k] + (z[k+1] - z[k]) * (sdf[k] / (sdf[k] - sdf[k+1])) at the first k with sdf[k] > 0 and !(sdf[k+1] > 0)
+ *                   (sdf = raw[n,:,3]; float32, every operation rounded, no contraction); 0 where there is none
+ *   render view     ONE launch, one wave per ray: ray, coarse pass of n_coarse uniform depths in [near, far] (skipped when target_d is given:
+ *                   then z* = target_d), crossing, naruto_render_fwd's depth-guided pass around z* without jitter, compositing.  Outputs
+ *                   are whole images [n_poses,H,W(,3)] written at the flat pixels of the range; any may be NULL.  Both sample counts must
+ *                   lie in 2 .. 1024 (naruto_render_fwd's per-ray limit): NARUTO_ERR_INVALID otherwise.  The fine pass runs in the tiles
+ *                   naruto_render_fwd's four-wave launch forms over the same rays (for at most 64 fine samples: groups of 16 rays counted
+ *                   from p0, whose samples share 64-sample tiles), and equals it in every bit; a caller who wants bits that do not move
+ *                   with the ranges starts every range at a multiple of 16.
+ *   image metrics   out float64 [n_views,6] = sum of squared colour errors, pixels, sum of |d - d_gt| over the valid pixels (d_gt > 0 and,
+ *                   with has_depth_trunc, d_gt <= depth_trunc), valid pixels, sum of SSIM, SSIM terms.  window: HOST array of the 11
+ *                   normalised Gaussian taps.  Optional float64 maps: squared error [n_views,H,W,3], absolute depth error [n_views,H,W]
+ *                   (0 where invalid), SSIM [n_views,H-10,W-10,3].  Per-workgroup partials and one finishing pass in a fixed order, no
+ *                   atomics: bitwise reproducible.  workspace: naruto_image_metrics_workspace() bytes (0: unsupported sizes). */
+typedef struct NarutoViewRender {
+    uint32_t n_poses; const float* poses;             /* [n_poses,4,4]                                               */
+    uint32_t p0, p1;                                  /* flat pixels [p0, p1) of the launch                          */
+    const float* target_d;                            /* [n_poses,H,W] sensor depth, or NULL: search the surface     */
+    uint32_t n_samples_d, n_range_d; float range_d;   /* the fine pass (training.n_samples_d / n_range_d / range_d)  */
+    uint32_t n_coarse;
+    float *rgb, *depth, *acc, *depth_var, *uncert_map, *surface_z;
+} NarutoViewRender;
+int naruto_view_rays(const NarutoCullCam* cam, uint32_t n_poses, const float* poses, uint32_t p0, uint32_t p1, float* rays_o, float* rays_d, void* stream);
+int naruto_view_crossing(uint32_t n_rays, uint32_t n_samples, const float* raw, const float* z_vals, float* z_star, void* stream);
+int naruto_render_view(const NarutoField* f, const NarutoParams* p, const NarutoCullCam* cam, const NarutoViewRender* r, void* stream);
+size_t naruto_image_metrics_workspace(uint32_t n_views, uint32_t H, uint32_t W);
+int naruto_image_metrics(uint32_t n_views, uint32_t H, uint32_t W, const float* rgb, const float* depth, const float* gt_rgb, const float* gt_depth, int has_depth_trunc,
+                         float depth_trunc, const double* window, void* workspace, double* out, double* se_map, double* de_map, double* ssim_map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NARUTO_HIP_LIB") or os.path.join(_HERE, "libnaruto_hip.so")      # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["naruto_api.hip", "naruto_field.hip", "naruto_binned.hip", "naruto_render.hip", "naruto_rays.hip", "naruto_train.hip", "naruto_renderfused.hip", "naruto_planner.hip", "naruto_mesh.hip", "naruto_parts.hip",
-           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_subdiv.hip", "naruto_sim.hip", "naruto_frame.hip", "naruto_posechain.hip", "naruto_icp.hip", "naruto_icp.h", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
+           "naruto_sorted.hip", "naruto_pointgrad.hip", "naruto_track.hip", "naruto_bapose.hip", "naruto_rrt.hip", "naruto_recon.hip", "naruto_cull.hip", "naruto_subdiv.hip", "naruto_sim.hip", "naruto_frame.hip", "naruto_posechain.hip", "naruto_icp.hip", "naruto_view.hip", "naruto_icp.h", "naruto_pose.h", "naruto_mc_table.inc", "naruto_common.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "naruto_hip.h")
 
 MAX_LEVELS = 16
@@ -165,6 +165,13 @@ class NarutoRender(C.Structure):
                 ("uncert_map", C.c_void_p), ("weights", C.c_void_p), ("raw", C.c_void_p), ("z_vals", C.c_void_p)]
 
 
+class NarutoViewRender(C.Structure):
+    _fields_ = [("n_poses", C.c_uint32), ("poses", C.c_void_p), ("p0", C.c_uint32), ("p1", C.c_uint32), ("target_d", C.c_void_p),
+                ("n_samples_d", C.c_uint32), ("n_range_d", C.c_uint32), ("range_d", C.c_float), ("n_coarse", C.c_uint32),
+                ("rgb", C.c_void_p), ("depth", C.c_void_p), ("acc", C.c_void_p), ("depth_var", C.c_void_p), ("uncert_map", C.c_void_p),
+                ("surface_z", C.c_void_p)]
+
+
 class NarutoPoints(C.Structure):
     _fields_ = [("x", C.c_void_p), ("rays_o", C.c_void_p), ("rays_d", C.c_void_p), ("z_vals", C.c_void_p),
                 ("n_samples", C.c_uint32)]
@@ -286,6 +293,11 @@ SIGNATURES = {
     "naruto_depth_to_dist": (_I, [_U32, _U32, _U32, _F, _F, _F, _F, _V, _V, _V]),
     "naruto_sim_erp": (_I, [_U32, _U32, _U64, _V, _V, _V, _F, _V, _V, _V, _V]),
     "naruto_debug_atomic_min64_rate": (_I, [_U64, _U32, _U32, _V, _V]),
+    "naruto_view_rays": (_I, [C.POINTER(NarutoCullCam), _U32, _V, _U32, _U32, _V, _V, _V]),
+    "naruto_view_crossing": (_I, [_U32, _U32, _V, _V, _V, _V]),
+    "naruto_render_view": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoCullCam), C.POINTER(NarutoViewRender), _V]),
+    "naruto_image_metrics_workspace": (C.c_size_t, [_U32, _U32, _U32]),
+    "naruto_image_metrics": (_I, [_U32, _U32, _U32, _V, _V, _V, _V, _I, _F, C.POINTER(C.c_double), _V, _V, _V, _V, _V, _V]),
     "naruto_adam_multi": (_I, [C.POINTER(NarutoAdamSeg), _U32, _F, _F, _U32, _V, _U32, _V]),
     "naruto_train_workspace": (C.c_size_t, [_V, C.POINTER(NarutoTrainStep)]),
     "naruto_train_forward": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), _I, _V]),

@@ -32,6 +32,7 @@
 #include "naruto_frame.hip"
 #include "naruto_posechain.hip"
 #include "naruto_icp.hip"
+#include "naruto_view.hip"
 
 using namespace naruto;
 
@@ -3155,6 +3156,106 @@ int naruto_debug_icp_solve(const double* sums, const double* origin, double* dT,
     double ratio;
     *status = icp_solve(sums, origin != nullptr ? origin : zero, dT, ratio);
     return NARUTO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// workspace of the image metrics over P views of H x W: | six partial sums per 16 x 16 tile and view |
+struct MetricWs { double* partial; uint32_t tiles_x, tiles_y; size_t total; };
+MetricWs metric_ws(uint32_t P, uint32_t H, uint32_t W, void* workspace) {
+    const uint32_t tx = (W + kMetTile - 1u) / kMetTile, ty = (H + kMetTile - 1u) / kMetTile;
+    Carve c(workspace);
+    return {c.take<double>((size_t)P * tx * ty * 6u * sizeof(double)), tx, ty, c.size()};
+}
+int view_check(const NarutoCullCam* cam, uint32_t n_poses, const float* poses, uint32_t p0, uint32_t p1, const char* who) {
+    if (int rc = cull_cam_check(cam, who)) return rc;
+    if (n_poses == 0 || poses == nullptr) return fail(NARUTO_ERR_INVALID, "%s: no poses", who);
+    if ((uint64_t)n_poses * cam->H * cam->W >= (1ull << 32)) return fail(NARUTO_ERR_INVALID, "%s: poses x pixels per call must stay below 2^32: use fewer poses per call", who);
+    if (p0 > p1 || (uint64_t)p1 > (uint64_t)n_poses * cam->H * cam->W) return fail(NARUTO_ERR_INVALID, "%s: pixel range [%u, %u) of %u poses x %u x %u", who, p0, p1, n_poses, cam->H, cam->W);
+    return NARUTO_OK;
+}
+ViewCam view_cam(const NarutoCullCam* cam) { return ViewCam{cam->H, cam->W, cam->fx, cam->fy, cam->cx, cam->cy}; }
+}  // namespace
+
+extern "C" {
+
+int naruto_view_rays(const NarutoCullCam* cam, uint32_t n_poses, const float* poses, uint32_t p0, uint32_t p1, float* rays_o, float* rays_d, void* stream) {
+    if (int rc = view_check(cam, n_poses, poses, p0, p1, "view_rays")) return rc;
+    if (rays_o == nullptr || rays_d == nullptr) return fail(NARUTO_ERR_INVALID, "view_rays: NULL output");
+    const uint32_t n = p1 - p0;
+    if (n == 0) return NARUTO_OK;
+    hipLaunchKernelGGL(k_view_rays, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, view_cam(cam), poses, p0, n, rays_o, rays_d);
+    return check_launch("view_rays");
+}
+
+int naruto_view_crossing(uint32_t n_rays, uint32_t n_samples, const float* raw, const float* z_vals, float* z_star, void* stream) {
+    if (raw == nullptr || z_vals == nullptr || z_star == nullptr) return fail(NARUTO_ERR_INVALID, "view_crossing: NULL argument");
+    if (n_samples < 2 || n_samples > (uint32_t)kMaxSamples) return fail(NARUTO_ERR_INVALID, "view_crossing: need 2 <= samples per ray <= %d (got %u)", kMaxSamples, n_samples);
+    if (n_rays == 0) return NARUTO_OK;
+    hipLaunchKernelGGL(k_view_crossing, dim3((n_rays + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, n_rays, n_samples, raw, z_vals, z_star);
+    return check_launch("view_crossing");
+}
+
+int naruto_render_view(const NarutoField* f, const NarutoParams* p, const NarutoCullCam* cam, const NarutoViewRender* r, void* stream) {
+    if (f == nullptr || p == nullptr || r == nullptr) return fail(NARUTO_ERR_INVALID, "render_view: NULL argument");
+    if (int rc = check_params(p, "render_view")) return rc;
+    if (int rc = view_check(cam, r->n_poses, r->poses, r->p0, r->p1, "render_view")) return rc;
+    const uint32_t S = r->n_samples_d + r->n_range_d;
+    // the per-ray LDS limit of naruto_render_fwd's one-wave-per-ray launch
+    if (S < 2 || S > (uint32_t)kMaxSamples) return fail(NARUTO_ERR_INVALID, "render_view: need 2 <= fine samples per ray <= %d (got %u)", kMaxSamples, S);
+    if (r->target_d == nullptr && (r->n_coarse < 2 || r->n_coarse > (uint32_t)kMaxSamples))
+        return fail(NARUTO_ERR_INVALID, "render_view: need 2 <= n_coarse <= %d (got %u)", kMaxSamples, r->n_coarse);
+    const uint32_t n = r->p1 - r->p0;
+    if (n == 0) return NARUTO_OK;
+    ViewArgs a{};
+    a.cam = view_cam(cam); a.poses = r->poses; a.p0 = r->p0; a.n_rays = n; a.target_d = r->target_d;
+    a.near_ = cam->near_; a.far_ = cam->far_; a.range_d = r->range_d; a.nu = r->n_samples_d; a.nr = r->n_range_d; a.n_coarse = r->n_coarse;
+    a.trunc = f->desc.trunc; a.sc_factor = f->desc.sc_factor; a.white_bkgd = f->desc.white_bkgd;
+    a.rgb = r->rgb; a.depth = r->depth; a.acc = r->acc; a.depth_var = r->depth_var; a.uncert_map = r->uncert_map; a.surface_z = r->surface_z;
+    // naruto_render_fwd's two four-wave forms, chosen as it chooses them: the fine pass's tiles are then that launch's
+    const bool bf = f->desc.mlp_mode == NARUTO_MLP_BF16;
+    const uint32_t cap = cu_count(f) * 4u;
+    const hipStream_t st = (hipStream_t)stream;
+    if (S <= 64u) {
+        static bool attr_packed = false;
+        const size_t reserved = render_packed_lds_bytes(64u), dyn = render_packed_lds_bytes(S);
+        if (int rc = reserve_lds(attr_packed, {lds_use(k_render_view_packed<false>, reserved), lds_use(k_render_view_packed<true>, reserved)}, "render_view: cannot reserve %zu bytes of LDS", reserved)) return rc;
+        const uint32_t groups = (n + kPackRays - 1u) / kPackRays, blocks = groups < cap ? groups : cap;
+        if (bf) hipLaunchKernelGGL(k_render_view_packed<true>, dim3(blocks), dim3(256), dyn, st, f->lt, f->ut, f->bt, *p, a);
+        else hipLaunchKernelGGL(k_render_view_packed<false>, dim3(blocks), dim3(256), dyn, st, f->lt, f->ut, f->bt, *p, a);
+        return check_launch("render_view_packed");
+    }
+    static bool attr_set = false;
+    const size_t reserved = ray_scratch_bytes(kMaxSamples), dyn = ray_scratch_bytes(S);
+    if (int rc = reserve_lds(attr_set, {lds_use(k_render_view<false>, reserved), lds_use(k_render_view<true>, reserved)}, "render_view: cannot reserve %zu bytes of LDS", reserved)) return rc;
+    const uint32_t blocks = (n + 3u) / 4u < cap ? (n + 3u) / 4u : cap;
+    if (bf) hipLaunchKernelGGL(k_render_view<true>, dim3(blocks), dim3(256), dyn, st, f->lt, f->ut, f->bt, *p, a);
+    else hipLaunchKernelGGL(k_render_view<false>, dim3(blocks), dim3(256), dyn, st, f->lt, f->ut, f->bt, *p, a);
+    return check_launch("render_view");
+}
+
+size_t naruto_image_metrics_workspace(uint32_t n_views, uint32_t H, uint32_t W) {
+    if (n_views == 0 || H == 0 || W == 0 || n_views > 65535u || (uint64_t)H * W > (1ull << 30)) return 0;
+    return metric_ws(n_views, H, W, nullptr).total;
+}
+
+int naruto_image_metrics(uint32_t n_views, uint32_t H, uint32_t W, const float* rgb, const float* depth, const float* gt_rgb, const float* gt_depth, int has_depth_trunc,
+                         float depth_trunc, const double* window, void* workspace, double* out, double* se_map, double* de_map, double* ssim_map, void* stream) {
+    if (naruto_image_metrics_workspace(n_views, H, W) == 0) return fail(NARUTO_ERR_INVALID, "image_metrics: need 1 .. 65535 views of 1 .. 2^30 pixels");
+    if (rgb == nullptr || depth == nullptr || gt_rgb == nullptr || gt_depth == nullptr || window == nullptr || workspace == nullptr || out == nullptr)
+        return fail(NARUTO_ERR_INVALID, "image_metrics: NULL argument");
+    const MetricWs w = metric_ws(n_views, H, W, workspace);
+    MetricArgs a{};
+    a.P = n_views; a.H = H; a.W = W; a.tiles_x = w.tiles_x; a.tiles_y = w.tiles_y;
+    a.rgb = rgb; a.depth = depth; a.gt_rgb = gt_rgb; a.gt_depth = gt_depth; a.depth_trunc = depth_trunc; a.has_trunc = has_depth_trunc != 0;
+    a.partial = w.partial; a.se_map = se_map; a.de_map = de_map; a.ssim_map = ssim_map;
+    MetricWin win;
+    for (int t = 0; t < kMetWin; ++t) win.w[t] = window[t];                 // HOST array of 11 doubles
+    hipLaunchKernelGGL(k_metrics_tile, dim3(w.tiles_x, w.tiles_y, n_views), dim3(256), 0, (hipStream_t)stream, a, win);
+    if (int rc = check_launch("metrics_tile")) return rc;
+    hipLaunchKernelGGL(k_metrics_finish, dim3(n_views), dim3(64), 0, (hipStream_t)stream, w.tiles_x * w.tiles_y, w.partial, out);
+    return check_launch("metrics_finish");
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ pose of step i is the trajectory's and the planner is skipped.
 Command line::
 
     python -m naruto_amd.run --config <coslam.yaml> --mesh <scene.ply> --num_iter N --result_dir D [--start x y z] [--traj traj.txt]
-                             [--no_active_ray] [--seed S] [--track] [--planner key=value ...]
+                             [--no_active_ray] [--seed S] [--track] [--eval_views K] [--planner key=value ...]
 
 ``--config`` is a Co-SLAM yaml (``naruto_amd.config.load_config``).  The reference's ``.py`` config files are not read: the planner's
 settings are ``naruto_amd.planner.DEFAULTS`` (the values of the reference's configs/default.py, restated as data) with ``--planner
@@ -19,7 +19,8 @@ defaults.  ``--traj`` reads a Replica trajectory file: sixteen numbers per line,
 rotation negated as the reference's ``load_Replica_pose`` does.  The run's trajectory length goes to ``<result_dir>/results.txt`` as
 ``traj_len(m),<value>`` (``evaluation.update_results_file``'s format).  ``--track`` estimates the camera poses during the run
 (``CoSLAMNarutoHIP(track=True)``) and adds ``ate_rmse(cm)`` / ``ate_mean(cm)``: the estimated trajectory against the poses the frames were
-taken at (``evaluation.ate``).
+taken at (``evaluation.ate``).  ``--eval_views K`` renders every K-th pose of the run from the final map and scores it against the
+simulator: ``psnr``, ``ssim`` and ``depth_l1(cm)`` (``naruto_amd.render``).
 """
 
 from __future__ import annotations
@@ -55,7 +56,8 @@ def load_replica_traj(path: str) -> torch.Tensor:
     return torch.stack(poses)
 
 
-def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optional[Callable] = None, traj: Optional[torch.Tensor] = None) -> Dict:
+def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optional[Callable] = None, traj: Optional[torch.Tensor] = None,
+                    eval_views: Optional[int] = None) -> Dict:
     """main.py:90-146.  ``planner`` is set up by the caller (``update_sim``, ``init_data``, ``init_local_planner``) or None with ``traj``
     ([N,4,4], N >= num_iter: the pose of step i is ``traj[i]``).  ``on_step(i, c2w, vols, state)`` is called at the end of every step.
     Returns ``poses`` [num_iter,4,4] (the pose each frame was taken at), ``states`` (the planner's state after each step), ``fresh``
@@ -63,11 +65,15 @@ def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optio
     SLAM phase ends with whatever the step waited for, not with a device synchronisation), ``mesh`` and ``ckpt_path`` of the final
     save.  When ``slam`` tracks (``CoSLAMNarutoHIP(track=True)``): also ``est_poses`` [num_iter,4,4] (``slam.resolved_poses()``, on the
     host) and ``ate`` (``evaluation.ate(est_poses, poses)``; None below 3 steps).  The planner keeps receiving the COMMANDED pose, the
-    one the frame was rendered at, not the estimate -- as the reference's loop does (main.py:135-137)."""
+    one the frame was rendered at, not the estimate -- as the reference's loop does (main.py:135-137).  ``eval_views`` = K: after the final
+    mesh every K-th pose of the run is rendered from the map and scored against the simulator (``render.evaluate_views``): the result
+    gains ``render_eval``.  None: no launch is added."""
     if planner is None and traj is None:
         raise ValueError("run_exploration: a planner or a predefined trajectory")
     if traj is not None and len(traj) < num_iter:
         raise ValueError(f"run_exploration: the trajectory has {len(traj)} poses, the run {num_iter} steps")
+    if eval_views is not None and int(eval_views) < 1:
+        raise ValueError("run_exploration: eval_views is a positive stride over the run's poses (or None)")
     c2w = torch.as_tensor(start_c2w if traj is None else traj[0]).detach().to("cpu", torch.float32).reshape(4, 4).clone()
     spent = {k: [0.0, 0] for k in PHASES}
 
@@ -107,6 +113,11 @@ def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optio
         from .evaluation import ate
         out["est_poses"] = slam.resolved_poses().cpu()
         out["ate"] = ate(out["est_poses"], out["poses"]) if len(poses) >= 3 else None
+    if eval_views is not None and poses:
+        from .render import evaluate_views
+        cam = {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}
+        cam.update(near=slam.config["cam"]["near"], far=slam.config["cam"]["far"])
+        out["render_eval"] = evaluate_views(slam.model, slam.config, sim, out["poses"][::int(eval_views)], cam=cam)
     return out
 
 
@@ -136,12 +147,15 @@ def parse_args(argv=None):
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--track", action="store_true", help="estimate the camera poses during the run (tracking + pose refinement); adds the ATE to results.txt")
     parser.add_argument("--dataset", type=str, default="NARUTO", choices=["Replica", "MP3D", "NARUTO"], help="the planner's collision rule")
+    parser.add_argument("--eval_views", type=int, default=None, metavar="K", help="after the run, render every K-th pose from the map and score it against the simulator (psnr, ssim, depth_l1(cm) in results.txt)")
     parser.add_argument("--planner", type=str, nargs="*", default=[], metavar="KEY=VALUE", help="planner settings over naruto_amd.planner.DEFAULTS")
     args = parser.parse_args(argv)
     if args.num_iter <= 0:
         parser.error("--num_iter must be positive")
     if not args.mesh.lower().endswith(".ply"):
         parser.error(f"--mesh {args.mesh}: only .ply meshes are read")
+    if args.eval_views is not None and args.eval_views < 1:
+        parser.error("--eval_views must be positive")
     if args.traj is not None and args.start is not None:
         parser.error("--start and --traj exclude each other: the trajectory's first pose is the start")
     args.planner = _planner_overrides(args.planner)
@@ -172,11 +186,14 @@ def main(argv=None) -> Dict:
         planner.init_local_planner()
     start = torch.eye(4)
     start[:3, 3] = torch.tensor(args.start if args.start is not None else [0.5 * (b[0] + b[1]) for b in cfg["mapping"]["bound"]])
-    out = run_exploration(slam, sim, planner, start, args.num_iter, traj=traj)
+    out = run_exploration(slam, sim, planner, start, args.num_iter, traj=traj, eval_views=args.eval_views)
     length = trajectory_length(out["poses"])
     results = {"traj_len(m)": length}
     if out.get("ate") is not None:
         results.update({"ate_rmse(cm)": out["ate"]["ate_rmse_cm"], "ate_mean(cm)": out["ate"]["ate_mean_cm"]})
+    if out.get("render_eval") is not None:
+        from .render import results_rows
+        results.update(results_rows(out["render_eval"]))
     update_results_file(results, os.path.join(args.result_dir, "results.txt"))
     torch.cuda.synchronize(slam.device)
     for k, v in out["timing"].items():

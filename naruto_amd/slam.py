@@ -335,6 +335,30 @@ class CoSLAMNarutoHIP:
         torch.save({"pose": self.est_c2w_data.as_dict(), "pose_rel": self.est_c2w_data_rel.as_dict(), "model": model}, path)
         return path
 
+    def load_ckpt(self, path: str) -> None:
+        """The inverse of ``save_ckpt``: the model's ``state_dict`` (``render.load_field_state``) and both pose dicts."""
+        from .render import load_checkpoint, load_field_state
+        ckpt = load_checkpoint(path)
+        for name, store in (("pose", self.est_c2w_data), ("pose_rel", self.est_c2w_data_rel)):
+            poses = ckpt.get(name)
+            if not isinstance(poses, dict):
+                raise ValueError(f"{path}: no '{name}' dict of frame id -> [4,4] in the checkpoint")
+            if poses and max(poses) >= self.num_frames:
+                raise ValueError(f"{path}: frame {max(poses)} in '{name}', this run holds {self.num_frames} frames")
+        load_field_state(self.model, ckpt["model"])
+        for name, store in (("pose", self.est_c2w_data), ("pose_rel", self.est_c2w_data_rel)):
+            store.tensor.zero_()
+            store._have = [False] * self.num_frames
+            for k, v in ckpt[name].items():
+                store[int(k)] = v
+
+    def render_view(self, c2w, **kw) -> Dict[str, torch.Tensor]:
+        """Images of the map from the pose(s) ``c2w`` through this run's camera (``render.FieldViewRendererHIP.render``)."""
+        from .render import FieldViewRendererHIP
+        cam = {k: getattr(self, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}
+        cam.update(near=self.config["cam"]["near"], far=self.config["cam"]["far"])
+        return FieldViewRendererHIP(self.model, self.config, cam).render(c2w, **kw)
+
     @torch.no_grad()
     def predict_sdf(self, points: torch.Tensor) -> torch.Tensor:
         """coslam.py:519-535 / coslam_utils.py:35-56: points [N,K,3] in field coordinates -> sdf [N,K] (units of ``training.trunc``)."""
