@@ -602,8 +602,9 @@ int naruto_sample_z(uint32_t n_rays, const float* target_d, float near_, float f
 }
 
 int naruto_hash_encode_fwd(const NarutoField* f, uint32_t M, const float* x, const float* table, float* feat, void* stream) {
-    if (f == nullptr || x == nullptr || table == nullptr || feat == nullptr) return fail(NARUTO_ERR_INVALID, "hash_encode_fwd: NULL argument");
-    if (M == 0) return NARUTO_OK;
+    if (f == nullptr || table == nullptr) return fail(NARUTO_ERR_INVALID, "hash_encode_fwd: NULL argument");
+    if (M == 0) return NARUTO_OK;                     // empty batch: its (NULL) point and feature pointers are not an error
+    if (x == nullptr || feat == nullptr) return fail(NARUTO_ERR_INVALID, "hash_encode_fwd: NULL argument");
     hipLaunchKernelGGL(k_hash_encode_fwd, dim3((M + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, f->lt, x,
                        reinterpret_cast<const float2*>(table), M, feat);
     return check_launch("hash_encode_fwd");
@@ -643,9 +644,9 @@ int naruto_field_scatter_overwrites(const NarutoField* f) { return (f != nullptr
 
 int naruto_hash_encode_bwd(const NarutoField* f, uint32_t M, const float* x, const float* d_feat, const float* d_feat_scale, float* d_table,
                            void* workspace, void* stream) {
-    if (f == nullptr || x == nullptr || d_feat == nullptr || d_table == nullptr || workspace == nullptr)
-        return fail(NARUTO_ERR_INVALID, "hash_encode_bwd: NULL argument");
-    if (M == 0) return NARUTO_OK;
+    if (f == nullptr || d_table == nullptr) return fail(NARUTO_ERR_INVALID, "hash_encode_bwd: NULL argument");
+    if (M == 0) return NARUTO_OK;                     // empty batch: d_table is left as it is
+    if (x == nullptr || d_feat == nullptr || workspace == nullptr) return fail(NARUTO_ERR_INVALID, "hash_encode_bwd: NULL argument");
     PointSrc ps{};
     ps.x = x;
     ps.S = 1;

@@ -76,6 +76,16 @@ __device__ __forceinline__ unsigned long long fix40_prod(float a, float w) {
     return to_fix40(a * w);
 }
 
+// the range contract (fix_add_corners on the tiled levels), per feature component: a cotangent that is NaN, Inf or not
+// below 2^22 in magnitude contributes nothing at any corner.  fix40_prod alone would only drop the PRODUCTS that leave the range and
+// keep such a cotangent's corners of small weight.  The component counts as 0 -- in k_bin_count and k_bin_fill alike, so that both see
+// the same items -- and a point whose two components are zero or dropped makes no item.
+__device__ __forceinline__ float2 bin_cotangent(float2 g) {
+    g.x = fabsf(g.x) < 4194304.0f ? g.x : 0.0f;
+    g.y = fabsf(g.y) < 4194304.0f ? g.y : 0.0f;
+    return g;
+}
+
 // this (row)'s share of the point list: multiples of kBinRound so that count and fill walk the same rounds
 __device__ __forceinline__ void bin_row_range(uint32_t M, uint32_t rows, uint32_t row, uint32_t& m_lo, uint32_t& m_hi) {
     const uint32_t per = ((M + rows - 1u) / rows + (uint32_t)kBinRound - 1u) / (uint32_t)kBinRound * (uint32_t)kBinRound;
@@ -96,7 +106,7 @@ __global__ __launch_bounds__(kBinThreads) void k_bin_count(LevelTab lt, BoxTab b
     bin_row_range(M, gridDim.x, row, m_lo, m_hi);
     const uint32_t sm32 = (uint32_t)stride_m, sl32 = (uint32_t)stride_l;
     for (uint32_t m = m_lo + threadIdx.x; m < m_hi; m += kBinThreads) {
-        const float2 g = *reinterpret_cast<const float2*>(d_feat + (size_t)m * sm32 + (size_t)level * sl32);
+        const float2 g = bin_cotangent(*reinterpret_cast<const float2*>(d_feat + (size_t)m * sm32 + (size_t)level * sl32));
         if (g.x == 0.0f && g.y == 0.0f) continue;
         float x, y, z;
         load_point(ps, bt, m, x, y, z);
@@ -220,7 +230,7 @@ __global__ __launch_bounds__(ROUND) void k_bin_fill(LevelTab lt, BoxTab bt, Poin
     PointRaw p_nxt{};
     if (m_lo < m_hi) load_in(m_lo, g_nxt, p_nxt);
     for (uint32_t r0 = m_lo; r0 < m_hi; r0 += (uint32_t)ROUND) {
-        const float2 g = g_nxt;
+        const float2 g = bin_cotangent(g_nxt);
         const PointRaw pr = p_nxt;
         if (r0 + (uint32_t)ROUND < m_hi) load_in(r0 + (uint32_t)ROUND, g_nxt, p_nxt);
         // 1. this thread's point -> its pair items in registers, rank of each item within (round, bin)

@@ -2148,7 +2148,8 @@ def test_scatter_drops_nan_cotangents(gpu):
     """a point whose cotangent is NaN / Inf (or beyond the fixed point's 2^22) contributes nothing to the table gradient
     -- the reference's float atomics would spread it -- and takes nothing of its neighbours with it (the dense levels sum the points
     of a cell in registers first).  Every 97th point's cotangents are NaN, Inf or 1e9: the result must be the gradient of the same batch
-    with those cotangents zeroed, bit for bit on every level."""
+    with those cotangents zeroed, bit for bit on every level.  (office_cfg(12) has no binned level: the same on levels of more than 2^17
+    entries, and per feature component, is test_gpu_binned.py::test_binned_levels_drop_out_of_range_cotangents.)"""
     cfg = H.office_cfg(12)
     ora = H.make_oracle(cfg, 0.25, 59)
     m = H.make_hip_from_oracle(cfg, ora, gpu)
