@@ -786,6 +786,11 @@ size_t naruto_debug_query_bwd_lds_bytes(void);
 /* profiling (bench.py's roofline): k_hash_scatter_lds alone, over the point list the preceding naruto_train_backward left in the
  * workspace, in the launch shape of the iteration; writes the scatter's partial tables only (no gradient, no parameter). */
 int naruto_debug_train_scatter(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, void* stream);
+/* testing (tests/test_gpu_scatter_visit.py): the table scatter over a caller-made point list in the training layout -- x_soa [3][cap]
+ * normalised points, d_feat [16][cap][2] cotangents, cap a multiple of 4, *n_dev (device) the number of list points <= cap -- i.e. the
+ * hashed levels' list route with prescribed cotangents.  Adds into d_table like naruto_hash_encode_bwd; workspace: naruto_scatter_workspace(f, cap). */
+int naruto_debug_scatter_list(const NarutoField* f, uint32_t cap, const uint32_t* n_dev, const float* x_soa, const float* d_feat, float* d_table,
+                              void* workspace, void* stream);
 
 /* The launch plans, host only (nothing is launched, no GPU needed; tests/test_launch_plans_host.py, tests/test_gpu_launch_forms.py).
  * naruto_debug_train_plan: what naruto_train_forward's field-query launch is for this step (only n_rays, n_samples_d and n_range_d of t

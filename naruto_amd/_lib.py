@@ -315,6 +315,7 @@ SIGNATURES = {
     "naruto_debug_fwd_image": (_I, [_V, C.POINTER(NarutoParams), _V, _V]),
     "naruto_debug_fwd_image_map": (_I, [_V, _V]),
     "naruto_debug_train_scatter": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoTrainStep), _V]),
+    "naruto_debug_scatter_list": (_I, [_V, _U32, _V, _V, _V, _V, _V, _V]),
     "naruto_debug_train_plan": (_I, [_V, C.POINTER(NarutoTrainStep), _I, _I, C.POINTER(_U32)]),
     "naruto_debug_render_plan": (_I, [_V, _U32, _U32, _I, _I, C.POINTER(_U32)]),
     "naruto_render_fwd": (_I, [_V, C.POINTER(NarutoParams), C.POINTER(NarutoRender), _V]),

@@ -310,6 +310,15 @@ int launch_scatter(const NarutoField* f, const PointSrc& ps, uint32_t M, const f
     if (f->plan.n_dense + f->plan.n_hashed > 0) {
         static bool attr_set = false;
         const size_t lds = kScatterLdsBytes;
+        if (!attr_set) {
+            // the hashed units' list visit addresses the image from LDS offset 0 (the contract at `acc` in k_hash_scatter_lds): static LDS in
+            // the kernel would put the dynamic allocation behind it, and the visit would add into whatever lies at the front
+            hipFuncAttributes fa{};
+            if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_hash_scatter_lds)) != hipSuccess)
+                return fail(NARUTO_ERR_LAUNCH, "hash_scatter: cannot read the kernel's attributes: %s", hipGetErrorString(hipGetLastError()));
+            if (fa.sharedSizeBytes != 0)
+                return fail(NARUTO_ERR_LAUNCH, "hash_scatter: k_hash_scatter_lds has %zu bytes of static LDS; its image must start at LDS offset 0", (size_t)fa.sharedSizeBytes);
+        }
         if (int rc = reserve_lds(attr_set, {lds_use(k_hash_scatter_lds, lds)}, "hash_scatter: cannot reserve %zu bytes of LDS", lds)) return rc;
         const uint32_t blocks = ((uint32_t)plan.n_level_blocks + (us.g != nullptr ? plan.n_uncert * us.n_splits : 0u) + 7u) / 8u * 8u;      // XCD-aware order: multiple of 8
         hipLaunchKernelGGL(k_hash_scatter_lds, dim3(blocks), dim3(kScatterThreads), lds, st, f->lt, f->bt, ps, M, d_feat, stride_m, stride_l, plan,
@@ -1541,6 +1550,17 @@ int naruto_debug_train_scatter(const NarutoField* f, const NarutoParams* p, cons
     // d_table / d_uncert only select the roles here: without the reduce nothing is written through them
     return launch_scatter(f, list_points(bw.x_soa, cap), cap, bw.d_feat, (size_t)2, (size_t)2 * (size_t)cap, const_cast<float*>(p->table), bw.scatter_ws, (hipStream_t)stream, cnt, nullptr, 1, false,
                           nullptr, unc_g, unc_g != nullptr ? const_cast<float*>(p->uncert_grid) : nullptr, n_front);
+}
+
+// testing: the table scatter over a caller-made point list in the TRAINING layout (x_soa [3][cap], d_feat [16][cap][2], cap % 4 == 0, the count
+// on the device) -- the hashed units' list route with prescribed cotangents, which the public backward derives itself.  Adds into d_table, as
+// naruto_hash_encode_bwd does over the generic layout: same count, same plan, same split bounds.
+int naruto_debug_scatter_list(const NarutoField* f, uint32_t cap, const uint32_t* n_dev, const float* x_soa, const float* d_feat, float* d_table,
+                              void* workspace, void* stream) {
+    if (f == nullptr || n_dev == nullptr || x_soa == nullptr || d_feat == nullptr || d_table == nullptr || workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "debug_scatter_list: NULL argument");
+    if (cap == 0 || (cap & 3u) != 0u) return fail(NARUTO_ERR_INVALID, "debug_scatter_list: the list's capacity must be a positive multiple of 4");
+    return launch_scatter(f, list_points(x_soa, cap), cap, d_feat, (size_t)2, (size_t)2 * (size_t)cap, d_table, workspace, (hipStream_t)stream, n_dev);
 }
 
 namespace {

@@ -510,6 +510,13 @@ __device__ __forceinline__ void fwd_tile(const FwdLds& L, const LevelTab& lt, co
 #ifndef NARUTO_FWD_GATHER_PRIO
 #define NARUTO_FWD_GATHER_PRIO 3
 #endif
+// The walk (k_query_fwd_loss<*, true>, naruto_train.hip) gathers the FIRST tile of a ray that may stop after it one level lower: the rays that need
+// their second tile a priori (a sixth of the benchmark's) get through tile 0's gathers ahead of their SIMD partners -- 26.3 -> 23.3 us -- and gather
+// tile 1 while the others are still in tile 0; k_query_fwd_loss_img 58.8 -> 57.8 us (profiles/walk_short_ray_prio_*.txt; 1 measured the same as 2).
+// Equal to NARUTO_FWD_GATHER_PRIO: every ray at the top level, as before.
+#ifndef NARUTO_FWD_SHORT_RAY_PRIO
+#define NARUTO_FWD_SHORT_RAY_PRIO 2
+#endif
 struct FwdSlab { float feat[kLevels][2][64]; };          // [level][tile half][lane]: the MFMA B operands of the hash part
 
 // dead lanes (MASK: ee_lane_live) fetch entry 0 of the level -- one shared line per instruction instead of a branch around the loads --
@@ -1473,8 +1480,13 @@ __device__ __forceinline__ void hash_corner_addr8(const LevelTab& lt, float x, f
     for (int c = 0; c < 8; ++c) a8[c] = (((c & 1) ? gx1 : gx0) ^ ((c & 2) ? hy1 : hy0) ^ ((c & 4) ? hz1 : hz0)) & mask8;
     f[0] = 1.0f - wx; f[1] = wx; f[2] = 1.0f - wy; f[3] = wy; f[4] = 1.0f - wz; f[5] = wz;
 }
-__device__ __forceinline__ void fix_add_corners8(unsigned long long* __restrict__ acc, const uint32_t (&a8)[8], const float (&f)[6], float g) {
-    char* __restrict__ base = reinterpret_cast<char*>(acc);
+// The image is k_hash_scatter_lds's dynamic LDS and starts at LDS address 0 (the kernel has no static LDS: see where `acc` is declared), so
+// a8 IS the ds_add_u64's address.  Formed as `acc + offset` it costs a v_add_u32 vN, 0, vM in front of every LDS atomic -- the symbol's
+// address is not known to be 0 before link time and the add is not folded; formed from the integer it costs nothing.
+__device__ __forceinline__ void lds_add_u64_at(uint32_t a8, unsigned long long v) {
+    __hip_atomic_fetch_add((__attribute__((address_space(3))) unsigned long long*)(uintptr_t)a8, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void fix_add_corners8(const uint32_t (&a8)[8], const float (&f)[6], float g) {
     if (__builtin_expect(fabsf(g) <= kFixMagicRange, 1)) {             // per LANE: what a point adds does not depend on its wave
         const double gd = (double)g;
         const double gx0 = gd * (double)f[0], gx1 = gd * (double)f[1];
@@ -1483,13 +1495,14 @@ __device__ __forceinline__ void fix_add_corners8(unsigned long long* __restrict_
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const double s = __fma_rn(gxy[c & 3], (c & 4) ? z1 : z0, kFixMagic);
-            if (a8[c] < kChunk * 8u) atomicAdd(reinterpret_cast<unsigned long long*>(base + a8[c]), fix40_bits(s));
+            if (a8[c] < kChunk * 8u) lds_add_u64_at(a8[c], fix40_bits(s));
         }
         return;
     }
     if (!(fabsf(g) < 4194304.0f)) return;                   // NaN / Inf / beyond the fixed point's range: the point adds nothing (as on the dense levels)
 #pragma unroll
-    for (int c = 0; c < 8; ++c) fix_add_rel(acc, a8[c] >> 3, (f[c & 1] * f[2 + ((c >> 1) & 1)] * f[4 + (c >> 2)]) * g);
+    for (int c = 0; c < 8; ++c)
+        if (a8[c] < kChunk * 8u) lds_add_u64_at(a8[c], to_fix40((f[c & 1] * f[2 + ((c >> 1) & 1)] * f[4 + (c >> 2)]) * g));      // fix_add_rel's test and value
 }
 
 template <int T>
@@ -1544,7 +1557,7 @@ __device__ __forceinline__ void scatter_tile_points(const LevelTab& lt, const Bo
                     uint32_t a8[8];
                     float f[6];
                     hash_corner_addr8<T>(lt, q.x[b], q.y[b], q.z[b], chunk << (kChunkLog2 + 3), a8, f);
-                    fix_add_corners8(acc, a8, f, q.g[b]);
+                    fix_add_corners8(a8, f, q.g[b]);
                 }
             }
             return;
@@ -1717,6 +1730,10 @@ __global__ __launch_bounds__(kScatterThreads) void k_hash_scatter_lds(LevelTab l
                                                                        float* __restrict__ partial, size_t n_params,
                                                                        const uint32_t* __restrict__ m_dev, const float* __restrict__ scale_dev, UncertScatter unc,
                                                                        unsigned long long* __restrict__ timeline) {
+    // CONTRACT: the image `acc` starts at LDS address 0.  The hashed units' list visit (fix_add_corners8) forms its LDS addresses from the byte
+    // offset alone, without this symbol.  It holds while the kernel has NO static LDS (group_segment_fixed_size == 0: dynamic LDS follows the
+    // static part) -- no __shared__ variable here or in anything inlined here.  launch_scatter refuses to launch otherwise, and
+    // tests/test_scatter_lds_contract.py reads the figure from the built code object.
     extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];
     // profiling (naruto_debug_fwd_timeline's buffer; NULL otherwise): thread 0 of every workgroup stamps the 100 MHz counter -- 0 start, 1 image
     // zeroed, 2 points done, 3 end, 4 = (unit << 8 | split) + 1 or 0x10000 + uncertainty block (tools/scatter_timeline.py)
@@ -1757,7 +1774,8 @@ __global__ __launch_bounds__(kScatterThreads) void k_hash_scatter_lds(LevelTab l
         // 52 -> 29 us per workgroup at the headline; the launch 57 -> 51 us (profiles/r05_scatter_timeline.txt).
         {
             // (the queue sits BEHIND the image in the dynamic allocation: static LDS in this kernel would move the image off address 0, and
-            // every address the level units form would carry the offset -- 127 -> 307 spilled scalar registers, measured)
+            // every address the level units form would carry the offset -- 127 -> 307 spilled scalar registers, measured.  Since the list visit
+            // takes the image's offset 0 for granted -- the contract at `acc` -- static LDS here would be WRONG, not only slower.)
             uint16_t* __restrict__ q = reinterpret_cast<uint16_t*>(acc + kChunk);
             uint32_t& q_n = *reinterpret_cast<uint32_t*>(q + kUncBatch);
             const int lane = threadIdx.x & 63;

@@ -303,7 +303,21 @@ __device__ __forceinline__ void query_fwd_loss_body(const LevelTab& lt, const Un
                     // the full tiles behind the first -- was measured: the kernel's code outgrows the instruction cache, 60 -> 89 us.)
                     bool half = false;
                     if constexpr (kX3) half = tq > 0u && !__any(live && lane >= 32);      // (the half tile exists for the x3 image only)
-                    if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(NARUTO_FWD_GATHER_PRIO);
+                    if constexpr (NARUTO_FWD_GATHER_PRIO != 0) {
+                        // A ray whose 64th depth is not beyond measured depth + truncation (or that has no measured depth) needs its second tile whatever the
+                        // field says (ee_after_tile_r): its first tile's gathers go ahead of its SIMD partner's, so that the second tile is gathered while
+                        // the short rays are still in their first.  A hint: s_setprio is not arithmetic.  Consumed at once, nothing is carried over the tile loop.
+                        bool long_ray = true;
+                        if constexpr (NARUTO_FWD_SHORT_RAY_PRIO != NARUTO_FWD_GATHER_PRIO) {
+                            if (tq == 0u && tpr > 1u) {
+                                const float td_u = lane_f32(td_ee, 0), z63 = lane_f32(zv, 63);
+                                const float lim = td_u + ee.trunc_sc;
+                                long_ray = (td_u == 0.0f) || !(z63 > lim + 1e-5f * fabsf(lim) + 1e-6f);
+                            }
+                        }
+                        if (long_ray) __builtin_amdgcn_s_setprio(NARUTO_FWD_GATHER_PRIO);
+                        else __builtin_amdgcn_s_setprio(NARUTO_FWD_SHORT_RAY_PRIO);
+                    }
                     if (half) fwd_gather_tile_deep<true>(lt, table, x, y, z, feat_save, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, slabs[wave], live);
                     else fwd_gather_tile<true>(lt, table, x, y, z, feat_save, M, t0 + (uint32_t)j, t0 + (uint32_t)j + 32u, lane, slabs[wave], live);
                     if constexpr (NARUTO_FWD_GATHER_PRIO != 0) __builtin_amdgcn_s_setprio(0);
