@@ -13,6 +13,13 @@
  *   - gradients are ACCUMULATED (+=) into the buffers of NarutoGrads, so the caller zeroes them
  *     (this is what torch's .grad accumulation needs, reference coslam.py:368-399);
  *   - a NarutoField handle is immutable after creation and may be shared by streams/threads.
+ *
+ * This file is the ONE statement of the ABI: naruto_amd/_lib.py reads it at import and derives its ctypes structures, constants and
+ * argument types from the declarations below, and refuses what it cannot read.  So the declarations stay plain: `typedef struct X { ... } X;`
+ * of fixed-width scalars, pointers and arrays; `#define NARUTO_X <integer literal>`; one prototype per function.  A parameter that
+ * is a HOST pointer carries NARUTO_HOST (the macro is empty): the binding types it POINTER(<its scalar>), so that ctypes converts
+ * arrays and passes a bare scalar by reference; every unmarked pointer is an address (c_void_p), or POINTER(<struct>) for the
+ * structs declared here.
  */
 #ifndef NARUTO_HIP_H
 #define NARUTO_HIP_H
@@ -24,6 +31,7 @@
 extern "C" {
 #endif
 
+#define NARUTO_HOST                   /* marks a parameter that points to HOST memory (see above) */
 #define NARUTO_MAX_LEVELS 16
 #define NARUTO_OK 0
 #define NARUTO_ERR_INVALID (-22)      /* bad argument / unsupported configuration */
@@ -96,11 +104,12 @@ typedef struct NarutoPoints {
 const char* naruto_last_error(void);
 int naruto_version(void);
 
-int  naruto_field_create(const NarutoFieldDesc* desc, NarutoField** out);
+int  naruto_field_create(const NarutoFieldDesc* desc, NARUTO_HOST NarutoField** out);
 void naruto_field_destroy(NarutoField* f);
 /* Level tables the library derived (tcnn GridEncodingTemplated constructor): host arrays of
  * n_levels (scale, resolution, size) and n_levels+1 (offset, in entries). */
-int  naruto_field_levels(const NarutoField* f, float* scale, uint32_t* resolution, uint32_t* size, uint32_t* offset);
+int  naruto_field_levels(const NarutoField* f, NARUTO_HOST float* scale, NARUTO_HOST uint32_t* resolution, NARUTO_HOST uint32_t* size,
+                          NARUTO_HOST uint32_t* offset);
 uint64_t naruto_field_n_entries(const NarutoField* f);
 
 /* A1 -- depth sampling, scene_rep.py:158-180.  target_d may be NULL (then n_samples uniform depths,
@@ -319,7 +328,7 @@ int naruto_map_volumes(uint32_t M, const float* sdf_uncert, float* out, void* st
 size_t naruto_active_ray_workspace(uint32_t n_total, uint32_t K);
 int naruto_active_ray_select(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o,
                              const float* rays_d, const float* target_s, const float* target_d,
-                             const float* uncert_vol, const uint32_t* vol_dims, const float* bbox_min,
+                             const float* uncert_vol, NARUTO_HOST const uint32_t* vol_dims, NARUTO_HOST const float* bbox_min,
                              float voxel_scale, float* out_o, float* out_d, float* out_s, float* out_t,
                              void* workspace, void* stream);
 
@@ -334,7 +343,7 @@ int naruto_active_ray_select_keyed(uint32_t n_total, uint32_t base, uint32_t K, 
  * rays through it: id of output row r = ids[src_rows[r]]. */
 int naruto_active_ray_select_rows(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o,
                                   const float* rays_d, const float* target_s, const float* target_d,
-                                  const float* uncert_vol, const uint32_t* vol_dims, const float* bbox_min,
+                                  const float* uncert_vol, NARUTO_HOST const uint32_t* vol_dims, NARUTO_HOST const float* bbox_min,
                                   float voxel_scale, float* out_o, float* out_d, float* out_s, float* out_t,
                                   uint32_t* src_rows, void* workspace, void* stream);
 int naruto_active_ray_select_keyed_rows(uint32_t n_total, uint32_t base, uint32_t K, uint32_t n_tail, const float* rays_o,
@@ -391,7 +400,7 @@ int naruto_assemble_rays(const NarutoRayBatch* b, void* stream);
  * buffers and ids_out are ignored and may be NULL); base / K / n_tail / volume arguments and the result are naruto_active_ray_select's.
  * At most 8 192 candidates (n_global + n_cur - base - n_tail): NARUTO_ERR_INVALID beyond -- use the two calls. */
 int naruto_assemble_select(const NarutoRayBatch* b, uint32_t base, uint32_t K, uint32_t n_tail, const float* uncert_vol,
-                           const uint32_t* vol_dims, const float* bbox_min, float voxel_scale, float* out_o, float* out_d,
+                           NARUTO_HOST const uint32_t* vol_dims, NARUTO_HOST const float* bbox_min, float voxel_scale, float* out_o, float* out_d,
                            float* out_s, float* out_t, void* stream);
 int naruto_sample_distinct(uint64_t n, uint32_t count, uint64_t seed, uint64_t counter, int64_t* out, void* stream);
 uint64_t naruto_perm_index(uint64_t i, uint64_t n, uint64_t seed, uint64_t counter, uint64_t salt);
@@ -445,9 +454,9 @@ int naruto_debug_pose_log(uint32_t P, const float* c2w, float* pose6);
  *   30 points of the segment goal -> target (truncated to voxels); else 0.  aggregated[g] = sum_k collections[g][k].
  *   goal_idx int32 [G,3], targets int32 [k,3]. */
 size_t naruto_goal_targets_workspace(uint32_t n_voxels, uint32_t top_k);
-int naruto_goal_targets(const uint32_t* dims, const float* uncert_vol, uint32_t top_k, uint32_t top_k_subset,
+int naruto_goal_targets(NARUTO_HOST const uint32_t* dims, const float* uncert_vol, uint32_t top_k, uint32_t top_k_subset,
                         int32_t* targets, void* workspace, void* stream);
-int naruto_goal_aggregate(const uint32_t* dims, const float* uncert_vol, const float* sdf_vol, uint32_t n_goals,
+int naruto_goal_aggregate(NARUTO_HOST const uint32_t* dims, const float* uncert_vol, const float* sdf_vol, uint32_t n_goals,
                           const int32_t* goal_idx, uint32_t n_targets, const int32_t* targets, float min_dist,
                           float max_dist, float safe_sdf, float* collections, float* aggregated, void* stream);
 
@@ -466,9 +475,10 @@ int naruto_goal_aggregate(const uint32_t* dims, const float* uncert_vol, const f
  * bbox_min: HOST double[3].  NARUTO_ERR_INVALID for G == 0, K == 0, obs_per_goal == 0 or K > 4096.  The result does not depend
  * on the launch shape: every comparison is on integer keys and indices. */
 #define NARUTO_GOAL_SEARCH_HEAD_INTS 8
+#define NARUTO_GOAL_SEARCH_MAX_TARGETS 4096     /* K beyond this is refused: the row's keys sit in LDS */
 #define NARUTO_GOAL_SEARCH_BYTES(m) (4u * NARUTO_GOAL_SEARCH_HEAD_INTS + 44u * (size_t)(m))
 int naruto_goal_search(uint32_t n_goals, uint32_t n_targets, const float* aggregated, const float* collections,
-                       const int32_t* targets, const int32_t* goal_idx, uint32_t obs_per_goal, const double* bbox_min,
+                       const int32_t* targets, const int32_t* goal_idx, uint32_t obs_per_goal, NARUTO_HOST const double* bbox_min,
                        double voxel_size, void* out, void* stream);
 
 /* N4 ("next" row) -- the dense volume -> mesh path (reference src/slam/coslam/coslam_utils.py:100-226 extract_mesh,
@@ -482,12 +492,12 @@ int naruto_goal_search(uint32_t n_goals, uint32_t n_targets, const float* aggreg
  * naruto_mesh_emit: pass 2: vertices float64 [V,3] in lattice-index coordinates (one per crossed lattice edge, at
  *   t = (isolevel - v0) / (v1 - v0) in float64, ordered by (owner voxel, axis)), triangles int32 [F,3] ordered by
  *   (cell, case-table order), normals towards larger values.  At most cap_* entries are written. */
-int naruto_lattice_points(const uint32_t* dims, const float* tx, const float* ty, const float* tz, float* x,
+int naruto_lattice_points(NARUTO_HOST const uint32_t* dims, const float* tx, const float* ty, const float* tz, float* x,
                           void* stream);
-size_t naruto_mesh_workspace(const uint32_t* dims);
-int naruto_mesh_count(const uint32_t* dims, const float* sdf_vol, double isolevel, double truncation,
+size_t naruto_mesh_workspace(NARUTO_HOST const uint32_t* dims);
+int naruto_mesh_count(NARUTO_HOST const uint32_t* dims, const float* sdf_vol, double isolevel, double truncation,
                       void* workspace, uint64_t* counts, void* stream);
-int naruto_mesh_emit(const uint32_t* dims, const float* sdf_vol, double isolevel, const void* workspace,
+int naruto_mesh_emit(NARUTO_HOST const uint32_t* dims, const float* sdf_vol, double isolevel, const void* workspace,
                      uint64_t cap_vertices, uint64_t cap_triangles, double* vertices, int32_t* triangles,
                      void* stream);
 
@@ -533,7 +543,7 @@ int naruto_surface_areas(uint64_t n_faces, uint64_t n_vertices, const void* vert
                          double* areas, void* stream);
 int naruto_surface_sample(uint64_t n_faces, uint64_t n_vertices, const void* vertices, int vertices_f64, const int32_t* faces,
                           const double* cum_area, uint64_t count, uint64_t seed, float* points, int32_t* face_index, void* stream);
-int naruto_nn_grid_plan(uint64_t n_points, const double* lo, const double* hi, double cell, uint64_t max_cells, NarutoNnGrid* grid);
+int naruto_nn_grid_plan(uint64_t n_points, NARUTO_HOST const double* lo, NARUTO_HOST const double* hi, double cell, uint64_t max_cells, NarutoNnGrid* grid);
 size_t naruto_nn_grid_workspace(const NarutoNnGrid* grid);
 int naruto_nn_grid_build(const NarutoNnGrid* grid, const float* points, void* workspace, void* stream);
 int naruto_nn_grid_query(const NarutoNnGrid* grid, uint64_t n_queries, const float* queries, const void* queries_sorted,
@@ -578,10 +588,10 @@ int naruto_dist_reduce(uint64_t n, const double* dist, double threshold, void* w
 int naruto_icp_transform(uint64_t n, const void* points, int points_f64, const double* T, void* out, void* stream);
 size_t naruto_icp_accumulate_workspace(uint64_t n);
 int naruto_icp_accumulate(uint64_t n, const float* points, uint64_t n_targets, const float* targets, const int32_t* index,
-                          const double* dist, double max_distance, const double* origin, void* workspace, double* sums, void* stream);
-int naruto_icp_step(const double* sums, uint64_t n_source, const double* origin, uint32_t max_iteration, double relative_fitness,
+                          const double* dist, double max_distance, NARUTO_HOST const double* origin, void* workspace, double* sums, void* stream);
+int naruto_icp_step(const double* sums, uint64_t n_source, NARUTO_HOST const double* origin, uint32_t max_iteration, double relative_fitness,
                     double relative_rmse, double* state, void* stream);
-int naruto_debug_icp_solve(const double* sums, const double* origin, double* dT, int32_t* status);
+int naruto_debug_icp_solve(NARUTO_HOST const double* sums, NARUTO_HOST const double* origin, NARUTO_HOST double* dT, NARUTO_HOST int32_t* status);
 
 /* The planner's local RRT (reference src/planner/rrt.py and src/planner/rrt_naruto.py: class RRTNaruto, the
  * local_planner_method of every shipped config), on the volumes of naruto_map_volumes.  Unit: voxel.
@@ -639,6 +649,7 @@ int naruto_debug_icp_solve(const double* sums, const double* origin, double* dT,
 #define NARUTO_RRT_STATE_MID_ITER 7     /* the direct-line half of iteration ITER is already in the tree (a stop fell after it) */
 #define NARUTO_RRT_STATE_USE_CELLS 9    /* the cell lists are valid (the start lay inside the grid): nearest search and mask may use them;
                                            clearing it sends naruto_reachable_mask through node tiles instead */
+#define NARUTO_RRT_STATE_INTS 16        /* length of the state block, in int32 */
 typedef struct NarutoRrtPlan {
     uint32_t dims[3];
     double range[3][2], full_range[3][2];
@@ -649,12 +660,12 @@ typedef struct NarutoRrtPlan {
     double* nodes_xyz; float* nodes_xyz32; int32_t* parent; int32_t* next;
     uint32_t capacity, cell_threshold;
 } NarutoRrtPlan;
-size_t naruto_rrt_workspace(const uint32_t* dims /* HOST {X,Y,Z} */);
-int naruto_rrt_start(const NarutoRrtPlan* plan, const double* start, const double* goal, void* stream);
+size_t naruto_rrt_workspace(NARUTO_HOST const uint32_t* dims /* HOST {X,Y,Z} */);
+int naruto_rrt_start(const NarutoRrtPlan* plan, NARUTO_HOST const double* start, NARUTO_HOST const double* goal, void* stream);
 int naruto_rrt_grow(const NarutoRrtPlan* plan, int mode, const double* rows, uint32_t n_rows, uint32_t max_iter,
                     int restart, void* stream);
 int naruto_rrt_path(const NarutoRrtPlan* plan, int32_t* path, void* stream);
-int naruto_segments_free(const uint32_t* dims /* HOST */, const float* sdf_vol, uint32_t n, const double* pa,
+int naruto_segments_free(NARUTO_HOST const uint32_t* dims /* HOST */, const float* sdf_vol, uint32_t n, const double* pa,
                          const double* pb, double step_size, double collision_thre, int32_t* num_collision_free,
                          uint8_t* complete_free, void* stream);
 int naruto_reachable_mask(const NarutoRrtPlan* plan, float* mask, void* stream);
@@ -760,7 +771,7 @@ int naruto_train_backward(const NarutoField* f, const NarutoParams* p, const Nar
 
 /* NarutoTrainStep.fwd_image: its size (returned; optionally the image part's bytes and the number of MLP weights, 5 184), and its one-time
  * preparation from the weights in p (one small launch + one upload; NOT inside a stream capture). */
-size_t naruto_fwd_image_bytes(size_t* image_bytes, uint32_t* n_weights);
+size_t naruto_fwd_image_bytes(NARUTO_HOST size_t* image_bytes, NARUTO_HOST uint32_t* n_weights);
 int naruto_fwd_image_init(const NarutoField* f, const NarutoParams* p, void* fwd_image, void* stream);
 /* tests: what one workgroup of the training forward stages from the weights in p, copied out (image_bytes bytes, 16-byte aligned), and -- host
  * only -- where the finishing launch puts each weight: slots [n_weights] (low half: byte offset of the first piece / of the float; high half:
@@ -802,14 +813,14 @@ int naruto_debug_scatter_list(const NarutoField* f, uint32_t cap, const uint32_t
  *   NARUTO_RENDER_WIDE as the launcher does, 0 / 1 / 2 override it.  out = {form (0 k_render_fwd, 1 k_render_fwd_packed<*, 256>,
  *   2 k_render_fwd_packed<*, 512>), rays per group, workgroups, rays per pass of the grid-stride loop, dynamic LDS bytes of the launch,
  *   dynamic LDS bytes reserved for the kernel, the kernel's static LDS bytes, threads per workgroup}. */
-int naruto_debug_train_plan(const NarutoField* f, const NarutoTrainStep* t, int with_loss, int deferred, uint32_t out[8]);
-int naruto_debug_render_plan(const NarutoField* f, uint32_t n_rays, uint32_t S, int bf16, int wide, uint32_t out[8]);
+int naruto_debug_train_plan(const NarutoField* f, const NarutoTrainStep* t, int with_loss, int deferred, NARUTO_HOST uint32_t out[8]);
+int naruto_debug_render_plan(const NarutoField* f, uint32_t n_rays, uint32_t S, int bf16, int wide, NARUTO_HOST uint32_t out[8]);
 
 /* Measurement aid (bench.py, workloads whose table fits no cache): one launch that reads RANDOM 64-byte lines out of `table`
  * (table_bytes of it) -- the access pattern of the hash gather on the T = 2^22 levels, without the kernel around it; *n_lines_out
  * (host) = distinct lines the launch requests.  Timed with HIP events it gives the memory system's random-line rate, the ceiling
  * `roofline.random_line_roof` prices the gather against (tools/hbm_random_line_bench.hip: the standalone sweep). */
-int naruto_debug_random_lines(const float* table, uint64_t table_bytes, uint32_t iters, float* sink, uint64_t* n_lines_out, void* stream);
+int naruto_debug_random_lines(const float* table, uint64_t table_bytes, uint32_t iters, float* sink, NARUTO_HOST uint64_t* n_lines_out, void* stream);
 
 /* Hardware self-checks used by the GPU tests: the MFMA / permlane layouts the kernels rely on.
  * out: device buffer of 64*16 floats; returns 0 and fills out (see tests/test_gpu_parity.py: test_mfma_layout, test_permlane32_swap). */
@@ -855,7 +866,7 @@ int naruto_track_draw(const NarutoTrackStep* k, const NarutoTrainStep* t, void* 
 int naruto_track_rays(const NarutoTrackStep* k, const NarutoTrainStep* t, void* stream);
 int naruto_track_backward(const NarutoField* f, const NarutoParams* p, const NarutoTrainStep* t, const NarutoTrackStep* k, void* stream);
 /* host only: R(w) (row-major) and the VJP d_w of sum(G * R(w)), in fp64, by the tracking kernels' own code (R or d_w may be NULL) */
-int naruto_debug_rodrigues(const double* w, const double* G, double* R, double* d_w);
+int naruto_debug_rodrigues(NARUTO_HOST const double* w, NARUTO_HOST const double* G, NARUTO_HOST double* R, NARUTO_HOST double* d_w);
 
 
 /* Pose refinement inside global_BA: the pose optimiser of the reference's loop (coslam.py:256-281, 342-344, 378-407; parity unpinned --
@@ -905,8 +916,9 @@ int naruto_train_backward_poses(const NarutoField* f, const NarutoParams* p, con
  * naruto_debug_ba_pose_sums: pose `pose`'s sums of one batch in the accumulation kernel's order, ADDED to sums [12] (host arrays
  *   throughout); grad [6] (optional, needs pose6 [6]): (d_omega, d_t) from the sums as the pose step forms it. */
 int naruto_debug_ba_poses_check(const NarutoBAPoses* b, uint32_t n_rays);
-int naruto_debug_ba_poses_fields(const NarutoBAPoses* b, uint64_t out[25]);
-int naruto_debug_pose_adam(float* pose, const float* grad, float* exp_avg, float* exp_avg_sq, int32_t step, float lr_rot, float lr_trans,
+int naruto_debug_ba_poses_fields(const NarutoBAPoses* b, NARUTO_HOST uint64_t out[25]);
+int naruto_debug_pose_adam(NARUTO_HOST float* pose, NARUTO_HOST const float* grad, NARUTO_HOST float* exp_avg, NARUTO_HOST float* exp_avg_sq, int32_t step,
+                           float lr_rot, float lr_trans,
                            float beta1, float beta2, float eps);
 int naruto_debug_ba_pose_sums(uint32_t n_rays, const int64_t* ids, uint32_t n_ids, const uint32_t* src_rows, uint32_t n_poses, uint32_t pose,
                               const float* rays_d, const float* d_rays_o, const float* d_rays_d, const float* pose6, double* sums, float* grad);
@@ -1032,7 +1044,7 @@ int naruto_view_crossing(uint32_t n_rays, uint32_t n_samples, const float* raw, 
 int naruto_render_view(const NarutoField* f, const NarutoParams* p, const NarutoCullCam* cam, const NarutoViewRender* r, void* stream);
 size_t naruto_image_metrics_workspace(uint32_t n_views, uint32_t H, uint32_t W);
 int naruto_image_metrics(uint32_t n_views, uint32_t H, uint32_t W, const float* rgb, const float* depth, const float* gt_rgb, const float* gt_depth, int has_depth_trunc,
-                         float depth_trunc, const double* window, void* workspace, double* out, double* se_map, double* de_map, double* ssim_map, void* stream);
+                         float depth_trunc, NARUTO_HOST const double* window, void* workspace, double* out, double* se_map, double* de_map, double* ssim_map, void* stream);
 
 #ifdef __cplusplus
 }

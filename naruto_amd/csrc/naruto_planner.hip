@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void k_goal_aggregate(VolDims d, const float* 
 // ordered by the key of k_topk_keys above (~sortable_key: ascending key = descending value, NaN first), so every comparison is an
 // integer one and the result does not depend on the number of threads or on which lane meets which element.
 
-constexpr uint32_t kGoalSearchMaxTargets = 4096;      // the row's keys sit in LDS (16 KiB)
+constexpr uint32_t kGoalSearchMaxTargets = NARUTO_GOAL_SEARCH_MAX_TARGETS;     // the row's keys sit in LDS (16 KiB)
 constexpr uint32_t kGoalSearchHeadInts = NARUTO_GOAL_SEARCH_HEAD_INTS;
 
 struct GoalSearchFrame { double bx, by, bz, voxel; };

@@ -24,7 +24,7 @@ struct RrtVol { const float* v; int X, Y, Z; };
 // layout of the int32 state block at the head of the workspace (NARUTO_RRT_STATE_* in the header)
 enum { kRrtNodes = NARUTO_RRT_STATE_NODES, kRrtIter = NARUTO_RRT_STATE_ITER, kRrtRrtIter = NARUTO_RRT_STATE_RRT_ITER, kRrtStatus = NARUTO_RRT_STATE_STATUS,
        kRrtRowsUsed = NARUTO_RRT_STATE_ROWS_USED, kRrtGoalParent = NARUTO_RRT_STATE_GOAL_PARENT, kRrtReachable = NARUTO_RRT_STATE_REACHABLE,
-       kRrtMidIter = NARUTO_RRT_STATE_MID_ITER, kRrtUseCells = NARUTO_RRT_STATE_USE_CELLS, kRrtStateInts = 16 };
+       kRrtMidIter = NARUTO_RRT_STATE_MID_ITER, kRrtUseCells = NARUTO_RRT_STATE_USE_CELLS, kRrtStateInts = NARUTO_RRT_STATE_INTS };
 constexpr int kRrtGoalOffset = 64;        // bytes: fp64[4]
 constexpr int kRrtHeadOffset = 128;       // bytes: int32[X*Y*Z]
 
