@@ -593,6 +593,71 @@ int naruto_icp_step(const double* sums, uint64_t n_source, NARUTO_HOST const dou
                     double relative_rmse, double* state, void* stream);
 int naruto_debug_icp_solve(NARUTO_HOST const double* sums, NARUTO_HOST const double* origin, NARUTO_HOST double* dT, NARUTO_HOST int32_t* status);
 
+/* Depth odometry: the relative motion T (current camera to previous camera, est[i] = est[i-1] @ T) between two consecutive depth frames by
+ * coarse-to-fine projective point-to-plane ICP, a motion prior for the tracker that needs no field (nothing like it is in the reference
+ * tree: PARITY UNPINNED; the contract is restated in naruto_amd/odometry.py).  Camera convention: pixel (u, v) has direction
+ * ((u-cx)/fx, -(v-cy)/fy, -1), depth is measured along -z; a depth that is not a finite positive number is missing.  Everything runs on the
+ * caller's stream in the caller's buffers; nothing synchronises, allocates, reads back or uses atomics; results are bitwise reproducible.
+ *
+ * NarutoOdomDesc (HOST): the frame H x W and its intrinsics, `levels` pyramid levels (1 .. NARUTO_ODOM_MAX_LEVELS; level 0 is the frame),
+ *   iters[k] the iteration cap of the k-th level FROM THE COARSEST (level levels-1-k), max_dist (association), jump (normals), band (pyramid).
+ *   Level l+1 has floor(h/2) x floor(w/2) pixels, f/2 and c' = (c + 0.5)/2 - 0.5 (float32, level by level).
+ * maps block: DEVICE float32, naruto_odom_maps_bytes; per level l, at 7 x (the pixels of the levels before it) floats:
+ *   depth [h,w] | vertex [h,w,3] | normal [h,w,3].  depth: level 0 is the frame with missing depths as 0; a pixel of level l+1 is the mean of its
+ *   2 x 2 block's valid depths d with d - m <= band, m the block's smallest valid depth, summed in the order (0,0), (0,1), (1,0), (1,1)
+ *   (row, column), 0 when none is valid; an odd last row / column is not read.  vertex = depth * direction ((0,0,0) = missing).  normal =
+ *   the normalised cross product of V(u+1,v) - V(u,v) and V(u,v+1) - V(u,v) when all three are valid, both differences have |dz| < jump
+ *   and the length is positive, else (0,0,0); the last row and column have none.  float32, every operation rounded (no contraction).
+ * state block: DEVICE float64 [NARUTO_ODOM_STATE_DOUBLES]: [0..15] T row-major [4,4]; then NARUTO_ODOM_LEVEL_WORDS per level l at
+ *   16 + 8 l: done (0 / 1), status (NARUTO_ICP_*: RUNNING until done), updates applied, the last evaluation's inlier count and rmse,
+ *   |omega| and |t| of the last update, 0.  naruto_odom_state_init writes it: T = init->T (a HOST struct, like the desc) when init is given, else
+ *   inv(est[i-2]) @ est[i-1] (the last motion once more; est as in the pose chain) when est is given, const_speed != 0 and i > 1, else the
+ *   identity; the level words 0.
+ * naruto_odom_accumulate at `level`, per pixel of the CURRENT frame's vertex map, in fp64 without contraction: q = T p as
+ *   ((r0*x + r1*y) + r2*z) + t; rejected when -q.z <= 1e-6; u = floor(((fx*q.x)/(-q.z) + cx) + 0.5), v = floor(((-(fy*q.y))/(-q.z) + cy) + 0.5),
+ *   rejected outside the image, where the PREVIOUS frame's normal n is missing, or when |q - V_prev|^2 > max_dist^2.  r = n . (q - V_prev),
+ *   J = [q x n, n] (left perturbation T <- exp(xi) T, xi = (omega, t)).  sums: DEVICE float64 [NARUTO_ODOM_SUMS] = the 21 upper entries of
+ *   J^T J (row-major), the 6 of J^T r, sum r^2, the count; thread t of workgroup b adds pixels b*2048 + t + 256 k, k = 0..7 in turn, 256
+ *   partial vectors fold by halves in LDS, a second launch folds the workgroups' vectors the same way.  workspace:
+ *   naruto_odom_workspace_bytes.  rows (DEVICE float64 [pixels of the level, 2], or NULL): the associated previous pixel (-1 = rejected) and r.
+ * naruto_odom_step (one thread): inliers and rmse into the state; DEGENERATE (T unchanged, level done) when the count is below 6 or a
+ *   pivot of the Cholesky factorisation of J^T J is <= 1e-12 x its largest diagonal entry; else xi = -(J^T J)^-1 J^T r, T <- exp(xi) T
+ *   (the se(3) exponential, Rodrigues), updates += 1, and the level is done CONVERGED when |omega| < 1e-6 and |t| < 1e-6, or
+ *   MAX_ITERATION when the updates reached the level's cap.  Accumulate and step launches of a level that is done return at once and
+ *   write nothing, so an estimate is a fixed sequence of launches: for each level from the coarsest, cap x (accumulate, step).
+ * naruto_pose_predict_relative: est[i] = est[i-1] @ T (fp64 from the float32 matrix, rounded once; state_T = 16 DEVICE doubles, the head of
+ *   a state block); pose6_out [6] = naruto_pose_log of est[i] as stored, exactly as naruto_pose_predict ends.  1 <= i < num_frames.
+ * naruto_debug_odom_solve is the solver on the host (a HOST struct, nothing launched): sums [29] -> xi [6], dT = exp(xi) [16],
+ *   status = NARUTO_ICP_RUNNING or NARUTO_ICP_DEGENERATE (xi = 0, dT = identity). */
+#define NARUTO_ODOM_SUMS 29
+#define NARUTO_ODOM_MAX_LEVELS 4
+#define NARUTO_ODOM_LEVEL_WORDS 8
+#define NARUTO_ODOM_STATE_DOUBLES 48
+typedef struct NarutoOdomDesc {
+    uint32_t H, W, levels;
+    uint32_t iters[NARUTO_ODOM_MAX_LEVELS];
+    float fx, fy, cx, cy;
+    float max_dist, jump, band;
+} NarutoOdomDesc;
+typedef struct NarutoOdomInit {    /* HOST: an initial transform, row-major [4,4] */
+    double T[16];
+} NarutoOdomInit;
+typedef struct NarutoOdomSolve {   /* HOST: naruto_debug_odom_solve's input (sums) and outputs */
+    double sums[NARUTO_ODOM_SUMS];
+    double xi[6];
+    double dT[16];
+    int32_t status;
+} NarutoOdomSolve;
+size_t naruto_odom_maps_bytes(const NarutoOdomDesc* desc);
+size_t naruto_odom_workspace_bytes(const NarutoOdomDesc* desc);
+int naruto_odom_frame_maps(const NarutoOdomDesc* desc, const float* depth, float* maps, void* stream);
+int naruto_odom_state_init(const NarutoOdomInit* init, const float* est, uint32_t num_frames, uint32_t i, int32_t const_speed, double* state, void* stream);
+int naruto_odom_accumulate(const NarutoOdomDesc* desc, uint32_t level, const float* maps_prev, const float* maps_cur, const double* state, double* sums,
+                           void* workspace, double* rows, void* stream);
+int naruto_odom_step(const NarutoOdomDesc* desc, uint32_t level, const double* sums, double* state, void* stream);
+int naruto_pose_predict_relative(float* est, uint32_t num_frames, uint32_t i, const double* state_T, float* pose6_out, void* stream);
+int naruto_debug_odom_solve(NarutoOdomSolve* solve);
+
 /* The planner's local RRT (reference src/planner/rrt.py and src/planner/rrt_naruto.py: class RRTNaruto, the
  * local_planner_method of every shipped config), on the volumes of naruto_map_volumes.  Unit: voxel.
  *

@@ -32,6 +32,7 @@
 #include "naruto_frame.hip"
 #include "naruto_posechain.hip"
 #include "naruto_icp.hip"
+#include "naruto_odom.hip"
 #include "naruto_view.hip"
 
 using namespace naruto;
@@ -2433,6 +2434,113 @@ int naruto_icp_step(const double* sums, uint64_t n_source, const double* origin,
     return check_launch("icp_step");
 }
 
+// ---- depth odometry (naruto_odom.hip) -----------------------------------------------------------------------------------
+namespace {
+// the pyramid of a desc: sizes, intrinsics (float32, level by level), where each level's maps start; false when the desc is refused
+bool odom_geom(const NarutoOdomDesc* d, const char* who, OdomGeom* g) {
+    if (d == nullptr) { fail(NARUTO_ERR_INVALID, "%s: NULL desc", who); return false; }
+    if (d->H == 0u || d->W == 0u || d->H > 16384u || d->W > 16384u || (uint64_t)d->H * d->W > (1ull << 27)) {
+        fail(NARUTO_ERR_INVALID, "%s: a frame of %u x %u pixels", who, d->H, d->W);
+        return false;
+    }
+    if (d->levels == 0u || d->levels > (uint32_t)kOdomMaxLevels) { fail(NARUTO_ERR_INVALID, "%s: %u levels (1 .. %d)", who, d->levels, kOdomMaxLevels); return false; }
+    if (!(d->fx > 0.0f) || !(d->fy > 0.0f) || !std::isfinite(d->fx) || !std::isfinite(d->fy) || !std::isfinite(d->cx) || !std::isfinite(d->cy)) {
+        fail(NARUTO_ERR_INVALID, "%s: intrinsics must be finite and the focal lengths positive", who);
+        return false;
+    }
+    if (!(d->max_dist >= 0.0f) || !(d->jump >= 0.0f) || !(d->band >= 0.0f)) { fail(NARUTO_ERR_INVALID, "%s: a threshold is negative or not a number", who); return false; }
+    *g = OdomGeom{};
+    g->levels = d->levels; g->W = d->W; g->band = d->band; g->jump = d->jump;
+    uint32_t h = d->H, w = d->W, start = 0u, offset = 0u;
+    float fx = d->fx, fy = d->fy, cx = d->cx, cy = d->cy;
+    for (uint32_t l = 0; l < d->levels; ++l) {
+        g->lv[l] = OdomLevel{h, w, start, offset, fx, fy, cx, cy};
+        start += h * w;
+        offset += 7u * h * w;
+        h /= 2u; w /= 2u;
+        fx = fx / 2.0f; fy = fy / 2.0f;
+        cx = (cx + 0.5f) / 2.0f - 0.5f; cy = (cy + 0.5f) / 2.0f - 0.5f;
+    }
+    g->total = start;
+    return true;
+}
+uint32_t odom_parts(const OdomLevel& lv) {
+    const uint32_t n = lv.h * lv.w, per = kOdomThreads * kOdomPer;
+    return n == 0u ? 1u : (n + per - 1u) / per;
+}
+}  // namespace
+
+size_t naruto_odom_maps_bytes(const NarutoOdomDesc* desc) {
+    OdomGeom g;
+    return odom_geom(desc, "odom_maps_bytes", &g) ? (size_t)g.total * 7u * sizeof(float) : 0;
+}
+
+size_t naruto_odom_workspace_bytes(const NarutoOdomDesc* desc) {
+    OdomGeom g;
+    return odom_geom(desc, "odom_workspace_bytes", &g) ? (size_t)odom_parts(g.lv[0]) * kOdomSums * sizeof(double) : 0;
+}
+
+int naruto_odom_frame_maps(const NarutoOdomDesc* desc, const float* depth, float* maps, void* stream) {
+    OdomGeom g;
+    if (!odom_geom(desc, "odom_frame_maps", &g)) return NARUTO_ERR_INVALID;
+    if (depth == nullptr || maps == nullptr) return fail(NARUTO_ERR_INVALID, "odom_frame_maps: NULL argument");
+    hipLaunchKernelGGL(k_odom_maps, dim3((g.total + kOdomThreads - 1u) / kOdomThreads), dim3(kOdomThreads), 0, (hipStream_t)stream, g, depth, maps);
+    return check_launch("odom_maps");
+}
+
+int naruto_odom_state_init(const NarutoOdomInit* T_init, const float* est, uint32_t num_frames, uint32_t i, int32_t const_speed, double* state, void* stream) {
+    if (state == nullptr) return fail(NARUTO_ERR_INVALID, "odom_state_init: NULL state");
+    OdomInit init{};
+    int32_t mode = 2;
+    if (T_init != nullptr) {
+        for (int k = 0; k < 16; ++k) {
+            if (!std::isfinite(T_init->T[k])) return fail(NARUTO_ERR_INVALID, "odom_state_init: the initial transform is not finite");
+            init.T[k] = T_init->T[k];
+        }
+        mode = 0;
+    } else if (est != nullptr && const_speed != 0 && i > 1u) {
+        if (i >= num_frames) return fail(NARUTO_ERR_INVALID, "odom_state_init: frame %u of %u", i, num_frames);
+        mode = 1;
+    }
+    hipLaunchKernelGGL(k_odom_init, dim3(1), dim3(64), 0, (hipStream_t)stream, mode, init, est, i, state);
+    return check_launch("odom_init");
+}
+
+int naruto_odom_accumulate(const NarutoOdomDesc* desc, uint32_t level, const float* maps_prev, const float* maps_cur, const double* state, double* sums,
+                           void* workspace, double* rows, void* stream) {
+    OdomGeom g;
+    if (!odom_geom(desc, "odom_accumulate", &g)) return NARUTO_ERR_INVALID;
+    if (level >= g.levels) return fail(NARUTO_ERR_INVALID, "odom_accumulate: level %u of %u", level, g.levels);
+    if (maps_prev == nullptr || maps_cur == nullptr || state == nullptr || sums == nullptr || workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "odom_accumulate: NULL argument");
+    const OdomLevel lv = g.lv[level];
+    const uint32_t parts = odom_parts(lv);
+    const double md = (double)desc->max_dist;
+    hipLaunchKernelGGL(k_odom_accumulate, dim3(parts), dim3(kOdomThreads), 0, (hipStream_t)stream, lv, (int32_t)level, md * md, maps_prev, maps_cur, state,
+                       reinterpret_cast<double*>(workspace), rows);
+    if (int rc = check_launch("odom_accumulate")) return rc;
+    hipLaunchKernelGGL(k_odom_finish, dim3(1), dim3(kOdomThreads), 0, (hipStream_t)stream, (int32_t)level, state, parts,
+                       reinterpret_cast<const double*>(workspace), sums);
+    return check_launch("odom_finish");
+}
+
+int naruto_odom_step(const NarutoOdomDesc* desc, uint32_t level, const double* sums, double* state, void* stream) {
+    OdomGeom g;
+    if (!odom_geom(desc, "odom_step", &g)) return NARUTO_ERR_INVALID;
+    if (level >= g.levels) return fail(NARUTO_ERR_INVALID, "odom_step: level %u of %u", level, g.levels);
+    if (sums == nullptr || state == nullptr) return fail(NARUTO_ERR_INVALID, "odom_step: NULL argument");
+    const uint32_t cap = desc->iters[g.levels - 1u - level];
+    hipLaunchKernelGGL(k_odom_step, dim3(1), dim3(64), 0, (hipStream_t)stream, (int32_t)level, (double)cap, sums, state);
+    return check_launch("odom_step");
+}
+
+int naruto_pose_predict_relative(float* est, uint32_t num_frames, uint32_t i, const double* state_T, float* pose6_out, void* stream) {
+    if (est == nullptr || state_T == nullptr || pose6_out == nullptr) return fail(NARUTO_ERR_INVALID, "pose_predict_relative: NULL argument");
+    if (i < 1u || i >= num_frames) return fail(NARUTO_ERR_INVALID, "pose_predict_relative: frame %u of %u (the first frame is given, not predicted)", i, num_frames);
+    hipLaunchKernelGGL(k_pose_predict_relative, dim3(1), dim3(64), 0, (hipStream_t)stream, est, i, state_T, pose6_out);
+    return check_launch("pose_predict_relative");
+}
+
 // ---- mesh culling (naruto_cull.hip) -------------------------------------------------------------------------------------
 namespace {
 constexpr uint32_t kCullLargeGrid = 2048;                     // workgroups of the large route: 8 per CU, grid-stride over the chunks
@@ -3176,6 +3284,13 @@ int naruto_debug_icp_solve(const double* sums, const double* origin, double* dT,
     const double zero[3] = {0.0, 0.0, 0.0};
     double ratio;
     *status = icp_solve(sums, origin != nullptr ? origin : zero, dT, ratio);
+    return NARUTO_OK;
+}
+
+int naruto_debug_odom_solve(NarutoOdomSolve* solve) {
+    if (solve == nullptr) return fail(NARUTO_ERR_INVALID, "debug_odom_solve: NULL argument");
+    solve->status = odom_solve(solve->sums, solve->xi);
+    odom_exp(solve->xi, solve->dT);
     return NARUTO_OK;
 }
 

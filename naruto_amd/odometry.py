@@ -1,0 +1,154 @@
+"""Depth odometry on the device (csrc/naruto_odom.hip, csrc/naruto_odom.h; include/naruto_hip.h states the layout of the maps and state
+blocks): the relative motion between two consecutive depth frames by coarse-to-fine projective point-to-plane ICP.  It needs no field, so
+it gives the tracker (``CoSLAMNarutoHIP(track=True, motion_prior="depth_icp")``) a start within its reach when the camera moves in a stop,
+turn, go pattern that constant-speed extrapolation cannot follow.  Nothing like it is in the reference tree: PARITY UNPINNED, the contract
+is this text; tests/odometry_spec.py is its numpy twin.
+
+Convention.  Pixel (u, v) has direction ((u-cx)/fx, -(v-cy)/fy, -1); depth is measured along -z; a depth that is not a finite positive
+number is missing.  The estimate ``T`` maps the current camera's coordinates to the previous camera's: ``c2w[i] = c2w[i-1] @ T``.
+
+Frame maps (one launch per frame, kept: the current frame's maps are the next frame's previous maps), float32, every operation rounded:
+  * a depth pyramid of ``levels`` levels; level l+1 has floor(h/2) x floor(w/2) pixels (an odd last row / column is not read); a pixel is the
+    mean of its 2 x 2 block's valid depths d with d - m <= ``band``, m the block's smallest valid depth, summed in the order (0,0), (0,1),
+    (1,0), (1,1); 0 when none is valid.  Intrinsics per level: f/2 and c' = (c + 0.5)/2 - 0.5;
+  * per level the vertex map V = depth * direction and the normal map: the normalised cross product of V(u+1,v) - V(u,v) and
+    V(u,v+1) - V(u,v), valid when all three vertices are valid, both differences have |dz| < ``jump`` and the length is positive; the last row
+    and column have none.  Missing vertices and normals are (0,0,0).
+
+One iteration at level l with the fp64 transform T of the device state block:
+  * accumulate, per pixel of the current frame: q = T p (fp64 from the float32 vertex, ((r0*x + r1*y) + r2*z) + t); rejected when
+    -q.z <= 1e-6; projected to u = floor(fx*q.x/(-q.z) + cx + 0.5), v likewise with -fy; rejected outside the image, where the previous
+    frame has no normal n, or when |q - V_prev| > ``max_dist``.  Residual r = n . (q - V_prev), row J = [q x n, n]: a left perturbation
+    T <- exp(xi) T, xi = (omega, t).  29 fp64 sums (the 21 upper entries of J^T J, the 6 of J^T r, sum r^2, the count) in an order that
+    depends on the pixel count alone: no atomics, bitwise reproducible;
+  * step, one thread: ``degenerate`` (T unchanged) when the count is below 6 or a Cholesky pivot is <= 1e-12 x the largest diagonal entry;
+    else xi = -(J^T J)^-1 J^T r and T <- exp(xi) T.  A level is finished when |omega| < 1e-6 and |t| < 1e-6 (``converged``) or after its
+    iteration cap (``max_iteration``); ``iters`` lists the caps from the coarsest level to the finest.
+The step writes a per-level done word into the state; launches of a finished level return at once.  A whole estimate is therefore a FIXED
+sequence of launches -- for each level from the coarsest, cap x (accumulate, step) -- with nothing read back: ``estimate_device`` never
+waits for the host.  When every level is degenerate the state's T is still the initial one.
+
+Limits: frame-to-frame only (drift is left to the tracker and global_BA); depth only, no photometric term; the two views must overlap.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from types import SimpleNamespace
+from typing import Dict, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+from .ops import _on_device, _stream
+
+
+def _intrinsics(cam) -> tuple:
+    if isinstance(cam, dict):
+        return tuple(cam[k] for k in ("H", "W", "fx", "fy", "cx", "cy"))
+    cam = tuple(cam)
+    if len(cam) != 6:
+        raise ValueError("DepthOdometryHIP: the camera is a dict with H, W, fx, fy, cx, cy or that tuple")
+    return cam
+
+
+class DepthOdometryHIP:
+    def __init__(self, cam: Union[Dict, Sequence], levels: int = 3, iters: Sequence[int] = (10, 5, 4), max_dist: float = 0.25, jump: float = 0.15,
+                 band: float = 0.1, device="cuda"):
+        H, W, fx, fy, cx, cy = _intrinsics(cam)
+        self.H, self.W, self.levels, self.iters = int(H), int(W), int(levels), tuple(int(k) for k in iters)
+        if not 1 <= self.levels <= _lib.ODOM_MAX_LEVELS or len(self.iters) != self.levels or min(self.iters) < 1:
+            raise ValueError(f"DepthOdometryHIP: levels = {levels} (1 .. {_lib.ODOM_MAX_LEVELS}) needs as many iteration caps >= 1, coarse to fine; got {iters!r}")
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.desc = _lib.NarutoOdomDesc(H=self.H, W=self.W, levels=self.levels, iters=(C.c_uint32 * _lib.ODOM_MAX_LEVELS)(*self.iters),
+                                        fx=float(fx), fy=float(fy), cx=float(cx), cy=float(cy), max_dist=float(max_dist), jump=float(jump), band=float(band))
+        lib = _lib.load()
+        self.maps_bytes = int(lib.naruto_odom_maps_bytes(C.byref(self.desc)))
+        ws = int(lib.naruto_odom_workspace_bytes(C.byref(self.desc)))
+        if self.maps_bytes == 0 or ws == 0:
+            raise ValueError("DepthOdometryHIP: " + lib.naruto_last_error().decode("utf-8", "replace"))
+        self.workspace = _lib.workspace(ws, self.device, torch.float64)
+        self.sums = torch.zeros(_lib.ODOM_SUMS, dtype=torch.float64, device=self.device)
+        self.state = torch.zeros(_lib.ODOM_STATE_DOUBLES, dtype=torch.float64, device=self.device)
+        # (h, w, offset in floats) of every level inside a maps block
+        self.level_shapes, off, h, w = [], 0, self.H, self.W
+        for _ in range(self.levels):
+            self.level_shapes.append((h, w, off))
+            off, h, w = off + 7 * h * w, h // 2, w // 2
+
+    def new_maps(self) -> torch.Tensor:
+        return torch.empty(self.maps_bytes // 4, dtype=torch.float32, device=self.device)
+
+    def frame_maps(self, depth: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The maps block of the depth frame [H,W] (float32 on the device): one launch."""
+        depth = depth.to(self.device, torch.float32).contiguous()
+        if depth.numel() != self.H * self.W:
+            raise ValueError(f"DepthOdometryHIP: a depth frame of {tuple(depth.shape)}, built for {self.H} x {self.W}")
+        out = self.new_maps() if out is None else out
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() * 4 == self.maps_bytes):
+            raise ValueError("DepthOdometryHIP: out must be a maps block of new_maps()")
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_frame_maps(C.byref(self.desc), depth.data_ptr(), out.data_ptr(), _stream()), "naruto_odom_frame_maps")
+        return out
+
+    def level_views(self, maps: torch.Tensor, level: int):
+        """(depth [h,w], vertex [h,w,3], normal [h,w,3]): views into a maps block."""
+        h, w, off = self.level_shapes[level]
+        n = h * w
+        return maps[off:off + n].view(h, w), maps[off + n:off + 4 * n].view(h, w, 3), maps[off + 4 * n:off + 7 * n].view(h, w, 3)
+
+    def init_state(self, init=None, est: Optional[torch.Tensor] = None, i: int = 0, const_speed: bool = False, state: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The state block with T = ``init`` ([4,4], host), else the last motion inv(est[i-2]) @ est[i-1] read ON THE DEVICE when ``est`` is
+        given with ``const_speed`` and i > 1, else the identity: one launch."""
+        state = self.state if state is None else state
+        T = None
+        if init is not None:
+            T = C.byref(_lib.NarutoOdomInit(T=(C.c_double * 16)(*np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init,
+                                                                             dtype=np.float64).reshape(16))))
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_state_init(T, None if est is None else est.data_ptr(), 0 if est is None else est.shape[0], int(i),
+                                                     1 if const_speed else 0, state.data_ptr(), _stream()), "naruto_odom_state_init")
+        return state
+
+    def accumulate(self, level: int, maps_prev: torch.Tensor, maps_cur: torch.Tensor, state: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None):
+        state = self.state if state is None else state
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_accumulate(C.byref(self.desc), int(level), maps_prev.data_ptr(), maps_cur.data_ptr(), state.data_ptr(),
+                                                     self.sums.data_ptr(), self.workspace.data_ptr(), None if rows is None else rows.data_ptr(), _stream()),
+                  "naruto_odom_accumulate")
+        return self.sums
+
+    def step(self, level: int, state: Optional[torch.Tensor] = None) -> None:
+        state = self.state if state is None else state
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_step(C.byref(self.desc), int(level), self.sums.data_ptr(), state.data_ptr(), _stream()), "naruto_odom_step")
+
+    def run_levels(self, maps_prev: torch.Tensor, maps_cur: torch.Tensor, state: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The fixed launch sequence over an initialised state: for each level from the coarsest, cap x (accumulate, step)."""
+        state = self.state if state is None else state
+        for k, cap in enumerate(self.iters):
+            level = self.levels - 1 - k
+            for _ in range(cap):
+                self.accumulate(level, maps_prev, maps_cur, state)
+                self.step(level, state)
+        return state
+
+    def estimate_device(self, maps_prev: torch.Tensor, maps_cur: torch.Tensor, init=None) -> torch.Tensor:
+        """Launches only.  Returns the device state block (float64 [48]; its first 16 doubles are T), owned by this object."""
+        return self.run_levels(maps_prev, maps_cur, self.init_state(init))
+
+    def read_state(self, state: Optional[torch.Tensor] = None) -> SimpleNamespace:
+        """The state block on the host (synchronises)."""
+        s = (self.state if state is None else state).cpu().numpy()
+        words = s[16:16 + _lib.ODOM_LEVEL_WORDS * self.levels].reshape(self.levels, _lib.ODOM_LEVEL_WORDS)
+        return SimpleNamespace(transformation=s[:16].reshape(4, 4).copy(), status=[_lib.ICP_STATUS[int(w[1])] for w in words],
+                               iterations=[int(w[2]) for w in words], inliers=[int(w[3]) for w in words], rmse=[float(w[4]) for w in words])
+
+    def estimate(self, depth_prev: torch.Tensor, depth_cur: torch.Tensor, init=None) -> SimpleNamespace:
+        """``.transformation`` float64 [4,4] (current camera to previous camera), and per level (index = pyramid level, 0 the finest)
+        ``.status``, ``.iterations``, ``.inliers``, ``.rmse``.  This call synchronises."""
+        return self.read_state(self.estimate_device(self.frame_maps(depth_prev), self.frame_maps(depth_cur), init))

@@ -6,6 +6,7 @@ current stream, allocates only the output it returns when none is given, and nev
 
   * ``pose_log(c2w)``                                   [P,4,4] -> (omega, t) [P,6]: ``tracking.matrices_to_pose6`` on the device
   * ``pose_predict(est, i, const_speed, pose6_out)``    ``predict_current_pose`` into ``est[i]`` and the tracker's ``pose_init``
+  * ``pose_predict_relative(est, i, state_T, pose6_out)``   ``est[i] = est[i-1] @ T`` from a depth-odometry state block, and ``pose_init``
   * ``pose_commit(est, rel, i, keyframe_every, c2w)``   the tracked pose into ``est[i]``; ``rel[i]`` for a frame that is no keyframe
   * ``pose_scatter(est, refined, P, keyframe_every, cur_id, optim_cur)``   ``global_BA``'s write-back (coslam.py:401-407)
   * ``pose_resolve(est, rel, n, keyframe_every)``       ``convert_relative_pose``: [n,4,4], every frame relative to its refined keyframe
@@ -55,6 +56,18 @@ def pose_predict(est: torch.Tensor, i: int, const_speed: bool, pose6_out: torch.
     with _on_device(est.device):
         check(_lib.load().naruto_pose_predict(est.data_ptr(), est.shape[0], int(i), 1 if const_speed else 0, pose6_out.data_ptr(), _stream()),
               "naruto_pose_predict")
+
+
+def pose_predict_relative(est: torch.Tensor, i: int, state_T: torch.Tensor, pose6_out: torch.Tensor) -> None:
+    """``est[i]`` <- ``est[i-1] @ T`` with ``T`` the 16 float64 at the head of ``state_T`` (a ``DepthOdometryHIP`` state block on the device);
+    ``pose6_out`` [6] <- its (omega, t), exactly as ``pose_predict`` ends."""
+    est = _mats(est, "est")
+    _vec6(pose6_out, "pose6_out", 1)
+    if not (isinstance(state_T, torch.Tensor) and state_T.is_cuda and state_T.dtype == torch.float64 and state_T.is_contiguous() and state_T.numel() >= 16):
+        raise ValueError("pose_chain: state_T must be a contiguous float64 tensor of at least 16 elements on the GPU")
+    with _on_device(est.device):
+        check(_lib.load().naruto_pose_predict_relative(est.data_ptr(), est.shape[0], int(i), state_T.data_ptr(), pose6_out.data_ptr(), _stream()),
+              "naruto_pose_predict_relative")
 
 
 def pose_commit(est: torch.Tensor, rel: torch.Tensor, i: int, keyframe_every: int, c2w: torch.Tensor) -> None:

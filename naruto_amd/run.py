@@ -146,6 +146,8 @@ def parse_args(argv=None):
     parser.add_argument("--no_active_ray", action="store_true", help="switch the active ray sampler off")
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--track", action="store_true", help="estimate the camera poses during the run (tracking + pose refinement); adds the ATE to results.txt")
+    parser.add_argument("--motion_prior", type=str, default=None, choices=["const_speed", "depth_icp"],
+                        help="with --track: the tracker's initial pose from constant-speed extrapolation (default) or from frame-to-frame depth odometry")
     parser.add_argument("--dataset", type=str, default="NARUTO", choices=["Replica", "MP3D", "NARUTO"], help="the planner's collision rule")
     parser.add_argument("--eval_views", type=int, default=None, metavar="K", help="after the run, render every K-th pose from the map and score it against the simulator (psnr, ssim, depth_l1(cm) in results.txt)")
     parser.add_argument("--planner", type=str, nargs="*", default=[], metavar="KEY=VALUE", help="planner settings over naruto_amd.planner.DEFAULTS")
@@ -176,7 +178,8 @@ def main(argv=None) -> Dict:
     traj = load_replica_traj(args.traj) if args.traj else None
     np.random.seed(args.seed)                      # the planner's RRT draws from numpy's generator
     os.makedirs(args.result_dir, exist_ok=True)
-    slam = CoSLAMNarutoHIP(cfg, active_ray=not args.no_active_ray, num_frames=args.num_iter, seed=args.seed, result_dir=args.result_dir, track=args.track)
+    slam = CoSLAMNarutoHIP(cfg, active_ray=not args.no_active_ray, num_frames=args.num_iter, seed=args.seed, result_dir=args.result_dir, track=args.track,
+                           motion_prior=args.motion_prior)
     sim = MeshSimHIP(args.mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=slam.device)
     planner = None
     if traj is None:

@@ -52,6 +52,13 @@ mapped one waits once, for the same 8-byte count as without tracking.  ``resolve
 (refined) keyframe; ``save_ckpt`` writes the raw ``pose`` / ``pose_rel`` as the reference does.  The tracker is captured once, at the end
 of frame 0, and keeps its own random word (derived from ``seed``).  ``track=False`` is the object without any of this, launch for launch.
 
+MOTION PRIOR (``motion_prior="const_speed"`` | ``"depth_icp"``, with ``track=True`` only).  ``"const_speed"``, the default, is step 1 as
+written.  With ``"depth_icp"`` the prediction comes from the two depth frames themselves (``naruto_amd.odometry.DepthOdometryHIP``): frame
+0 makes its maps; every frame i > 0 makes its maps, runs the frame-to-frame estimate from the last relative motion
+``inv(est[i-2]) @ est[i-1]`` (``tracking.const_speed`` and i > 1; the identity otherwise), and ``pose_predict_relative`` stands in the place
+of ``pose_predict``: ``est[i] = est[i-1] @ T``.  When every level is degenerate T is still that initial motion -- decided on the device;
+the estimate is a fixed sequence of launches and adds no wait for the host.  ``odometry.state`` keeps the last estimate's state block.
+
 A config with ``tracking.disable: False`` and no ``track=True`` is refused (``NotImplementedError``) before the library is touched:
 tracking is switched on by the keyword, whatever ``tracking.disable`` says.  Out of scope: ``tracking.iter_point > 0`` (``tracking_pc``),
 other ``training.rot_rep`` (both refused by ``tracking.tracking_settings``), data-parallel pose refinement.
@@ -71,7 +78,7 @@ from .capture import no_collection
 from .field import _map_lattice, get_map_volumes
 from .keyframe_store import KeyFrameStoreHIP, frame_ingest
 from .mesh import extract_mesh
-from .pose_chain import pose_commit, pose_log, pose_predict, pose_resolve, pose_scatter
+from .pose_chain import pose_commit, pose_log, pose_predict, pose_predict_relative, pose_resolve, pose_scatter
 from .trainer import MappingTrainer
 
 
@@ -130,15 +137,21 @@ class DevicePoses:
 class CoSLAMNarutoHIP:
     def __init__(self, config: Dict, voxel_size: float = 0.1, active_ray: Optional[bool] = None, act_ray_num_uncert_sample: int = 500,
                  act_ray_oversample_mul: int = 4, num_frames: int = 2000, seed: Optional[int] = 0, result_dir: Optional[str] = None, device="cuda",
-                 track: bool = False):
+                 track: bool = False, motion_prior: Optional[str] = None):
         """``config``: a Co-SLAM config (``naruto_amd.config.load_config``); it is kept and, as in the reference's ``override_config``,
         ``mapping.active_ray`` is overwritten when ``active_ray`` is given.  ``num_frames``: the length of the run (sizes the keyframe store
         and the pose tensor).  ``seed``: keys the keyframe store's draws and, through ``torch.manual_seed`` (None: left alone), the
         network's initial values and the trainer's in-kernel random streams.  ``result_dir``: meshes and checkpoints go under
         ``<result_dir>/coslam`` (None: ``save_*`` need an explicit directory).  ``track``: estimate the camera poses during the run
-        (module docstring) with ``tracking_settings(config)``, whatever ``tracking.disable`` says."""
+        (module docstring) with ``tracking_settings(config)``, whatever ``tracking.disable`` says.  ``motion_prior``: where a tracked
+        frame's initial pose comes from, ``"const_speed"`` (the default) or ``"depth_icp"`` (module docstring); needs ``track=True``."""
         tk = config.get("tracking") or {}
         self.track = bool(track)
+        if motion_prior is not None and motion_prior not in ("const_speed", "depth_icp"):
+            raise ValueError(f"CoSLAMNarutoHIP: motion_prior = {motion_prior!r}; 'const_speed' or 'depth_icp'")
+        if motion_prior is not None and not self.track:
+            raise ValueError("CoSLAMNarutoHIP: motion_prior is the tracker's initial pose and needs track=True")
+        self.motion_prior = motion_prior or "const_speed"
         if not self.track and not bool(tk.get("disable", True)):
             raise NotImplementedError("CoSLAMNarutoHIP: tracking.disable: False asks for camera tracking and pose refinement during the run; they are "
                                       "switched on by the keyword track=True (naruto_amd.tracking.TrackerHIP, FusedBA(optimize_poses=True)), not by the config")
@@ -181,6 +194,11 @@ class CoSLAMNarutoHIP:
             from .tracking import TrackerHIP
             # the tracker's own random word: the seed's, moved off the keyframe store's and the trainer's streams
             self.tracker = TrackerHIP(self.model, config, self.H, self.W, device=self.device, rng_seed=(int(seed or 0) * 0x9E3779B1 + 0x7F4A7C15) % (1 << 62))
+        self.odometry = None
+        if self.motion_prior == "depth_icp":
+            from .odometry import DepthOdometryHIP
+            self.odometry = DepthOdometryHIP((self.H, self.W, self.fx, self.fy, self.cx, self.cy), device=self.device)
+            self._odom_maps = [self.odometry.new_maps(), self.odometry.new_maps()]          # frame i's maps live in [i & 1]
         self.cached_uncert = None
         self.filter_depth = bool(mp.get("filter_depth", False))
         self._n_valid = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -232,7 +250,14 @@ class CoSLAMNarutoHIP:
         if (i - 1) not in est or (i % every != 0 and (i // every) * every not in est):
             raise KeyError(f"CoSLAMNarutoHIP: frame {i} is tracked from frame {i - 1} (and stored relative to keyframe {(i // every) * every}); "
                            "step the frames in order")
-        pose_predict(est.tensor, i, bool(self.tracking["const_speed"]), self.tracker.pose_init)
+        if self.odometry is not None:
+            od, cur = self.odometry, self._odom_maps[i & 1]
+            od.frame_maps(depth, out=cur)
+            state = od.init_state(est=est.tensor, i=i, const_speed=bool(self.tracking["const_speed"]))
+            od.run_levels(self._odom_maps[(i - 1) & 1], cur, state)
+            pose_predict_relative(est.tensor, i, state, self.tracker.pose_init)
+        else:
+            pose_predict(est.tensor, i, bool(self.tracking["const_speed"]), self.tracker.pose_init)
         tracked = self.tracker.track_device(self.rays_d, color, depth)
         pose_commit(est.tensor, rel.tensor, i, every, tracked)
         est.mark(i)
@@ -274,6 +299,8 @@ class CoSLAMNarutoHIP:
                 vols = self._volumes()
                 if self.track:
                     self._capture_tracker(color, depth)
+                if self.odometry is not None:
+                    self.odometry.frame_maps(depth, out=self._odom_maps[0])
             else:
                 every = int(mp["keyframe_every"])
                 if self.track:

@@ -1,0 +1,144 @@
+"""Time the depth odometry on the device (naruto_amd.odometry.DepthOdometryHIP, csrc/naruto_odom.hip) at office_0 size: 1200 x 680,
+f = 600, frames rendered by MeshSimHIP from the room-plus-sphere mesh of tools/time_tracked_run.py (n_lat = 632: 1 595 181 faces).
+Recorded:
+
+  * the frame maps of one frame (one launch);
+  * one iteration per level: state init + accumulate (two launches) + step, from the identity, for a 3 cm / 2 degree motion;
+  * a whole estimate (the fixed sequence of 1 + 3 x (10 + 5 + 4) launches), and the maps + estimate + pose_predict_relative a tracked frame
+    adds, next to the tracked frame's device time recorded in profiles/time_tracked_run.json;
+  * the basin at this size: the largest step of a fixed ladder of yaws about the camera's y axis, and of translations along
+    (0.6, 0.3, -0.74), that one estimate from the identity recovers to 5 mm / 0.25 degrees.
+
+    python tools/time_odometry.py [--out profiles/time_odometry.json] [--n-lat 632]
+
+Host wall clock ending in a device synchronise, every shape warmed up first, the MEDIAN of --repeat.  Nothing is asserted."""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from naruto_amd import pose_chain as PC  # noqa: E402
+from naruto_amd import synthetic as syn  # noqa: E402
+from naruto_amd.odometry import DepthOdometryHIP  # noqa: E402
+from naruto_amd.planner import compute_camera_pose  # noqa: E402
+from naruto_amd.simulator import MeshSimHIP  # noqa: E402
+
+YAWS_DEG = (2.0, 5.0, 10.0, 15.0, 20.0, 30.0, 40.0, 60.0)
+STEPS_M = (0.03, 0.1, 0.2, 0.4, 0.8, 1.2)
+ALONG = (0.6, 0.3, -0.74)
+BOUND_M, BOUND_DEG = 5e-3, 0.25
+
+
+def timed(fn, repeat, warm=1):
+    for _ in range(warm):
+        fn()
+    times = []
+    for _ in range(repeat):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t)
+    return statistics.median(times) * 1e3
+
+
+def rotation(axis, theta):
+    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.eye(3) + math.sin(theta) * K + (1.0 - math.cos(theta)) * (K @ K)
+
+
+def motion(axis, deg, dist):
+    T = np.eye(4)
+    T[:3, :3] = rotation(axis, math.radians(deg))
+    T[:3, 3] = dist * np.asarray(ALONG) / np.linalg.norm(ALONG)
+    return T
+
+
+def error(T, ref):
+    R = T[:3, :3].T @ ref[:3, :3]
+    return float(np.linalg.norm(T[:3, 3] - ref[:3, 3])), math.degrees(math.acos(min(1.0, max(-1.0, (np.trace(R) - 1.0) / 2.0))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--repeat", type=int, default=9)
+    ap.add_argument("--n-lat", type=int, default=632)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/time_odometry.py measures on the GPU; there is none here")
+    dev = torch.device("cuda:0")
+    cam = {"H": 680, "W": 1200, "fx": 600.0, "fy": 600.0, "cx": 599.5, "cy": 339.5}
+    mesh = syn.room_sphere_mesh(n_lat=args.n_lat, n_lon=2 * args.n_lat)
+    sim = MeshSimHIP(mesh, cam, device=dev)
+    base = np.eye(4)
+    pos, at = np.array([2.0, 4.0, 1.2]), np.array([3.0, 2.5, 1.4])
+    base[:3, :3], base[:3, 3] = compute_camera_pose(pos, at), pos
+    rels = [motion((0, 1, 0), 2.0, 0.03)] + [motion((0, 1, 0), a, 0.0) for a in YAWS_DEG] + [motion((0, 1, 0), 0.0, d) for d in STEPS_M]
+    poses = torch.from_numpy(np.stack([base] + [base @ r for r in rels]).astype(np.float32))
+    depth = torch.stack([sim.simulate(p.numpy(), no_print=True)[1].to(dev) for p in poses])
+    # the relative motions as the float32 poses carry them
+    gt = poses.double().numpy()
+    rels = [np.linalg.inv(gt[0]) @ gt[k] for k in range(1, len(gt))]
+    od = DepthOdometryHIP(cam, device=dev)
+    res = {"image": [cam["W"], cam["H"]], "focal": cam["fx"], "faces": len(mesh[1]), "levels": od.levels, "iters_coarse_to_fine": list(od.iters),
+           "valid_depth_fraction": float((depth[0] > 0).float().mean())}
+    maps_prev, maps_cur = od.frame_maps(depth[0]), od.new_maps()
+    res["frame_maps_ms"] = timed(lambda: od.frame_maps(depth[1], out=maps_cur), args.repeat)
+    for level in range(od.levels):
+        def one(level=level):
+            od.init_state(None)
+            od.accumulate(level, maps_prev, maps_cur)
+            od.step(level)
+        res[f"level_{level}_init_accumulate_step_ms"] = timed(one, args.repeat)
+    res["state_init_ms"] = timed(lambda: od.init_state(None), args.repeat)
+    res["estimate_ms"] = timed(lambda: od.estimate_device(maps_prev, maps_cur), args.repeat)
+    est = torch.zeros(4, 4, 4, device=dev)
+    est[0] = poses[0].to(dev)
+    pose6 = torch.zeros(6, device=dev)
+
+    def added():
+        od.frame_maps(depth[1], out=maps_cur)
+        PC.pose_predict_relative(est, 1, od.estimate_device(maps_prev, maps_cur), pose6)
+    res["maps_estimate_predict_ms"] = timed(added, args.repeat)
+    got = od.read_state()
+    dm, dd = error(got.transformation, rels[0])
+    res["estimate_3cm_2deg"] = {"error_mm": dm * 1e3, "error_deg": dd, "status": got.status, "iterations": got.iterations, "inliers": got.inliers, "rmse": got.rmse}
+    tracked = os.path.join(ROOT, "profiles", "time_tracked_run.json")
+    if os.path.exists(tracked):
+        with open(tracked) as fh:
+            res["tracked_frame_device_chain_ms_device_from_time_tracked_run"] = json.load(fh)["office_0_size"]["frames"]["tracked_frame_device_chain_ms_device"]
+    basin = {"bound": {"mm": BOUND_M * 1e3, "deg": BOUND_DEG}, "yaw_deg": [], "translation_m": []}
+    for name, ladder, first in (("yaw_deg", YAWS_DEG, 2), ("translation_m", STEPS_M, 2 + len(YAWS_DEG))):
+        largest = None
+        for k, s in enumerate(ladder):
+            out = od.estimate(depth[0], depth[first + k])
+            dm, dd = error(out.transformation, rels[first + k - 1])
+            ok = dm <= BOUND_M and dd <= BOUND_DEG
+            basin[name].append({"step": s, "error_mm": dm * 1e3, "error_deg": dd, "recovered": ok, "status": out.status})
+            if all(e["recovered"] for e in basin[name]):               # the basin ends at the first step that is lost
+                largest = s
+        basin[name + "_largest_recovered"] = largest
+    res["basin"] = basin
+    print(json.dumps(res, indent=1))
+    if args.out:
+        doc = {"device": torch.cuda.get_device_name(0),
+               "what": "tools/time_odometry.py: host wall clock ending in a device synchronise, warmed up, median of --repeat; milliseconds", "office_0_size": res}
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(doc, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()

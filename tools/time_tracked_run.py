@@ -11,7 +11,11 @@ the mapping schedule of tools/time_run.py, tracking with replica_coslam.yaml's s
     the others, the trajectory error of the estimate and the motion per step the planner commands (against what one tracking call
     can cover: iter x lr).
 
-    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632]
+    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632] [--motion-prior depth_icp]
+
+With --motion-prior only the run is made, with CoSLAMNarutoHIP(motion_prior=...), and it is MERGED into the output file as
+office_0_size.run_motion_prior_<name>, beside the run of the default prior (--no-const-speed: tracking.const_speed off, key suffix
+_const_speed_off).
 
 Host timers (time.perf_counter), medians over --repeat.  Nothing is asserted.  There is NO reference number: the reference's loop needs
 Habitat-Sim and tiny-cuda-nn, neither of which is on this stack."""
@@ -38,9 +42,11 @@ from naruto_amd.simulator import MeshSimHIP  # noqa: E402
 from naruto_amd.slam import CoSLAMNarutoHIP  # noqa: E402
 
 
-def config():
+def config(const_speed=True):
     cfg = TR.config()
     cfg["tracking"] = dict(tracking.TRACKING_DEFAULTS, disable=False)
+    if not const_speed:
+        cfg["tracking"]["const_speed"] = False
     return cfg
 
 
@@ -107,9 +113,9 @@ def frames(args, dev, mesh):
 
 
 def whole_run(args, dev, mesh):
-    cfg = config()
+    cfg = config(not args.no_const_speed)
     np.random.seed(args.seed)
-    slam = CoSLAMNarutoHIP(cfg, active_ray=True, num_frames=args.steps, seed=args.seed, device=dev, track=True)
+    slam = CoSLAMNarutoHIP(cfg, active_ray=True, num_frames=args.steps, seed=args.seed, device=dev, track=True, motion_prior=args.motion_prior)
     sim = MeshSimHIP(mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=dev)
     planner = NarutoPlannerHIP(dataset="NARUTO", device=dev)
     planner.update_sim(sim)
@@ -159,12 +165,25 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--n-lat", type=int, default=632)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--motion-prior", default=None, choices=["const_speed", "depth_icp"], help="only the run, with this prior, merged into --out")
+    ap.add_argument("--no-const-speed", action="store_true", help="with --motion-prior: tracking.const_speed off (depth_icp then starts from the identity)")
     ap.add_argument("--small-test", default=None, help="JSON object merged into the document (figures of tests/test_gpu_tracked_run.py)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     mesh = syn.room_sphere_mesh(n_lat=args.n_lat, n_lon=2 * args.n_lat)
     res = {"image": [1200, 680], "focal": 600.0, "faces": len(mesh[1]), "active_ray": True,
            "reference": "none: the reference's loop needs Habitat-Sim and tiny-cuda-nn, which are not on this stack"}
+    if args.motion_prior is not None:
+        run = whole_run(args, dev, mesh)
+        print(json.dumps(run, indent=1), flush=True)
+        if args.out:
+            with open(args.out) as fh:
+                doc = json.load(fh)
+            doc["office_0_size"]["run_motion_prior_" + args.motion_prior + ("_const_speed_off" if args.no_const_speed else "")] = run
+            with open(args.out, "w") as fh:
+                json.dump(doc, fh, indent=1)
+                fh.write("\n")
+        return
     res["frames"] = frames(args, dev, mesh)
     print(json.dumps(res["frames"], indent=1), flush=True)
     res["run"] = whole_run(args, dev, mesh)
