@@ -658,6 +658,43 @@ int naruto_odom_step(const NarutoOdomDesc* desc, uint32_t level, const double* s
 int naruto_pose_predict_relative(float* est, uint32_t num_frames, uint32_t i, const double* state_T, float* pose6_out, void* stream);
 int naruto_debug_odom_solve(NarutoOdomSolve* solve);
 
+/* RGB-D odometry: the depth odometry above with a photometric row per pixel beside the geometric one, which pins the motions a plane
+ * leaves free (nothing like it is in the reference tree: PARITY UNPINNED; the contract is restated in naruto_amd/odometry.py and
+ * tests/odometry_rgbd_spec.py is its numpy twin).  The camera convention, T, the desc, the state block, the level schedule, the done
+ * words, naruto_odom_state_init and naruto_odom_step are the depth odometry's.  The intensity is assumed constant between the frames.
+ *
+ * intensity maps, float32, every operation rounded (no contraction): level 0 I = (0.299 r + 0.587 g) + 0.114 b of the colour frame
+ *   [H,W,3] (float32, 0 .. 1); level l+1 (((a + b) + c) + d) * 0.25 over the 2 x 2 block in the order (0,0), (0,1), (1,0), (1,1) (row,
+ *   column), an odd last row / column not read; gx(u,v) = (I(u+1,v) - I(u-1,v)) * 0.5 for 1 <= u <= w-2, else 0; gy the same in v.
+ * RGB-D maps block: DEVICE float32, naruto_odom_rgbd_maps_bytes: the depth maps block, the layout and bits naruto_odom_frame_maps
+ *   writes (7 x the pixels of all levels), then the intensity block: per level l, at 3 x (the pixels of the levels before it) floats,
+ *   I [h,w] | gx [h,w] | gy [h,w].  naruto_odom_rgbd_frame_maps writes both in one launch.
+ * naruto_odom_rgbd_accumulate at `level`, per pixel i of the CURRENT frame, fp64 without contraction, with q = T p, zc = -q.z > 1e-6,
+ *   uc = (fx*q.x)/zc + cx, vc = (-(fy*q.y))/zc + cy and j the nearest pixel (floor(uc + 0.5), floor(vc + 0.5)) as naruto_odom_accumulate:
+ *   1. the geometric row, exactly naruto_odom_accumulate's;
+ *   2. the photometric row, only when photo->weight > 0: u0 = floor(uc), v0 = floor(vc); rejected unless 1 <= u0, u0 + 1 <= w - 2,
+ *      1 <= v0, v0 + 1 <= h - 2, V_prev[j].z < 0 and |q - V_prev[j]|^2 <= max_dist^2 (an occlusion test; no normal is needed).  With
+ *      a = uc - u0, b = vc - v0 a map m is sampled as top = m00 + a (m10 - m00), bot = m01 + a (m11 - m01), top + b (bot - top), m10 at
+ *      (u0+1, v0).  r_I = I_prev(uc, vc) - I_cur[i]; rejected unless |r_I| <= photo->max_diff and the sampled gx, gy are finite (a NaN
+ *      fails the comparison).  With w = photo->weight (metres per unit of intensity), A = gx*fx, B = gy*fy:
+ *      g = (w*(A/zc), w*(-(B/zc)), w*((A*q.x - B*q.y)/(zc*zc))), r = w*r_I, J = [q x g, g]: the geometric row's form with g for n.
+ *   sums: DEVICE float64 [NARUTO_ODOM_RGBD_SUMS]: [0..28] as NARUTO_ODOM_SUMS over the rows of BOTH kinds (the count [28] too), [29] the
+ *   geometric rows, [30] the photometric rows, [31] sum r_I^2 unweighted.  Per pixel the geometric row's terms are added first, then the
+ *   photometric row's; pixels, threads, the fold and the finishing launch in naruto_odom_accumulate's order: no atomics, bitwise
+ *   reproducible.  workspace: naruto_odom_rgbd_workspace_bytes.  rows (DEVICE float64 [pixels of the level, 4], or NULL): the geometric
+ *   j (-1 = rejected), r, the photometric j (-1 = rejected), r_I.  A level that is done: both launches return at once, nothing written.
+ * naruto_odom_step runs unchanged on the first 29 sums: the level words' inliers and rmse then count and mix both kinds of rows. */
+#define NARUTO_ODOM_RGBD_SUMS 32
+typedef struct NarutoOdomPhoto {   /* HOST: the photometric term; weight 0 switches it off */
+    float weight;
+    float max_diff;
+} NarutoOdomPhoto;
+size_t naruto_odom_rgbd_maps_bytes(const NarutoOdomDesc* desc);
+size_t naruto_odom_rgbd_workspace_bytes(const NarutoOdomDesc* desc);
+int naruto_odom_rgbd_frame_maps(const NarutoOdomDesc* desc, const float* depth, const float* color, float* maps, void* stream);
+int naruto_odom_rgbd_accumulate(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* maps_prev, const float* maps_cur,
+                                const double* state, double* sums, void* workspace, double* rows, void* stream);
+
 /* The planner's local RRT (reference src/planner/rrt.py and src/planner/rrt_naruto.py: class RRTNaruto, the
  * local_planner_method of every shipped config), on the volumes of naruto_map_volumes.  Unit: voxel.
  *

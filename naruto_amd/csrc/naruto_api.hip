@@ -2534,6 +2534,45 @@ int naruto_odom_step(const NarutoOdomDesc* desc, uint32_t level, const double* s
     return check_launch("odom_step");
 }
 
+size_t naruto_odom_rgbd_maps_bytes(const NarutoOdomDesc* desc) {
+    OdomGeom g;
+    return odom_geom(desc, "odom_rgbd_maps_bytes", &g) ? (size_t)g.total * 10u * sizeof(float) : 0;
+}
+
+size_t naruto_odom_rgbd_workspace_bytes(const NarutoOdomDesc* desc) {
+    OdomGeom g;
+    return odom_geom(desc, "odom_rgbd_workspace_bytes", &g) ? (size_t)odom_parts(g.lv[0]) * kOdomRgbdSums * sizeof(double) : 0;
+}
+
+int naruto_odom_rgbd_frame_maps(const NarutoOdomDesc* desc, const float* depth, const float* color, float* maps, void* stream) {
+    OdomGeom g;
+    if (!odom_geom(desc, "odom_rgbd_frame_maps", &g)) return NARUTO_ERR_INVALID;
+    if (depth == nullptr || color == nullptr || maps == nullptr) return fail(NARUTO_ERR_INVALID, "odom_rgbd_frame_maps: NULL argument");
+    hipLaunchKernelGGL(k_odom_rgbd_maps, dim3((g.total + kOdomThreads - 1u) / kOdomThreads), dim3(kOdomThreads), 0, (hipStream_t)stream, g, depth, color, maps);
+    return check_launch("odom_rgbd_maps");
+}
+
+int naruto_odom_rgbd_accumulate(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* maps_prev, const float* maps_cur,
+                                const double* state, double* sums, void* workspace, double* rows, void* stream) {
+    OdomGeom g;
+    if (!odom_geom(desc, "odom_rgbd_accumulate", &g)) return NARUTO_ERR_INVALID;
+    if (photo == nullptr) return fail(NARUTO_ERR_INVALID, "odom_rgbd_accumulate: NULL photo");
+    if (!(photo->weight >= 0.0f) || !std::isfinite(photo->weight) || !(photo->max_diff >= 0.0f))
+        return fail(NARUTO_ERR_INVALID, "odom_rgbd_accumulate: the photometric weight must be finite and >= 0, max_diff >= 0");
+    if (level >= g.levels) return fail(NARUTO_ERR_INVALID, "odom_rgbd_accumulate: level %u of %u", level, g.levels);
+    if (maps_prev == nullptr || maps_cur == nullptr || state == nullptr || sums == nullptr || workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "odom_rgbd_accumulate: NULL argument");
+    const OdomLevel lv = g.lv[level];
+    const uint32_t parts = odom_parts(lv), ioff = g.total * 7u + lv.start * 3u;
+    const double md = (double)desc->max_dist;
+    hipLaunchKernelGGL(k_odom_rgbd_accumulate, dim3(parts), dim3(kOdomThreads), 0, (hipStream_t)stream, lv, ioff, (int32_t)level, md * md,
+                       (double)photo->weight, (double)photo->max_diff, maps_prev, maps_cur, state, reinterpret_cast<double*>(workspace), rows);
+    if (int rc = check_launch("odom_rgbd_accumulate")) return rc;
+    hipLaunchKernelGGL(k_odom_rgbd_finish, dim3(1), dim3(kOdomThreads), 0, (hipStream_t)stream, (int32_t)level, state, parts,
+                       reinterpret_cast<const double*>(workspace), sums);
+    return check_launch("odom_rgbd_finish");
+}
+
 int naruto_pose_predict_relative(float* est, uint32_t num_frames, uint32_t i, const double* state_T, float* pose6_out, void* stream) {
     if (est == nullptr || state_T == nullptr || pose6_out == nullptr) return fail(NARUTO_ERR_INVALID, "pose_predict_relative: NULL argument");
     if (i < 1u || i >= num_frames) return fail(NARUTO_ERR_INVALID, "pose_predict_relative: frame %u of %u (the first frame is given, not predicted)", i, num_frames);

@@ -66,16 +66,18 @@ __device__ inline void odom_vertex(const OdomLevel& g, uint32_t u, uint32_t v, f
     V[0] = d * dx; V[1] = d * dy; V[2] = -d;
 }
 
-// maps block, per level at lv.offset: depth [h*w], vertex [h*w,3], normal [h*w,3]
-__global__ __launch_bounds__(kOdomThreads) void k_odom_maps(OdomGeom g, const float* __restrict__ depth, float* __restrict__ maps) {
-#pragma clang fp contract(off)
-    const uint32_t gid = blockIdx.x * kOdomThreads + threadIdx.x;
-    if (gid >= g.total) return;
+// the pyramid level thread gid of a maps launch works on
+__device__ inline int odom_level_of(const OdomGeom& g, uint32_t gid) {
     int level = 0;
     for (int l = 1; l < (int)g.levels; ++l)
         if (gid >= g.lv[l].start) level = l;
-    const OdomLevel lv = g.lv[level];
-    const uint32_t i = gid - lv.start, u = i % lv.w, v = i / lv.w, n = lv.h * lv.w;
+    return level;
+}
+
+// pixel i of `level` into the depth part of a maps block, per level at lv.offset: depth [h*w], vertex [h*w,3], normal [h*w,3]
+__device__ inline void odom_maps_pixel(const OdomGeom& g, int level, const OdomLevel& lv, uint32_t i, const float* __restrict__ depth, float* __restrict__ maps) {
+#pragma clang fp contract(off)
+    const uint32_t u = i % lv.w, v = i / lv.w, n = lv.h * lv.w;
     const float d = odom_depth_at(level, depth, g.W, u, v, g.band);
     float V[3], N[3] = {0.0f, 0.0f, 0.0f};
     odom_vertex(lv, u, v, d, V);
@@ -98,6 +100,14 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_maps(OdomGeom g, const fl
         base[(size_t)n + 3u * i + k] = V[k];
         base[(size_t)n * 4u + 3u * i + k] = N[k];
     }
+}
+
+__global__ __launch_bounds__(kOdomThreads) void k_odom_maps(OdomGeom g, const float* __restrict__ depth, float* __restrict__ maps) {
+    const uint32_t gid = blockIdx.x * kOdomThreads + threadIdx.x;
+    if (gid >= g.total) return;
+    const int level = odom_level_of(g, gid);
+    const OdomLevel lv = g.lv[level];
+    odom_maps_pixel(g, level, lv, gid - lv.start, depth, maps);
 }
 
 // mode 0: T = init.T; 1: T = inv(est[i-2]) @ est[i-1] (the last relative motion once more); 2: identity
@@ -226,6 +236,195 @@ __global__ __launch_bounds__(64) void k_odom_step(int32_t level, double cap, con
 #pragma unroll
     for (int k = 0; k < kOdomSums; ++k) s[k] = sums[k];
     odom_step(s, level, cap, state);                                     // on the state block itself: T and the level's words
+}
+
+// ---- RGB-D odometry: the depth odometry plus a photometric row per pixel (contract: naruto_amd/odometry.py, include/naruto_hip.h) ----------
+//
+//   k_odom_rgbd_maps        one thread per pixel of every level: the depth part exactly as k_odom_maps (odom_maps_pixel), then the intensity
+//                           I (the 2 x 2 means nested down to level 0) and its central differences gx, gy into the intensity block
+//   k_odom_rgbd_accumulate  k_odom_accumulate over 32 sums: per pixel the geometric row first, then the photometric row
+//   k_odom_rgbd_finish      k_odom_finish over 32 sums
+constexpr int kOdomRgbdSums = 32;                                        // [0..28] as kOdomSums over both kinds of rows; geometric rows, photometric rows, sum r_I^2
+
+// intensity of pixel (u, v) of level L from the level-0 colour frame [H,W,3]: level 0 is (0.299 r + 0.587 g) + 0.114 b, level L the mean
+// (((a + b) + c) + d) * 0.25 of its 2 x 2 block in the order (0,0), (0,1), (1,0), (1,1)
+template <int L>
+__device__ inline float odom_intensity(const float* __restrict__ color, uint32_t W, uint32_t u, uint32_t v) {
+#pragma clang fp contract(off)
+    if constexpr (L == 0) {
+        const float* c = color + 3u * ((size_t)v * W + u);
+        return (0.299f * c[0] + 0.587f * c[1]) + 0.114f * c[2];
+    } else {
+        const float a = odom_intensity<L - 1>(color, W, 2u * u, 2u * v), b = odom_intensity<L - 1>(color, W, 2u * u + 1u, 2u * v);
+        const float c = odom_intensity<L - 1>(color, W, 2u * u, 2u * v + 1u), d = odom_intensity<L - 1>(color, W, 2u * u + 1u, 2u * v + 1u);
+        return (((a + b) + c) + d) * 0.25f;
+    }
+}
+
+__device__ inline float odom_intensity_at(int level, const float* __restrict__ color, uint32_t W, uint32_t u, uint32_t v) {
+    switch (level) {
+        case 0: return odom_intensity<0>(color, W, u, v);
+        case 1: return odom_intensity<1>(color, W, u, v);
+        case 2: return odom_intensity<2>(color, W, u, v);
+        default: return odom_intensity<3>(color, W, u, v);
+    }
+}
+
+// RGB-D maps block: the depth maps block (7 x g.total floats), then per level at 7 x g.total + 3 x lv.start: I [h*w], gx [h*w], gy [h*w]
+__global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_maps(OdomGeom g, const float* __restrict__ depth, const float* __restrict__ color,
+                                                                 float* __restrict__ maps) {
+#pragma clang fp contract(off)
+    const uint32_t gid = blockIdx.x * kOdomThreads + threadIdx.x;
+    if (gid >= g.total) return;
+    const int level = odom_level_of(g, gid);
+    const OdomLevel lv = g.lv[level];
+    const uint32_t i = gid - lv.start, u = i % lv.w, v = i / lv.w, n = lv.h * lv.w;
+    odom_maps_pixel(g, level, lv, i, depth, maps);
+    float gx = 0.0f, gy = 0.0f;
+    if (u >= 1u && u + 2u <= lv.w) gx = (odom_intensity_at(level, color, g.W, u + 1u, v) - odom_intensity_at(level, color, g.W, u - 1u, v)) * 0.5f;
+    if (v >= 1u && v + 2u <= lv.h) gy = (odom_intensity_at(level, color, g.W, u, v + 1u) - odom_intensity_at(level, color, g.W, u, v - 1u)) * 0.5f;
+    float* base = maps + (size_t)g.total * 7u + (size_t)lv.start * 3u;
+    base[i] = odom_intensity_at(level, color, g.W, u, v);
+    base[(size_t)n + i] = gx;
+    base[(size_t)n * 2u + i] = gy;
+}
+
+// odom_fold over N sums: s is [N][kOdomThreads] in LDS
+template <int N>
+__device__ __forceinline__ void odom_fold_n(double* s, double acc[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k * kOdomThreads + threadIdx.x] = acc[k];
+    __syncthreads();
+    for (uint32_t w = kOdomThreads / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k * kOdomThreads + threadIdx.x] += s[k * kOdomThreads + threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] = s[k * kOdomThreads];
+    }
+}
+
+// one row J = [q x n, n] with residual r into the sums [0..28], in k_odom_accumulate's order
+__device__ __forceinline__ void odom_add_row(double* acc, const double q[3], const double nn[3], double r) {
+#pragma clang fp contract(off)
+    const double J[6] = {q[1] * nn[2] - q[2] * nn[1], q[2] * nn[0] - q[0] * nn[2], q[0] * nn[1] - q[1] * nn[0], nn[0], nn[1], nn[2]};
+    int m = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b, ++m) acc[m] += J[a] * J[b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
+    acc[27] += r * r;
+    acc[28] += 1.0;
+}
+
+// m at (u0 + a, v0 + b), a, b in [0, 1): top = s00 + a (s10 - s00), bot = s01 + a (s11 - s01), top + b (bot - top); s10 is (u0 + 1, v0)
+__device__ __forceinline__ double odom_bilinear(const float* __restrict__ m, uint32_t j00, uint32_t w, double a, double b) {
+#pragma clang fp contract(off)
+    const double s00 = (double)m[j00], s10 = (double)m[j00 + 1u], s01 = (double)m[j00 + w], s11 = (double)m[j00 + w + 1u];
+    const double top = s00 + a * (s10 - s00), bot = s01 + a * (s11 - s01);
+    return top + b * (bot - top);
+}
+
+// part: [workgroups][kOdomRgbdSums]; rows (or NULL): [n][4] = (geometric j or -1, r, photometric j or -1, r_I); ioff: floats to the level's I
+__global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_accumulate(OdomLevel lv, uint32_t ioff, int32_t level, double max_dist2, double weight,
+                                                                       double max_diff, const float* __restrict__ prev, const float* __restrict__ cur,
+                                                                       const double* __restrict__ state, double* __restrict__ part, double* __restrict__ rows) {
+#pragma clang fp contract(off)
+    __shared__ double s[kOdomRgbdSums * kOdomThreads];
+    if (state[16 + kOdomLevelWords * level] != 0.0) return;              // uniform: the level is finished
+    double T[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = state[k];
+    const uint32_t n = lv.h * lv.w;
+    const float* cv = cur + lv.offset + n;
+    const float* pv = prev + lv.offset + n;
+    const float* pn = prev + lv.offset + (size_t)n * 4u;
+    const float* ci = cur + ioff;
+    const float* pi = prev + ioff;
+    const double fx = (double)lv.fx, fy = (double)lv.fy, cx = (double)lv.cx, cy = (double)lv.cy;
+    double acc[kOdomRgbdSums];
+#pragma unroll
+    for (int k = 0; k < kOdomRgbdSums; ++k) acc[k] = 0.0;
+#pragma unroll 1
+    for (uint32_t k = 0; k < kOdomPer; ++k) {
+        const uint64_t i64 = (uint64_t)blockIdx.x * (kOdomThreads * kOdomPer) + k * kOdomThreads + threadIdx.x;
+        if (i64 >= n) continue;
+        const uint32_t i = (uint32_t)i64;
+        double index = -1.0, r = 0.0, pindex = -1.0, rI = 0.0;
+        const double x = (double)cv[3u * i], y = (double)cv[3u * i + 1u], z = (double)cv[3u * i + 2u];
+        if (z < 0.0) {                                                   // a valid vertex lies in front of its camera
+            const double q[3] = {((T[0] * x + T[1] * y) + T[2] * z) + T[3], ((T[4] * x + T[5] * y) + T[6] * z) + T[7],
+                                 ((T[8] * x + T[9] * y) + T[10] * z) + T[11]};
+            const double zc = -q[2];
+            if (zc > 1e-6) {
+                const double uc = (fx * q[0]) / zc + cx, vc = (-(fy * q[1])) / zc + cy;
+                const double u = floor(uc + 0.5), v = floor(vc + 0.5);
+                if (u >= 0.0 && u < (double)lv.w && v >= 0.0 && v < (double)lv.h) {
+                    const uint32_t j = (uint32_t)v * lv.w + (uint32_t)u;
+                    const double d[3] = {q[0] - (double)pv[3u * j], q[1] - (double)pv[3u * j + 1u], q[2] - (double)pv[3u * j + 2u]};
+                    const bool near = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] <= max_dist2;
+                    const double nn[3] = {(double)pn[3u * j], (double)pn[3u * j + 1u], (double)pn[3u * j + 2u]};
+                    if ((nn[0] != 0.0 || nn[1] != 0.0 || nn[2] != 0.0) && near) {
+                        index = (double)j;
+                        r = (nn[0] * d[0] + nn[1] * d[1]) + nn[2] * d[2];
+                        odom_add_row(acc, q, nn, r);
+                        acc[29] += 1.0;
+                    }
+                    const double u0 = floor(uc), v0 = floor(vc);
+                    if (weight > 0.0 && u0 >= 1.0 && u0 + 1.0 <= (double)lv.w - 2.0 && v0 >= 1.0 && v0 + 1.0 <= (double)lv.h - 2.0 &&
+                        (double)pv[3u * j + 2u] < 0.0 && near) {         // the four neighbours are interior pixels; the nearest one has a vertex close to q
+                        const uint32_t j00 = (uint32_t)v0 * lv.w + (uint32_t)u0;
+                        const double a = uc - u0, b = vc - v0;
+                        const double res = odom_bilinear(pi, j00, lv.w, a, b) - (double)ci[i];
+                        const double gx = odom_bilinear(pi + n, j00, lv.w, a, b), gy = odom_bilinear(pi + 2u * (size_t)n, j00, lv.w, a, b);
+                        if (fabs(res) <= max_diff && fabs(gx) < (double)INFINITY && fabs(gy) < (double)INFINITY) {
+                            const double ga = gx * fx, gb = gy * fy;
+                            const double g[3] = {weight * (ga / zc), weight * (-(gb / zc)), weight * ((ga * q[0] - gb * q[1]) / (zc * zc))};
+                            pindex = (double)j;
+                            rI = res;
+                            odom_add_row(acc, q, g, weight * res);
+                            acc[30] += 1.0;
+                            acc[31] += res * res;
+                        }
+                    }
+                }
+            }
+        }
+        if (rows != nullptr) {
+            rows[4u * (size_t)i] = index; rows[4u * (size_t)i + 1u] = r;
+            rows[4u * (size_t)i + 2u] = pindex; rows[4u * (size_t)i + 3u] = rI;
+        }
+    }
+    odom_fold_n<kOdomRgbdSums>(s, acc);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kOdomRgbdSums; ++k) part[(size_t)blockIdx.x * kOdomRgbdSums + k] = acc[k];
+    }
+}
+
+__global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_finish(int32_t level, const double* __restrict__ state, uint32_t n_parts,
+                                                                   const double* __restrict__ part, double* __restrict__ sums) {
+#pragma clang fp contract(off)
+    __shared__ double s[kOdomRgbdSums * kOdomThreads];
+    if (state[16 + kOdomLevelWords * level] != 0.0) return;
+    double acc[kOdomRgbdSums];
+#pragma unroll
+    for (int k = 0; k < kOdomRgbdSums; ++k) acc[k] = 0.0;
+    for (uint32_t i = threadIdx.x; i < n_parts; i += kOdomThreads) {
+#pragma unroll
+        for (int k = 0; k < kOdomRgbdSums; ++k) acc[k] += part[(size_t)i * kOdomRgbdSums + k];
+    }
+    odom_fold_n<kOdomRgbdSums>(s, acc);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kOdomRgbdSums; ++k) sums[k] = acc[k];
+    }
 }
 
 // est[i] = est[i-1] @ T (fp64 from the float32 matrix, rounded once); pose6_out = the log of est[i] as stored

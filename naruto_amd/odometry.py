@@ -29,11 +29,44 @@ sequence of launches -- for each level from the coarsest, cap x (accumulate, ste
 waits for the host.  When every level is degenerate the state's T is still the initial one.
 
 Limits: frame-to-frame only (drift is left to the tracker and global_BA); depth only, no photometric term; the two views must overlap.
+
+RGB-D ODOMETRY (``RGBDOdometryHIP``, ``motion_prior="rgbd_icp"``): the same estimate with a photometric row per pixel beside the geometric
+one.  A plane seen head on leaves three motions free for the depth rows (degenerate, T unchanged); the image on the plane pins them.
+PARITY UNPINNED as above; tests/odometry_rgbd_spec.py is the numpy twin.  The camera convention, T, the state block, the level schedule,
+the done words and the step are those of the depth odometry.
+
+Intensity maps, float32 with contraction off like the depth maps:
+  * level 0: I = (0.299 r + 0.587 g) + 0.114 b of the colour frame [H,W,3] (float32, 0 .. 1); level l+1: (((a + b) + c) + d) * 0.25 over
+    the 2 x 2 block in the order (0,0), (0,1), (1,0), (1,1), an odd last row / column not read; every thread nests the means down to level 0;
+  * gx(u,v) = (I(u+1,v) - I(u-1,v)) * 0.5 for 1 <= u <= w-2, else 0; gy the same in v.
+RGB-D maps block: the depth maps block (same layout, same bits as ``DepthOdometryHIP.frame_maps``), then the intensity block: per level, at
+3 x (the pixels of the levels before it) floats, I [h*w] | gx [h*w] | gy [h*w].  One launch per frame writes both.
+
+One evaluation at a level, per pixel i of the current frame, fp64 without contraction:
+  1. the geometric row, exactly the depth odometry's (association, rejections, J, r, order);
+  2. the photometric row, only when ``photo_weight`` > 0, from the same q = T p with p.z < 0 and zc = -q.z > 1e-6:
+     uc = (fx q.x)/zc + cx, vc = (-(fy q.y))/zc + cy, u0 = floor(uc), v0 = floor(vc); rejected unless 1 <= u0, u0+1 <= w-2, 1 <= v0,
+     v0+1 <= h-2 (the four neighbours are interior pixels whose gradients are central differences); with j the geometric row's nearest
+     pixel (floor(uc+0.5), floor(vc+0.5)), rejected unless V_prev[j].z < 0 and |q - V_prev[j]|^2 <= max_dist^2 (an occlusion test; no
+     normal is needed).  I_prev, gx_prev, gy_prev are sampled bilinearly with a = uc - u0, b = vc - v0: top = s00 + a (s10 - s00),
+     bot = s01 + a (s11 - s01), s = top + b (bot - top) (s10 at (u0+1, v0)).  r_I = I_prev(uc,vc) - I_cur[i]; rejected unless
+     |r_I| <= ``photo_max_diff`` and both sampled gradients are finite (a NaN fails the comparison, so non-finite colours drop out here).
+     With w = ``photo_weight`` (metres per unit of intensity; the float32 value as a double), A = gx fx, B = gy fy, in this order:
+     g = (w (A/zc), w (-(B/zc)), w ((A q.x - B q.y)/(zc zc))), r = w r_I, J = [q x g, g]: the geometric row's form with g for n, so one
+     accumulation routine serves both;
+  3. 32 fp64 sums: [0..28] as above over the rows of BOTH kinds (the count too), [29] the geometric rows, [30] the photometric rows,
+     [31] sum r_I^2 unweighted.  Per pixel the geometric row's terms are added first, then the photometric row's; pixels, threads, the fold
+     and the finishing launch in the depth odometry's order: no atomics, bitwise reproducible;
+  4. the step is the depth odometry's, unchanged, on the first 29 sums: a level's ``inliers`` and ``rmse`` then count and mix both kinds of
+     rows (rmse^2 = (sum r^2 + w^2 sum r_I^2) / rows).
+Defaults ``photo_weight = 0.1``, ``photo_max_diff = 0.3``.  Limits: the photometric term needs texture and overlap, and assumes that a
+surface point's intensity is the same in both frames; a failed estimate is still not detected.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from types import SimpleNamespace
 from typing import Dict, Optional, Sequence, Union
 
@@ -152,3 +185,68 @@ class DepthOdometryHIP:
         """``.transformation`` float64 [4,4] (current camera to previous camera), and per level (index = pyramid level, 0 the finest)
         ``.status``, ``.iterations``, ``.inliers``, ``.rmse``.  This call synchronises."""
         return self.read_state(self.estimate_device(self.frame_maps(depth_prev), self.frame_maps(depth_cur), init))
+
+
+class RGBDOdometryHIP(DepthOdometryHIP):
+    """The depth odometry with a photometric row per pixel (module docstring).  The maps block is the depth odometry's followed by the
+    intensity block; ``init_state`` and ``step`` are the parent's (the step reads the first 29 of the 32 sums)."""
+
+    def __init__(self, cam: Union[Dict, Sequence], levels: int = 3, iters: Sequence[int] = (10, 5, 4), max_dist: float = 0.25, jump: float = 0.15,
+                 band: float = 0.1, photo_weight: float = 0.1, photo_max_diff: float = 0.3, device="cuda"):
+        super().__init__(cam, levels, iters, max_dist, jump, band, device=device)
+        if not (math.isfinite(photo_weight) and photo_weight >= 0.0 and photo_max_diff >= 0.0):
+            raise ValueError(f"RGBDOdometryHIP: photo_weight = {photo_weight!r} must be finite and >= 0, photo_max_diff = {photo_max_diff!r} >= 0")
+        self.photo = _lib.NarutoOdomPhoto(weight=float(photo_weight), max_diff=float(photo_max_diff))
+        lib = _lib.load()
+        self.depth_maps_bytes = self.maps_bytes
+        self.maps_bytes = int(lib.naruto_odom_rgbd_maps_bytes(C.byref(self.desc)))
+        ws = int(lib.naruto_odom_rgbd_workspace_bytes(C.byref(self.desc)))
+        if self.maps_bytes == 0 or ws == 0:
+            raise ValueError("RGBDOdometryHIP: " + lib.naruto_last_error().decode("utf-8", "replace"))
+        self.workspace = _lib.workspace(ws, self.device, torch.float64)
+        self.sums = torch.zeros(_lib.ODOM_RGBD_SUMS, dtype=torch.float64, device=self.device)
+        # offset in floats of every level's I | gx | gy inside a maps block
+        self.intensity_offsets, off = [], self.depth_maps_bytes // 4
+        for h, w, _ in self.level_shapes:
+            self.intensity_offsets.append(off)
+            off += 3 * h * w
+
+    def frame_maps(self, depth: torch.Tensor, color: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The RGB-D maps block of the frame: depth [H,W], colour [H,W,3] (float32 on the device): one launch."""
+        depth = depth.to(self.device, torch.float32).contiguous()
+        color = color.to(self.device, torch.float32).contiguous()
+        if depth.numel() != self.H * self.W or color.numel() != 3 * self.H * self.W:
+            raise ValueError(f"RGBDOdometryHIP: a depth frame of {tuple(depth.shape)} and a colour frame of {tuple(color.shape)}, built for {self.H} x {self.W}")
+        out = self.new_maps() if out is None else out
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() * 4 == self.maps_bytes):
+            raise ValueError("RGBDOdometryHIP: out must be a maps block of new_maps()")
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_rgbd_frame_maps(C.byref(self.desc), depth.data_ptr(), color.data_ptr(), out.data_ptr(), _stream()),
+                  "naruto_odom_rgbd_frame_maps")
+        return out
+
+    def level_views(self, maps: torch.Tensor, level: int):
+        """(depth [h,w], vertex [h,w,3], normal [h,w,3], I [h,w], gx [h,w], gy [h,w]): views into an RGB-D maps block."""
+        h, w, _ = self.level_shapes[level]
+        n, off = h * w, self.intensity_offsets[level]
+        return super().level_views(maps, level) + tuple(maps[off + k * n:off + (k + 1) * n].view(h, w) for k in range(3))
+
+    def accumulate(self, level: int, maps_prev: torch.Tensor, maps_cur: torch.Tensor, state: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None):
+        """The 32 sums of one evaluation.  ``rows``: float64 [pixels of the level, 4] = (geometric j or -1, r, photometric j or -1, r_I)."""
+        state = self.state if state is None else state
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_rgbd_accumulate(C.byref(self.desc), C.byref(self.photo), int(level), maps_prev.data_ptr(), maps_cur.data_ptr(),
+                                                          state.data_ptr(), self.sums.data_ptr(), self.workspace.data_ptr(),
+                                                          None if rows is None else rows.data_ptr(), _stream()), "naruto_odom_rgbd_accumulate")
+        return self.sums
+
+    def read_state(self, state: Optional[torch.Tensor] = None) -> SimpleNamespace:
+        """The parent's, plus the last evaluation's ``geometric_rows`` and ``photometric_rows`` read from the sums (synchronises)."""
+        out = super().read_state(state)
+        s = self.sums.cpu().numpy()
+        out.geometric_rows, out.photometric_rows = int(s[29]), int(s[30])
+        return out
+
+    def estimate(self, depth_prev: torch.Tensor, color_prev: torch.Tensor, depth_cur: torch.Tensor, color_cur: torch.Tensor, init=None) -> SimpleNamespace:
+        """As ``DepthOdometryHIP.estimate`` from two RGB-D frames.  This call synchronises."""
+        return self.read_state(self.estimate_device(self.frame_maps(depth_prev, color_prev), self.frame_maps(depth_cur, color_cur), init))

@@ -146,8 +146,9 @@ def parse_args(argv=None):
     parser.add_argument("--no_active_ray", action="store_true", help="switch the active ray sampler off")
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--track", action="store_true", help="estimate the camera poses during the run (tracking + pose refinement); adds the ATE to results.txt")
-    parser.add_argument("--motion_prior", type=str, default=None, choices=["const_speed", "depth_icp"],
-                        help="with --track: the tracker's initial pose from constant-speed extrapolation (default) or from frame-to-frame depth odometry")
+    parser.add_argument("--motion_prior", type=str, default=None, choices=["const_speed", "depth_icp", "rgbd_icp"],
+                        help="with --track: the tracker's initial pose from constant-speed extrapolation (default), from frame-to-frame depth odometry, "
+                             "or from RGB-D odometry (depth plus a photometric term)")
     parser.add_argument("--dataset", type=str, default="NARUTO", choices=["Replica", "MP3D", "NARUTO"], help="the planner's collision rule")
     parser.add_argument("--eval_views", type=int, default=None, metavar="K", help="after the run, render every K-th pose from the map and score it against the simulator (psnr, ssim, depth_l1(cm) in results.txt)")
     parser.add_argument("--planner", type=str, nargs="*", default=[], metavar="KEY=VALUE", help="planner settings over naruto_amd.planner.DEFAULTS")

@@ -52,12 +52,14 @@ mapped one waits once, for the same 8-byte count as without tracking.  ``resolve
 (refined) keyframe; ``save_ckpt`` writes the raw ``pose`` / ``pose_rel`` as the reference does.  The tracker is captured once, at the end
 of frame 0, and keeps its own random word (derived from ``seed``).  ``track=False`` is the object without any of this, launch for launch.
 
-MOTION PRIOR (``motion_prior="const_speed"`` | ``"depth_icp"``, with ``track=True`` only).  ``"const_speed"``, the default, is step 1 as
+MOTION PRIOR (``motion_prior="const_speed"`` | ``"depth_icp"`` | ``"rgbd_icp"``, with ``track=True`` only).  ``"const_speed"``, the default, is step 1 as
 written.  With ``"depth_icp"`` the prediction comes from the two depth frames themselves (``naruto_amd.odometry.DepthOdometryHIP``): frame
 0 makes its maps; every frame i > 0 makes its maps, runs the frame-to-frame estimate from the last relative motion
 ``inv(est[i-2]) @ est[i-1]`` (``tracking.const_speed`` and i > 1; the identity otherwise), and ``pose_predict_relative`` stands in the place
 of ``pose_predict``: ``est[i] = est[i-1] @ T``.  When every level is degenerate T is still that initial motion -- decided on the device;
 the estimate is a fixed sequence of launches and adds no wait for the host.  ``odometry.state`` keeps the last estimate's state block.
+``"rgbd_icp"`` is the same step with ``naruto_amd.odometry.RGBDOdometryHIP``: the frame's colour image goes into the maps as well, and every
+pixel adds a photometric row, which pins the motions a bare wall leaves free for the depth rows; launch for launch the same sequence.
 
 A config with ``tracking.disable: False`` and no ``track=True`` is refused (``NotImplementedError``) before the library is touched:
 tracking is switched on by the keyword, whatever ``tracking.disable`` says.  Out of scope: ``tracking.iter_point > 0`` (``tracking_pc``),
@@ -144,11 +146,11 @@ class CoSLAMNarutoHIP:
         network's initial values and the trainer's in-kernel random streams.  ``result_dir``: meshes and checkpoints go under
         ``<result_dir>/coslam`` (None: ``save_*`` need an explicit directory).  ``track``: estimate the camera poses during the run
         (module docstring) with ``tracking_settings(config)``, whatever ``tracking.disable`` says.  ``motion_prior``: where a tracked
-        frame's initial pose comes from, ``"const_speed"`` (the default) or ``"depth_icp"`` (module docstring); needs ``track=True``."""
+        frame's initial pose comes from, ``"const_speed"`` (the default), ``"depth_icp"`` or ``"rgbd_icp"`` (module docstring); needs ``track=True``."""
         tk = config.get("tracking") or {}
         self.track = bool(track)
-        if motion_prior is not None and motion_prior not in ("const_speed", "depth_icp"):
-            raise ValueError(f"CoSLAMNarutoHIP: motion_prior = {motion_prior!r}; 'const_speed' or 'depth_icp'")
+        if motion_prior is not None and motion_prior not in ("const_speed", "depth_icp", "rgbd_icp"):
+            raise ValueError(f"CoSLAMNarutoHIP: motion_prior = {motion_prior!r}; 'const_speed', 'depth_icp' or 'rgbd_icp'")
         if motion_prior is not None and not self.track:
             raise ValueError("CoSLAMNarutoHIP: motion_prior is the tracker's initial pose and needs track=True")
         self.motion_prior = motion_prior or "const_speed"
@@ -199,6 +201,10 @@ class CoSLAMNarutoHIP:
             from .odometry import DepthOdometryHIP
             self.odometry = DepthOdometryHIP((self.H, self.W, self.fx, self.fy, self.cx, self.cy), device=self.device)
             self._odom_maps = [self.odometry.new_maps(), self.odometry.new_maps()]          # frame i's maps live in [i & 1]
+        elif self.motion_prior == "rgbd_icp":
+            from .odometry import RGBDOdometryHIP
+            self.odometry = RGBDOdometryHIP((self.H, self.W, self.fx, self.fy, self.cx, self.cy), device=self.device)
+            self._odom_maps = [self.odometry.new_maps(), self.odometry.new_maps()]
         self.cached_uncert = None
         self.filter_depth = bool(mp.get("filter_depth", False))
         self._n_valid = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -241,6 +247,13 @@ class CoSLAMNarutoHIP:
         with no_collection():
             tr.capture()
 
+    def _odom_frame_maps(self, color: torch.Tensor, depth: torch.Tensor, out: torch.Tensor) -> None:
+        """The frame's odometry maps into ``out``: one launch; the RGB-D odometry takes the colour frame too."""
+        if self.motion_prior == "rgbd_icp":
+            self.odometry.frame_maps(depth, color, out=out)
+        else:
+            self.odometry.frame_maps(depth, out=out)
+
     def _track(self, i: int, color: torch.Tensor, depth: torch.Tensor, every: int):
         """Frame ``i > 0`` of a tracked run: predict, track, commit (module docstring) -- launches only.  Returns the frame as the
         float32 device tensors the tracker took."""
@@ -252,7 +265,7 @@ class CoSLAMNarutoHIP:
                            "step the frames in order")
         if self.odometry is not None:
             od, cur = self.odometry, self._odom_maps[i & 1]
-            od.frame_maps(depth, out=cur)
+            self._odom_frame_maps(color, depth, cur)
             state = od.init_state(est=est.tensor, i=i, const_speed=bool(self.tracking["const_speed"]))
             od.run_levels(self._odom_maps[(i - 1) & 1], cur, state)
             pose_predict_relative(est.tensor, i, state, self.tracker.pose_init)
@@ -300,7 +313,7 @@ class CoSLAMNarutoHIP:
                 if self.track:
                     self._capture_tracker(color, depth)
                 if self.odometry is not None:
-                    self.odometry.frame_maps(depth, out=self._odom_maps[0])
+                    self._odom_frame_maps(color, depth, self._odom_maps[0])
             else:
                 every = int(mp["keyframe_every"])
                 if self.track:

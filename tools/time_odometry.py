@@ -10,6 +10,11 @@ Recorded:
     (0.6, 0.3, -0.74), that one estimate from the identity recovers to 5 mm / 0.25 degrees.
 
     python tools/time_odometry.py [--out profiles/time_odometry.json] [--n-lat 632]
+    python tools/time_odometry.py --rgbd [--out profiles/time_odometry_rgbd.json]
+
+With --rgbd only this is recorded: the frame maps and a whole estimate of the depth odometry and of the RGB-D odometry
+(naruto_amd.odometry.RGBDOdometryHIP) on the same two frames of the mesh coloured by a smooth function of position, the four calls
+alternating in one loop.
 
 Host wall clock ending in a device synchronise, every shape warmed up first, the MEDIAN of --repeat.  Nothing is asserted."""
 import argparse
@@ -28,7 +33,7 @@ sys.path.insert(0, ROOT)
 
 from naruto_amd import pose_chain as PC  # noqa: E402
 from naruto_amd import synthetic as syn  # noqa: E402
-from naruto_amd.odometry import DepthOdometryHIP  # noqa: E402
+from naruto_amd.odometry import DepthOdometryHIP, RGBDOdometryHIP  # noqa: E402
 from naruto_amd.planner import compute_camera_pose  # noqa: E402
 from naruto_amd.simulator import MeshSimHIP  # noqa: E402
 
@@ -69,16 +74,67 @@ def error(T, ref):
     return float(np.linalg.norm(T[:3, 3] - ref[:3, 3])), math.degrees(math.acos(min(1.0, max(-1.0, (np.trace(R) - 1.0) / 2.0))))
 
 
+def rgbd(args, dev, cam):
+    """--rgbd: the frame maps and a whole estimate of DepthOdometryHIP and RGBDOdometryHIP on the same two frames (3 cm / 2 degrees), the
+    two alternating inside one timing loop so that both see the same machine state; the mesh coloured by a smooth function of position."""
+    from time_tracked_run import smooth_colours
+    v, f = syn.room_sphere_mesh(n_lat=args.n_lat, n_lon=2 * args.n_lat)[:2]
+    sim = MeshSimHIP((v, f, smooth_colours(v)), cam, device=dev)
+    base = np.eye(4)
+    pos, at = np.array([2.0, 4.0, 1.2]), np.array([3.0, 2.5, 1.4])
+    base[:3, :3], base[:3, 3] = compute_camera_pose(pos, at), pos
+    poses = np.stack([base, base @ motion((0, 1, 0), 2.0, 0.03)]).astype(np.float32)
+    frames = [sim.simulate(p, no_print=True) for p in poses]
+    color, depth = [c.to(dev) for c, _ in frames], [d.to(dev) for _, d in frames]
+    rel = np.linalg.inv(poses[0].astype(np.float64)) @ poses[1].astype(np.float64)
+    dod, rod = DepthOdometryHIP(cam, device=dev), RGBDOdometryHIP(cam, device=dev)
+    dprev, dcur, rprev, rcur = dod.frame_maps(depth[0]), dod.new_maps(), rod.frame_maps(depth[0], color[0]), rod.new_maps()
+    calls = {"depth_frame_maps_ms": lambda: dod.frame_maps(depth[1], out=dcur), "rgbd_frame_maps_ms": lambda: rod.frame_maps(depth[1], color[1], out=rcur),
+             "depth_estimate_ms": lambda: dod.estimate_device(dprev, dcur), "rgbd_estimate_ms": lambda: rod.estimate_device(rprev, rcur)}
+    times = {k: [] for k in calls}
+    for k, fn in calls.items():
+        fn()
+    for _ in range(args.repeat):
+        for k, fn in calls.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t)
+    res = {"image": [cam["W"], cam["H"]], "focal": cam["fx"], "faces": len(f), "levels": rod.levels, "iters_coarse_to_fine": list(rod.iters),
+           "photo_weight": float(rod.photo.weight), "photo_max_diff": float(rod.photo.max_diff), "repeat": args.repeat}
+    res.update({k: statistics.median(v) * 1e3 for k, v in times.items()})
+    for name, got in (("depth", dod.read_state()), ("rgbd", rod.read_state())):
+        dm, dd = error(got.transformation, rel)
+        res[name + "_estimate_3cm_2deg"] = {"error_mm": dm * 1e3, "error_deg": dd, "status": got.status, "iterations": got.iterations, "inliers": got.inliers,
+                                            "rmse": got.rmse}
+    res["rgbd_estimate_3cm_2deg"].update(geometric_rows=rod.read_state().geometric_rows, photometric_rows=rod.read_state().photometric_rows)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=9)
     ap.add_argument("--n-lat", type=int, default=632)
+    ap.add_argument("--rgbd", action="store_true", help="depth-only and RGB-D odometry alternating in one run (write to profiles/time_odometry_rgbd.json)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_odometry.py measures on the GPU; there is none here")
     dev = torch.device("cuda:0")
     cam = {"H": 680, "W": 1200, "fx": 600.0, "fy": 600.0, "cx": 599.5, "cy": 339.5}
+    if args.rgbd:
+        res = rgbd(args, dev, cam)
+        print(json.dumps(res, indent=1))
+        if args.out:
+            doc = {"device": torch.cuda.get_device_name(0),
+                   "what": "tools/time_odometry.py --rgbd: host wall clock ending in a device synchronise, warmed up, the four calls alternating, median of "
+                           "--repeat; milliseconds", "office_0_size": res}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(doc, fh, indent=1)
+                fh.write("\n")
+        return
     mesh = syn.room_sphere_mesh(n_lat=args.n_lat, n_lon=2 * args.n_lat)
     sim = MeshSimHIP(mesh, cam, device=dev)
     base = np.eye(4)

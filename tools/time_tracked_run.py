@@ -11,11 +11,11 @@ the mapping schedule of tools/time_run.py, tracking with replica_coslam.yaml's s
     the others, the trajectory error of the estimate and the motion per step the planner commands (against what one tracking call
     can cover: iter x lr).
 
-    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632] [--motion-prior depth_icp]
+    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632] [--motion-prior depth_icp | rgbd_icp]
 
 With --motion-prior only the run is made, with CoSLAMNarutoHIP(motion_prior=...), and it is MERGED into the output file as
 office_0_size.run_motion_prior_<name>, beside the run of the default prior (--no-const-speed: tracking.const_speed off, key suffix
-_const_speed_off).
+_const_speed_off).  rgbd_icp needs an image: the tool's mesh has no colours, so its vertices are then coloured by a smooth function of position.
 
 Host timers (time.perf_counter), medians over --repeat.  Nothing is asserted.  There is NO reference number: the reference's loop needs
 Habitat-Sim and tiny-cuda-nn, neither of which is on this stack."""
@@ -40,6 +40,16 @@ from naruto_amd.planner import NarutoPlannerHIP, compute_camera_pose  # noqa: E4
 from naruto_amd.run import run_exploration  # noqa: E402
 from naruto_amd.simulator import MeshSimHIP  # noqa: E402
 from naruto_amd.slam import CoSLAMNarutoHIP  # noqa: E402
+
+
+def smooth_colours(vertices):
+    """float32 [V,3] in 0 .. 1: a smooth function of position with structure at the scale of a metre (a mesh without colours renders white)."""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    c = np.stack([0.5 + 0.25 * np.sin(2.3 * x + 1.1 * y + 0.4) + 0.2 * np.cos(1.7 * z - 0.8 * y),
+                  0.5 + 0.25 * np.cos(1.9 * y - 1.3 * z + 0.2) + 0.2 * np.sin(2.9 * x + 0.6 * z),
+                  0.5 + 0.25 * np.sin(2.1 * z + 0.9 * x - 0.5) + 0.2 * np.cos(2.6 * y + 1.2 * x)], -1)
+    return np.clip(c, 0.0, 1.0).astype(np.float32)
 
 
 def config(const_speed=True):
@@ -165,12 +175,14 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--n-lat", type=int, default=632)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--motion-prior", default=None, choices=["const_speed", "depth_icp"], help="only the run, with this prior, merged into --out")
+    ap.add_argument("--motion-prior", default=None, choices=["const_speed", "depth_icp", "rgbd_icp"], help="only the run, with this prior, merged into --out")
     ap.add_argument("--no-const-speed", action="store_true", help="with --motion-prior: tracking.const_speed off (depth_icp then starts from the identity)")
     ap.add_argument("--small-test", default=None, help="JSON object merged into the document (figures of tests/test_gpu_tracked_run.py)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     mesh = syn.room_sphere_mesh(n_lat=args.n_lat, n_lon=2 * args.n_lat)
+    if args.motion_prior == "rgbd_icp" and len(mesh) < 3:               # the photometric term needs an image: colour the bare mesh
+        mesh = (mesh[0], mesh[1], smooth_colours(mesh[0]))
     res = {"image": [1200, 680], "focal": 600.0, "faces": len(mesh[1]), "active_ray": True,
            "reference": "none: the reference's loop needs Habitat-Sim and tiny-cuda-nn, which are not on this stack"}
     if args.motion_prior is not None:
