@@ -14,11 +14,14 @@ constexpr int kMaxSamples = 1024;      // per-ray samples the per-wave LDS scrat
 constexpr int kRaysPerBlock = 4;       // 4 waves per block, one ray each
 
 // torch.linspace (aten RangeFactoriesKernel.cpp): symmetric two-sided formula
+// The multiply-add of an element is ONE rounding, written out as fmaf (as load_point's, naruto_common.h): the clang HIP headers define
+// __fmul_rn / __fadd_rn as the plain operators and hipcc contracts by default, so this is what the separately written multiply and add
+// always compiled to -- stated, it no longer is the compiler's choice at each of the call sites.  tests/sample_z_spec.py is the contract.
 __device__ __forceinline__ float linspace_at(float start, float end, uint32_t steps, uint32_t i) {
     if (steps == 1u) return start;                          // torch.linspace(a, b, 1) == [a]
     const float step = __fdiv_rn(__fsub_rn(end, start), (float)(steps - 1u));
-    if (i < steps / 2u) return __fadd_rn(start, __fmul_rn(step, (float)i));
-    return __fsub_rn(end, __fmul_rn(step, (float)(steps - i - 1u)));
+    if (i < steps / 2u) return fmaf(step, (float)i, start);
+    return fmaf(-step, (float)(steps - i - 1u), end);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -81,7 +84,7 @@ __device__ __forceinline__ float sample_z_jitter(uint32_t n, uint32_t s, uint32_
         const float lo = s == 0 ? zs[0] : 0.5f * (zs[s] + zs[s - 1]);
         const float up = s == S - 1 ? zs[S - 1] : 0.5f * (zs[s + 1] + zs[s]);
         const float r = rand != nullptr ? rand[(size_t)n * S + s] : rng_uniform(key, (uint64_t)n * S + s);
-        v = __fadd_rn(lo, __fmul_rn(__fsub_rn(up, lo), r));
+        v = fmaf(__fsub_rn(up, lo), r, lo);             // (one rounding, as linspace_at's)
     }
     return v;
 }
