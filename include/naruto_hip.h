@@ -1101,8 +1101,47 @@ int naruto_subdivide_emit(uint64_t n_faces, uint64_t n_vertices, const int32_t* 
  *   sim erp         per panorama: six cube planes of depth [6,s,s] (rendered with fx = fy = cx = cy = (s-1)/2; 0 or +inf = nothing hit) and
  *                   optionally colour [6,s,s,3] -> radial distance [n_erp] (1e8 * ray norm where nothing is hit), colour [n_erp,3], and
  *                   stats uint32 [2]: the bit pattern of the minimum distance and the number of pixels with distance > invalid_thre.
- *                   erp_dist, erp_color and stats may each be NULL. */
+ *                   erp_dist, erp_color and stats may each be NULL.
+ *   textures        every texture's mip chain in ONE buffer of RGBA8 words (R in the lowest byte), texture after texture, level after
+ *                   level; desc uint32 [n_textures][4] = word offset of level 0, W, H, n_levels = 1 + floor(log2(max(W, H))).  Level l+1 has
+ *                   max(1, w >> 1) x max(1, h >> 1) texels; per channel, alpha included, texel (x, y) of it is
+ *                   (t(xa,ya) + t(xb,ya) + t(xa,yb) + t(xb,yb) + 2) >> 2 with xa = min(2x, w-1), xb = min(2x+1, w-1), ya and yb likewise.
+ *                   tex bytes: the bytes of ONE texture's chain (0: a side outside 1 .. 16384).  tex build: copies level0 (W x H words,
+ *                   row-major from the first stored row; host or device memory) to word `offset` of texels, builds the texture's levels
+ *                   behind it on the device in integer arithmetic, writes its four descriptor words to desc, and returns when all is
+ *                   done.  All chains together stay below 2^32 words: descriptors hold 32-bit offsets.
+ *   render rgbd tex render rgbd with materials (NarutoSimTextures; every pointer in it is device memory): depth and face id are render
+ *                   rgbd's bits.  The colour of a hit pixel by its face's material face_material[f]:
+ *                     -1 or out of range, or a texture index >= n_textures: render rgbd's vertex colours, in the same bits;
+ *                     a material without a texture (index < 0): factor.rgb;
+ *                     a texture: fp32, each operation rounded, no contraction -- u = (w_a*u_a + w_b*u_b) + w_c*u_c (v likewise) with render
+ *                     rgbd's barycentrics; the same expression at the rays of pixels (i+1, j) and (i, j+1) with the same face's edge values
+ *                     gives (u_x, v_x), (u_y, v_y); ax = (u_x - u)*W, bx = (v_x - v)*H, rx = ax*ax + bx*bx, ry likewise; rho2 = rx, or ry
+ *                     where ry > rx; level = the number of k in 0 .. n_levels-2 with rho2 > 4^k (NaN: 0).  One bilinear tap at that level
+ *                     (w, h): x = u*w - 0.5f, y = v*h - 0.5f; unless |x| < 2^30 and |y| < 2^30 the texel colour is 0; x0 = floor(x),
+ *                     a = x - x0 (y0, b likewise); the indices x0, x0+1, y0, y0+1 wrapped by the axis's mode -- REPEAT 10497 (and any other
+ *                     value): mod w; MIRRORED_REPEAT 33648: m = mod 2w, m < w ? m : 2w-1-m; CLAMP_TO_EDGE 33071: clamp to [0, w-1] --
+ *                     t = byte/255.0f, top = t00 + a*(t10 - t00), bot = t01 + a*(t11 - t01), c = top + b*(bot - top); colour = c * factor.
+ *                   Alpha is stored and ignored: blended and masked materials render opaque.  One level per pixel: no trilinear blend.
+ *                   materials uint32 [n_materials][8] = texture index (int32), wrap_s, wrap_t, 0, factor[4] (float32).  The kernel trusts
+ *                   no index it reads from memory; a NarutoSimTextures whose struct_size is below sizeof(NarutoSimTextures) is refused. */
 #define NARUTO_SIM_KEEP_INF 1u
+typedef struct NarutoSimTextures {
+    uint32_t struct_size;                             /* sizeof(NarutoSimTextures)                                   */
+    uint32_t n_materials, n_textures;
+    uint32_t reserved_;                               /* 0                                                           */
+    uint64_t n_texels;                                /* words in texels                                             */
+    const float* uv;                                  /* [V,2]                                                       */
+    const int32_t* face_material;                     /* [F], -1: none                                               */
+    const uint32_t* materials;                        /* [n_materials][8]                                            */
+    const uint32_t* tex_desc;                         /* [n_textures][4]                                             */
+    const uint32_t* texels;                           /* [n_texels]                                                  */
+} NarutoSimTextures;
+size_t naruto_tex_bytes(uint32_t W, uint32_t H);
+int naruto_tex_build(uint32_t W, uint32_t H, uint64_t offset, const void* level0, uint32_t* desc, uint32_t* texels, void* stream);
+int naruto_render_rgbd_tex(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const void* colors, int colors_f32,
+                           uint32_t n_poses, const float* poses, uint32_t large_threshold, uint32_t flags, void* workspace, float* depth, float* color, int32_t* face_id,
+                           const NarutoSimTextures* tex, void* stream);
 size_t naruto_render_rgbd_workspace(uint64_t n_vertices, uint64_t n_faces, uint32_t n_poses, uint32_t H, uint32_t W);
 int naruto_render_rgbd(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const void* colors, int colors_f32,
                        uint32_t n_poses, const float* poses, uint32_t large_threshold, uint32_t flags, void* workspace, float* depth, float* color, int32_t* face_id,

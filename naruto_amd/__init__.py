@@ -13,7 +13,7 @@ from . import config, synthetic  # noqa: F401
 def __getattr__(name):
     # torch-dependent modules are imported lazily so that `import naruto_amd` stays cheap
     if name in ("ops", "field", "parallel", "trainer", "_lib", "graphed", "ba_loop", "keyframe_store", "active_ray_sampler", "planner_aggregation", "mesh",
-                "tracking", "pose_chain", "rrt", "evaluation", "culling", "simulator", "planner"):
+                "tracking", "pose_chain", "rrt", "evaluation", "culling", "simulator", "planner", "gltf"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "NarutoFieldHIP":

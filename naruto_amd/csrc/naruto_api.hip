@@ -2784,9 +2784,80 @@ size_t naruto_render_rgbd_workspace(uint64_t n_vertices, uint64_t n_faces, uint3
     return cull_ws(n_vertices, n_faces, n_poses, nullptr, H, W).total;
 }
 
+namespace {
+// the texel words of one texture's chain, level 0 included; 0: a side outside 1 .. 16384
+uint64_t tex_chain_words(uint32_t w, uint32_t h, uint32_t* n_levels) {
+    if (w == 0 || h == 0 || w > kSimTexMaxSide || h > kSimTexMaxSide) return 0;
+    uint64_t words = 0;
+    uint32_t levels = 0;
+    for (;;) {
+        words += (uint64_t)w * h;
+        ++levels;
+        if (w == 1u && h == 1u) break;
+        w = std::max(1u, w >> 1); h = std::max(1u, h >> 1);
+    }
+    if (n_levels != nullptr) *n_levels = levels;                 // = 1 + floor(log2(max(W, H)))
+    return words;
+}
+}  // namespace
+
+size_t naruto_tex_bytes(uint32_t W, uint32_t H) { return (size_t)(tex_chain_words(W, H, nullptr) * 4u); }
+
+int naruto_tex_build(uint32_t W, uint32_t H, uint64_t offset, const void* level0, uint32_t* desc, uint32_t* texels, void* stream) {
+    if (level0 == nullptr || desc == nullptr || texels == nullptr) return fail(NARUTO_ERR_INVALID, "tex_build: NULL argument");
+    uint32_t levels = 0;
+    const uint64_t words = tex_chain_words(W, H, &levels);
+    if (words == 0 || offset + words >= (1ull << 32))
+        return fail(NARUTO_ERR_INVALID, "tex_build: a texture of %u x %u at word %llu (sides 1 .. 16384, all chains within 2^32 words)", W, H, (unsigned long long)offset);
+    hipStream_t st = (hipStream_t)stream;
+    // level 0 from wherever it lies, then the chain on the stream; the call returns when all is done, so the source may be freed
+    if (hipMemcpyAsync(texels + offset, level0, (size_t)W * H * 4u, hipMemcpyDefault, st) != hipSuccess) return check_launch("tex_build: upload");
+    uint32_t w = W, h = H;
+    uint64_t at = offset;
+    for (uint32_t l = 1; l < levels; ++l) {
+        const uint32_t wd = std::max(1u, w >> 1), hd = std::max(1u, h >> 1);
+        hipLaunchKernelGGL(k_tex_down, dim3((wd * hd + kSimThreads - 1u) / kSimThreads), dim3(kSimThreads), 0, st, w, h, wd, hd, texels + at, texels + at + (uint64_t)w * h);
+        if (int rc = check_launch("tex_down")) return rc;
+        at += (uint64_t)w * h;
+        w = wd; h = hd;
+    }
+    const uint32_t d[4] = {(uint32_t)offset, W, H, levels};
+    if (hipMemcpyAsync(desc, d, sizeof(d), hipMemcpyHostToDevice, st) != hipSuccess) return check_launch("tex_build: descriptor");
+    if (hipStreamSynchronize(st) != hipSuccess) return check_launch("tex_build: synchronise");
+    return NARUTO_OK;
+}
+
+namespace {
+int sim_render(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const void* colors, int colors_f32,
+               uint32_t n_poses, const float* poses, uint32_t large_threshold, uint32_t flags, void* workspace, float* depth, float* color, int32_t* face_id,
+               const NarutoSimTextures* tex, void* stream);
+}  // namespace
+
 int naruto_render_rgbd(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const void* colors, int colors_f32,
                        uint32_t n_poses, const float* poses, uint32_t large_threshold, uint32_t flags, void* workspace, float* depth, float* color, int32_t* face_id,
                        void* stream) {
+    return sim_render(cam, n_vertices, vertices, n_faces, faces, colors, colors_f32, n_poses, poses, large_threshold, flags, workspace, depth, color, face_id,
+                      nullptr, stream);
+}
+
+int naruto_render_rgbd_tex(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const void* colors, int colors_f32,
+                           uint32_t n_poses, const float* poses, uint32_t large_threshold, uint32_t flags, void* workspace, float* depth, float* color, int32_t* face_id,
+                           const NarutoSimTextures* tex, void* stream) {
+    if (tex == nullptr) return fail(NARUTO_ERR_INVALID, "render_rgbd_tex: NULL textures");
+    if (tex->struct_size < sizeof(NarutoSimTextures))
+        return fail(NARUTO_ERR_INVALID, "render_rgbd_tex: NarutoSimTextures of %u bytes, this library reads %zu", tex->struct_size, sizeof(NarutoSimTextures));
+    if (tex->uv == nullptr || tex->face_material == nullptr || (tex->n_materials != 0 && tex->materials == nullptr) ||
+        (tex->n_textures != 0 && (tex->tex_desc == nullptr || tex->texels == nullptr)))
+        return fail(NARUTO_ERR_INVALID, "render_rgbd_tex: NULL uv, face materials, material table, descriptors or texels");
+    if (tex->n_texels >= (1ull << 32)) return fail(NARUTO_ERR_INVALID, "render_rgbd_tex: 2^32 texels or more");
+    return sim_render(cam, n_vertices, vertices, n_faces, faces, colors, colors_f32, n_poses, poses, large_threshold, flags, workspace, depth, color, face_id,
+                      tex, stream);
+}
+
+namespace {
+int sim_render(const NarutoCullCam* cam, uint64_t n_vertices, const float* vertices, uint64_t n_faces, const int32_t* faces, const void* colors, int colors_f32,
+               uint32_t n_poses, const float* poses, uint32_t large_threshold, uint32_t flags, void* workspace, float* depth, float* color, int32_t* face_id,
+               const NarutoSimTextures* tex, void* stream) {
     if (int rc = cull_cam_check(cam, "render_rgbd")) return rc;
     if (!(cam->near_ > 0.0f) || !(cam->near_ < cam->far_)) return fail(NARUTO_ERR_INVALID, "render_rgbd: need 0 < near < far");
     if (int rc = cull_raster_sizes_check(cam, n_vertices, n_faces, n_poses, "render_rgbd")) return rc;
@@ -2810,10 +2881,18 @@ int naruto_render_rgbd(const NarutoCullCam* cam, uint64_t n_vertices, const floa
     if (int rc = check_launch("sim_raster_small")) return rc;
     hipLaunchKernelGGL(k_cull_raster_large<unsigned long long>, dim3(kCullLargeGrid), block, 0, st, c, nf, nv, faces, w.camv, cells, w.counter, w.ent_id, w.ent_start, cap);
     if (int rc = check_launch("sim_raster_large")) return rc;
-    hipLaunchKernelGGL(k_sim_shade, dim3((n_px + kSimThreads - 1u) / kSimThreads, n_poses), dim3(kSimThreads), 0, st, c, nf, nv, faces, colors, colors_f32, w.camv, cells,
-                       (int)(flags & NARUTO_SIM_KEEP_INF), depth, color, face_id);
-    return check_launch("sim_shade");
+    const dim3 shade_grid((n_px + kSimThreads - 1u) / kSimThreads, n_poses);
+    if (tex == nullptr) {
+        hipLaunchKernelGGL(k_sim_shade, shade_grid, dim3(kSimThreads), 0, st, c, nf, nv, faces, colors, colors_f32, w.camv, cells, (int)(flags & NARUTO_SIM_KEEP_INF), depth, color,
+                           face_id);
+        return check_launch("sim_shade");
+    }
+    const SimTex t{tex->n_materials, tex->n_textures, (unsigned long long)tex->n_texels, tex->uv, tex->face_material, tex->materials, tex->tex_desc, tex->texels};
+    hipLaunchKernelGGL(k_sim_shade_tex, shade_grid, dim3(kSimThreads), 0, st, c, nf, nv, faces, colors, colors_f32, w.camv, cells, (int)(flags & NARUTO_SIM_KEEP_INF), t, depth,
+                       color, face_id);
+    return check_launch("sim_shade_tex");
 }
+}  // namespace
 
 int naruto_cube_to_erp(uint32_t n_channels, uint32_t face_w, uint64_t n_erp, const int32_t* table, const void* cube, void* erp, void* stream) {
     if (n_channels == 0 || n_erp == 0) return NARUTO_OK;

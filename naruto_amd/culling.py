@@ -105,7 +105,7 @@ def _poses(poses) -> torch.Tensor:
 def _as_mesh(mesh):
     """Mesh | (vertices, faces[, colors]) | path -> (vertices, faces, colors or None, kind) with kind 'mesh' or 'tuple'."""
     if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
-        mesh = M.load_ply(mesh)
+        mesh = M.Mesh.load(mesh)
     if isinstance(mesh, M.Mesh):
         return mesh.vertices, mesh.faces, mesh.vertex_colors, "mesh"
     if not isinstance(mesh, (tuple, list)) or len(mesh) not in (2, 3):
@@ -220,7 +220,7 @@ def cull_mesh(mesh, poses, cam: Dict, bounds=None, remove_occlusion: bool = True
               pose_chunk: int = 8, plan=None, max_edge: Optional[float] = None, max_iter: int = RM.DEFAULT_MAX_ITER, max_faces: int = RM.DEFAULT_MAX_FACES):
     """The culled mesh (module docstring); with ``max_edge`` the subdivided, culled one (step 0; ``max_iter``, ``max_faces``:
     :func:`naruto_amd.remesh.subdivide_to_size`), as the protocol's output file is; ``max_edge=None`` launches what it always launched.
-    ``mesh``: a :class:`naruto_amd.mesh.Mesh` or the path of a ``.ply`` -> a Mesh (float64 vertices, int64 faces, colours carried along); a tuple (vertices, faces[, colors RGBA8 [V,4]]) of arrays or device tensors -> the same tuple
+    ``mesh``: a :class:`naruto_amd.mesh.Mesh` or the path of a ``.ply`` (or of a ``.glb`` / ``.gltf``: its geometry) -> a Mesh (float64 vertices, int64 faces, colours carried along); a tuple (vertices, faces[, colors RGBA8 [V,4]]) of arrays or device tensors -> the same tuple
     as device tensors (vertices in their own dtype, faces int32), so a caller can stay on the device.  The loop over the pose chunks has
     no host synchronisation; one copy of two numbers at the end reads the kept counts (the subdivision reads two more per generation)."""
     return _cull(mesh, poses, cam, bounds, remove_occlusion, occluder, eps, near, far, pose_chunk, plan, max_edge, max_iter, max_faces)[0]
@@ -336,11 +336,11 @@ def main(argv=None) -> str:
     parser.add_argument("--max_edge", type=float, default=None, help="subdivide to this edge length (metres) before culling; the protocol's tool uses 0.015; off when absent")
     parser.add_argument("--max_iter", type=int, default=RM.DEFAULT_MAX_ITER, help="generations of subdivision at the most")
     args = parser.parse_args(argv)
-    if not args.input_mesh.lower().endswith(".ply"):
-        raise ValueError(f"{args.input_mesh}: only .ply meshes are read")
+    if not args.input_mesh.lower().endswith((".ply", ".glb", ".gltf")):
+        raise ValueError(f"{args.input_mesh}: only .ply, .glb and .gltf meshes are read")
     cfg = cfgmod.load_config(args.config)
     poses, bounds = to_metric(cfg, poses_from_checkpoint(args.ckpt_path), cfg.get("mapping", {}).get("marching_cubes_bound"))
-    mesh, sub = _cull(M.load_ply(args.input_mesh), poses, cfg["cam"], bounds, args.remove_occlusion, None, 0.03, 0.01, 10.0, 8, None, args.max_edge, args.max_iter,
+    mesh, sub = _cull(M.Mesh.load(args.input_mesh), poses, cfg["cam"], bounds, args.remove_occlusion, None, 0.03, 0.01, 10.0, 8, None, args.max_edge, args.max_iter,
                       RM.DEFAULT_MAX_FACES)
     out = culled_path(args.input_mesh, args.remove_occlusion)
     mesh.export(out)

@@ -87,7 +87,7 @@ def _device(device=None) -> torch.device:
 def _mesh_tensors(mesh, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Mesh | (vertices, faces) | path -> (vertices float32 or float64 [V,3], faces int32 [F,3]), contiguous on the device."""
     if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
-        mesh = M.load_ply(mesh)
+        mesh = M.Mesh.load(mesh)
     if isinstance(mesh, M.Mesh):
         mesh = (mesh.vertices, mesh.faces)
     v, f = mesh
@@ -326,7 +326,7 @@ def icp(source, target, max_correspondence_distance: float = 0.1, max_iteration:
 
 def _mesh_vertices(mesh):
     if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
-        mesh = M.load_ply(mesh)
+        mesh = M.Mesh.load(mesh)
     return mesh.vertices if isinstance(mesh, M.Mesh) else mesh[0]
 
 
@@ -354,7 +354,7 @@ class ReconEvaluatorHIP:
 
     def __init__(self, gt_mesh, n_samples: int = 200000, threshold: float = 0.05, seed: int = 0, device=None, **grid_args):
         if isinstance(gt_mesh, (str, bytes)) or hasattr(gt_mesh, "__fspath__"):
-            gt_mesh = M.load_ply(gt_mesh)
+            gt_mesh = M.Mesh.load(gt_mesh)
         if _n_faces(gt_mesh) == 0:
             raise ValueError("ReconEvaluatorHIP: the ground-truth mesh has no faces")
         v, f = _mesh_tensors(gt_mesh, device)
@@ -440,7 +440,7 @@ def calc_3d_mesh_metric(mesh_gt, mesh_rec, n_samples: int = 200000, threshold: f
     """Accuracy / Completion / Completion ratio of ``mesh_rec`` against ``mesh_gt`` (module docstring).  Either mesh is a
     ``naruto_amd.mesh.Mesh``, a (vertices, faces) tuple of numpy arrays or device tensors, or the path of a ``.ply`` file.  ``align``:
     ``mesh_rec`` is first moved onto ``mesh_gt`` (``ReconEvaluatorHIP.evaluate_mesh``)."""
-    load = lambda m: M.load_ply(m) if isinstance(m, (str, bytes)) or hasattr(m, "__fspath__") else m      # noqa: E731
+    load = lambda m: M.Mesh.load(m) if isinstance(m, (str, bytes)) or hasattr(m, "__fspath__") else m      # noqa: E731
     mesh_gt, mesh_rec = load(mesh_gt), load(mesh_rec)
     if _n_faces(mesh_gt) == 0:
         raise ValueError("calc_3d_mesh_metric: the ground-truth mesh has no faces")
@@ -518,8 +518,8 @@ def main(argv=None) -> Dict[str, float]:
         raise NotImplementedError("--align: the reference's get_align_transformation is third-party code outside its tree; --icp_align runs this library's "
                                   "restatement of it (point-to-point ICP of the vertices)")
     for path in (args.rec_mesh, args.gt_mesh):
-        if not path.lower().endswith(".ply"):
-            raise ValueError(f"{path}: only .ply meshes are read (.obj scenes are not)")
+        if not path.lower().endswith((".ply", ".glb", ".gltf")):
+            raise ValueError(f"{path}: only .ply, .glb and .gltf meshes are read (.obj scenes are not)")
     result = calc_3d_mesh_metric(args.gt_mesh, args.rec_mesh, align=True) if args.icp_align else calc_3d_mesh_metric(args.gt_mesh, args.rec_mesh)
     print(result)
     if args.result_txt:

@@ -22,8 +22,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from dataclasses import dataclass
-from typing import Callable, Optional, Tuple
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -93,8 +93,33 @@ class Mesh:
             f.write(face.tobytes())
 
     @staticmethod
-    def load(path: str) -> "Mesh":
+    def load(path: str, frame: str = "gltf") -> "Mesh":
+        """By the extension: ``.glb`` / ``.gltf`` -> :class:`TexturedMesh` (``naruto_amd.gltf.load_gltf``; ``frame`` is its argument);
+        anything else is read as a PLY."""
+        if os.fsdecode(path).lower().endswith((".glb", ".gltf")):
+            from .gltf import load_gltf
+            return load_gltf(path, frame)
         return load_ply(path)
+
+
+@dataclass
+class Material:
+    """A base colour: ``texture`` indexes ``TexturedMesh.textures`` (-1: none, the colour is ``factor``'s rgb); ``wrap_s`` / ``wrap_t`` are
+    glTF's sampler modes (10497 REPEAT, 33648 MIRRORED_REPEAT, 33071 CLAMP_TO_EDGE); ``factor`` multiplies the texel (RGBA)."""
+    texture: int = -1
+    wrap_s: int = 10497
+    wrap_t: int = 10497
+    factor: Tuple[float, float, float, float] = (1.0, 1.0, 1.0, 1.0)
+
+
+@dataclass
+class TexturedMesh(Mesh):
+    """A :class:`Mesh` with base-colour materials (``naruto_amd.gltf.load_gltf`` makes one; tests build them from arrays).  A face without
+    a material (-1) is coloured by ``vertex_colors``.  ``export`` writes the geometry and the vertex colours only."""
+    uv: Optional[np.ndarray] = None                  # float32 [V,2], glTF's convention: (0, 0) is the corner of the image's first row
+    face_material: Optional[np.ndarray] = None       # int32 [F], -1: none
+    materials: List[Material] = field(default_factory=list)
+    textures: List[np.ndarray] = field(default_factory=list)        # uint8 [H,W,4] each
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",

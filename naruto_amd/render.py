@@ -38,7 +38,7 @@ H or W is below 11.
 
 Command line::
 
-    python -m naruto_amd.render --config <coslam.yaml> --ckpt <ckpt.pt> --mesh <scene.ply> (--traj traj.txt | --poses)
+    python -m naruto_amd.render --config <coslam.yaml> --ckpt <ckpt.pt> --mesh <scene.ply | scene.glb | scene.gltf> (--traj traj.txt | --poses)
                                 --out_dir D [--every K] [--png] [--result_txt results.txt]
 
 renders every K-th pose of the trajectory file (``--traj``) or of the checkpoint (``--poses``), writes the image stacks as ``.npy`` (with
@@ -336,7 +336,8 @@ def parse_args(argv=None):
     parser = argparse.ArgumentParser(prog="python -m naruto_amd.render", description="Render views of a checkpoint's field and score them against a mesh.")
     parser.add_argument("--config", type=str, required=True, help="Co-SLAM yaml config")
     parser.add_argument("--ckpt", type=str, required=True, help="checkpoint written by save_ckpt")
-    parser.add_argument("--mesh", type=str, required=True, help="ground-truth mesh the simulator renders (.ply)")
+    parser.add_argument("--mesh", type=str, required=True, help="ground-truth mesh the simulator renders (.ply, or a textured .glb / .gltf)")
+    parser.add_argument("--mesh_frame", type=str, default="gltf", choices=["gltf", "mp3d"], help="a glTF scene's frame: as stored, or MP3D's (x, y, z) -> (x, -z, y)")
     src = parser.add_mutually_exclusive_group(required=True)
     src.add_argument("--traj", type=str, help="Replica trajectory file with the poses to render")
     src.add_argument("--poses", action="store_true", help="render the checkpoint's own poses")
@@ -348,8 +349,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.every < 1:
         parser.error("--every must be positive")
-    if not args.mesh.lower().endswith(".ply"):
-        parser.error(f"--mesh {args.mesh}: only .ply meshes are read")
+    if not args.mesh.lower().endswith((".ply", ".glb", ".gltf")):
+        parser.error(f"--mesh {args.mesh}: only .ply, .glb and .gltf meshes are read")
     return args
 
 
@@ -363,7 +364,7 @@ def main(argv=None) -> Dict:
     model = field_from_checkpoint(args.ckpt, cfg)
     poses = (load_replica_traj(args.traj) if args.traj else CU.poses_from_checkpoint(args.ckpt))[::args.every]
     cam = view_camera(cfg)
-    sim = MeshSimHIP(args.mesh, cam, device=model.embed_fn.params.device)
+    sim = MeshSimHIP(args.mesh, cam, device=model.embed_fn.params.device, mesh_frame=args.mesh_frame)
     sc = float(cfg["data"]["sc_factor"])
     gt_rgb, gt_depth = sim.simulate_batch(CU.to_metric(cfg, CU._poses(poses))[0])[:2]
     views = FieldViewRendererHIP(model, cfg).render(poses, target_depth=gt_depth * sc if args.depth_guided else None)

@@ -9,7 +9,8 @@ pose of step i is the trajectory's and the planner is skipped.
 
 Command line::
 
-    python -m naruto_amd.run --config <coslam.yaml> --mesh <scene.ply> --num_iter N --result_dir D [--start x y z] [--traj traj.txt]
+    python -m naruto_amd.run --config <coslam.yaml> --mesh <scene.ply | scene.glb | scene.gltf> [--mesh_frame gltf|mp3d] --num_iter N --result_dir D [--start x y z]
+        [--traj traj.txt]
                              [--no_active_ray] [--seed S] [--track] [--eval_views K] [--planner key=value ...]
 
 ``--config`` is a Co-SLAM yaml (``naruto_amd.config.load_config``).  The reference's ``.py`` config files are not read: the planner's
@@ -138,7 +139,9 @@ def parse_args(argv=None):
     import argparse
     parser = argparse.ArgumentParser(prog="python -m naruto_amd.run", description="Run an exploration on a mesh: simulate, map, plan.")
     parser.add_argument("--config", type=str, required=True, help="Co-SLAM yaml config (inherit_from chains are followed)")
-    parser.add_argument("--mesh", type=str, required=True, help="scene mesh the simulator renders (.ply)")
+    parser.add_argument("--mesh", type=str, required=True, help="scene mesh the simulator renders (.ply, or a textured .glb / .gltf)")
+    parser.add_argument("--mesh_frame", type=str, default=None, choices=["gltf", "mp3d"],
+                        help="a glTF scene's frame: as stored, or MP3D's (x, y, z) -> (x, -z, y); default: mp3d with --dataset MP3D, else gltf")
     parser.add_argument("--num_iter", type=int, required=True, help="number of steps")
     parser.add_argument("--result_dir", type=str, required=True, help="meshes, checkpoints and results.txt go here")
     parser.add_argument("--start", type=float, nargs=3, metavar=("X", "Y", "Z"), help="start position (identity rotation); default: the bound's centre")
@@ -155,8 +158,10 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.num_iter <= 0:
         parser.error("--num_iter must be positive")
-    if not args.mesh.lower().endswith(".ply"):
-        parser.error(f"--mesh {args.mesh}: only .ply meshes are read")
+    if not args.mesh.lower().endswith((".ply", ".glb", ".gltf")):
+        parser.error(f"--mesh {args.mesh}: only .ply, .glb and .gltf meshes are read")
+    if args.mesh_frame is None:
+        args.mesh_frame = "mp3d" if args.dataset == "MP3D" and args.mesh.lower().endswith((".glb", ".gltf")) else "gltf"
     if args.eval_views is not None and args.eval_views < 1:
         parser.error("--eval_views must be positive")
     if args.traj is not None and args.start is not None:
@@ -181,7 +186,7 @@ def main(argv=None) -> Dict:
     os.makedirs(args.result_dir, exist_ok=True)
     slam = CoSLAMNarutoHIP(cfg, active_ray=not args.no_active_ray, num_frames=args.num_iter, seed=args.seed, result_dir=args.result_dir, track=args.track,
                            motion_prior=args.motion_prior)
-    sim = MeshSimHIP(args.mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=slam.device)
+    sim = MeshSimHIP(args.mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=slam.device, mesh_frame=args.mesh_frame)
     planner = None
     if traj is None:
         planner = NarutoPlannerHIP(dataset=args.dataset, device=slam.device, **args.planner)

@@ -4,14 +4,17 @@ The reference's run loop (src/naruto/main.py) starts every step with ``sim.simul
 planned pose, and -- with ``return_erp`` -- an equirectangular (ERP) colour image and radial-distance map, which the planner's movement
 check reads (``NarutoPlanner.detect_collision_v2``, naruto_planner.py:544-547: ``erp_depth.min()`` and the share of pixels above 1e6).
 Habitat-Sim is an external renderer that is not on this stack.  :class:`MeshSimHIP` renders a mesh instead -- a ground-truth ``.ply``,
-the room-plus-sphere of ``naruto_amd.synthetic``, or a mesh this library extracted -- with the call surface of ``HabitatSim.simulate``.
+a textured ``.glb`` / ``.gltf`` scene (``naruto_amd.gltf``), the room-plus-sphere of ``naruto_amd.synthetic``, or a mesh this library
+extracted -- with the call surface of ``HabitatSim.simulate``.
 
 PARITY UNPINNED against Habitat.  Pinned, by the reference's recorded results (tests/golden/g13_c2e.npz): the cube-to-panorama gather
 (``C2E``, src/layers/c2e.py, through :func:`cube_table`) and ``erp_conversions.depth2dist`` (:func:`depth_to_dist`).  Differences from
 Habitat:
 
-  * colours are the vertex colours interpolated in float32, not 8-bit images; a mesh without colours renders white;
-  * no lighting, no textures, no physics, no objects;
+  * colours are the vertex colours interpolated in float32 or, on faces with a material, its base colour: the factor, times one
+    bilinear tap of the base-colour texture at one mip level; a mesh with neither renders white;
+  * no lighting, no alpha (blended and masked materials render opaque), no trilinear or anisotropic filtering, no texture
+    transform, no physics, no objects;
   * the reference's ``depth2dist`` call uses ``K = face_w / 2``, half a pixel off the grid ``C2E`` samples; the simulator uses the
     consistent ``(face_w - 1) / 2``.  :func:`depth_to_dist` takes any intrinsics;
   * the front half of ``ERPDepth2Dist`` -- six bilinear ``E2P`` resamplings of a Habitat ERP image into cube faces -- is NOT built:
@@ -25,6 +28,17 @@ it in every bit):
   clipping.  Per pixel the nearest hit inside (near, far) wins; among the faces whose depth equals the minimum in every bit, the lowest
   face index.  Colour: perspective-correct barycentrics from the rasteriser's own edge values.  A pixel nothing covers has depth 0
   (Habitat's invalid value; Co-SLAM masks ``depth > 0``), colour 0 and face id -1.
+
+  Materials (a :class:`naruto_amd.mesh.TexturedMesh`): the rasteriser, depth and face id do not change.  A hit pixel's colour by its
+  face's material: -1: the vertex colours, in the untextured render's bits; a material without a texture: factor.rgb; a texture:
+  u = (w_a*u_a + w_b*u_b) + w_c*u_c (v likewise); the same expression at the rays of pixels (i+1, j) and (i, j+1) with the same face's
+  edge values gives (u_x, v_x) and (u_y, v_y); ax = (u_x - u)*W0, bx = (v_x - v)*H0, rx = ax*ax + bx*bx, ry likewise from (u_y, v_y);
+  rho2 = rx, or ry where ry > rx; level = the number of k in 0 .. n_levels-2 with rho2 > 4^k (NaN: level 0; no blend between levels).
+  One bilinear tap at the level's size (w, h), uv (0, 0) the corner of the first stored row: x = u*w - 0.5f, y = v*h - 0.5f; unless
+  |x| < 2^30 and |y| < 2^30 the texel colour is 0; x0 = floor(x), a = x - x0 (y0, b likewise); x0, x0+1, y0, y0+1 wrapped by the
+  axis's mode (REPEAT: mod w; MIRRORED_REPEAT: m = mod 2w, m < w ? m : 2w-1-m; CLAMP_TO_EDGE: clamp); t = byte/255.0f;
+  top = t00 + a*(t10 - t00), bot = t01 + a*(t11 - t01), c = top + b*(bot - top); colour = c * factor.  Alpha is stored and ignored.
+  The mip chains: :func:`texture_pyramid`.  tests/sim_texture_spec.py restates all of it.
 
   Cube faces, in the reference's order F R B L U D, each a ``face_w`` x ``face_w`` pinhole image with fx = fy = cx = cy = (face_w-1)/2
   (pixel i at tangent -1 + 2i/(face_w-1), as C2E assumes) and pose ``c2w @ R_face``; right, up and view vectors in the camera frame:
@@ -175,6 +189,83 @@ def _colors(colors, n_vertices: int):
     return c.reshape(-1, 3).to(torch.float32), True
 
 
+WRAP_MODES = (10497, 33648, 33071)                     # glTF's REPEAT, MIRRORED_REPEAT, CLAMP_TO_EDGE
+MAX_TEXTURE_SIDE = 16384
+MAX_UV = 1024.0
+
+
+def _images(images):
+    """-> [uint8 [H,W,4] contiguous host arrays], checked."""
+    out = []
+    for k, im in enumerate(images):
+        a = im.cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4 or not (1 <= a.shape[0] <= MAX_TEXTURE_SIDE and 1 <= a.shape[1] <= MAX_TEXTURE_SIDE):
+            raise ValueError(f"simulator: texture {k} is {a.dtype} {a.shape}: uint8 [H,W,4] with sides 1 .. {MAX_TEXTURE_SIDE}")
+        out.append(np.ascontiguousarray(a))
+    if not out:
+        raise ValueError("simulator: no texture")
+    return out
+
+
+def texture_pyramid(images, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Textures (uint8 [H,W,4] each) -> (texels int32 [n_words], desc int32 [n,4]) on the device: every texture's mip chain in one buffer
+    of RGBA8 words (R in the lowest byte), level after level, built on the device in integers -- level l+1 is max(1, w >> 1) x
+    max(1, h >> 1), each channel (t(xa,ya) + t(xb,ya) + t(xa,yb) + t(xb,yb) + 2) >> 2 over xa = min(2x, w-1), xb = min(2x+1, w-1) and ya,
+    yb likewise; desc = word offset of level 0, W, H, n_levels = 1 + floor(log2(max(W, H)))."""
+    ims = _images(images)
+    device = _device(device)
+    lib = _lib.load()
+    words = [lib.naruto_tex_bytes(a.shape[1], a.shape[0]) // 4 for a in ims]
+    if sum(words) >= 2 ** 32:
+        raise ValueError("simulator: the textures' mip chains must hold fewer than 2^32 texels")
+    texels = torch.empty(sum(words), dtype=torch.int32, device=device)
+    desc = torch.empty(len(ims), 4, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        off = 0
+        for k, a in enumerate(ims):
+            check(lib.naruto_tex_build(a.shape[1], a.shape[0], off, a.ctypes.data, desc[k].data_ptr(), texels.data_ptr(), CU._stream()), "naruto_tex_build")
+            off += words[k]
+    return texels, desc
+
+
+class _Textures:
+    """The material side of a :class:`naruto_amd.mesh.TexturedMesh` on the device, validated on the host: ``struct`` is the
+    ``NarutoSimTextures`` the render takes (this object keeps its tensors alive)."""
+
+    def __init__(self, mesh, n_vertices: int, n_faces: int, device):
+        fm = np.asarray(mesh.face_material)
+        if fm.shape != (n_faces,) or fm.dtype.kind not in "iu":
+            raise ValueError(f"simulator: face_material is one integer per face ({fm.shape} for {n_faces} faces)")
+        n_mat = len(mesh.materials)
+        if int(fm.min()) < -1 or int(fm.max()) >= n_mat:
+            raise ValueError(f"simulator: face material out of range ({int(fm.min())} .. {int(fm.max())} for {n_mat} materials; -1: none)")
+        uv = np.asarray(mesh.uv if mesh.uv is not None else np.zeros((n_vertices, 2)), dtype=np.float32)
+        if uv.shape != (n_vertices, 2):
+            raise ValueError(f"simulator: uv is [V,2] ({uv.shape} for {n_vertices} vertices)")
+        if not np.isfinite(uv).all() or float(np.abs(uv).max(initial=0.0)) > MAX_UV:
+            raise ValueError(f"simulator: uv must be finite with |uv| <= {MAX_UV:g}")
+        n_tex = len(mesh.textures)
+        table = np.zeros((n_mat, 8), dtype=np.uint32)
+        for k, m in enumerate(mesh.materials):
+            tex, ws, wt, factor = (m.texture, m.wrap_s, m.wrap_t, m.factor) if hasattr(m, "texture") else m
+            factor = np.asarray(factor, dtype=np.float32).reshape(-1)
+            if int(tex) < -1 or int(tex) >= n_tex:
+                raise ValueError(f"simulator: material {k} names texture {tex} of {n_tex} (-1: none)")
+            if int(ws) not in WRAP_MODES or int(wt) not in WRAP_MODES:
+                raise ValueError(f"simulator: material {k} has wrap modes {ws}, {wt} (10497, 33648 or 33071)")
+            if factor.shape != (4,) or not np.isfinite(factor).all():
+                raise ValueError(f"simulator: material {k}'s factor is four finite numbers")
+            table[k, 0], table[k, 1], table[k, 2] = np.int32(tex).astype(np.uint32), int(ws), int(wt)
+            table[k, 4:] = factor.view(np.uint32)
+        self.uv = torch.from_numpy(uv.copy()).to(device).contiguous()
+        self.face_material = torch.from_numpy(fm.astype(np.int32)).to(device).contiguous()
+        self.materials = torch.from_numpy(table.view(np.int32)).to(device).contiguous()
+        self.texels, self.desc = texture_pyramid(mesh.textures, device) if n_tex else (None, None)
+        ptr = lambda t: t.data_ptr() if t is not None else None                                                   # noqa: E731
+        self.struct = _lib.NarutoSimTextures(C.sizeof(_lib.NarutoSimTextures), n_mat, n_tex, 0, self.texels.numel() if n_tex else 0, self.uv.data_ptr(),
+                                             self.face_material.data_ptr(), ptr(self.materials) if n_mat else None, ptr(self.desc), ptr(self.texels))
+
+
 class _RasterRGBD:
     """Workspace and arguments of the RGB-D render of one camera, reused over the calls."""
 
@@ -190,6 +281,11 @@ class _RasterRGBD:
         """poses [B,4,4] float32 on the device, B <= chunk -> depth [B,H,W], color [B,H,W,3], face_id [B,H,W] (each optional)."""
         s = self.sim
         ptr = lambda t: t.data_ptr() if t is not None else None                                                   # noqa: E731
+        if s.tex is not None:
+            check(_lib.load().naruto_render_rgbd_tex(C.byref(self.cam), len(s.v), s.v.data_ptr(), len(s.f), s.f.data_ptr(), s.col.data_ptr(), int(s.col_f32), len(poses),
+                                                     poses.data_ptr(), s.threshold, _lib.SIM_KEEP_INF if keep_inf else 0, self.ws.data_ptr(), ptr(depth), ptr(color),
+                                                     ptr(face_id), C.byref(s.tex.struct), CU._stream()), "naruto_render_rgbd_tex")
+            return
         check(_lib.load().naruto_render_rgbd(C.byref(self.cam), len(s.v), s.v.data_ptr(), len(s.f), s.f.data_ptr(), s.col.data_ptr(), int(s.col_f32), len(poses),
                                              poses.data_ptr(), s.threshold, _lib.SIM_KEEP_INF if keep_inf else 0, self.ws.data_ptr(), ptr(depth), ptr(color), ptr(face_id),
                                              CU._stream()), "naruto_render_rgbd")
@@ -202,12 +298,12 @@ class _RasterRGBD:
 
 
 class MeshSimHIP:
-    """``HabitatSim`` over a mesh (module docstring).  ``mesh``: a :class:`naruto_amd.mesh.Mesh`, the path of a ``.ply`` or a tuple
-    (vertices, faces[, colors]) with colours RGBA8 [V,4] or float [V,3]; uploaded once.  ``cam``: H, W, fx, fy, cx, cy of the pinhole
+    """``HabitatSim`` over a mesh (module docstring).  ``mesh``: a :class:`naruto_amd.mesh.Mesh` or ``TexturedMesh``, the path of a ``.ply``, ``.glb`` or ``.gltf``
+    (``mesh_frame``: ``naruto_amd.gltf.load_gltf``'s ``frame``) or a tuple (vertices, faces[, colors]) with colours RGBA8 [V,4] or float [V,3]; uploaded once.  ``cam``: H, W, fx, fy, cx, cy of the pinhole
     sensor (``config["cam"]``).  ``erp_hw``, ``face_w``: the panorama and the cube faces it is gathered from.  ``plan``: a
     :class:`naruto_amd.culling.RasterPlan`; no bit of any result depends on it."""
 
-    def __init__(self, mesh, cam: Dict, erp_hw: Tuple[int, int] = (1024, 2048), face_w: int = 512, near: float = 0.01, far: float = 100.0, device=None, plan=None):
+    def __init__(self, mesh, cam: Dict, erp_hw: Tuple[int, int] = (1024, 2048), face_w: int = 512, near: float = 0.01, far: float = 100.0, device=None, plan=None, mesh_frame: str = "gltf"):
         self.cam_dict = dict(cam)
         self.cam = CU._camera(cam, near, far)
         self.h, self.w = (int(x) for x in erp_hw)
@@ -216,6 +312,9 @@ class MeshSimHIP:
         k = (self.face_w - 1) / 2.0
         self.cube_cam = CU._camera({"H": self.face_w, "W": self.face_w, "fx": k, "fy": k, "cx": k, "cy": k}, near, far)
         self.threshold = CU._threshold(plan)
+        if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
+            from .mesh import Mesh
+            mesh = Mesh.load(mesh, mesh_frame)
         vertices, faces, colors, _ = CU._as_mesh(mesh)
         col, self.col_f32 = _colors(colors, torch.as_tensor(vertices).numel() // 3)
         v, self.f = CU._geometry(vertices, faces, device)
@@ -224,6 +323,9 @@ class MeshSimHIP:
         self.device = v.device
         self.v = v.to(torch.float32)
         self.col = col.to(self.device).contiguous()
+        # materials: only a mesh that has a face with one takes the textured shade; any other goes through the launches it always did
+        fm = getattr(mesh, "face_material", None)
+        self.tex = _Textures(mesh, len(self.v), len(self.f), self.device) if fm is not None and len(fm) and int(np.asarray(fm).max()) >= 0 else None
         self.table = torch.from_numpy(table).to(self.device).reshape(-1).contiguous()
         self.face_rot = torch.from_numpy(face_rotations()).to(torch.float32)                # (host: face poses are made before the upload)
         self._rasters: Dict[Tuple[str, int], _RasterRGBD] = {}
