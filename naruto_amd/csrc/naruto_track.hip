@@ -36,12 +36,15 @@ struct TrackArgs {
     float* trace_loss; float* trace_pose; float* trace_d_pose; uint32_t max_trace;
 };
 
-// rays_o[r] = t, rays_d[r] = R d_cam[r] in fp32, in the order of coslam.py:343 (torch.sum(d[..., None, :] * R, -1))
+// rays_o[r] = t, rays_d[r] = R d_cam[r] in fp32, in the order of coslam.py:343 (torch.sum(d[..., None, :] * R, -1)): three rounded
+// products added left to right.  Contraction is switched off for it: the clang HIP headers define __fmul_rn / __fadd_rn as the plain
+// operators, and hipcc fused the first two terms into one fma (tests/tracking_spec.py: rays_from_pose is the contract)
 __device__ __forceinline__ void track_write_ray(const TrackArgs& a, uint32_t r, const float Rf[9], const float t[3]) {
+#pragma clang fp contract(off)
     const float dx = a.d_cam[3 * (size_t)r], dy = a.d_cam[3 * (size_t)r + 1], dz = a.d_cam[3 * (size_t)r + 2];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        a.rays_d[3 * (size_t)r + i] = __fadd_rn(__fadd_rn(__fmul_rn(dx, Rf[3 * i]), __fmul_rn(dy, Rf[3 * i + 1])), __fmul_rn(dz, Rf[3 * i + 2]));
+        a.rays_d[3 * (size_t)r + i] = (dx * Rf[3 * i] + dy * Rf[3 * i + 1]) + dz * Rf[3 * i + 2];
         a.rays_o[3 * (size_t)r + i] = t[i];
     }
 }

@@ -268,20 +268,20 @@ class TrackerHIP:
                 self._run(rand)
         return self.c2w.clone()
 
-    def track_device(self, direction, rgb, depth) -> torch.Tensor:
+    def track_device(self, direction, rgb, depth, rand: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One frame whose initial pose is ALREADY in ``self.pose_init`` as (omega, t) -- ``pose_chain.pose_predict(est, i, const_speed,
         tracker.pose_init)`` wrote it on the device: only the frame is copied, then the captured call is replayed (or run).  Nothing
         goes to the host.  Returns ``self.c2w`` itself, the [4,4] buffer the next call overwrites (``pose_chain.pose_commit`` reads it on
-        the same stream)."""
+        the same stream).  ``rand``: as in ``track`` (an eager run with the caller's depth jitter)."""
         check_frame(direction, rgb, depth, self.H, self.W)
         with torch.no_grad():
             self.direction.copy_(direction)
             self.rgb.copy_(rgb)
             self.depth.copy_(depth)
-            if self._graph is not None:
+            if self._graph is not None and rand is None:
                 self._graph.replay()
             else:
-                self._run(None)
+                self._run(rand)
         return self.c2w
 
     def capture(self, warmup: int = 1):

@@ -12,7 +12,7 @@ import helpers as H
 from naruto_amd import synthetic as syn
 from naruto_amd import trainer
 from naruto_amd import tracking as TK
-from oracle import spec_torch as S
+from tracking_spec import oracle_track as _oracle_track, schedule as _schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -96,53 +96,6 @@ def _err(c2w, true):
 def _gathered(trk, frame):
     pix = trk.drawn_pixels()
     return frame[0].reshape(-1, 3)[pix], frame[1].reshape(-1, 3)[pix], frame[2].reshape(-1)[pix]
-
-
-def _oracle_track(ora, cfg, d_cam, rgb, dep, pose0, rand):
-    """The contract in torch: rays from (omega, t), the oracle's training forward and total loss, best-pose bookkeeping, torch Adam."""
-    tk = cfg["tracking"]
-    w = pose0[:3].clone().requires_grad_(True)
-    t = pose0[3:].clone().requires_grad_(True)
-    opt = torch.optim.Adam([{"params": [w], "lr": tk["lr_rot"]}, {"params": [t], "lr": tk["lr_trans"]}], betas=(0.9, 0.999), eps=1e-8)
-    poses, losses, grads = [], [], []
-    best, best_pose, thresh, last = None, None, 0, None
-    ora.train()
-    for i in range(tk["iter"]):
-        opt.zero_grad()
-        rays_d = torch.sum(d_cam[..., None, :] * TK.axis_angle_to_matrix(w)[None], -1)
-        rays_o = t[None].expand(d_cam.shape[0], 3)
-        ret = ora.forward(rays_o, rays_d, rgb, dep[:, None], rand=rand[i])
-        loss = S.total_loss(ret, cfg["training"])
-        last = torch.cat([w, t]).detach().clone()
-        poses.append(last)
-        losses.append(float(loss))
-        if i == 0:
-            best, best_pose = float(loss), last
-        if float(loss) < best:
-            best, best_pose, thresh = float(loss), last, 0
-        else:
-            thresh += 1
-        if thresh > tk["wait_iters"]:
-            break
-        loss.backward()
-        grads.append(torch.cat([w.grad, t.grad]).detach().clone())
-        opt.step()
-    return {"poses": poses, "losses": losses, "grads": grads, "result": best_pose if tk["best"] else last}
-
-
-def _schedule(losses, poses, wait_iters, best_flag):
-    """Co-SLAM's bookkeeping over recorded losses (fp32 values compared as the device compares them)."""
-    best, best_pose, thresh = None, None, 0
-    for i, L in enumerate(losses):
-        if i == 0:
-            best, best_pose = L, poses[0]
-        if L < best:
-            best, best_pose, thresh = L, poses[i], 0
-        else:
-            thresh += 1
-        if thresh > wait_iters:
-            return {"stopped": True, "n": i + 1, "best_pose": best_pose, "thresh": thresh, "result": best_pose if best_flag else poses[i]}
-    return {"stopped": False, "n": len(losses), "best_pose": best_pose, "thresh": thresh, "result": best_pose if best_flag else poses[-1]}
 
 
 # --------------------------------------------------------------------------------------------- 1. against the oracle
