@@ -695,6 +695,53 @@ int naruto_odom_rgbd_frame_maps(const NarutoOdomDesc* desc, const float* depth, 
 int naruto_odom_rgbd_accumulate(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* maps_prev, const float* maps_cur,
                                 const double* state, double* sums, void* workspace, double* rows, void* stream);
 
+/* Scored starts and a verdict for the odometry prior (opt-in; nothing above changes its bits or its launches; the contract is restated in
+ * naruto_amd/odometry.py and tests/odometry_gate_spec.py is the numpy twin).  A frame-to-frame estimate converges only from a start inside
+ * its basin, and a failed one looks like any other: so K candidate starts are scored at the coarsest level and the cheapest one is
+ * taken, and after the level loop four plain checks at level 0 give a verdict.  Launches only, nothing is read back.
+ *
+ * naruto_odom_score: K (1 .. NARUTO_ODOM_MAX_CANDS) transforms cands (DEVICE float64 [K,16], row-major [4,4] each; a state block's head
+ *   is one) scored in one pass over `level`.  photo == NULL: the maps are depth blocks; photo given: RGB-D blocks.  Per pixel of the current
+ *   level the vertex p is read once; sums[0] counts the pixels with p.z < 0.  Per candidate k, fp64 without contraction, the association,
+ *   rejections and residual r of naruto_odom_accumulate (the same device function): sums[1+4k] = the accepted rows, sums[2+4k] = the sum of
+ *   (r*r < trunc*trunc ? r*r : trunc*trunc), trunc in metres, finite and positive.  When photo->weight > 0 the acceptance of
+ *   naruto_odom_rgbd_accumulate's photometric row, gradient test included: sums[3+4k] = the accepted rows, sums[4+4k] = the sum of r_I*r_I;
+ *   both 0 otherwise.  sums: DEVICE float64 [1 + 4 K].  Pixels, threads, the halving tree and the finishing launch are
+ *   naruto_odom_accumulate's: no atomics, bitwise reproducible; at K = 1 with a state's T and trunc = max_dist, sums[1], sums[2] are that
+ *   call's sums[28], sums[27] in every bit, and sums[1], sums[3], sums[4] are naruto_odom_rgbd_accumulate's [29], [30], [31].  A candidate
+ *   with a non-finite entry fails every comparison: its sums are 0 and no other candidate's change.  workspace:
+ *   naruto_odom_score_workspace_bytes(desc, K).  No state block is read, so no done word stops it.
+ * naruto_odom_candidates (one thread): cands[0] = the identity; cands[1] = inv(est[i-2]) @ est[i-1] for i > 1 (the constant-speed T of
+ *   naruto_odom_state_init, the same device function and bits), else the identity.  cands: DEVICE float64 [2,16].  i < num_frames.
+ * naruto_odom_choose (one thread): with n_valid = sums[0], t2 = tau*tau, term(n, s, tau) = (s + (n_valid - n)*t2) / (n_valid*t2), 1 when
+ *   n_valid == 0, +inf when not finite: cost[k] = term(sums[1+4k], sums[2+4k], trunc), plus term(sums[3+4k], sums[4+4k], photo_max_diff)
+ *   when photo_on != 0; +inf when not finite.  The lowest cost wins, ties go to the lowest index, index 0 when all are +inf.  The state
+ *   block is written as naruto_odom_state_init writes it with T = cands[chosen]; the record (below) gets [1] and [2..5], the rest 0.
+ * naruto_odom_verdict (one thread): sums = a K = 1 score of the state's T at level 0 with trunc = max_dist.  PASS iff level 0's status word
+ *   is not NARUTO_ICP_DEGENERATE, n_geo >= min_overlap * n_valid, n_geo > 0, s_geo <= max_rmse^2 * n_geo, |t|^2 <= max_trans^2 and
+ *   trace(R) >= min_trace (= 1 + 2 cos(max_rot), computed by the caller: the kernel has no transcendental function), with
+ *   |t|^2 = (tx*tx + ty*ty) + tz*tz and trace = (r00 + r11) + r22 of the state's T.  A NaN fails its comparison: FAIL.  On FAIL the state's
+ *   T becomes cands[record[1]], the candidate naruto_odom_choose took.  NarutoOdomGate is a HOST struct.
+ * record: DEVICE float64 [NARUTO_ODOM_GATE_WORDS] per frame: [0] verdict (1 PASS, 0 FAIL), [1] the chosen index, [2..5] the costs (-1 =
+ *   unused), [6] n_valid, [7] n_geo, [8] rmse = sqrt(s_geo / n_geo) (0 without rows), [9] |t|, [10] trace, [11] level 0's status,
+ *   [12] n_photo, [13] sqrt(s_photo / n_photo) (0 without rows), [14], [15] 0.  A value of [8], [9], [10], [13] that is not finite is
+ *   written as -1, so a record is always finite.
+ * The gated estimate is the fixed sequence: maps, candidates, score at the coarsest level (K = 2, the score trunc), choose, the level
+ * loop as it is, score at level 0 (K = 1 on the state block, trunc = max_dist), verdict, naruto_pose_predict_relative. */
+#define NARUTO_ODOM_MAX_CANDS 4
+#define NARUTO_ODOM_GATE_WORDS 16
+typedef struct NarutoOdomGate {    /* HOST: the verdict's thresholds; min_trace = 1 + 2 cos(the largest rotation) */
+    double max_trans, min_trace, min_overlap, max_rmse;
+} NarutoOdomGate;
+size_t naruto_odom_score_workspace_bytes(const NarutoOdomDesc* desc, uint32_t K);
+int naruto_odom_score(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* maps_prev, const float* maps_cur,
+                      const double* cands, uint32_t K, double trunc, double* sums, void* workspace, void* stream);
+int naruto_odom_candidates(const float* est, uint32_t num_frames, uint32_t i, double* cands, void* stream);
+int naruto_odom_choose(uint32_t K, const double* sums, const double* cands, int32_t photo_on, double trunc, double photo_max_diff, double* state,
+                       double* record, void* stream);
+int naruto_odom_verdict(const NarutoOdomDesc* desc, const NarutoOdomGate* gate, const double* sums, const double* cands, double* state, double* record,
+                        void* stream);
+
 /* The planner's local RRT (reference src/planner/rrt.py and src/planner/rrt_naruto.py: class RRTNaruto, the
  * local_planner_method of every shipped config), on the volumes of naruto_map_volumes.  Unit: voxel.
  *

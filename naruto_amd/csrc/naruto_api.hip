@@ -2573,6 +2573,88 @@ int naruto_odom_rgbd_accumulate(const NarutoOdomDesc* desc, const NarutoOdomPhot
     return check_launch("odom_rgbd_finish");
 }
 
+// ---- scored starts and a verdict for the odometry prior -------------------------------------------------------------------
+extern "C++" {
+namespace {
+template <int K>
+int odom_score_launch(bool photo_on, const OdomLevel& lv, uint32_t ioff, uint32_t parts, double md2, double trunc2, double max_diff, const float* maps_prev,
+                      const float* maps_cur, const double* cands, double* sums, double* part, hipStream_t stream) {
+    if (photo_on)
+        hipLaunchKernelGGL((k_odom_score<K, true>), dim3(parts), dim3(kOdomThreads), 0, stream, lv, ioff, md2, trunc2, max_diff, maps_prev, maps_cur, cands, part);
+    else
+        hipLaunchKernelGGL((k_odom_score<K, false>), dim3(parts), dim3(kOdomThreads), 0, stream, lv, ioff, md2, trunc2, max_diff, maps_prev, maps_cur, cands, part);
+    if (int rc = check_launch("odom_score")) return rc;
+    hipLaunchKernelGGL((k_odom_score_finish<K>), dim3(1), dim3(kOdomThreads), 0, stream, parts, (const double*)part, sums);
+    return check_launch("odom_score_finish");
+}
+}  // namespace
+}  // extern "C++"
+
+size_t naruto_odom_score_workspace_bytes(const NarutoOdomDesc* desc, uint32_t K) {
+    OdomGeom g;
+    if (!odom_geom(desc, "odom_score_workspace_bytes", &g)) return 0;
+    if (K == 0u || K > (uint32_t)kOdomMaxCands) { fail(NARUTO_ERR_INVALID, "odom_score_workspace_bytes: %u candidates (1 .. %d)", K, kOdomMaxCands); return 0; }
+    return (size_t)odom_parts(g.lv[0]) * (1u + 4u * K) * sizeof(double);
+}
+
+int naruto_odom_score(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* maps_prev, const float* maps_cur,
+                      const double* cands, uint32_t K, double trunc, double* sums, void* workspace, void* stream) {
+    OdomGeom g;
+    if (!odom_geom(desc, "odom_score", &g)) return NARUTO_ERR_INVALID;
+    if (photo != nullptr && (!(photo->weight >= 0.0f) || !std::isfinite(photo->weight) || !(photo->max_diff >= 0.0f)))
+        return fail(NARUTO_ERR_INVALID, "odom_score: the photometric weight must be finite and >= 0, max_diff >= 0");
+    if (level >= g.levels) return fail(NARUTO_ERR_INVALID, "odom_score: level %u of %u", level, g.levels);
+    if (K == 0u || K > (uint32_t)kOdomMaxCands) return fail(NARUTO_ERR_INVALID, "odom_score: %u candidates (1 .. %d)", K, kOdomMaxCands);
+    if (!(trunc > 0.0) || !std::isfinite(trunc)) return fail(NARUTO_ERR_INVALID, "odom_score: trunc must be a finite positive number of metres");
+    if (maps_prev == nullptr || maps_cur == nullptr || cands == nullptr || sums == nullptr || workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "odom_score: NULL argument");
+    const OdomLevel lv = g.lv[level];
+    const uint32_t parts = odom_parts(lv), ioff = g.total * 7u + lv.start * 3u;     // ioff is read with a photometric term only (RGB-D blocks)
+    const double md = (double)desc->max_dist;
+    const bool photo_on = photo != nullptr && photo->weight > 0.0f;
+    const double max_diff = photo != nullptr ? (double)photo->max_diff : 0.0;
+    double* part = reinterpret_cast<double*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    switch (K) {
+        case 1: return odom_score_launch<1>(photo_on, lv, ioff, parts, md * md, trunc * trunc, max_diff, maps_prev, maps_cur, cands, sums, part, st);
+        case 2: return odom_score_launch<2>(photo_on, lv, ioff, parts, md * md, trunc * trunc, max_diff, maps_prev, maps_cur, cands, sums, part, st);
+        case 3: return odom_score_launch<3>(photo_on, lv, ioff, parts, md * md, trunc * trunc, max_diff, maps_prev, maps_cur, cands, sums, part, st);
+        default: return odom_score_launch<4>(photo_on, lv, ioff, parts, md * md, trunc * trunc, max_diff, maps_prev, maps_cur, cands, sums, part, st);
+    }
+}
+
+int naruto_odom_candidates(const float* est, uint32_t num_frames, uint32_t i, double* cands, void* stream) {
+    if (est == nullptr || cands == nullptr) return fail(NARUTO_ERR_INVALID, "odom_candidates: NULL argument");
+    if (i >= num_frames) return fail(NARUTO_ERR_INVALID, "odom_candidates: frame %u of %u", i, num_frames);
+    hipLaunchKernelGGL(k_odom_candidates, dim3(1), dim3(64), 0, (hipStream_t)stream, est, i, cands);
+    return check_launch("odom_candidates");
+}
+
+int naruto_odom_choose(uint32_t K, const double* sums, const double* cands, int32_t photo_on, double trunc, double photo_max_diff, double* state,
+                       double* record, void* stream) {
+    if (K == 0u || K > (uint32_t)kOdomMaxCands) return fail(NARUTO_ERR_INVALID, "odom_choose: %u candidates (1 .. %d)", K, kOdomMaxCands);
+    if (!(trunc > 0.0) || !std::isfinite(trunc)) return fail(NARUTO_ERR_INVALID, "odom_choose: trunc must be a finite positive number of metres");
+    if (photo_on != 0 && (!(photo_max_diff > 0.0) || !std::isfinite(photo_max_diff)))
+        return fail(NARUTO_ERR_INVALID, "odom_choose: photo_max_diff must be a finite positive number when the photometric cost is on");
+    if (sums == nullptr || cands == nullptr || state == nullptr || record == nullptr) return fail(NARUTO_ERR_INVALID, "odom_choose: NULL argument");
+    hipLaunchKernelGGL(k_odom_choose, dim3(1), dim3(64), 0, (hipStream_t)stream, K, photo_on, trunc, photo_max_diff, sums, cands, state, record);
+    return check_launch("odom_choose");
+}
+
+int naruto_odom_verdict(const NarutoOdomDesc* desc, const NarutoOdomGate* gate, const double* sums, const double* cands, double* state, double* record,
+                        void* stream) {
+    OdomGeom g;
+    if (!odom_geom(desc, "odom_verdict", &g)) return NARUTO_ERR_INVALID;
+    if (gate == nullptr) return fail(NARUTO_ERR_INVALID, "odom_verdict: NULL gate");
+    if (!(gate->max_trans >= 0.0) || !(gate->min_trace >= -1.0 && gate->min_trace <= 3.0) || !(gate->min_overlap >= 0.0 && gate->min_overlap <= 1.0) ||
+        !(gate->max_rmse >= 0.0) || !std::isfinite(gate->max_trans) || !std::isfinite(gate->max_rmse))
+        return fail(NARUTO_ERR_INVALID, "odom_verdict: the gate needs finite max_trans, max_rmse >= 0, min_trace in -1 .. 3, min_overlap in 0 .. 1");
+    if (sums == nullptr || cands == nullptr || state == nullptr || record == nullptr) return fail(NARUTO_ERR_INVALID, "odom_verdict: NULL argument");
+    hipLaunchKernelGGL(k_odom_verdict, dim3(1), dim3(64), 0, (hipStream_t)stream, OdomGate{gate->max_trans, gate->min_trace, gate->min_overlap, gate->max_rmse},
+                       sums, cands, state, record);
+    return check_launch("odom_verdict");
+}
+
 int naruto_pose_predict_relative(float* est, uint32_t num_frames, uint32_t i, const double* state_T, float* pose6_out, void* stream) {
     if (est == nullptr || state_T == nullptr || pose6_out == nullptr) return fail(NARUTO_ERR_INVALID, "pose_predict_relative: NULL argument");
     if (i < 1u || i >= num_frames) return fail(NARUTO_ERR_INVALID, "pose_predict_relative: frame %u of %u (the first frame is given, not predicted)", i, num_frames);

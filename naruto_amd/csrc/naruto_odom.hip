@@ -110,6 +110,15 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_maps(OdomGeom g, const fl
     odom_maps_pixel(g, level, lv, gid - lv.start, depth, maps);
 }
 
+// the last relative motion inv(est[i-2]) @ est[i-1], i > 1: the constant-speed guess of k_odom_init and k_odom_candidates
+__device__ inline void odom_last_motion(const float* __restrict__ est, uint32_t i, double T[16]) {
+    double A[16], B[16], Binv[16];
+    pose_load(est + 16 * (size_t)(i - 1u), A);
+    pose_load(est + 16 * (size_t)(i - 2u), B);
+    pose_affine_inverse(B, Binv);
+    pose_mul(Binv, A, T);
+}
+
 // mode 0: T = init.T; 1: T = inv(est[i-2]) @ est[i-1] (the last relative motion once more); 2: identity
 __global__ __launch_bounds__(64) void k_odom_init(int32_t mode, OdomInit init, const float* __restrict__ est, uint32_t i, double* __restrict__ state) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -117,11 +126,7 @@ __global__ __launch_bounds__(64) void k_odom_init(int32_t mode, OdomInit init, c
     if (mode == 0) {
         for (int k = 0; k < 16; ++k) T[k] = init.T[k];
     } else if (mode == 1) {
-        double A[16], B[16], Binv[16];
-        pose_load(est + 16 * (size_t)(i - 1u), A);
-        pose_load(est + 16 * (size_t)(i - 2u), B);
-        pose_affine_inverse(B, Binv);
-        pose_mul(Binv, A, T);
+        odom_last_motion(est, i, T);
     } else {
         icp_identity(T);
     }
@@ -147,6 +152,36 @@ __device__ __forceinline__ void odom_fold(double* s, double acc[kOdomSums]) {
     }
 }
 
+// The association of one current-frame vertex (x, y, z), z < 0, under the transform T (its first 12 doubles): q = T p, the projection
+// (uc, vc), the nearest previous pixel j, `near` (|q - V_prev[j]|^2 <= max_dist2) and the geometric row's acceptance and residual -- the
+// one statement of the rule k_odom_accumulate, k_odom_rgbd_accumulate and k_odom_score share, fp64 without contraction.
+struct OdomHit { double q[3], zc, uc, vc, nn[3], r; uint32_t j; bool inside, near, geo; };
+
+__device__ __forceinline__ void odom_associate(const double* T, const OdomLevel& lv, const float* __restrict__ pv, const float* __restrict__ pn,
+                                               double x, double y, double z, double max_dist2, OdomHit& h) {
+#pragma clang fp contract(off)
+    h.inside = false; h.near = false; h.geo = false; h.r = 0.0; h.j = 0u;
+    h.q[0] = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+    h.q[1] = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+    h.q[2] = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+    h.zc = -h.q[2];
+    if (!(h.zc > 1e-6)) return;
+    h.uc = ((double)lv.fx * h.q[0]) / h.zc + (double)lv.cx;
+    h.vc = (-((double)lv.fy * h.q[1])) / h.zc + (double)lv.cy;
+    const double u = floor(h.uc + 0.5), v = floor(h.vc + 0.5);
+    if (!(u >= 0.0 && u < (double)lv.w && v >= 0.0 && v < (double)lv.h)) return;
+    h.inside = true;
+    const uint32_t j = (uint32_t)v * lv.w + (uint32_t)u;
+    h.j = j;
+    const double d[3] = {h.q[0] - (double)pv[3u * j], h.q[1] - (double)pv[3u * j + 1u], h.q[2] - (double)pv[3u * j + 2u]};
+    h.near = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] <= max_dist2;
+    h.nn[0] = (double)pn[3u * j]; h.nn[1] = (double)pn[3u * j + 1u]; h.nn[2] = (double)pn[3u * j + 2u];
+    if ((h.nn[0] != 0.0 || h.nn[1] != 0.0 || h.nn[2] != 0.0) && h.near) {
+        h.geo = true;
+        h.r = (h.nn[0] * d[0] + h.nn[1] * d[1]) + h.nn[2] * d[2];
+    }
+}
+
 // part: [workgroups][kOdomSums]; rows (or NULL): [n][2] = (the associated previous pixel or -1, the residual or 0)
 __global__ __launch_bounds__(kOdomThreads) void k_odom_accumulate(OdomLevel lv, int32_t level, double max_dist2, const float* __restrict__ prev,
                                                                   const float* __restrict__ cur, const double* __restrict__ state,
@@ -161,7 +196,6 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_accumulate(OdomLevel lv, 
     const float* cv = cur + lv.offset + n;
     const float* pv = prev + lv.offset + n;
     const float* pn = prev + lv.offset + (size_t)n * 4u;
-    const double fx = (double)lv.fx, fy = (double)lv.fy, cx = (double)lv.cx, cy = (double)lv.cy;
     double acc[kOdomSums];
 #pragma unroll
     for (int k = 0; k < kOdomSums; ++k) acc[k] = 0.0;
@@ -173,32 +207,23 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_accumulate(OdomLevel lv, 
         double index = -1.0, r = 0.0;
         const double x = (double)cv[3u * i], y = (double)cv[3u * i + 1u], z = (double)cv[3u * i + 2u];
         if (z < 0.0) {                                                   // a valid vertex lies in front of its camera
-            const double q[3] = {((T[0] * x + T[1] * y) + T[2] * z) + T[3], ((T[4] * x + T[5] * y) + T[6] * z) + T[7],
-                                 ((T[8] * x + T[9] * y) + T[10] * z) + T[11]};
-            const double zc = -q[2];
-            if (zc > 1e-6) {
-                const double u = floor(((fx * q[0]) / zc + cx) + 0.5), v = floor(((-(fy * q[1])) / zc + cy) + 0.5);
-                if (u >= 0.0 && u < (double)lv.w && v >= 0.0 && v < (double)lv.h) {
-                    const uint32_t j = (uint32_t)v * lv.w + (uint32_t)u;
-                    const double nn[3] = {(double)pn[3u * j], (double)pn[3u * j + 1u], (double)pn[3u * j + 2u]};
-                    if (nn[0] != 0.0 || nn[1] != 0.0 || nn[2] != 0.0) {
-                        const double d[3] = {q[0] - (double)pv[3u * j], q[1] - (double)pv[3u * j + 1u], q[2] - (double)pv[3u * j + 2u]};
-                        if ((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] <= max_dist2) {
-                            index = (double)j;
-                            r = (nn[0] * d[0] + nn[1] * d[1]) + nn[2] * d[2];
-                            const double J[6] = {q[1] * nn[2] - q[2] * nn[1], q[2] * nn[0] - q[0] * nn[2], q[0] * nn[1] - q[1] * nn[0], nn[0], nn[1], nn[2]};
-                            int m = 0;
+            OdomHit h;
+            odom_associate(T, lv, pv, pn, x, y, z, max_dist2, h);
+            if (h.geo) {
+                index = (double)h.j;
+                r = h.r;
+                const double* q = h.q;
+                const double* nn = h.nn;
+                const double J[6] = {q[1] * nn[2] - q[2] * nn[1], q[2] * nn[0] - q[0] * nn[2], q[0] * nn[1] - q[1] * nn[0], nn[0], nn[1], nn[2]};
+                int m = 0;
 #pragma unroll
-                            for (int a = 0; a < 6; ++a)
+                for (int a = 0; a < 6; ++a)
 #pragma unroll
-                                for (int b = a; b < 6; ++b, ++m) acc[m] += J[a] * J[b];
+                    for (int b = a; b < 6; ++b, ++m) acc[m] += J[a] * J[b];
 #pragma unroll
-                            for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
-                            acc[27] += r * r;
-                            acc[28] += 1.0;
-                        }
-                    }
-                }
+                for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
+                acc[27] += r * r;
+                acc[28] += 1.0;
             }
         }
         if (rows != nullptr) { rows[2u * (size_t)i] = index; rows[2u * (size_t)i + 1u] = r; }
@@ -331,6 +356,25 @@ __device__ __forceinline__ double odom_bilinear(const float* __restrict__ m, uin
     return top + b * (bot - top);
 }
 
+// The photometric row's acceptance for an associated vertex h (pi: the previous frame's I | gx | gy of the level, Icur: the current
+// pixel's intensity): the four neighbours of (uc, vc) are interior pixels, the nearest pixel has a vertex close to q, |r_I| <= max_diff and
+// the sampled gradients are finite.  res = r_I, gx, gy = the sampled gradients.
+__device__ __forceinline__ bool odom_photo_accept(const OdomHit& h, const OdomLevel& lv, const float* __restrict__ pv, const float* __restrict__ pi,
+                                                  double Icur, double max_diff, double& res, double& gx, double& gy) {
+#pragma clang fp contract(off)
+    if (!h.inside) return false;
+    const uint32_t n = lv.h * lv.w;
+    const double u0 = floor(h.uc), v0 = floor(h.vc);
+    if (!(u0 >= 1.0 && u0 + 1.0 <= (double)lv.w - 2.0 && v0 >= 1.0 && v0 + 1.0 <= (double)lv.h - 2.0 && (double)pv[3u * h.j + 2u] < 0.0 && h.near))
+        return false;
+    const uint32_t j00 = (uint32_t)v0 * lv.w + (uint32_t)u0;
+    const double a = h.uc - u0, b = h.vc - v0;
+    res = odom_bilinear(pi, j00, lv.w, a, b) - Icur;
+    gx = odom_bilinear(pi + n, j00, lv.w, a, b);
+    gy = odom_bilinear(pi + 2u * (size_t)n, j00, lv.w, a, b);
+    return fabs(res) <= max_diff && fabs(gx) < (double)INFINITY && fabs(gy) < (double)INFINITY;
+}
+
 // part: [workgroups][kOdomRgbdSums]; rows (or NULL): [n][4] = (geometric j or -1, r, photometric j or -1, r_I); ioff: floats to the level's I
 __global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_accumulate(OdomLevel lv, uint32_t ioff, int32_t level, double max_dist2, double weight,
                                                                        double max_diff, const float* __restrict__ prev, const float* __restrict__ cur,
@@ -347,7 +391,7 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_accumulate(OdomLevel
     const float* pn = prev + lv.offset + (size_t)n * 4u;
     const float* ci = cur + ioff;
     const float* pi = prev + ioff;
-    const double fx = (double)lv.fx, fy = (double)lv.fy, cx = (double)lv.cx, cy = (double)lv.cy;
+    const double fx = (double)lv.fx, fy = (double)lv.fy;
     double acc[kOdomRgbdSums];
 #pragma unroll
     for (int k = 0; k < kOdomRgbdSums; ++k) acc[k] = 0.0;
@@ -359,41 +403,25 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_accumulate(OdomLevel
         double index = -1.0, r = 0.0, pindex = -1.0, rI = 0.0;
         const double x = (double)cv[3u * i], y = (double)cv[3u * i + 1u], z = (double)cv[3u * i + 2u];
         if (z < 0.0) {                                                   // a valid vertex lies in front of its camera
-            const double q[3] = {((T[0] * x + T[1] * y) + T[2] * z) + T[3], ((T[4] * x + T[5] * y) + T[6] * z) + T[7],
-                                 ((T[8] * x + T[9] * y) + T[10] * z) + T[11]};
-            const double zc = -q[2];
-            if (zc > 1e-6) {
-                const double uc = (fx * q[0]) / zc + cx, vc = (-(fy * q[1])) / zc + cy;
-                const double u = floor(uc + 0.5), v = floor(vc + 0.5);
-                if (u >= 0.0 && u < (double)lv.w && v >= 0.0 && v < (double)lv.h) {
-                    const uint32_t j = (uint32_t)v * lv.w + (uint32_t)u;
-                    const double d[3] = {q[0] - (double)pv[3u * j], q[1] - (double)pv[3u * j + 1u], q[2] - (double)pv[3u * j + 2u]};
-                    const bool near = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] <= max_dist2;
-                    const double nn[3] = {(double)pn[3u * j], (double)pn[3u * j + 1u], (double)pn[3u * j + 2u]};
-                    if ((nn[0] != 0.0 || nn[1] != 0.0 || nn[2] != 0.0) && near) {
-                        index = (double)j;
-                        r = (nn[0] * d[0] + nn[1] * d[1]) + nn[2] * d[2];
-                        odom_add_row(acc, q, nn, r);
-                        acc[29] += 1.0;
-                    }
-                    const double u0 = floor(uc), v0 = floor(vc);
-                    if (weight > 0.0 && u0 >= 1.0 && u0 + 1.0 <= (double)lv.w - 2.0 && v0 >= 1.0 && v0 + 1.0 <= (double)lv.h - 2.0 &&
-                        (double)pv[3u * j + 2u] < 0.0 && near) {         // the four neighbours are interior pixels; the nearest one has a vertex close to q
-                        const uint32_t j00 = (uint32_t)v0 * lv.w + (uint32_t)u0;
-                        const double a = uc - u0, b = vc - v0;
-                        const double res = odom_bilinear(pi, j00, lv.w, a, b) - (double)ci[i];
-                        const double gx = odom_bilinear(pi + n, j00, lv.w, a, b), gy = odom_bilinear(pi + 2u * (size_t)n, j00, lv.w, a, b);
-                        if (fabs(res) <= max_diff && fabs(gx) < (double)INFINITY && fabs(gy) < (double)INFINITY) {
-                            const double ga = gx * fx, gb = gy * fy;
-                            const double g[3] = {weight * (ga / zc), weight * (-(gb / zc)), weight * ((ga * q[0] - gb * q[1]) / (zc * zc))};
-                            pindex = (double)j;
-                            rI = res;
-                            odom_add_row(acc, q, g, weight * res);
-                            acc[30] += 1.0;
-                            acc[31] += res * res;
-                        }
-                    }
-                }
+            OdomHit h;
+            odom_associate(T, lv, pv, pn, x, y, z, max_dist2, h);
+            if (h.geo) {
+                index = (double)h.j;
+                r = h.r;
+                odom_add_row(acc, h.q, h.nn, r);
+                acc[29] += 1.0;
+            }
+            double res, gx, gy;
+            if (weight > 0.0 && odom_photo_accept(h, lv, pv, pi, (double)ci[i], max_diff, res, gx, gy)) {
+                const double* q = h.q;
+                const double zc = h.zc;
+                const double ga = gx * fx, gb = gy * fy;
+                const double g[3] = {weight * (ga / zc), weight * (-(gb / zc)), weight * ((ga * q[0] - gb * q[1]) / (zc * zc))};
+                pindex = (double)h.j;
+                rI = res;
+                odom_add_row(acc, q, g, weight * res);
+                acc[30] += 1.0;
+                acc[31] += res * res;
             }
         }
         if (rows != nullptr) {
@@ -424,6 +452,163 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_finish(int32_t level
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < kOdomRgbdSums; ++k) sums[k] = acc[k];
+    }
+}
+
+// ---- scored starts and a verdict (contract: naruto_amd/odometry.py, include/naruto_hip.h; numpy twin: tests/odometry_gate_spec.py) ---------
+//
+//   k_odom_score         k_odom_accumulate's pixel order over K candidate transforms at once: the vertex is read once, every candidate
+//                        makes odom_associate's association (and, PHOTO, odom_photo_accept's); 1 + 4 K fp64 sums, no state, no done word
+//   k_odom_score_finish  k_odom_finish over 1 + 4 K sums
+//   k_odom_candidates    one thread: cands[0] = identity, cands[1] = the last motion (odom_last_motion) or the identity
+//   k_odom_choose        one thread: the truncated cost per candidate, the lowest one's T into the state block, the record's head
+//   k_odom_verdict       one thread: the five checks at level 0, the record's tail; on FAIL the state's T becomes the chosen candidate
+constexpr int kOdomMaxCands = 4;
+constexpr int kOdomGateWords = 16;
+
+// cands: [K][16] row-major transforms; part: [workgroups][1 + 4 K]: [0] pixels with p.z < 0, then per candidate the geometric rows, the sum
+// of min(r^2, trunc2), the photometric rows, the sum of r_I^2.  A candidate with a non-finite entry fails odom_associate's comparisons.
+template <int K, bool PHOTO>
+__global__ __launch_bounds__(kOdomThreads) void k_odom_score(OdomLevel lv, uint32_t ioff, double max_dist2, double trunc2, double max_diff,
+                                                             const float* __restrict__ prev, const float* __restrict__ cur,
+                                                             const double* __restrict__ cands, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    constexpr int N = 1 + 4 * K;
+    __shared__ double s[N * kOdomThreads];
+    const uint32_t n = lv.h * lv.w;
+    const float* cv = cur + lv.offset + n;
+    const float* pv = prev + lv.offset + n;
+    const float* pn = prev + lv.offset + (size_t)n * 4u;
+    const float* ci = cur + ioff;
+    const float* pi = prev + ioff;
+    double acc[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = 0.0;
+#pragma unroll 1
+    for (uint32_t k = 0; k < kOdomPer; ++k) {
+        const uint64_t i64 = (uint64_t)blockIdx.x * (kOdomThreads * kOdomPer) + k * kOdomThreads + threadIdx.x;
+        if (i64 >= n) continue;
+        const uint32_t i = (uint32_t)i64;
+        const double x = (double)cv[3u * i], y = (double)cv[3u * i + 1u], z = (double)cv[3u * i + 2u];
+        if (!(z < 0.0)) continue;
+        acc[0] += 1.0;
+        double Icur = 0.0;
+        if constexpr (PHOTO) Icur = (double)ci[i];
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            OdomHit h;
+            odom_associate(cands + 16 * c, lv, pv, pn, x, y, z, max_dist2, h);
+            if (h.geo) {
+                const double rr = h.r * h.r;
+                acc[1 + 4 * c] += 1.0;
+                acc[2 + 4 * c] += rr < trunc2 ? rr : trunc2;
+            }
+            if constexpr (PHOTO) {
+                double res, gx, gy;
+                if (odom_photo_accept(h, lv, pv, pi, Icur, max_diff, res, gx, gy)) {
+                    acc[3 + 4 * c] += 1.0;
+                    acc[4 + 4 * c] += res * res;
+                }
+            }
+        }
+    }
+    odom_fold_n<N>(s, acc);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) part[(size_t)blockIdx.x * N + k] = acc[k];
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(kOdomThreads) void k_odom_score_finish(uint32_t n_parts, const double* __restrict__ part, double* __restrict__ sums) {
+#pragma clang fp contract(off)
+    constexpr int N = 1 + 4 * K;
+    __shared__ double s[N * kOdomThreads];
+    double acc[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = 0.0;
+    for (uint32_t i = threadIdx.x; i < n_parts; i += kOdomThreads) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] += part[(size_t)i * N + k];
+    }
+    odom_fold_n<N>(s, acc);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) sums[k] = acc[k];
+    }
+}
+
+__global__ __launch_bounds__(64) void k_odom_candidates(const float* __restrict__ est, uint32_t i, double* __restrict__ cands) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double T[16];
+    icp_identity(T);
+    for (int k = 0; k < 16; ++k) cands[k] = T[k];
+    if (i > 1u) odom_last_motion(est, i, T);
+    for (int k = 0; k < 16; ++k) cands[16 + k] = T[k];
+}
+
+// (s + (n_valid - n) tau^2) / (n_valid tau^2): every valid pixel without a row costs tau^2; 1 when no pixel is valid; +inf when not finite
+__device__ inline double odom_cost_term(double n_valid, double n, double s, double tau) {
+#pragma clang fp contract(off)
+    if (n_valid == 0.0) return 1.0;
+    const double t2 = tau * tau;
+    const double c = (s + (n_valid - n) * t2) / (n_valid * t2);
+    return fabs(c) < (double)INFINITY ? c : (double)INFINITY;
+}
+
+__device__ inline double odom_finite_or(double v, double other) { return fabs(v) < (double)INFINITY ? v : other; }
+
+__global__ __launch_bounds__(64) void k_odom_choose(uint32_t K, int32_t photo_on, double trunc, double photo_max_diff, const double* __restrict__ sums,
+                                                    const double* __restrict__ cands, double* __restrict__ state, double* __restrict__ record) {
+#pragma clang fp contract(off)
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const double n_valid = sums[0];
+    double best = (double)INFINITY;
+    uint32_t chosen = 0u;
+    for (int k = 0; k < kOdomGateWords; ++k) record[k] = 0.0;
+    for (uint32_t k = 0; k < (uint32_t)kOdomMaxCands; ++k) {
+        double c = -1.0;
+        if (k < K) {
+            c = odom_cost_term(n_valid, sums[1u + 4u * k], sums[2u + 4u * k], trunc);
+            if (photo_on) c = c + odom_cost_term(n_valid, sums[3u + 4u * k], sums[4u + 4u * k], photo_max_diff);
+            if (!(fabs(c) < (double)INFINITY)) c = (double)INFINITY;
+            if (c < best) { best = c; chosen = k; }
+        }
+        record[2u + k] = c;
+    }
+    record[1] = (double)chosen;
+    for (int k = 0; k < 16; ++k) state[k] = cands[16u * chosen + k];
+    for (int k = 16; k < kOdomStateDoubles; ++k) state[k] = 0.0;
+}
+
+struct OdomGate { double max_trans, min_trace, min_overlap, max_rmse; };
+
+// sums: a K = 1 score of the state's T at level 0 with trunc = max_dist.  A NaN fails every comparison it enters, so it is a FAIL.
+__global__ __launch_bounds__(64) void k_odom_verdict(OdomGate gate, const double* __restrict__ sums, const double* __restrict__ cands,
+                                                     double* __restrict__ state, double* __restrict__ record) {
+#pragma clang fp contract(off)
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const double n_valid = sums[0], n_geo = sums[1], s_geo = sums[2], n_photo = sums[3], s_photo = sums[4];
+    const double status = state[16 + 1];
+    const double t2 = (state[3] * state[3] + state[7] * state[7]) + state[11] * state[11];
+    const double trace = (state[0] + state[5]) + state[10];
+    const bool pass = status >= 0.0 && status != (double)kIcpDegenerate && n_geo >= gate.min_overlap * n_valid && n_geo > 0.0 &&
+                      s_geo <= (gate.max_rmse * gate.max_rmse) * n_geo && t2 <= gate.max_trans * gate.max_trans && trace >= gate.min_trace;
+    record[0] = pass ? 1.0 : 0.0;
+    record[6] = n_valid;
+    record[7] = n_geo;
+    record[8] = n_geo > 0.0 ? odom_finite_or(sqrt(s_geo / n_geo), -1.0) : 0.0;
+    record[9] = odom_finite_or(sqrt(t2), -1.0);
+    record[10] = odom_finite_or(trace, -1.0);
+    record[11] = status;
+    record[12] = n_photo;
+    record[13] = n_photo > 0.0 ? odom_finite_or(sqrt(s_photo / n_photo), -1.0) : 0.0;
+    record[14] = 0.0;
+    record[15] = 0.0;
+    if (!pass) {
+        const double c = record[1];                                      // k_odom_choose's; anything else reads candidate 0
+        const uint32_t chosen = (c >= 0.0 && c < (double)kOdomMaxCands) ? (uint32_t)c : 0u;
+        for (int k = 0; k < 16; ++k) state[k] = cands[16u * chosen + k];
     }
 }
 

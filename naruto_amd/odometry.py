@@ -60,13 +60,42 @@ One evaluation at a level, per pixel i of the current frame, fp64 without contra
   4. the step is the depth odometry's, unchanged, on the first 29 sums: a level's ``inliers`` and ``rmse`` then count and mix both kinds of
      rows (rmse^2 = (sum r^2 + w^2 sum r_I^2) / rows).
 Defaults ``photo_weight = 0.1``, ``photo_max_diff = 0.3``.  Limits: the photometric term needs texture and overlap, and assumes that a
-surface point's intensity is the same in both frames; a failed estimate is still not detected.
+surface point's intensity is the same in both frames; a failed estimate is not detected unless the gate below is on.
+
+SCORED STARTS AND A VERDICT (``OdometryGate``; ``estimate_gated``, ``estimate_gated_device``; opt-in for both classes, nothing above changes;
+``CoSLAMNarutoHIP(prior_gate=...)``).  PARITY UNPINNED as above; tests/odometry_gate_spec.py is the numpy twin and
+tests/test_odometry_gate_host.py the study the defaults come from.  An estimate converges only from a start inside its basin and a lost one
+looks like any other, so:
+  * ``score``: K <= 4 candidate transforms in one pass over a level.  Per pixel the vertex p is read once; [0] counts the pixels with
+    p.z < 0 (``n_valid``).  Per candidate k the geometric row's association, rejections and residual r exactly as ``accumulate`` makes them
+    (the same device function): [1+4k] the rows, [2+4k] the sum of min(r*r, trunc*trunc) (r*r < trunc*trunc ? r*r : trunc*trunc).  With
+    ``photo_weight`` > 0 (RGB-D blocks) the photometric row's acceptance, gradient test included: [3+4k] the rows, [4+4k] the sum of
+    r_I*r_I; else 0.  fp64, no contraction, pixels / threads / fold / finishing launch in ``accumulate``'s order: no atomics, bitwise
+    reproducible.  At K = 1 with trunc = max_dist, [1], [2] are ``accumulate``'s [28], [27] bit for bit, and [1], [3], [4] the RGB-D
+    ``accumulate``'s [29], [30], [31].  A candidate with a non-finite entry gets no rows and changes no other candidate's sums;
+  * ``candidates`` (one thread): the identity and the last motion inv(est[i-2]) @ est[i-1] (i > 1; ``init_state``'s bits), else the identity;
+  * ``choose`` (one thread): cost[k] = (s + (n_valid - n) tau^2) / (n_valid tau^2) with s = [2+4k], n = [1+4k], tau = trunc -- every valid
+    pixel without a row costs as much as a truncated one -- plus the same expression of the photometric pair with tau = ``photo_max_diff``
+    when the photometric term is on; 1 per term when n_valid = 0, +inf when not finite.  The lowest cost wins, ties go to the lowest index,
+    index 0 when all are +inf.  The state block is written as ``init_state`` writes it with that T;
+  * the level loop, untouched;
+  * a K = 1 score of the state's T at level 0 with trunc = max_dist, and ``verdict`` (one thread): PASS iff level 0's status is not
+    ``degenerate``, n_geo >= ``min_overlap`` n_valid, n_geo > 0 and s_geo <= ``max_rmse``^2 n_geo, |t|^2 <= ``max_trans``^2 and
+    trace(R) >= 1 + 2 cos(``max_rot_deg``) (the host computes that bound).  A NaN fails its comparison.  On FAIL the state's T becomes the
+    chosen start.  No second attempt, no photometric verdict (those figures are only recorded).
+Record, 16 doubles per estimate: verdict (1 PASS / 0 FAIL), chosen index, four costs (-1 = unused), n_valid, n_geo, rmse, |t|, trace,
+level 0's status, n_photo, photometric rmse, 0, 0; rmse, |t|, trace and the photometric rmse are -1 where not finite.  The whole gated
+estimate is a fixed sequence of launches -- candidates, score, finish, choose, the level loop, score, finish, verdict: six more than
+``init_state`` + the level loop -- and nothing is read back.  Defaults (the study: zero lost estimates passed, zero converged ones refused
+over 80): ``max_trans`` 0.3 m, ``max_rot_deg`` 30, ``min_overlap`` 0.25, ``max_rmse`` 6 mm, ``score_trunc`` 5 cm.  Limits: views without
+overlap fail from every start and are only flagged; the thresholds were chosen at 80 x 60 and 160 x 120 in a closed room.
 """
 
 from __future__ import annotations
 
 import ctypes as C
 import math
+from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Dict, Optional, Sequence, Union
 
@@ -85,6 +114,35 @@ def _intrinsics(cam) -> tuple:
     if len(cam) != 6:
         raise ValueError("DepthOdometryHIP: the camera is a dict with H, W, fx, fy, cx, cy or that tuple")
     return cam
+
+
+@dataclass
+class OdometryGate:
+    """The gate of the odometry prior (module docstring): the verdict's four thresholds and the truncation of the start's cost."""
+    max_trans: float = 0.3          # metres between two consecutive frames
+    max_rot_deg: float = 30.0       # degrees
+    min_overlap: float = 0.25       # geometric rows / valid pixels at level 0
+    max_rmse: float = 0.006         # metres, over the geometric rows at level 0
+    score_trunc: float = 0.05       # metres: tau of the start's cost
+
+    def __post_init__(self):
+        if not (all(math.isfinite(v) for v in (self.max_trans, self.max_rot_deg, self.min_overlap, self.max_rmse, self.score_trunc))
+                and self.max_trans >= 0 and 0 <= self.max_rot_deg <= 180 and 0 <= self.min_overlap <= 1 and self.max_rmse >= 0 and self.score_trunc > 0):
+            raise ValueError(f"OdometryGate: {self!r}: max_trans, max_rmse >= 0, max_rot_deg in 0 .. 180, min_overlap in 0 .. 1, score_trunc > 0")
+
+    @staticmethod
+    def of(gate) -> "OdometryGate":
+        """None or True: the defaults; an OdometryGate: itself."""
+        if gate is None or gate is True:
+            return OdometryGate()
+        if not isinstance(gate, OdometryGate):
+            raise ValueError(f"the gate is None, True or an OdometryGate; got {gate!r}")
+        return gate
+
+    def abi(self):
+        """The HOST struct of naruto_odom_verdict: min_trace = 1 + 2 cos(max_rot), made here so that the kernel needs no cosine."""
+        return _lib.NarutoOdomGate(max_trans=float(self.max_trans), min_trace=1.0 + 2.0 * math.cos(math.radians(self.max_rot_deg)),
+                                   min_overlap=float(self.min_overlap), max_rmse=float(self.max_rmse))
 
 
 class DepthOdometryHIP:
@@ -174,6 +232,128 @@ class DepthOdometryHIP:
         """Launches only.  Returns the device state block (float64 [48]; its first 16 doubles are T), owned by this object."""
         return self.run_levels(maps_prev, maps_cur, self.init_state(init))
 
+    # ------------------------------------------------------------------------------------ scored starts and a verdict (module docstring)
+    _photo_on = False
+
+    def _photo_ref(self):
+        return None                                                        # the maps are depth blocks
+
+    def _gate_buffers(self) -> None:
+        if getattr(self, "cands", None) is None:
+            lib = _lib.load()
+            self.cands = torch.zeros(_lib.ODOM_MAX_CANDS * 16, dtype=torch.float64, device=self.device)
+            self.score_sums = torch.zeros(1 + 4 * _lib.ODOM_MAX_CANDS, dtype=torch.float64, device=self.device)
+            self.score_workspace = _lib.workspace(int(lib.naruto_odom_score_workspace_bytes(C.byref(self.desc), _lib.ODOM_MAX_CANDS)), self.device, torch.float64)
+            self.record = torch.zeros(_lib.ODOM_GATE_WORDS, dtype=torch.float64, device=self.device)
+
+    def _candidates(self, candidates) -> int:
+        """``candidates`` ([K,4,4] on the host, or a float64 device tensor of K x 16 doubles) into ``self.cands``; returns K."""
+        self._gate_buffers()
+        if isinstance(candidates, torch.Tensor) and candidates.is_cuda:
+            c = candidates.to(torch.float64).reshape(-1)
+        else:
+            c = torch.from_numpy(np.ascontiguousarray(np.asarray(candidates.cpu() if isinstance(candidates, torch.Tensor) else candidates,
+                                                                 dtype=np.float64).reshape(-1)))
+        K = c.numel() // 16
+        if c.numel() != 16 * K or not 1 <= K <= _lib.ODOM_MAX_CANDS:
+            raise ValueError(f"{type(self).__name__}: candidates are 1 .. {_lib.ODOM_MAX_CANDS} transforms [K,4,4]; got {c.numel()} numbers")
+        if c.data_ptr() != self.cands.data_ptr():
+            self.cands[:16 * K].copy_(c, non_blocking=True)
+        return K
+
+    def _score(self, level: int, maps_prev: torch.Tensor, maps_cur: torch.Tensor, cands: torch.Tensor, K: int, trunc: float, sums: torch.Tensor) -> None:
+        check(_lib.load().naruto_odom_score(C.byref(self.desc), self._photo_ref(), int(level), maps_prev.data_ptr(), maps_cur.data_ptr(), cands.data_ptr(),
+                                            int(K), float(trunc), sums.data_ptr(), self.score_workspace.data_ptr(), _stream()), "naruto_odom_score")
+
+    def score(self, maps_prev: torch.Tensor, maps_cur: torch.Tensor, candidates, level: Optional[int] = None, trunc: Optional[float] = None) -> torch.Tensor:
+        """The 1 + 4 K sums of K candidate transforms at ``level`` (default: the coarsest) with the residual truncated at ``trunc`` metres
+        (default: ``OdometryGate.score_trunc``): float64 on the device, a view of ``score_sums``, owned by this object.  ``candidates``: [K,4,4] on the
+        host (copied into ``self.cands``) or a contiguous float64 device tensor [K,16], read in place.  Launches only."""
+        self._gate_buffers()
+        if isinstance(candidates, torch.Tensor) and candidates.is_cuda:        # read in place: a state block's head is one candidate
+            if candidates.dtype != torch.float64 or not candidates.is_contiguous() or candidates.numel() % 16 or not 16 <= candidates.numel() <= 16 * _lib.ODOM_MAX_CANDS:
+                raise ValueError(f"{type(self).__name__}: device candidates are contiguous float64 [K,16], K = 1 .. {_lib.ODOM_MAX_CANDS}")
+            cands, K = candidates, candidates.numel() // 16
+        else:
+            cands, K = self.cands, self._candidates(candidates)
+        level = self.levels - 1 if level is None else int(level)
+        with _on_device(self.device):
+            self._score(level, maps_prev, maps_cur, cands, K, OdometryGate.score_trunc if trunc is None else trunc, self.score_sums)
+        return self.score_sums[:1 + 4 * K]
+
+    def candidates(self, est: torch.Tensor, i: int) -> torch.Tensor:
+        """The two starts of frame ``i`` into ``self.cands``, made on the device: the identity and inv(est[i-2]) @ est[i-1] (i > 1, else the
+        identity once more).  ``est``: float32 [num_frames,4,4] on the device.  Returns the view [2,16]: one launch."""
+        self._gate_buffers()
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_candidates(est.data_ptr(), est.shape[0], int(i), self.cands.data_ptr(), _stream()), "naruto_odom_candidates")
+        return self.cands[:32].view(2, 16)
+
+    def choose(self, K: int, trunc: float, state: torch.Tensor, record: torch.Tensor) -> None:
+        """``naruto_odom_choose`` on ``score_sums`` and ``cands``: the cheapest start's T into ``state``, the record's head: one launch."""
+        with _on_device(self.device):
+            self._choose(K, trunc, state, record)
+
+    def verdict(self, gate=None, state: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None) -> None:
+        """``naruto_odom_verdict`` on ``score_sums`` (a K = 1 score of the state's T at level 0 with trunc = max_dist): one launch."""
+        gate, state, record = OdometryGate.of(gate), self.state if state is None else state, self.record if record is None else record
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_verdict(C.byref(self.desc), C.byref(gate.abi()), self.score_sums.data_ptr(), self.cands.data_ptr(), state.data_ptr(),
+                                                  record.data_ptr(), _stream()), "naruto_odom_verdict")
+
+    def _choose(self, K: int, trunc: float, state: torch.Tensor, record: torch.Tensor) -> None:
+        check(_lib.load().naruto_odom_choose(int(K), self.score_sums.data_ptr(), self.cands.data_ptr(), 1 if self._photo_on else 0, float(trunc),
+                                             float(self.photo.max_diff) if self._photo_on else 0.0, state.data_ptr(), record.data_ptr(), _stream()),
+              "naruto_odom_choose")
+
+    def costs(self, maps_prev: torch.Tensor, maps_cur: torch.Tensor, candidates, level: Optional[int] = None, trunc: Optional[float] = None) -> np.ndarray:
+        """The K costs ``naruto_odom_choose`` compares (float64 on the host; synchronises).  ``self.state`` and ``self.record`` are not touched."""
+        trunc = OdometryGate.score_trunc if trunc is None else trunc
+        K = self._candidates(candidates)
+        self.score(maps_prev, maps_cur, self.cands[:16 * K], level, trunc)
+        state, record = torch.empty_like(self.state), torch.empty_like(self.record)
+        self.choose(K, trunc, state, record)
+        return record[2:2 + K].cpu().numpy()
+
+    def estimate_gated_device(self, maps_prev: torch.Tensor, maps_cur: torch.Tensor, est: Optional[torch.Tensor] = None, i: int = 0, gate=None,
+                              record: Optional[torch.Tensor] = None, candidates=None) -> torch.Tensor:
+        """The gated estimate (module docstring): launches only.  The starts are the identity and the last motion of ``est`` at frame ``i``
+        (made on the device) when ``est`` is given, else ``candidates`` (default: the identity alone).  ``record``: float64 [16] on the device
+        (default ``self.record``).  Returns the state block; after a FAIL its T is the chosen start."""
+        gate = OdometryGate.of(gate)
+        self._gate_buffers()
+        record = self.record if record is None else record
+        if not (record.is_cuda and record.dtype == torch.float64 and record.is_contiguous() and record.numel() == _lib.ODOM_GATE_WORDS):
+            raise ValueError(f"{type(self).__name__}: record is float64 [{_lib.ODOM_GATE_WORDS}] on the device")
+        state = self.state
+        if est is None:
+            K = self._candidates(np.eye(4)[None] if candidates is None else candidates)
+        else:
+            self.candidates(est, i)
+            K = 2
+        with _on_device(self.device):
+            self._score(self.levels - 1, maps_prev, maps_cur, self.cands, K, gate.score_trunc, self.score_sums)
+            self._choose(K, gate.score_trunc, state, record)
+        self.run_levels(maps_prev, maps_cur, state)
+        with _on_device(self.device):
+            self._score(0, maps_prev, maps_cur, state, 1, float(self.desc.max_dist), self.score_sums)
+        self.verdict(gate, state, record)
+        return state
+
+    def _frame(self, frame) -> torch.Tensor:
+        return self.frame_maps(*frame) if isinstance(frame, (tuple, list)) else self.frame_maps(frame)
+
+    def estimate_gated(self, prev, cur, candidates=None, gate=None) -> SimpleNamespace:
+        """The gated estimate between two frames (a depth frame; for the RGB-D odometry a (depth, colour) pair).  ``.T`` float64 [4,4] (the
+        chosen start after a FAIL), ``.passed``, ``.chosen``, ``.costs`` (one per candidate), ``.overlap`` = n_geo / n_valid and ``.rmse`` at
+        level 0, ``.record`` [16], and ``read_state``'s per-level ``.status``, ``.iterations``, ``.inliers``.  This call synchronises."""
+        K = 1 if candidates is None else int(np.asarray(candidates.cpu() if isinstance(candidates, torch.Tensor) else candidates).size // 16)
+        state = self.estimate_gated_device(self._frame(prev), self._frame(cur), gate=gate, candidates=candidates)
+        out, rec = DepthOdometryHIP.read_state(self, state), self.record.cpu().numpy()
+        return SimpleNamespace(T=out.transformation, passed=bool(rec[0] == 1.0), chosen=int(rec[1]), costs=[float(c) for c in rec[2:2 + K]],
+                               overlap=float(rec[7] / rec[6]) if rec[6] > 0 else 0.0, rmse=float(rec[8]), record=rec, status=out.status,
+                               iterations=out.iterations, inliers=out.inliers)
+
     def read_state(self, state: Optional[torch.Tensor] = None) -> SimpleNamespace:
         """The state block on the host (synchronises)."""
         s = (self.state if state is None else state).cpu().numpy()
@@ -224,6 +404,13 @@ class RGBDOdometryHIP(DepthOdometryHIP):
             check(_lib.load().naruto_odom_rgbd_frame_maps(C.byref(self.desc), depth.data_ptr(), color.data_ptr(), out.data_ptr(), _stream()),
                   "naruto_odom_rgbd_frame_maps")
         return out
+
+    @property
+    def _photo_on(self) -> bool:
+        return float(self.photo.weight) > 0.0
+
+    def _photo_ref(self):
+        return C.byref(self.photo)                                         # the maps are RGB-D blocks
 
     def level_views(self, maps: torch.Tensor, level: int):
         """(depth [h,w], vertex [h,w,3], normal [h,w,3], I [h,w], gx [h,w], gy [h,w]): views into an RGB-D maps block."""

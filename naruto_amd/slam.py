@@ -61,6 +61,12 @@ the estimate is a fixed sequence of launches and adds no wait for the host.  ``o
 ``"rgbd_icp"`` is the same step with ``naruto_amd.odometry.RGBDOdometryHIP``: the frame's colour image goes into the maps as well, and every
 pixel adds a photometric row, which pins the motions a bare wall leaves free for the depth rows; launch for launch the same sequence.
 
+PRIOR GATE (``prior_gate=None`` | ``True`` | ``odometry.OdometryGate``, with an odometry prior only; ``None`` is the step above, launch for
+launch).  The estimate starts from the cheaper of two starts -- the identity and the last relative motion, scored on the device at the
+coarsest level -- and after the level loop four checks at level 0 give a verdict (``naruto_amd.odometry``); a FAIL hands the tracker the
+chosen start instead of the lost estimate.  Frame i's record goes into ``prior_log[i]`` ([num_frames,16] float64 on the device: verdict,
+chosen start, costs, overlap, rmse ...); six launches more per frame, still nothing read back.
+
 A config with ``tracking.disable: False`` and no ``track=True`` is refused (``NotImplementedError``) before the library is touched:
 tracking is switched on by the keyword, whatever ``tracking.disable`` says.  Out of scope: ``tracking.iter_point > 0`` (``tracking_pc``),
 other ``training.rot_rep`` (both refused by ``tracking.tracking_settings``), data-parallel pose refinement.
@@ -139,14 +145,16 @@ class DevicePoses:
 class CoSLAMNarutoHIP:
     def __init__(self, config: Dict, voxel_size: float = 0.1, active_ray: Optional[bool] = None, act_ray_num_uncert_sample: int = 500,
                  act_ray_oversample_mul: int = 4, num_frames: int = 2000, seed: Optional[int] = 0, result_dir: Optional[str] = None, device="cuda",
-                 track: bool = False, motion_prior: Optional[str] = None):
+                 track: bool = False, motion_prior: Optional[str] = None, prior_gate=None):
         """``config``: a Co-SLAM config (``naruto_amd.config.load_config``); it is kept and, as in the reference's ``override_config``,
         ``mapping.active_ray`` is overwritten when ``active_ray`` is given.  ``num_frames``: the length of the run (sizes the keyframe store
         and the pose tensor).  ``seed``: keys the keyframe store's draws and, through ``torch.manual_seed`` (None: left alone), the
         network's initial values and the trainer's in-kernel random streams.  ``result_dir``: meshes and checkpoints go under
         ``<result_dir>/coslam`` (None: ``save_*`` need an explicit directory).  ``track``: estimate the camera poses during the run
         (module docstring) with ``tracking_settings(config)``, whatever ``tracking.disable`` says.  ``motion_prior``: where a tracked
-        frame's initial pose comes from, ``"const_speed"`` (the default), ``"depth_icp"`` or ``"rgbd_icp"`` (module docstring); needs ``track=True``."""
+        frame's initial pose comes from, ``"const_speed"`` (the default), ``"depth_icp"`` or ``"rgbd_icp"`` (module docstring); needs ``track=True``.
+        ``prior_gate``: None (today's step, launch for launch), True or an ``odometry.OdometryGate``: the odometry prior scores its two starts
+        and judges its estimate (module docstring); needs an odometry prior."""
         tk = config.get("tracking") or {}
         self.track = bool(track)
         if motion_prior is not None and motion_prior not in ("const_speed", "depth_icp", "rgbd_icp"):
@@ -154,6 +162,8 @@ class CoSLAMNarutoHIP:
         if motion_prior is not None and not self.track:
             raise ValueError("CoSLAMNarutoHIP: motion_prior is the tracker's initial pose and needs track=True")
         self.motion_prior = motion_prior or "const_speed"
+        if prior_gate is not None and prior_gate is not False and self.motion_prior not in ("depth_icp", "rgbd_icp"):
+            raise ValueError("CoSLAMNarutoHIP: prior_gate judges the odometry prior and needs motion_prior='depth_icp' or 'rgbd_icp'")
         if not self.track and not bool(tk.get("disable", True)):
             raise NotImplementedError("CoSLAMNarutoHIP: tracking.disable: False asks for camera tracking and pose refinement during the run; they are "
                                       "switched on by the keyword track=True (naruto_amd.tracking.TrackerHIP, FusedBA(optimize_poses=True)), not by the config")
@@ -205,6 +215,11 @@ class CoSLAMNarutoHIP:
             from .odometry import RGBDOdometryHIP
             self.odometry = RGBDOdometryHIP((self.H, self.W, self.fx, self.fy, self.cx, self.cy), device=self.device)
             self._odom_maps = [self.odometry.new_maps(), self.odometry.new_maps()]
+        self.prior_gate, self.prior_log = None, None
+        if prior_gate is not None and prior_gate is not False:
+            from .odometry import OdometryGate
+            self.prior_gate = OdometryGate.of(prior_gate)
+            self.prior_log = torch.zeros(self.num_frames, 16, dtype=torch.float64, device=self.device)     # frame i's record (odometry.py)
         self.cached_uncert = None
         self.filter_depth = bool(mp.get("filter_depth", False))
         self._n_valid = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -266,8 +281,11 @@ class CoSLAMNarutoHIP:
         if self.odometry is not None:
             od, cur = self.odometry, self._odom_maps[i & 1]
             self._odom_frame_maps(color, depth, cur)
-            state = od.init_state(est=est.tensor, i=i, const_speed=bool(self.tracking["const_speed"]))
-            od.run_levels(self._odom_maps[(i - 1) & 1], cur, state)
+            if self.prior_gate is not None:
+                state = od.estimate_gated_device(self._odom_maps[(i - 1) & 1], cur, est=est.tensor, i=i, gate=self.prior_gate, record=self.prior_log[i])
+            else:
+                state = od.init_state(est=est.tensor, i=i, const_speed=bool(self.tracking["const_speed"]))
+                od.run_levels(self._odom_maps[(i - 1) & 1], cur, state)
             pose_predict_relative(est.tensor, i, state, self.tracker.pose_init)
         else:
             pose_predict(est.tensor, i, bool(self.tracking["const_speed"]), self.tracker.pose_init)

@@ -11,10 +11,14 @@ Recorded:
 
     python tools/time_odometry.py [--out profiles/time_odometry.json] [--n-lat 632]
     python tools/time_odometry.py --rgbd [--out profiles/time_odometry_rgbd.json]
+    python tools/time_odometry.py --gate [--out profiles/time_odometry_gate.json]
 
 With --rgbd only this is recorded: the frame maps and a whole estimate of the depth odometry and of the RGB-D odometry
 (naruto_amd.odometry.RGBDOdometryHIP) on the same two frames of the mesh coloured by a smooth function of position, the four calls
-alternating in one loop.
+alternating in one loop.  With --gate only this: the gated estimate (scored starts and a verdict, ``estimate_gated_device`` from a pose
+tensor) and the ungated one (``init_state`` + the level loop, today's path) alternating in one loop, for both odometry classes, and
+``score`` alone at K = 1, 2 and 4 at the coarsest level and at level 0; medians with their spread (min, max), the ratio gated / ungated
+and whether the difference exceeds twice the ungated call's own spread.
 
 Host wall clock ending in a device synchronise, every shape warmed up first, the MEDIAN of --repeat.  Nothing is asserted."""
 import argparse
@@ -112,17 +116,81 @@ def rgbd(args, dev, cam):
     return res
 
 
+def gate(args, dev, cam):
+    """--gate: gated and ungated estimates alternating in one loop, and the score kernel alone (module docstring)."""
+    from time_tracked_run import smooth_colours
+    v, f = syn.room_sphere_mesh(n_lat=args.n_lat, n_lon=2 * args.n_lat)[:2]
+    sim = MeshSimHIP((v, f, smooth_colours(v)), cam, device=dev)
+    base = np.eye(4)
+    pos, at = np.array([2.0, 4.0, 1.2]), np.array([3.0, 2.5, 1.4])
+    base[:3, :3], base[:3, 3] = compute_camera_pose(pos, at), pos
+    step = motion((0, 1, 0), 2.0, 0.03)
+    poses = np.stack([base @ np.linalg.inv(step), base, base @ step]).astype(np.float32)        # frames 0, 1, 2 of a steady motion
+    frames = [sim.simulate(p, no_print=True) for p in poses[1:]]
+    color, depth = [c.to(dev) for c, _ in frames], [d.to(dev) for _, d in frames]
+    rel = np.linalg.inv(poses[1].astype(np.float64)) @ poses[2].astype(np.float64)
+    est = torch.from_numpy(poses).to(dev)
+    ods = {"depth": DepthOdometryHIP(cam, device=dev), "rgbd": RGBDOdometryHIP(cam, device=dev)}
+    maps = {"depth": (ods["depth"].frame_maps(depth[0]), ods["depth"].frame_maps(depth[1])),
+            "rgbd": (ods["rgbd"].frame_maps(depth[0], color[0]), ods["rgbd"].frame_maps(depth[1], color[1]))}
+    calls = {}
+    for name, od in ods.items():
+        mp, mc = maps[name]
+        calls[name + "_ungated_ms"] = lambda od=od, mp=mp, mc=mc: od.run_levels(mp, mc, od.init_state(est=est, i=2, const_speed=True))
+        calls[name + "_gated_ms"] = lambda od=od, mp=mp, mc=mc: od.estimate_gated_device(mp, mc, est=est, i=2)
+        four = np.stack([np.eye(4), step, motion((0, 1, 0), -2.0, 0.0), motion((0, 1, 0), 4.0, 0.06)])
+        for level in (od.levels - 1, 0):
+            for K in (1, 2, 4):
+                calls[f"{name}_score_level{level}_K{K}_ms"] = lambda od=od, mp=mp, mc=mc, K=K, level=level: od.score(mp, mc, four[:K], level=level)
+    times = {k: [] for k in calls}
+    for fn in calls.values():
+        fn()
+    for _ in range(args.repeat):
+        for k, fn in calls.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t)
+    res = {"image": [cam["W"], cam["H"]], "focal": cam["fx"], "faces": len(f), "repeat": args.repeat}
+    for k, vals in times.items():
+        res[k] = {"median": statistics.median(vals) * 1e3, "min": min(vals) * 1e3, "max": max(vals) * 1e3}
+    for name, od in ods.items():
+        un, ga = res[name + "_ungated_ms"], res[name + "_gated_ms"]
+        spread = un["max"] - un["min"]
+        res[name + "_gated_over_ungated"] = {"ratio": ga["median"] / un["median"], "difference_ms": ga["median"] - un["median"], "ungated_spread_ms": spread,
+                                             "exceeds_twice_the_ungated_spread": bool(ga["median"] - un["median"] > 2.0 * spread)}
+        od.estimate_gated_device(*maps[name], est=est, i=2)
+        rec = od.record.cpu().numpy()
+        dm, dd = error(od.read_state().transformation, rel)
+        res[name + "_gated_estimate_3cm_2deg"] = {"error_mm": dm * 1e3, "error_deg": dd, "record": [float(x) for x in rec]}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat", type=int, default=9)
     ap.add_argument("--n-lat", type=int, default=632)
     ap.add_argument("--rgbd", action="store_true", help="depth-only and RGB-D odometry alternating in one run (write to profiles/time_odometry_rgbd.json)")
+    ap.add_argument("--gate", action="store_true", help="gated and ungated estimates alternating in one run, and the score kernel alone (write to profiles/time_odometry_gate.json)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_odometry.py measures on the GPU; there is none here")
     dev = torch.device("cuda:0")
     cam = {"H": 680, "W": 1200, "fx": 600.0, "fy": 600.0, "cx": 599.5, "cy": 339.5}
+    if args.gate:
+        res = gate(args, dev, cam)
+        print(json.dumps(res, indent=1))
+        if args.out:
+            doc = {"device": torch.cuda.get_device_name(0),
+                   "what": "tools/time_odometry.py --gate: host wall clock ending in a device synchronise, warmed up, all calls alternating in one loop, "
+                           "median (min, max) of --repeat; milliseconds.  score_* include the host's copy of the K candidates", "office_0_size": res}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(doc, fh, indent=1)
+                fh.write("\n")
+        return
     if args.rgbd:
         res = rgbd(args, dev, cam)
         print(json.dumps(res, indent=1))

@@ -11,7 +11,7 @@ the mapping schedule of tools/time_run.py, tracking with replica_coslam.yaml's s
     the others, the trajectory error of the estimate and the motion per step the planner commands (against what one tracking call
     can cover: iter x lr).
 
-    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632] [--motion-prior depth_icp | rgbd_icp]
+    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632] [--motion-prior depth_icp | rgbd_icp [--prior-gate]]
 
 With --motion-prior only the run is made, with CoSLAMNarutoHIP(motion_prior=...), and it is MERGED into the output file as
 office_0_size.run_motion_prior_<name>, beside the run of the default prior (--no-const-speed: tracking.const_speed off, key suffix
@@ -125,7 +125,8 @@ def frames(args, dev, mesh):
 def whole_run(args, dev, mesh):
     cfg = config(not args.no_const_speed)
     np.random.seed(args.seed)
-    slam = CoSLAMNarutoHIP(cfg, active_ray=True, num_frames=args.steps, seed=args.seed, device=dev, track=True, motion_prior=args.motion_prior)
+    slam = CoSLAMNarutoHIP(cfg, active_ray=True, num_frames=args.steps, seed=args.seed, device=dev, track=True, motion_prior=args.motion_prior,
+                           prior_gate=True if args.prior_gate else None)
     sim = MeshSimHIP(mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=dev)
     planner = NarutoPlannerHIP(dataset="NARUTO", device=dev)
     planner.update_sim(sim)
@@ -142,7 +143,14 @@ def whole_run(args, dev, mesh):
     slam.online_recon_step = timed_step
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = run_exploration(slam, sim, planner, TR.start_pose(), args.steps)
+    prior_poses, tracked_poses = [], []
+
+    def on_step(i, c2w, vols, state):
+        """--prior-gate: the pose the prior handed the tracker (est[i-1] @ T, as both stand at the end of the step) and the tracked pose."""
+        if i > 0:
+            prior_poses.append(slam.est_c2w_data.tensor[i - 1].double() @ slam.odometry.state[:16].view(4, 4))
+            tracked_poses.append(slam.est_c2w_data.tensor[i].double().clone())
+    out = run_exploration(slam, sim, planner, TR.start_pose(), args.steps, on_step=on_step if args.prior_gate else None)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     loop = sum(v["total_s"] for v in out["timing"].values())
@@ -156,7 +164,21 @@ def whole_run(args, dev, mesh):
     turn = torch.rad2deg(torch.acos(cos.clamp(-1.0, 1.0)))
     reach = {"translation_cm": slam.tracking["iter"] * slam.tracking["lr_trans"] * 100.0,
              "rotation_deg": float(np.degrees(slam.tracking["iter"] * slam.tracking["lr_rot"]))}
-    return {"steps": args.steps, "wall_s_with_final_mesh_and_checkpoint": wall, "loop_s": loop, "steps_per_second": args.steps / loop,
+    gated = {}
+    if args.prior_gate:
+        def errors(poses):
+            p = torch.stack(poses).cpu()
+            g = gt[1:]
+            c = ((p[:, :3, :3].transpose(1, 2) @ g[:, :3, :3]).diagonal(dim1=1, dim2=2).sum(1) - 1.0) / 2.0
+            return ((p[:, :3, 3] - g[:, :3, 3]).norm(dim=1) * 100.0).tolist(), torch.rad2deg(torch.acos(c.clamp(-1.0, 1.0))).tolist()
+        log = out["prior_log"]
+        failed = [int(i) for i in torch.nonzero(log[1:, 0] == 0.0).flatten() + 1]
+        pe, te = errors(prior_poses), errors(tracked_poses)
+        first = lambda cm: next((i + 1 for i, e in enumerate(cm) if e > 10.0), None)        # noqa: E731  the first frame more than 10 cm off
+        gated = {"prior_failed_frames": failed, "first_frame_prior_over_10cm": first(pe[0]), "first_frame_tracked_over_10cm": first(te[0]),
+                 "per_frame_from_1": {"prior_error_cm": pe[0], "prior_error_deg": pe[1], "tracked_error_cm": te[0], "tracked_error_deg": te[1],
+                                      "record": log[1:].tolist()}}
+    return {**gated, "steps": args.steps, "wall_s_with_final_mesh_and_checkpoint": wall, "loop_s": loop, "steps_per_second": args.steps / loop,
             "phases_total_s": {k: v["total_s"] for k, v in out["timing"].items()},
             "slam_first_frame_ms": slam_t[0] * 1e3,
             "slam_mapped_frame_median_ms": statistics.median([t for i, t in enumerate(slam_t) if i in mapped and i > 0]) * 1e3,
@@ -177,6 +199,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--motion-prior", default=None, choices=["const_speed", "depth_icp", "rgbd_icp"], help="only the run, with this prior, merged into --out")
     ap.add_argument("--no-const-speed", action="store_true", help="with --motion-prior: tracking.const_speed off (depth_icp then starts from the identity)")
+    ap.add_argument("--prior-gate", action="store_true", help="with --motion-prior depth_icp / rgbd_icp: the prior's scored starts and verdict on; key suffix _gated; "
+                    "per-frame errors of the prior and of the tracked pose against the commanded pose, and the records")
     ap.add_argument("--small-test", default=None, help="JSON object merged into the document (figures of tests/test_gpu_tracked_run.py)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -191,7 +215,7 @@ def main():
         if args.out:
             with open(args.out) as fh:
                 doc = json.load(fh)
-            doc["office_0_size"]["run_motion_prior_" + args.motion_prior + ("_const_speed_off" if args.no_const_speed else "")] = run
+            doc["office_0_size"]["run_motion_prior_" + args.motion_prior + ("_const_speed_off" if args.no_const_speed else "") + ("_gated" if args.prior_gate else "")] = run
             with open(args.out, "w") as fh:
                 json.dump(doc, fh, indent=1)
                 fh.write("\n")
