@@ -742,7 +742,64 @@ int naruto_odom_choose(uint32_t K, const double* sums, const double* cands, int3
 int naruto_odom_verdict(const NarutoOdomDesc* desc, const NarutoOdomGate* gate, const double* sums, const double* cands, double* state, double* record,
                         void* stream);
 
-/* The planner's local RRT (reference src/planner/rrt.py and src/planner/rrt_naruto.py: class RRTNaruto, the
+/* Frame-to-model alignment: a depth frame registered to the field's own SDF, an opt-in refinement between any motion prior and the
+ * tracker (nothing like it is in the reference tree: PARITY UNPINNED; the contract is restated in naruto_amd/registration.py and
+ * tests/field_registration_spec.py is the numpy twin).  Conventions, the maps block, the pyramid (NarutoOdomDesc), the state block's
+ * first NARUTO_ODOM_STATE_DOUBLES doubles and the level words are the depth odometry's, but T is the CAMERA-TO-FIELD POSE ITSELF,
+ * not a relative motion.  state: DEVICE float64 [NARUTO_SDFREG_STATE_DOUBLES]: the odometry's state block, then the start's T [16].
+ * The odom desc's iters hold this registration's caps (naruto_odom_step reads them); NarutoSdfRegDesc (HOST) holds trunc
+ * (training.trunc), sdf_gate, the field's bounding box, and the levels used from the coarsest to the finest with their caps.
+ *
+ * One iteration at `level` is five launches, nothing read back:
+ * 1. naruto_sdfreg_points, per pixel of the CURRENT frame's vertex map at `level` (thread t of workgroup b takes pixels b*2048 + t +
+ *    256 k): q = T p in fp64 as ((r0*x + r1*y) + r2*z) + t, rounded once to float32; x = (q - bbox_min) / (bbox_max - bbox_min) per axis
+ *    in float32 without contraction (run_network's normalisation); valid iff p.z < 0 and every x component is finite and in [0, 1].
+ *    x [M,3] float32 ((0.5, 0.5, 0.5) for an invalid point), q [M,3] float32, valid [M] bytes; M = the pixels of the level.
+ * 2. naruto_query_fwd on x: sdf_uncert [M,2] only.   3. naruto_query_bwd_points with d_raw = (0,0,0,1,0) per point, d_geo = NULL,
+ *    x-points form: d_x [M,3] = d sdf / d x.
+ * 4. naruto_sdfreg_accumulate, fp64 without contraction, per valid point: r = trunc * sdf, g = (trunc * d_x) / (bbox_max - bbox_min)
+ *    per axis (the extent the float32 difference); rejected unless |sdf| < sdf_gate and 0 < (g0*g0 + g1*g1) + g2*g2 < inf (a NaN fails
+ *    its comparison).  Row J = [q x g, g], residual r, left perturbation T <- exp(xi) T; no normalisation of g.  sums: DEVICE float64
+ *    [NARUTO_SDFREG_SUMS]: [0..28] in naruto_odom_accumulate's layout, [29] the count of valid points; threads, the halving fold in LDS
+ *    and the finishing launch as naruto_odom_accumulate: no atomics, bitwise reproducible.  workspace: naruto_sdfreg_workspace_bytes.
+ *    rows (DEVICE float64 [M,2], or NULL): the accepted flag (1 / 0) and r (0 when rejected).
+ * 5. naruto_odom_step, unchanged, on the first 29 sums.
+ * gated != 0: a points / accumulate launch of a level whose done word is set returns at once and writes nothing; gated == 0: the
+ * evaluation runs whatever the level words say (the start's and the final evaluation, which go to sums buffers of their own).
+ *
+ * naruto_sdfreg_init (one thread): T = est[i] (float32 -> fp64), the level words 0, the start's T = the same 16 doubles.
+ * naruto_sdfreg_verdict (one thread): sums_start / sums_final = ungated evaluations at the finest level used, of the start (made right
+ *   after init) and of the final T.  PASS iff that level's status is not NARUTO_ICP_DEGENERATE, rows >= min_overlap * n_valid, rows > 0,
+ *   sum r^2 / rows of the final T <= that of the start, |t|^2 <= max_trans^2 with t = the difference of the two translations, and
+ *   trace(R_start^T R) >= min_trace (= 1 + 2 cos(max_rot), computed by the caller).  A NaN fails its comparison.  On FAIL T becomes the
+ *   start.  record: DEVICE float64 [NARUTO_SDFREG_RECORD]: verdict (1 / 0), n_valid, rows, the start's rmse, the final rmse, |t|, trace,
+ *   that level's status; -1 where a figure is not finite.
+ * naruto_sdfreg_commit (one thread): est[i] = T rounded once to float32; pose6_out [6] = naruto_pose_log of the stored matrix, exactly
+ *   as naruto_pose_predict_relative ends.  i < num_frames. */
+#define NARUTO_SDFREG_SUMS 30
+#define NARUTO_SDFREG_STATE_DOUBLES 64
+#define NARUTO_SDFREG_RECORD 8
+typedef struct NarutoSdfRegDesc {  /* HOST */
+    float trunc, sdf_gate;
+    float bbox_min[3], bbox_max[3];
+    uint32_t n_levels;
+    uint32_t levels[NARUTO_ODOM_MAX_LEVELS];   /* from the coarsest to the finest */
+    uint32_t iters[NARUTO_ODOM_MAX_LEVELS];    /* the cap of levels[k] */
+} NarutoSdfRegDesc;
+typedef struct NarutoSdfRegGate {  /* HOST: the verdict's thresholds; min_trace = 1 + 2 cos(the largest rotation) */
+    double max_trans, min_trace, min_overlap;
+} NarutoSdfRegGate;
+size_t naruto_sdfreg_workspace_bytes(const NarutoOdomDesc* odom);
+int naruto_sdfreg_points(const NarutoOdomDesc* odom, const NarutoSdfRegDesc* reg, uint32_t level, int32_t gated, const float* maps_cur, const double* state,
+                         float* x, float* q, uint8_t* valid, void* stream);
+int naruto_sdfreg_accumulate(const NarutoOdomDesc* odom, const NarutoSdfRegDesc* reg, uint32_t level, int32_t gated, const float* sdf_uncert, const float* d_x,
+                             const float* q, const uint8_t* valid, const double* state, double* sums, void* workspace, double* rows, void* stream);
+int naruto_sdfreg_init(const float* est, uint32_t num_frames, uint32_t i, double* state, void* stream);
+int naruto_sdfreg_verdict(const NarutoSdfRegDesc* reg, const NarutoSdfRegGate* gate, const double* sums_start, const double* sums_final, double* state,
+                          double* record, void* stream);
+int naruto_sdfreg_commit(float* est, uint32_t num_frames, uint32_t i, const double* state, float* pose6_out, void* stream);
+
+/* The planner's local RRT(reference src/planner/rrt.py and src/planner/rrt_naruto.py: class RRTNaruto, the
  * local_planner_method of every shipped config), on the volumes of naruto_map_volumes.  Unit: voxel.
  *
  * NarutoRrtPlan (HOST struct) describes one planner and its caller-owned device buffers:

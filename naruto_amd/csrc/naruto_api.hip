@@ -33,6 +33,7 @@
 #include "naruto_posechain.hip"
 #include "naruto_icp.hip"
 #include "naruto_odom.hip"
+#include "naruto_sdfreg.hip"
 #include "naruto_view.hip"
 
 using namespace naruto;
@@ -2660,6 +2661,99 @@ int naruto_pose_predict_relative(float* est, uint32_t num_frames, uint32_t i, co
     if (i < 1u || i >= num_frames) return fail(NARUTO_ERR_INVALID, "pose_predict_relative: frame %u of %u (the first frame is given, not predicted)", i, num_frames);
     hipLaunchKernelGGL(k_pose_predict_relative, dim3(1), dim3(64), 0, (hipStream_t)stream, est, i, state_T, pose6_out);
     return check_launch("pose_predict_relative");
+}
+
+// ---- frame-to-model alignment (naruto_sdfreg.hip) -------------------------------------------------------------------------
+namespace {
+static_assert(kSdfRegSums == NARUTO_SDFREG_SUMS && kSdfRegStateDoubles == NARUTO_SDFREG_STATE_DOUBLES && kSdfRegRecord == NARUTO_SDFREG_RECORD, "naruto_hip.h");
+// the registration's desc: false when it is refused
+bool sdfreg_desc(const NarutoSdfRegDesc* r, const OdomGeom& g, const char* who, SdfRegBox* box) {
+    if (r == nullptr) { fail(NARUTO_ERR_INVALID, "%s: NULL registration desc", who); return false; }
+    if (!(r->trunc > 0.0f) || !std::isfinite(r->trunc) || !(r->sdf_gate > 0.0f) || !std::isfinite(r->sdf_gate)) {
+        fail(NARUTO_ERR_INVALID, "%s: trunc and sdf_gate must be finite and positive", who);
+        return false;
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(r->bbox_min[a]) || !std::isfinite(r->bbox_max[a]) || !(r->bbox_max[a] > r->bbox_min[a])) {
+            fail(NARUTO_ERR_INVALID, "%s: the bounding box must be finite with bbox_max > bbox_min", who);
+            return false;
+        }
+        box->lo[a] = r->bbox_min[a]; box->hi[a] = r->bbox_max[a];
+    }
+    if (r->n_levels == 0u || r->n_levels > g.levels) { fail(NARUTO_ERR_INVALID, "%s: %u levels of a pyramid of %u", who, r->n_levels, g.levels); return false; }
+    for (uint32_t k = 0; k < r->n_levels; ++k) {
+        if (r->levels[k] >= g.levels || (k > 0u && r->levels[k] >= r->levels[k - 1u]) || r->iters[k] == 0u) {
+            fail(NARUTO_ERR_INVALID, "%s: the levels run from the coarsest to the finest inside the pyramid, each with a cap >= 1", who);
+            return false;
+        }
+    }
+    return true;
+}
+}  // namespace
+
+size_t naruto_sdfreg_workspace_bytes(const NarutoOdomDesc* odom) {
+    OdomGeom g;
+    return odom_geom(odom, "sdfreg_workspace_bytes", &g) ? (size_t)odom_parts(g.lv[0]) * kSdfRegSums * sizeof(double) : 0;
+}
+
+int naruto_sdfreg_points(const NarutoOdomDesc* odom, const NarutoSdfRegDesc* reg, uint32_t level, int32_t gated, const float* maps_cur, const double* state,
+                         float* x, float* q, uint8_t* valid, void* stream) {
+    OdomGeom g;
+    SdfRegBox box;
+    if (!odom_geom(odom, "sdfreg_points", &g) || !sdfreg_desc(reg, g, "sdfreg_points", &box)) return NARUTO_ERR_INVALID;
+    if (level >= g.levels) return fail(NARUTO_ERR_INVALID, "sdfreg_points: level %u of %u", level, g.levels);
+    if (maps_cur == nullptr || state == nullptr || x == nullptr || q == nullptr || valid == nullptr) return fail(NARUTO_ERR_INVALID, "sdfreg_points: NULL argument");
+    const OdomLevel lv = g.lv[level];
+    const uint32_t n = lv.h * lv.w;
+    hipLaunchKernelGGL(k_sdfreg_points, dim3(odom_parts(lv)), dim3(kOdomThreads), 0, (hipStream_t)stream, n, (int32_t)level, gated, box,
+                       maps_cur + lv.offset + n, state, x, q, valid);
+    return check_launch("sdfreg_points");
+}
+
+int naruto_sdfreg_accumulate(const NarutoOdomDesc* odom, const NarutoSdfRegDesc* reg, uint32_t level, int32_t gated, const float* sdf_uncert, const float* d_x,
+                             const float* q, const uint8_t* valid, const double* state, double* sums, void* workspace, double* rows, void* stream) {
+    OdomGeom g;
+    SdfRegBox box;
+    if (!odom_geom(odom, "sdfreg_accumulate", &g) || !sdfreg_desc(reg, g, "sdfreg_accumulate", &box)) return NARUTO_ERR_INVALID;
+    if (level >= g.levels) return fail(NARUTO_ERR_INVALID, "sdfreg_accumulate: level %u of %u", level, g.levels);
+    if (sdf_uncert == nullptr || d_x == nullptr || q == nullptr || valid == nullptr || state == nullptr || sums == nullptr || workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "sdfreg_accumulate: NULL argument");
+    const OdomLevel lv = g.lv[level];
+    const uint32_t parts = odom_parts(lv);
+    hipLaunchKernelGGL(k_sdfreg_accumulate, dim3(parts), dim3(kOdomThreads), 0, (hipStream_t)stream, lv.h * lv.w, (int32_t)level, gated, (double)reg->trunc,
+                       (double)reg->sdf_gate, box, sdf_uncert, d_x, q, valid, state, reinterpret_cast<double*>(workspace), rows);
+    if (int rc = check_launch("sdfreg_accumulate")) return rc;
+    hipLaunchKernelGGL(k_sdfreg_finish, dim3(1), dim3(kOdomThreads), 0, (hipStream_t)stream, (int32_t)level, gated, state, parts,
+                       reinterpret_cast<const double*>(workspace), sums);
+    return check_launch("sdfreg_finish");
+}
+
+int naruto_sdfreg_init(const float* est, uint32_t num_frames, uint32_t i, double* state, void* stream) {
+    if (est == nullptr || state == nullptr) return fail(NARUTO_ERR_INVALID, "sdfreg_init: NULL argument");
+    if (i >= num_frames) return fail(NARUTO_ERR_INVALID, "sdfreg_init: frame %u of %u", i, num_frames);
+    hipLaunchKernelGGL(k_sdfreg_init, dim3(1), dim3(64), 0, (hipStream_t)stream, est, i, state);
+    return check_launch("sdfreg_init");
+}
+
+int naruto_sdfreg_verdict(const NarutoSdfRegDesc* reg, const NarutoSdfRegGate* gate, const double* sums_start, const double* sums_final, double* state,
+                          double* record, void* stream) {
+    if (reg == nullptr || gate == nullptr) return fail(NARUTO_ERR_INVALID, "sdfreg_verdict: NULL desc or gate");
+    if (reg->n_levels == 0u || reg->n_levels > (uint32_t)kOdomMaxLevels || reg->levels[reg->n_levels - 1u] >= (uint32_t)kOdomMaxLevels)
+        return fail(NARUTO_ERR_INVALID, "sdfreg_verdict: the desc names no finest level");
+    if (!(gate->max_trans >= 0.0) || !std::isfinite(gate->max_trans) || !(gate->min_trace >= -1.0 && gate->min_trace <= 3.0) ||
+        !(gate->min_overlap >= 0.0 && gate->min_overlap <= 1.0))
+        return fail(NARUTO_ERR_INVALID, "sdfreg_verdict: the gate needs a finite max_trans >= 0, min_trace in -1 .. 3, min_overlap in 0 .. 1");
+    if (sums_start == nullptr || sums_final == nullptr || state == nullptr || record == nullptr) return fail(NARUTO_ERR_INVALID, "sdfreg_verdict: NULL argument");
+    hipLaunchKernelGGL(k_sdfreg_verdict, dim3(1), dim3(64), 0, (hipStream_t)stream, SdfRegGate{gate->max_trans, gate->min_trace, gate->min_overlap},
+                       (int32_t)reg->levels[reg->n_levels - 1u], sums_start, sums_final, state, record);
+    return check_launch("sdfreg_verdict");
+}
+
+int naruto_sdfreg_commit(float* est, uint32_t num_frames, uint32_t i, const double* state, float* pose6_out, void* stream) {
+    if (est == nullptr || state == nullptr || pose6_out == nullptr) return fail(NARUTO_ERR_INVALID, "sdfreg_commit: NULL argument");
+    if (i >= num_frames) return fail(NARUTO_ERR_INVALID, "sdfreg_commit: frame %u of %u", i, num_frames);
+    hipLaunchKernelGGL(k_sdfreg_commit, dim3(1), dim3(64), 0, (hipStream_t)stream, est, i, state, pose6_out);
+    return check_launch("sdfreg_commit");
 }
 
 // ---- mesh culling (naruto_cull.hip) -------------------------------------------------------------------------------------

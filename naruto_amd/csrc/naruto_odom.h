@@ -1,7 +1,8 @@
 // The solver of the frame-to-frame depth odometry (naruto_odom.hip; the contract is restated in naruto_amd/odometry.py): from the 29 sums
 // of one point-to-plane evaluation -- the 21 upper entries of J^T J (row-major: (i, j), i <= j), the 6 of J^T r, sum r^2, the count -- to the
 // twist xi = (omega, t) = -(J^T J)^-1 J^T r by a Cholesky factorisation, and the left update T <- exp(xi) T of the rigid transform.
-// Host and device: naruto_debug_odom_solve runs the same code on the CPU.
+// Host and device: naruto_debug_odom_solve runs the same code on the CPU.  The fold of the per-thread sums (odom_fold_n, odom_add_row,
+// odom_fold_parts) is stated here once for naruto_odom.hip and naruto_sdfreg.hip.
 #pragma once
 
 #include "naruto_common.h"
@@ -116,6 +117,57 @@ __host__ __device__ inline void odom_step(const double sums[kOdomSums], int leve
     w[6] = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
     if (w[5] < kOdomConverged && w[6] < kOdomConverged) { w[1] = (double)kIcpConverged; w[0] = 1.0; }
     else if (w[2] >= cap) { w[1] = (double)kIcpMaxIteration; w[0] = 1.0; }
+}
+
+// ---- the summation rule of every accumulation over a pyramid level (naruto_odom.hip, naruto_sdfreg.hip): device only ----------------------
+constexpr int kOdomThreads = 256;
+constexpr uint32_t kOdomPer = 8;                                         // pixels per thread: thread t of workgroup b takes b*2048 + t + 256 k
+
+// odom_fold over N sums: s is [N][kOdomThreads] in LDS
+template <int N>
+__device__ __forceinline__ void odom_fold_n(double* s, double acc[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k * kOdomThreads + threadIdx.x] = acc[k];
+    __syncthreads();
+    for (uint32_t w = kOdomThreads / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k * kOdomThreads + threadIdx.x] += s[k * kOdomThreads + threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] = s[k * kOdomThreads];
+    }
+}
+
+// one row J = [q x n, n] with residual r into the sums [0..28], in k_odom_accumulate's order
+__device__ __forceinline__ void odom_add_row(double* acc, const double q[3], const double nn[3], double r) {
+#pragma clang fp contract(off)
+    const double J[6] = {q[1] * nn[2] - q[2] * nn[1], q[2] * nn[0] - q[0] * nn[2], q[0] * nn[1] - q[1] * nn[0], nn[0], nn[1], nn[2]};
+    int m = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b, ++m) acc[m] += J[a] * J[b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
+    acc[27] += r * r;
+    acc[28] += 1.0;
+}
+
+// the finishing workgroup of an accumulation over N sums: thread t adds the workgroups' vectors t, t + 256, ... in turn, then odom_fold_n
+template <int N>
+__device__ __forceinline__ void odom_fold_parts(double* s, uint32_t n_parts, const double* __restrict__ part, double acc[N]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = 0.0;
+    for (uint32_t i = threadIdx.x; i < n_parts; i += kOdomThreads) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] += part[(size_t)i * N + k];
+    }
+    odom_fold_n<N>(s, acc);
 }
 
 }  // namespace naruto

@@ -21,8 +21,6 @@
 
 namespace naruto {
 
-constexpr int kOdomThreads = 256;
-constexpr uint32_t kOdomPer = 8;                                         // pixels per thread of k_odom_accumulate
 
 struct OdomLevel { uint32_t h, w, start, offset; float fx, fy, cx, cy; }; // start: first thread of k_odom_maps; offset: floats into the maps block
 struct OdomGeom { OdomLevel lv[kOdomMaxLevels]; uint32_t levels, total, W; float band, jump; };
@@ -312,40 +310,6 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_maps(OdomGeom g, con
     base[i] = odom_intensity_at(level, color, g.W, u, v);
     base[(size_t)n + i] = gx;
     base[(size_t)n * 2u + i] = gy;
-}
-
-// odom_fold over N sums: s is [N][kOdomThreads] in LDS
-template <int N>
-__device__ __forceinline__ void odom_fold_n(double* s, double acc[N]) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) s[k * kOdomThreads + threadIdx.x] = acc[k];
-    __syncthreads();
-    for (uint32_t w = kOdomThreads / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) s[k * kOdomThreads + threadIdx.x] += s[k * kOdomThreads + threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) acc[k] = s[k * kOdomThreads];
-    }
-}
-
-// one row J = [q x n, n] with residual r into the sums [0..28], in k_odom_accumulate's order
-__device__ __forceinline__ void odom_add_row(double* acc, const double q[3], const double nn[3], double r) {
-#pragma clang fp contract(off)
-    const double J[6] = {q[1] * nn[2] - q[2] * nn[1], q[2] * nn[0] - q[0] * nn[2], q[0] * nn[1] - q[1] * nn[0], nn[0], nn[1], nn[2]};
-    int m = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = a; b < 6; ++b, ++m) acc[m] += J[a] * J[b];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
-    acc[27] += r * r;
-    acc[28] += 1.0;
 }
 
 // m at (u0 + a, v0 + b), a, b in [0, 1): top = s00 + a (s10 - s00), bot = s01 + a (s11 - s01), top + b (bot - top); s10 is (u0 + 1, v0)

@@ -21,7 +21,9 @@ rotation negated as the reference's ``load_Replica_pose`` does.  The run's traje
 ``traj_len(m),<value>`` (``evaluation.update_results_file``'s format).  ``--track`` estimates the camera poses during the run
 (``CoSLAMNarutoHIP(track=True)``) and adds ``ate_rmse(cm)`` / ``ate_mean(cm)``: the estimated trajectory against the poses the frames were
 taken at (``evaluation.ate``).  ``--prior_gate`` (with ``--motion_prior depth_icp`` or ``rgbd_icp``) switches on the odometry prior's scored
-starts and verdict (``CoSLAMNarutoHIP(prior_gate=True)``) and adds ``prior_failed_frames``, the frames whose prior was refused.  ``--eval_views K`` renders every K-th pose of the run from the final map and scores it against the
+starts and verdict (``CoSLAMNarutoHIP(prior_gate=True)``) and adds ``prior_failed_frames``, the frames whose prior was refused.
+``--model_align`` (with ``--track``) registers every predicted pose to the field's SDF before the tracker takes it
+(``CoSLAMNarutoHIP(model_align=True)``, ``naruto_amd.registration``) and adds ``align_failed_frames``, the frames whose alignment was refused.  ``--eval_views K`` renders every K-th pose of the run from the final map and scores it against the
 simulator: ``psnr``, ``ssim`` and ``depth_l1(cm)`` (``naruto_amd.render``).
 """
 
@@ -68,7 +70,8 @@ def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optio
     save.  When ``slam`` tracks (``CoSLAMNarutoHIP(track=True)``): also ``est_poses`` [num_iter,4,4] (``slam.resolved_poses()``, on the
     host) and ``ate`` (``evaluation.ate(est_poses, poses)``; None below 3 steps).  The planner keeps receiving the COMMANDED pose, the
     one the frame was rendered at, not the estimate -- as the reference's loop does (main.py:135-137).  With ``prior_gate``: also
-    ``prior_log`` [num_iter,16] float64 on the host, frame i's record of the odometry prior (``naruto_amd.odometry``; row 0 is zeros).  ``eval_views`` = K: after the final
+    ``prior_log`` [num_iter,16] float64 on the host, frame i's record of the odometry prior (``naruto_amd.odometry``; row 0 is zeros).  With
+    ``model_align``: also ``align_log`` [num_iter,8] float64 on the host, frame i's record of the model alignment (``naruto_amd.registration``).  ``eval_views`` = K: after the final
     mesh every K-th pose of the run is rendered from the map and scored against the simulator (``render.evaluate_views``): the result
     gains ``render_eval``.  None: no launch is added."""
     if planner is None and traj is None:
@@ -116,6 +119,8 @@ def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optio
         from .evaluation import ate
         out["est_poses"] = slam.resolved_poses().cpu()
         out["ate"] = ate(out["est_poses"], out["poses"]) if len(poses) >= 3 else None
+    if getattr(slam, "align_log", None) is not None:                       # the model alignment's records, one row per frame (row 0: zeros)
+        out["align_log"] = slam.align_log[:len(poses)].cpu()
     if getattr(slam, "prior_log", None) is not None:                       # the gated odometry prior's records, one row per frame (row 0: zeros)
         out["prior_log"] = slam.prior_log[:len(poses)].cpu()
     if eval_views is not None and poses:
@@ -156,6 +161,8 @@ def parse_args(argv=None):
     parser.add_argument("--motion_prior", type=str, default=None, choices=["const_speed", "depth_icp", "rgbd_icp"],
                         help="with --track: the tracker's initial pose from constant-speed extrapolation (default), from frame-to-frame depth odometry, "
                              "or from RGB-D odometry (depth plus a photometric term)")
+    parser.add_argument("--model_align", action="store_true",
+                        help="with --track: register every predicted pose to the field's SDF before the tracker takes it (adds align_failed_frames to results.txt)")
     parser.add_argument("--prior_gate", action="store_true",
                         help="with --motion_prior depth_icp / rgbd_icp: score the prior's two starts and judge its estimate (adds prior_failed_frames to results.txt)")
     parser.add_argument("--dataset", type=str, default="NARUTO", choices=["Replica", "MP3D", "NARUTO"], help="the planner's collision rule")
@@ -191,7 +198,8 @@ def main(argv=None) -> Dict:
     np.random.seed(args.seed)                      # the planner's RRT draws from numpy's generator
     os.makedirs(args.result_dir, exist_ok=True)
     slam = CoSLAMNarutoHIP(cfg, active_ray=not args.no_active_ray, num_frames=args.num_iter, seed=args.seed, result_dir=args.result_dir, track=args.track,
-                           motion_prior=args.motion_prior, prior_gate=True if args.prior_gate else None)
+                           motion_prior=args.motion_prior, prior_gate=True if args.prior_gate else None,
+                           model_align=True if args.model_align else None)
     sim = MeshSimHIP(args.mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=slam.device, mesh_frame=args.mesh_frame)
     planner = None
     if traj is None:
@@ -206,6 +214,8 @@ def main(argv=None) -> Dict:
     results = {"traj_len(m)": length}
     if out.get("ate") is not None:
         results.update({"ate_rmse(cm)": out["ate"]["ate_rmse_cm"], "ate_mean(cm)": out["ate"]["ate_mean_cm"]})
+    if out.get("align_log") is not None:
+        results["align_failed_frames"] = int((out["align_log"][1:, 0] == 0.0).sum())
     if out.get("prior_log") is not None:
         results["prior_failed_frames"] = int((out["prior_log"][1:, 0] == 0.0).sum())
     if out.get("render_eval") is not None:

@@ -67,6 +67,14 @@ coarsest level -- and after the level loop four checks at level 0 give a verdict
 chosen start instead of the lost estimate.  Frame i's record goes into ``prior_log[i]`` ([num_frames,16] float64 on the device: verdict,
 chosen start, costs, overlap, rmse ...); six launches more per frame, still nothing read back.
 
+MODEL ALIGNMENT (``model_align=None`` | ``True`` | ``registration.RegistrationGate``, with ``track=True`` and any ``motion_prior``; ``None`` is
+the step above, launch for launch and bit for bit).  Every prior above is frame to frame, so the chain drifts; with ``model_align`` the
+predicted ``est[i]`` is registered to the field's own SDF (``naruto_amd.registration.FieldRegistrationHIP.align_device``: the frame's depth
+back-projected, Gauss-Newton on the signed distance the field reports) after ``pose_predict`` / ``pose_predict_relative`` and before
+``track_device``; it rewrites ``est[i]`` and ``tracker.pose_init`` on the device, or leaves the prediction's bits when its verdict is FAIL.
+Frame i's record goes into ``align_log[i]`` ([num_frames,8] float64 on the device).  The odometry's current maps are reused when an
+odometry prior is on; otherwise the frame's maps are made here (one launch).  Launches only: a tracked frame still never waits for the host.
+
 A config with ``tracking.disable: False`` and no ``track=True`` is refused (``NotImplementedError``) before the library is touched:
 tracking is switched on by the keyword, whatever ``tracking.disable`` says.  Out of scope: ``tracking.iter_point > 0`` (``tracking_pc``),
 other ``training.rot_rep`` (both refused by ``tracking.tracking_settings``), data-parallel pose refinement.
@@ -145,7 +153,7 @@ class DevicePoses:
 class CoSLAMNarutoHIP:
     def __init__(self, config: Dict, voxel_size: float = 0.1, active_ray: Optional[bool] = None, act_ray_num_uncert_sample: int = 500,
                  act_ray_oversample_mul: int = 4, num_frames: int = 2000, seed: Optional[int] = 0, result_dir: Optional[str] = None, device="cuda",
-                 track: bool = False, motion_prior: Optional[str] = None, prior_gate=None):
+                 track: bool = False, motion_prior: Optional[str] = None, prior_gate=None, model_align=None):
         """``config``: a Co-SLAM config (``naruto_amd.config.load_config``); it is kept and, as in the reference's ``override_config``,
         ``mapping.active_ray`` is overwritten when ``active_ray`` is given.  ``num_frames``: the length of the run (sizes the keyframe store
         and the pose tensor).  ``seed``: keys the keyframe store's draws and, through ``torch.manual_seed`` (None: left alone), the
@@ -154,7 +162,9 @@ class CoSLAMNarutoHIP:
         (module docstring) with ``tracking_settings(config)``, whatever ``tracking.disable`` says.  ``motion_prior``: where a tracked
         frame's initial pose comes from, ``"const_speed"`` (the default), ``"depth_icp"`` or ``"rgbd_icp"`` (module docstring); needs ``track=True``.
         ``prior_gate``: None (today's step, launch for launch), True or an ``odometry.OdometryGate``: the odometry prior scores its two starts
-        and judges its estimate (module docstring); needs an odometry prior."""
+        and judges its estimate (module docstring); needs an odometry prior.  ``model_align``: None (today's step, launch for launch), True or a
+        ``registration.RegistrationGate``: every tracked frame's predicted pose is registered to the field's SDF before the tracker takes it
+        (module docstring); needs ``track=True``, works with every ``motion_prior``."""
         tk = config.get("tracking") or {}
         self.track = bool(track)
         if motion_prior is not None and motion_prior not in ("const_speed", "depth_icp", "rgbd_icp"):
@@ -162,6 +172,8 @@ class CoSLAMNarutoHIP:
         if motion_prior is not None and not self.track:
             raise ValueError("CoSLAMNarutoHIP: motion_prior is the tracker's initial pose and needs track=True")
         self.motion_prior = motion_prior or "const_speed"
+        if model_align is not None and model_align is not False and not self.track:
+            raise ValueError("CoSLAMNarutoHIP: model_align refines the tracker's initial pose and needs track=True")
         if prior_gate is not None and prior_gate is not False and self.motion_prior not in ("depth_icp", "rgbd_icp"):
             raise ValueError("CoSLAMNarutoHIP: prior_gate judges the odometry prior and needs motion_prior='depth_icp' or 'rgbd_icp'")
         if not self.track and not bool(tk.get("disable", True)):
@@ -220,6 +232,13 @@ class CoSLAMNarutoHIP:
             from .odometry import OdometryGate
             self.prior_gate = OdometryGate.of(prior_gate)
             self.prior_log = torch.zeros(self.num_frames, 16, dtype=torch.float64, device=self.device)     # frame i's record (odometry.py)
+        self.aligner, self.align_log = None, None
+        if model_align is not None and model_align is not False:
+            from .registration import FieldRegistrationHIP, RegistrationGate
+            self.aligner = FieldRegistrationHIP(self.model, config, (self.H, self.W, self.fx, self.fy, self.cx, self.cy), gate=RegistrationGate.of(model_align),
+                                                device=self.device)
+            self._align_maps = None if self.odometry is not None else self.aligner.pyramid.new_maps()    # an odometry prior's maps are read as they are
+            self.align_log = torch.zeros(self.num_frames, 8, dtype=torch.float64, device=self.device)      # frame i's record (registration.py)
         self.cached_uncert = None
         self.filter_depth = bool(mp.get("filter_depth", False))
         self._n_valid = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -289,6 +308,9 @@ class CoSLAMNarutoHIP:
             pose_predict_relative(est.tensor, i, state, self.tracker.pose_init)
         else:
             pose_predict(est.tensor, i, bool(self.tracking["const_speed"]), self.tracker.pose_init)
+        if self.aligner is not None:
+            maps = self._odom_maps[i & 1] if self.odometry is not None else self.aligner.frame_maps(depth, out=self._align_maps)
+            self.aligner.align_device(maps, est.tensor, i, self.tracker.pose_init, record=self.align_log[i])
         tracked = self.tracker.track_device(self.rays_d, color, depth)
         pose_commit(est.tensor, rel.tensor, i, every, tracked)
         est.mark(i)

@@ -11,11 +11,12 @@ the mapping schedule of tools/time_run.py, tracking with replica_coslam.yaml's s
     the others, the trajectory error of the estimate and the motion per step the planner commands (against what one tracking call
     can cover: iter x lr).
 
-    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632] [--motion-prior depth_icp | rgbd_icp [--prior-gate]]
+    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632] [--motion-prior depth_icp | rgbd_icp [--prior-gate] [--model-align]]
 
 With --motion-prior only the run is made, with CoSLAMNarutoHIP(motion_prior=...), and it is MERGED into the output file as
 office_0_size.run_motion_prior_<name>, beside the run of the default prior (--no-const-speed: tracking.const_speed off, key suffix
-_const_speed_off).  rgbd_icp needs an image: the tool's mesh has no colours, so its vertices are then coloured by a smooth function of position.
+_const_speed_off; --prior-gate: _gated; --model-align: the model alignment of naruto_amd.registration on, _aligned, with its per-frame
+records).  rgbd_icp needs an image: the tool's mesh has no colours, so its vertices are then coloured by a smooth function of position.
 
 Host timers (time.perf_counter), medians over --repeat.  Nothing is asserted.  There is NO reference number: the reference's loop needs
 Habitat-Sim and tiny-cuda-nn, neither of which is on this stack."""
@@ -122,11 +123,45 @@ def frames(args, dev, mesh):
     return out
 
 
+class OneLine:
+    """A list that ``dump_doc`` writes on one line."""
+
+    def __init__(self, values):
+        self.values = values
+
+
+def sig(values, digits=4):
+    """Nested lists of numbers at ``digits`` significant digits (integers stay integers): what a per-frame table needs, a fifth of the bytes."""
+    if isinstance(values, (list, tuple)):
+        return [sig(v, digits) for v in values]
+    return int(values) if float(values).is_integer() else float(f"{float(values):.{digits}g}")
+
+
+def dump_doc(doc, fh):
+    """The document with indent 1 as ever; the per-frame tables and frame lists of the ``_aligned`` runs one line each, so that two runs of
+    199 frames add some twenty lines to the file and not thirteen thousand."""
+    def wrap(v):
+        if isinstance(v, dict):
+            return {k: wrap(x) for k, x in v.items()}
+        return OneLine(v) if isinstance(v, list) else v
+    out = dict(doc, office_0_size={k: ({a: wrap(b) if a.endswith("per_frame_from_1") or a.endswith("failed_frames") else b for a, b in run.items()}
+                                       if k.endswith("_aligned") else run) for k, run in doc["office_0_size"].items()})
+    lines = []
+
+    def token(o):
+        lines.append(json.dumps(o.values, separators=(",", ":")))
+        return f"@@{len(lines) - 1}@@"
+    text = json.dumps(out, indent=1, default=token)
+    for n, line in enumerate(lines):
+        text = text.replace(f'"@@{n}@@"', line)
+    fh.write(text + "\n")
+
+
 def whole_run(args, dev, mesh):
     cfg = config(not args.no_const_speed)
     np.random.seed(args.seed)
     slam = CoSLAMNarutoHIP(cfg, active_ray=True, num_frames=args.steps, seed=args.seed, device=dev, track=True, motion_prior=args.motion_prior,
-                           prior_gate=True if args.prior_gate else None)
+                           prior_gate=True if args.prior_gate else None, model_align=True if args.model_align else None)
     sim = MeshSimHIP(mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=dev)
     planner = NarutoPlannerHIP(dataset="NARUTO", device=dev)
     planner.update_sim(sim)
@@ -178,6 +213,13 @@ def whole_run(args, dev, mesh):
         gated = {"prior_failed_frames": failed, "first_frame_prior_over_10cm": first(pe[0]), "first_frame_tracked_over_10cm": first(te[0]),
                  "per_frame_from_1": {"prior_error_cm": pe[0], "prior_error_deg": pe[1], "tracked_error_cm": te[0], "tracked_error_deg": te[1],
                                       "record": log[1:].tolist()}}
+    if args.model_align:                                                    # the alignment's records, frame 1 on, and every frame's tracked error
+        log = out["align_log"]
+        g = gt[:, :3, 3]
+        gated["align_failed_frames"] = [int(i) for i in torch.nonzero(log[1:, 0] == 0.0).flatten() + 1]
+        gated["align_per_frame_from_1"] = {"record": sig(log[1:].tolist()), "tracked_error_cm": sig(((out["est_poses"][1:, :3, 3].double() - g[1:]).norm(dim=1) * 100.0).tolist())}
+        if "per_frame_from_1" in gated:                                     # the prior's 16-double records stay with the runs without alignment
+            gated["per_frame_from_1"] = {k: sig(v) for k, v in gated["per_frame_from_1"].items() if k != "record"}
     return {**gated, "steps": args.steps, "wall_s_with_final_mesh_and_checkpoint": wall, "loop_s": loop, "steps_per_second": args.steps / loop,
             "phases_total_s": {k: v["total_s"] for k, v in out["timing"].items()},
             "slam_first_frame_ms": slam_t[0] * 1e3,
@@ -201,6 +243,8 @@ def main():
     ap.add_argument("--no-const-speed", action="store_true", help="with --motion-prior: tracking.const_speed off (depth_icp then starts from the identity)")
     ap.add_argument("--prior-gate", action="store_true", help="with --motion-prior depth_icp / rgbd_icp: the prior's scored starts and verdict on; key suffix _gated; "
                     "per-frame errors of the prior and of the tracked pose against the commanded pose, and the records")
+    ap.add_argument("--model-align", action="store_true", help="with --motion-prior: every predicted pose registered to the field's SDF before the tracker "
+                    "takes it (CoSLAMNarutoHIP(model_align=True)); key suffix _aligned; the per-frame records and tracked errors")
     ap.add_argument("--small-test", default=None, help="JSON object merged into the document (figures of tests/test_gpu_tracked_run.py)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -215,10 +259,10 @@ def main():
         if args.out:
             with open(args.out) as fh:
                 doc = json.load(fh)
-            doc["office_0_size"]["run_motion_prior_" + args.motion_prior + ("_const_speed_off" if args.no_const_speed else "") + ("_gated" if args.prior_gate else "")] = run
+            doc["office_0_size"]["run_motion_prior_" + args.motion_prior + ("_const_speed_off" if args.no_const_speed else "") + ("_gated" if args.prior_gate else "") +
+                                ("_aligned" if args.model_align else "")] = run
             with open(args.out, "w") as fh:
-                json.dump(doc, fh, indent=1)
-                fh.write("\n")
+                dump_doc(doc, fh)
         return
     res["frames"] = frames(args, dev, mesh)
     print(json.dumps(res["frames"], indent=1), flush=True)
