@@ -742,6 +742,65 @@ int naruto_odom_choose(uint32_t K, const double* sums, const double* cands, int3
 int naruto_odom_verdict(const NarutoOdomDesc* desc, const NarutoOdomGate* gate, const double* sums, const double* cands, double* state, double* record,
                         void* stream);
 
+/* Keyframe-anchored odometry prior: a ring of reference frames chosen on the device (opt-in; nothing above changes its bits or its
+ * launches; the contract is restated in naruto_amd/odometry.py and tests/odometry_anchor_spec.py is the numpy twin; nothing like it is in
+ * the reference tree: PARITY UNPINNED).  The gated estimate composes every T onto the frame before, so every estimate's bias and noise
+ * stays in the pose; here frame i is registered to one of `slots` kept frames and est[i] = est[that frame] @ T.
+ *
+ * ring: DEVICE float32, `slots` (1 .. NARUTO_ODOM_MAX_REFS) maps blocks back to back, the stride a block's byte size: depth blocks when
+ *   photo == NULL, RGB-D blocks when photo is given (as naruto_odom_score tells them apart).
+ * head: DEVICE int32 [NARUTO_ODOM_ANCHOR_HEAD]: [0] the slot written last, [1] the count of consecutive refused estimates, [2] the slot
+ *   chosen for the current frame, [3] the promote decision of the current frame (0 / 1), [4 + s] slot s's frame id (-1 = empty).  The
+ *   caller initialises it (frame 0 in slot 0: {0, 0, 0, 0, 0, -1, ...}) and copies frame 0's maps into slot 0.  A slot's pose is not
+ *   stored: it is est[frame id] as it stands when it is read.  A slot word that is not < slots reads slot slots - 1: no word leaves the ring.
+ * naruto_odom_anchor_candidates (one thread, 1 <= i < num_frames): cands [slots,2,16] DEVICE float64: for slot s with frame f the starts
+ *   R = inv(est[f]) @ est[i-1] and R @ M, M = inv(est[i-2]) @ est[i-1] (i > 1, else the identity), with the pose chain's inverse and
+ *   product, fp64 from the float32 matrices.  f == i-1 (and an empty slot): the identity and M, naruto_odom_candidates' bits.
+ * naruto_odom_score_refs: naruto_odom_score at K = 2 for every slot in one launch plus one finishing launch: slot s reads the ring's block s
+ *   as the previous frame and cands[s]; sums [slots, 9] equal naruto_odom_score(K = 2) on that block in every bit; an empty slot's
+ *   workgroups leave at once and its sums are zeros.  workspace: naruto_odom_score_refs_workspace_bytes.
+ * naruto_odom_anchor_choose (one thread): naruto_odom_choose's cost per (slot, start) of the slots that are not empty; the lowest wins, ties
+ *   go to the larger frame id, then to the lower start; no such slot or every cost +inf: the slot written last, start 0.  Writes head[2];
+ *   cands [2,16] = the chosen slot's pair (what naruto_odom_verdict reads); the state block as naruto_odom_choose writes it; record [1] the
+ *   start, [2], [3] the chosen slot's costs, [4], [5] -1, the rest 0; anchor_record [0], [1], [2], [6], [7] (below), [3..5] 0.
+ * naruto_odom_accumulate_anchored, naruto_odom_score_anchored (K = 1): naruto_odom_accumulate (photo == NULL) or
+ *   naruto_odom_rgbd_accumulate (photo given), and naruto_odom_score, with maps_prev = the ring's block head[2], resolved at kernel entry:
+ *   the same kernel bodies, the same bits as those calls on that block.  naruto_odom_step and naruto_odom_verdict run unchanged.
+ * naruto_odom_anchor_update (one thread), from the verdict's record (T is relative to the chosen reference): PASS: the streak is 0 and the
+ *   frame is promoted when n_geo < min_overlap * n_valid, |t| > max_trans or trace < min_trace.  FAIL: the streak grows, and at `refail` the
+ *   frame is promoted and the streak is 0 again.  A promoted frame takes slot (head[0] + 1) mod slots: head[0] and that slot's frame id = i
+ *   are written here; head[1], head[3]; anchor_record [3], [4], [5].  NarutoOdomAnchor is a HOST struct, min_trace as NarutoOdomGate's.
+ * naruto_odom_anchor_promote: when head[3] is set, maps_cur is copied into the ring's block head[0]; every workgroup reads head[3] first,
+ *   the other blocks' bytes are untouched, the head is only read.
+ * naruto_pose_predict_anchored: est[i] = est[f] @ T, f = anchor_record[1] (outside 0 .. i-1: i-1), fp64 from the float32 matrix, rounded once;
+ *   pose6_out as naruto_pose_predict_relative ends.  Before or after the update and the promote: the record keeps the reference's frame id.
+ * anchor_record: DEVICE float64 [NARUTO_ODOM_ANCHOR_WORDS] per frame: [0] the chosen slot, [1] its frame id, [2] the slots that were not
+ *   empty, [3] promoted (0 / 1), [4] the slot written (-1 = none), [5] the fail streak after the frame, [6] the best cost, [7] the runner-up
+ *   among all (slot, start) pairs (-1 where +inf).
+ * The anchored estimate is the fixed sequence: maps, anchor_candidates, score_refs at the coarsest level, anchor_choose, the level loop with
+ * accumulate_anchored, score_anchored at level 0, verdict, anchor_update, anchor_promote, pose_predict_anchored.  Nothing is read back. */
+#define NARUTO_ODOM_MAX_REFS 8
+#define NARUTO_ODOM_ANCHOR_HEAD 12
+#define NARUTO_ODOM_ANCHOR_WORDS 8
+typedef struct NarutoOdomAnchor {  /* HOST: the promote policy; min_trace = 1 + 2 cos(the largest rotation to a reference) */
+    uint32_t slots, refail;
+    double min_overlap, max_trans, min_trace;
+} NarutoOdomAnchor;
+size_t naruto_odom_score_refs_workspace_bytes(const NarutoOdomDesc* desc, uint32_t slots);
+int naruto_odom_anchor_candidates(const float* est, uint32_t num_frames, uint32_t i, const int32_t* head, uint32_t slots, double* cands, void* stream);
+int naruto_odom_score_refs(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* ring, const int32_t* head, uint32_t slots,
+                           const float* maps_cur, const double* cands, double trunc, double* sums, void* workspace, void* stream);
+int naruto_odom_anchor_choose(uint32_t slots, const double* sums, const double* cands_all, int32_t photo_on, double trunc, double photo_max_diff, int32_t* head,
+                              double* cands, double* state, double* record, double* anchor_record, void* stream);
+int naruto_odom_accumulate_anchored(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* ring, const int32_t* head,
+                                    uint32_t slots, const float* maps_cur, const double* state, double* sums, void* workspace, void* stream);
+int naruto_odom_score_anchored(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* ring, const int32_t* head, uint32_t slots,
+                               const float* maps_cur, const double* cands, double trunc, double* sums, void* workspace, void* stream);
+int naruto_odom_anchor_update(const NarutoOdomAnchor* anchor, uint32_t i, const double* record, int32_t* head, double* anchor_record, void* stream);
+int naruto_odom_anchor_promote(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t slots, const int32_t* head, const float* maps_cur, float* ring,
+                               void* stream);
+int naruto_pose_predict_anchored(float* est, uint32_t num_frames, uint32_t i, const double* anchor_record, const double* state_T, float* pose6_out, void* stream);
+
 /* Frame-to-model alignment: a depth frame registered to the field's own SDF, an opt-in refinement between any motion prior and the
  * tracker (nothing like it is in the reference tree: PARITY UNPINNED; the contract is restated in naruto_amd/registration.py and
  * tests/field_registration_spec.py is the numpy twin).  Conventions, the maps block, the pyramid (NarutoOdomDesc), the state block's

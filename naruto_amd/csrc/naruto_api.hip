@@ -33,6 +33,7 @@
 #include "naruto_posechain.hip"
 #include "naruto_icp.hip"
 #include "naruto_odom.hip"
+#include "naruto_odom_anchor.hip"
 #include "naruto_sdfreg.hip"
 #include "naruto_view.hip"
 
@@ -2661,6 +2662,160 @@ int naruto_pose_predict_relative(float* est, uint32_t num_frames, uint32_t i, co
     if (i < 1u || i >= num_frames) return fail(NARUTO_ERR_INVALID, "pose_predict_relative: frame %u of %u (the first frame is given, not predicted)", i, num_frames);
     hipLaunchKernelGGL(k_pose_predict_relative, dim3(1), dim3(64), 0, (hipStream_t)stream, est, i, state_T, pose6_out);
     return check_launch("pose_predict_relative");
+}
+
+// ---- keyframe-anchored odometry prior (naruto_odom_anchor.hip) --------------------------------------------------------------
+namespace {
+static_assert(kOdomMaxRefs == NARUTO_ODOM_MAX_REFS && kOdomAnchorHead == NARUTO_ODOM_ANCHOR_HEAD && kOdomAnchorWords == NARUTO_ODOM_ANCHOR_WORDS, "naruto_hip.h");
+// what every call on a ring checks: the desc, the photometric term and the slot count; the ring's stride in floats (photo given: RGB-D blocks)
+bool odom_ring(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t slots, const char* who, OdomGeom* g, uint64_t* stride) {
+    if (!odom_geom(desc, who, g)) return false;
+    if (photo != nullptr && (!(photo->weight >= 0.0f) || !std::isfinite(photo->weight) || !(photo->max_diff >= 0.0f))) {
+        fail(NARUTO_ERR_INVALID, "%s: the photometric weight must be finite and >= 0, max_diff >= 0", who);
+        return false;
+    }
+    if (slots == 0u || slots > (uint32_t)kOdomMaxRefs) { fail(NARUTO_ERR_INVALID, "%s: %u slots (1 .. %d)", who, slots, kOdomMaxRefs); return false; }
+    *stride = (uint64_t)g->total * (photo != nullptr ? 10u : 7u);
+    return true;
+}
+}  // namespace
+
+size_t naruto_odom_score_refs_workspace_bytes(const NarutoOdomDesc* desc, uint32_t slots) {
+    OdomGeom g;
+    uint64_t stride;
+    if (!odom_ring(desc, nullptr, slots, "odom_score_refs_workspace_bytes", &g, &stride)) return 0;
+    return (size_t)slots * odom_parts(g.lv[0]) * kOdomRefSums * sizeof(double);
+}
+
+int naruto_odom_anchor_candidates(const float* est, uint32_t num_frames, uint32_t i, const int32_t* head, uint32_t slots, double* cands, void* stream) {
+    if (est == nullptr || head == nullptr || cands == nullptr) return fail(NARUTO_ERR_INVALID, "odom_anchor_candidates: NULL argument");
+    if (i < 1u || i >= num_frames) return fail(NARUTO_ERR_INVALID, "odom_anchor_candidates: frame %u of %u (the first frame has no reference)", i, num_frames);
+    if (slots == 0u || slots > (uint32_t)kOdomMaxRefs) return fail(NARUTO_ERR_INVALID, "odom_anchor_candidates: %u slots (1 .. %d)", slots, kOdomMaxRefs);
+    hipLaunchKernelGGL(k_odom_anchor_candidates, dim3(1), dim3(64), 0, (hipStream_t)stream, est, i, head, slots, cands);
+    return check_launch("odom_anchor_candidates");
+}
+
+int naruto_odom_score_refs(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* ring, const int32_t* head, uint32_t slots,
+                           const float* maps_cur, const double* cands, double trunc, double* sums, void* workspace, void* stream) {
+    OdomGeom g;
+    uint64_t stride;
+    if (!odom_ring(desc, photo, slots, "odom_score_refs", &g, &stride)) return NARUTO_ERR_INVALID;
+    if (level >= g.levels) return fail(NARUTO_ERR_INVALID, "odom_score_refs: level %u of %u", level, g.levels);
+    if (!(trunc > 0.0) || !std::isfinite(trunc)) return fail(NARUTO_ERR_INVALID, "odom_score_refs: trunc must be a finite positive number of metres");
+    if (ring == nullptr || head == nullptr || maps_cur == nullptr || cands == nullptr || sums == nullptr || workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "odom_score_refs: NULL argument");
+    const OdomLevel lv = g.lv[level];
+    const uint32_t parts = odom_parts(lv), ioff = g.total * 7u + lv.start * 3u;
+    const double md = (double)desc->max_dist, max_diff = photo != nullptr ? (double)photo->max_diff : 0.0;
+    double* part = reinterpret_cast<double*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    if (photo != nullptr && photo->weight > 0.0f)
+        hipLaunchKernelGGL((k_odom_score_refs<true>), dim3(parts, slots), dim3(kOdomThreads), 0, st, lv, ioff, md * md, trunc * trunc, max_diff, stride, parts, head,
+                           ring, maps_cur, cands, part);
+    else
+        hipLaunchKernelGGL((k_odom_score_refs<false>), dim3(parts, slots), dim3(kOdomThreads), 0, st, lv, ioff, md * md, trunc * trunc, max_diff, stride, parts, head,
+                           ring, maps_cur, cands, part);
+    if (int rc = check_launch("odom_score_refs")) return rc;
+    hipLaunchKernelGGL(k_odom_score_refs_finish, dim3(slots), dim3(kOdomThreads), 0, st, parts, head, (const double*)part, sums);
+    return check_launch("odom_score_refs_finish");
+}
+
+int naruto_odom_anchor_choose(uint32_t slots, const double* sums, const double* cands_all, int32_t photo_on, double trunc, double photo_max_diff, int32_t* head,
+                              double* cands, double* state, double* record, double* anchor_record, void* stream) {
+    if (slots == 0u || slots > (uint32_t)kOdomMaxRefs) return fail(NARUTO_ERR_INVALID, "odom_anchor_choose: %u slots (1 .. %d)", slots, kOdomMaxRefs);
+    if (!(trunc > 0.0) || !std::isfinite(trunc)) return fail(NARUTO_ERR_INVALID, "odom_anchor_choose: trunc must be a finite positive number of metres");
+    if (photo_on != 0 && (!(photo_max_diff > 0.0) || !std::isfinite(photo_max_diff)))
+        return fail(NARUTO_ERR_INVALID, "odom_anchor_choose: photo_max_diff must be a finite positive number when the photometric cost is on");
+    if (sums == nullptr || cands_all == nullptr || head == nullptr || cands == nullptr || state == nullptr || record == nullptr || anchor_record == nullptr)
+        return fail(NARUTO_ERR_INVALID, "odom_anchor_choose: NULL argument");
+    hipLaunchKernelGGL(k_odom_anchor_choose, dim3(1), dim3(64), 0, (hipStream_t)stream, slots, photo_on, trunc, photo_max_diff, sums, cands_all, head, cands, state,
+                       record, anchor_record);
+    return check_launch("odom_anchor_choose");
+}
+
+int naruto_odom_accumulate_anchored(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* ring, const int32_t* head,
+                                    uint32_t slots, const float* maps_cur, const double* state, double* sums, void* workspace, void* stream) {
+    OdomGeom g;
+    uint64_t stride;
+    if (!odom_ring(desc, photo, slots, "odom_accumulate_anchored", &g, &stride)) return NARUTO_ERR_INVALID;
+    if (level >= g.levels) return fail(NARUTO_ERR_INVALID, "odom_accumulate_anchored: level %u of %u", level, g.levels);
+    if (ring == nullptr || head == nullptr || maps_cur == nullptr || state == nullptr || sums == nullptr || workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "odom_accumulate_anchored: NULL argument");
+    const OdomLevel lv = g.lv[level];
+    const uint32_t parts = odom_parts(lv), ioff = g.total * 7u + lv.start * 3u;
+    const double md = (double)desc->max_dist;
+    double* part = reinterpret_cast<double*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    if (photo == nullptr) {
+        hipLaunchKernelGGL(k_odom_accumulate_anchored, dim3(parts), dim3(kOdomThreads), 0, st, lv, (int32_t)level, md * md, stride, slots, head, ring, maps_cur, state,
+                           part);
+        if (int rc = check_launch("odom_accumulate_anchored")) return rc;
+        hipLaunchKernelGGL(k_odom_finish, dim3(1), dim3(kOdomThreads), 0, st, (int32_t)level, state, parts, (const double*)part, sums);
+        return check_launch("odom_finish");
+    }
+    hipLaunchKernelGGL(k_odom_rgbd_accumulate_anchored, dim3(parts), dim3(kOdomThreads), 0, st, lv, ioff, (int32_t)level, md * md, (double)photo->weight,
+                       (double)photo->max_diff, stride, slots, head, ring, maps_cur, state, part);
+    if (int rc = check_launch("odom_rgbd_accumulate_anchored")) return rc;
+    hipLaunchKernelGGL(k_odom_rgbd_finish, dim3(1), dim3(kOdomThreads), 0, st, (int32_t)level, state, parts, (const double*)part, sums);
+    return check_launch("odom_rgbd_finish");
+}
+
+int naruto_odom_score_anchored(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t level, const float* ring, const int32_t* head, uint32_t slots,
+                               const float* maps_cur, const double* cands, double trunc, double* sums, void* workspace, void* stream) {
+    OdomGeom g;
+    uint64_t stride;
+    if (!odom_ring(desc, photo, slots, "odom_score_anchored", &g, &stride)) return NARUTO_ERR_INVALID;
+    if (level >= g.levels) return fail(NARUTO_ERR_INVALID, "odom_score_anchored: level %u of %u", level, g.levels);
+    if (!(trunc > 0.0) || !std::isfinite(trunc)) return fail(NARUTO_ERR_INVALID, "odom_score_anchored: trunc must be a finite positive number of metres");
+    if (ring == nullptr || head == nullptr || maps_cur == nullptr || cands == nullptr || sums == nullptr || workspace == nullptr)
+        return fail(NARUTO_ERR_INVALID, "odom_score_anchored: NULL argument");
+    const OdomLevel lv = g.lv[level];
+    const uint32_t parts = odom_parts(lv), ioff = g.total * 7u + lv.start * 3u;
+    const double md = (double)desc->max_dist, max_diff = photo != nullptr ? (double)photo->max_diff : 0.0;
+    double* part = reinterpret_cast<double*>(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    if (photo != nullptr && photo->weight > 0.0f)
+        hipLaunchKernelGGL((k_odom_score_anchored<true>), dim3(parts), dim3(kOdomThreads), 0, st, lv, ioff, md * md, trunc * trunc, max_diff, stride, slots, head, ring,
+                           maps_cur, cands, part);
+    else
+        hipLaunchKernelGGL((k_odom_score_anchored<false>), dim3(parts), dim3(kOdomThreads), 0, st, lv, ioff, md * md, trunc * trunc, max_diff, stride, slots, head, ring,
+                           maps_cur, cands, part);
+    if (int rc = check_launch("odom_score_anchored")) return rc;
+    hipLaunchKernelGGL((k_odom_score_finish<1>), dim3(1), dim3(kOdomThreads), 0, st, parts, (const double*)part, sums);
+    return check_launch("odom_score_finish");
+}
+
+int naruto_odom_anchor_update(const NarutoOdomAnchor* anchor, uint32_t i, const double* record, int32_t* head, double* anchor_record, void* stream) {
+    if (anchor == nullptr || record == nullptr || head == nullptr || anchor_record == nullptr) return fail(NARUTO_ERR_INVALID, "odom_anchor_update: NULL argument");
+    if (anchor->slots == 0u || anchor->slots > (uint32_t)kOdomMaxRefs) return fail(NARUTO_ERR_INVALID, "odom_anchor_update: %u slots (1 .. %d)", anchor->slots, kOdomMaxRefs);
+    if (anchor->refail == 0u || anchor->refail > (1u << 30)) return fail(NARUTO_ERR_INVALID, "odom_anchor_update: refail = %u (at least 1)", anchor->refail);
+    if (!(anchor->min_overlap >= 0.0 && anchor->min_overlap <= 1.0) || !(anchor->max_trans >= 0.0) || !std::isfinite(anchor->max_trans) ||
+        !(anchor->min_trace >= -1.0 && anchor->min_trace <= 3.0))
+        return fail(NARUTO_ERR_INVALID, "odom_anchor_update: the policy needs min_overlap in 0 .. 1, a finite max_trans >= 0 and min_trace in -1 .. 3");
+    if (i > 0x7fffffffu) return fail(NARUTO_ERR_INVALID, "odom_anchor_update: frame %u", i);
+    hipLaunchKernelGGL(k_odom_anchor_update, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                       OdomAnchor{anchor->min_overlap, anchor->max_trans, anchor->min_trace, anchor->slots, anchor->refail}, i, record, head, anchor_record);
+    return check_launch("odom_anchor_update");
+}
+
+int naruto_odom_anchor_promote(const NarutoOdomDesc* desc, const NarutoOdomPhoto* photo, uint32_t slots, const int32_t* head, const float* maps_cur, float* ring,
+                               void* stream) {
+    OdomGeom g;
+    uint64_t stride;
+    if (!odom_ring(desc, photo, slots, "odom_anchor_promote", &g, &stride)) return NARUTO_ERR_INVALID;
+    if (head == nullptr || maps_cur == nullptr || ring == nullptr) return fail(NARUTO_ERR_INVALID, "odom_anchor_promote: NULL argument");
+    const uint64_t groups = (stride + 1023u) / 1024u;                     // four floats per thread when the block vectorises
+    hipLaunchKernelGGL(k_odom_anchor_promote, dim3((uint32_t)std::min<uint64_t>(groups, 4096u)), dim3(256), 0, (hipStream_t)stream, stride, slots, head, maps_cur,
+                       ring);
+    return check_launch("odom_anchor_promote");
+}
+
+int naruto_pose_predict_anchored(float* est, uint32_t num_frames, uint32_t i, const double* anchor_record, const double* state_T, float* pose6_out, void* stream) {
+    if (est == nullptr || anchor_record == nullptr || state_T == nullptr || pose6_out == nullptr)
+        return fail(NARUTO_ERR_INVALID, "pose_predict_anchored: NULL argument");
+    if (i < 1u || i >= num_frames) return fail(NARUTO_ERR_INVALID, "pose_predict_anchored: frame %u of %u (the first frame is given, not predicted)", i, num_frames);
+    hipLaunchKernelGGL(k_pose_predict_anchored, dim3(1), dim3(64), 0, (hipStream_t)stream, est, i, anchor_record, state_T, pose6_out);
+    return check_launch("pose_predict_anchored");
 }
 
 // ---- frame-to-model alignment (naruto_sdfreg.hip) -------------------------------------------------------------------------

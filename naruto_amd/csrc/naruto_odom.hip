@@ -10,6 +10,9 @@
 //   k_odom_finish      one workgroup: the partials the same way -> sums
 //   k_odom_step        one thread: Cholesky, xi = -A^-1 b, T <- exp(xi) T, the level's done word (naruto_odom.h)
 //
+// k_odom_accumulate, k_odom_rgbd_accumulate, k_odom_score and k_odom_score_finish are one-line wrappers around __device__ bodies
+// (odom_accumulate_body ...), which naruto_odom_anchor.hip wraps a second time with the previous frame taken from a ring of references.
+//
 // A level whose done word is set makes k_odom_accumulate, k_odom_finish and k_odom_step return at once with nothing written, so a whole
 // estimate is a fixed sequence of launches and nothing is read back.  The maps are float32 with contraction off (no fused multiply-add
 // is formed anywhere in this file: every product and sum is rounded, so numpy makes the same bits); the association and the sums are
@@ -181,9 +184,9 @@ __device__ __forceinline__ void odom_associate(const double* T, const OdomLevel&
 }
 
 // part: [workgroups][kOdomSums]; rows (or NULL): [n][2] = (the associated previous pixel or -1, the residual or 0)
-__global__ __launch_bounds__(kOdomThreads) void k_odom_accumulate(OdomLevel lv, int32_t level, double max_dist2, const float* __restrict__ prev,
-                                                                  const float* __restrict__ cur, const double* __restrict__ state,
-                                                                  double* __restrict__ part, double* __restrict__ rows) {
+__device__ __forceinline__ void odom_accumulate_body(const OdomLevel& lv, int32_t level, double max_dist2, const float* __restrict__ prev,
+                                                     const float* __restrict__ cur, const double* __restrict__ state,
+                                                     double* __restrict__ part, double* __restrict__ rows) {
 #pragma clang fp contract(off)
     __shared__ double s[kOdomSums * kOdomThreads];
     if (state[16 + kOdomLevelWords * level] != 0.0) return;              // uniform: the level is finished
@@ -231,6 +234,12 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_accumulate(OdomLevel lv, 
 #pragma unroll
         for (int k = 0; k < kOdomSums; ++k) part[(size_t)blockIdx.x * kOdomSums + k] = acc[k];
     }
+}
+
+__global__ __launch_bounds__(kOdomThreads) void k_odom_accumulate(OdomLevel lv, int32_t level, double max_dist2, const float* __restrict__ prev,
+                                                                  const float* __restrict__ cur, const double* __restrict__ state,
+                                                                  double* __restrict__ part, double* __restrict__ rows) {
+    odom_accumulate_body(lv, level, max_dist2, prev, cur, state, part, rows);
 }
 
 __global__ __launch_bounds__(kOdomThreads) void k_odom_finish(int32_t level, const double* __restrict__ state, uint32_t n_parts, const double* __restrict__ part,
@@ -340,9 +349,9 @@ __device__ __forceinline__ bool odom_photo_accept(const OdomHit& h, const OdomLe
 }
 
 // part: [workgroups][kOdomRgbdSums]; rows (or NULL): [n][4] = (geometric j or -1, r, photometric j or -1, r_I); ioff: floats to the level's I
-__global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_accumulate(OdomLevel lv, uint32_t ioff, int32_t level, double max_dist2, double weight,
-                                                                       double max_diff, const float* __restrict__ prev, const float* __restrict__ cur,
-                                                                       const double* __restrict__ state, double* __restrict__ part, double* __restrict__ rows) {
+__device__ __forceinline__ void odom_rgbd_accumulate_body(const OdomLevel& lv, uint32_t ioff, int32_t level, double max_dist2, double weight,
+                                                          double max_diff, const float* __restrict__ prev, const float* __restrict__ cur,
+                                                          const double* __restrict__ state, double* __restrict__ part, double* __restrict__ rows) {
 #pragma clang fp contract(off)
     __shared__ double s[kOdomRgbdSums * kOdomThreads];
     if (state[16 + kOdomLevelWords * level] != 0.0) return;              // uniform: the level is finished
@@ -400,6 +409,12 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_accumulate(OdomLevel
     }
 }
 
+__global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_accumulate(OdomLevel lv, uint32_t ioff, int32_t level, double max_dist2, double weight,
+                                                                       double max_diff, const float* __restrict__ prev, const float* __restrict__ cur,
+                                                                       const double* __restrict__ state, double* __restrict__ part, double* __restrict__ rows) {
+    odom_rgbd_accumulate_body(lv, ioff, level, max_dist2, weight, max_diff, prev, cur, state, part, rows);
+}
+
 __global__ __launch_bounds__(kOdomThreads) void k_odom_rgbd_finish(int32_t level, const double* __restrict__ state, uint32_t n_parts,
                                                                    const double* __restrict__ part, double* __restrict__ sums) {
 #pragma clang fp contract(off)
@@ -433,9 +448,9 @@ constexpr int kOdomGateWords = 16;
 // cands: [K][16] row-major transforms; part: [workgroups][1 + 4 K]: [0] pixels with p.z < 0, then per candidate the geometric rows, the sum
 // of min(r^2, trunc2), the photometric rows, the sum of r_I^2.  A candidate with a non-finite entry fails odom_associate's comparisons.
 template <int K, bool PHOTO>
-__global__ __launch_bounds__(kOdomThreads) void k_odom_score(OdomLevel lv, uint32_t ioff, double max_dist2, double trunc2, double max_diff,
-                                                             const float* __restrict__ prev, const float* __restrict__ cur,
-                                                             const double* __restrict__ cands, double* __restrict__ part) {
+__device__ __forceinline__ void odom_score_body(const OdomLevel& lv, uint32_t ioff, double max_dist2, double trunc2, double max_diff,
+                                                const float* __restrict__ prev, const float* __restrict__ cur,
+                                                const double* __restrict__ cands, double* __restrict__ part) {
 #pragma clang fp contract(off)
     constexpr int N = 1 + 4 * K;
     __shared__ double s[N * kOdomThreads];
@@ -483,8 +498,15 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_score(OdomLevel lv, uint3
     }
 }
 
+template <int K, bool PHOTO>
+__global__ __launch_bounds__(kOdomThreads) void k_odom_score(OdomLevel lv, uint32_t ioff, double max_dist2, double trunc2, double max_diff,
+                                                             const float* __restrict__ prev, const float* __restrict__ cur,
+                                                             const double* __restrict__ cands, double* __restrict__ part) {
+    odom_score_body<K, PHOTO>(lv, ioff, max_dist2, trunc2, max_diff, prev, cur, cands, part);
+}
+
 template <int K>
-__global__ __launch_bounds__(kOdomThreads) void k_odom_score_finish(uint32_t n_parts, const double* __restrict__ part, double* __restrict__ sums) {
+__device__ __forceinline__ void odom_score_finish_body(uint32_t n_parts, const double* __restrict__ part, double* __restrict__ sums) {
 #pragma clang fp contract(off)
     constexpr int N = 1 + 4 * K;
     __shared__ double s[N * kOdomThreads];
@@ -500,6 +522,11 @@ __global__ __launch_bounds__(kOdomThreads) void k_odom_score_finish(uint32_t n_p
 #pragma unroll
         for (int k = 0; k < N; ++k) sums[k] = acc[k];
     }
+}
+
+template <int K>
+__global__ __launch_bounds__(kOdomThreads) void k_odom_score_finish(uint32_t n_parts, const double* __restrict__ part, double* __restrict__ sums) {
+    odom_score_finish_body<K>(n_parts, part, sums);
 }
 
 __global__ __launch_bounds__(64) void k_odom_candidates(const float* __restrict__ est, uint32_t i, double* __restrict__ cands) {

@@ -89,6 +89,38 @@ estimate is a fixed sequence of launches -- candidates, score, finish, choose, t
 ``init_state`` + the level loop -- and nothing is read back.  Defaults (the study: zero lost estimates passed, zero converged ones refused
 over 80): ``max_trans`` 0.3 m, ``max_rot_deg`` 30, ``min_overlap`` 0.25, ``max_rmse`` 6 mm, ``score_trunc`` 5 cm.  Limits: views without
 overlap fail from every start and are only flagged; the thresholds were chosen at 80 x 60 and 160 x 120 in a closed room.
+
+A REFERENCE RING (``AnchorPolicy``; ``new_anchor``, ``anchor_reset``, ``estimate_anchored_device``, ``chain``; opt-in for both classes, nothing
+above changes; ``CoSLAMNarutoHIP(prior_anchor=...)``).  PARITY UNPINNED as above; tests/odometry_anchor_spec.py is the numpy twin.  The
+gated estimate composes every T onto the frame before it, so every estimate's bias and noise stays in the pose for good.  Here frame i
+is registered to one of ``slots`` kept frames and ``est[i] = est[that frame] @ T``.  All of it lives on the device:
+  * the ring: ``slots`` (1 .. 8, default 4) maps blocks of this odometry's own layout, back to back;
+  * the head, int32 [12]: [0] the slot written last, [1] the count of consecutive refused estimates, [2] the slot chosen for the current
+    frame, [3] the promote decision of the current frame, [4 + s] slot s's frame id (-1 = empty).  A slot's pose is not stored: it is
+    ``est[frame id]`` as it stands when it is read, so the tracker's result and a ``global_BA`` write-back reach it.  A slot word that is not
+    below ``slots`` reads the last slot: no word leaves the ring.
+Per frame i >= 1, after ``frame_maps`` (unchanged); every step is a launch, nothing is read back, no kernel waits on a device word:
+  * ``anchor_candidates`` (one thread): per slot s with frame f the two starts R = inv(est[f]) @ est[i-1] and R @ M, M the last motion
+    inv(est[i-2]) @ est[i-1] (i > 1, else the identity): the pose chain's inverse and product, fp64 from the float32 matrices.  When
+    f = i-1 (and for an empty slot) the pair is ``candidates``' own, bit for bit: no inverse times itself;
+  * ``score_refs``: ``score`` at K = 2 for every slot in one launch and one finishing launch; slot s's nine sums equal ``score`` on that
+    slot's block and pair in every bit; an empty slot's workgroups leave at once, its sums are zeros;
+  * ``anchor_choose`` (one thread): ``choose``'s cost per (slot, start) of the slots that hold a frame; the lowest wins, ties go to the
+    larger frame id, then to the lower start; a cost that is not finite is +inf; no such slot, or every cost +inf: the slot written last
+    with start 0.  It writes head[2], the chosen slot's pair into ``cands`` (what the unchanged ``verdict`` reads), the state block and
+    record [1..5] as ``choose`` does, and the anchor record's [0], [1], [2], [6], [7];
+  * the level loop and the K = 1 score at level 0: the existing kernels' bodies, with the previous maps = the ring's block head[2],
+    resolved at kernel entry; ``step`` and ``verdict`` unchanged;
+  * ``anchor_update`` (one thread), from the verdict's record, T being relative to the chosen reference: after a PASS the frame is promoted
+    when n_geo < ``min_overlap`` n_valid, |t| > ``max_trans`` or trace(R) < 1 + 2 cos(``max_rot_deg``), and the streak is 0; after a FAIL
+    the streak grows, and the ``refail``-th refusal in a row promotes the frame (which is what frame-to-frame odometry does every frame)
+    and clears the streak.  A promoted frame takes slot (head[0] + 1) mod ``slots``; the head records it there;
+  * ``anchor_promote``: a copy of the current maps into that slot; every workgroup reads the decision word first; other slots untouched;
+  * ``pose_chain.pose_predict_anchored``: est[i] = est[f] @ T, f read from the anchor record.
+Anchor record, 8 doubles per frame: the chosen slot, its frame id, the slots that held a frame, promoted, the slot written (-1 = none), the
+fail streak after the frame, the best cost, the runner-up among all (slot, start) pairs (-1 where +inf).  Defaults (the study of DESIGN 7o):
+``slots`` 4, ``min_overlap`` 0.7, ``max_trans`` 0.10 m, ``max_rot_deg`` 10, ``refail`` 2; they must lie strictly inside the gate's, or no
+passing frame could ever be promoted before the gate refuses.  Limits: no second attempt, no loop closure, eviction is the ring's.
 """
 
 from __future__ import annotations
@@ -143,6 +175,48 @@ class OdometryGate:
         """The HOST struct of naruto_odom_verdict: min_trace = 1 + 2 cos(max_rot), made here so that the kernel needs no cosine."""
         return _lib.NarutoOdomGate(max_trans=float(self.max_trans), min_trace=1.0 + 2.0 * math.cos(math.radians(self.max_rot_deg)),
                                    min_overlap=float(self.min_overlap), max_rmse=float(self.max_rmse))
+
+
+@dataclass
+class AnchorPolicy:
+    """The reference ring of the odometry prior (module docstring): its size and when a frame becomes a reference.  The three limits must
+    lie strictly inside those of ``gate`` (default: ``OdometryGate()``); ``within`` checks them against another gate."""
+    slots: int = 4
+    min_overlap: float = 0.7        # geometric rows / valid pixels against the chosen reference: below it the frame is promoted
+    max_trans: float = 0.10         # metres to the chosen reference: above it the frame is promoted
+    max_rot_deg: float = 10.0       # degrees to the chosen reference: above it the frame is promoted
+    refail: int = 2                 # this many refused estimates in a row promote the current frame
+    gate: Optional[OdometryGate] = None
+
+    def __post_init__(self):
+        if not (isinstance(self.slots, int) and 1 <= self.slots <= _lib.ODOM_MAX_REFS and isinstance(self.refail, int) and 1 <= self.refail < 2 ** 30):
+            raise ValueError(f"AnchorPolicy: slots = {self.slots!r} (1 .. {_lib.ODOM_MAX_REFS}), refail = {self.refail!r} (an int >= 1)")
+        if not (all(math.isfinite(v) for v in (self.min_overlap, self.max_trans, self.max_rot_deg)) and 0 <= self.min_overlap <= 1
+                and self.max_trans >= 0 and 0 <= self.max_rot_deg <= 180):
+            raise ValueError(f"AnchorPolicy: {self!r}: min_overlap in 0 .. 1, max_trans >= 0, max_rot_deg in 0 .. 180")
+        self.within(self.gate)
+
+    def within(self, gate) -> "AnchorPolicy":
+        """Raises ValueError unless every limit lies strictly inside ``gate``'s: otherwise the gate refuses before the ring can move on."""
+        gate = OdometryGate.of(gate)
+        if not (self.min_overlap > gate.min_overlap and self.max_trans < gate.max_trans and self.max_rot_deg < gate.max_rot_deg):
+            raise ValueError(f"AnchorPolicy: min_overlap {self.min_overlap} / max_trans {self.max_trans} / max_rot_deg {self.max_rot_deg} must lie strictly "
+                             f"inside the gate's {gate.min_overlap} / {gate.max_trans} / {gate.max_rot_deg}")
+        return self
+
+    @staticmethod
+    def of(policy) -> "AnchorPolicy":
+        """None or True: the defaults; an AnchorPolicy: itself."""
+        if policy is None or policy is True:
+            return AnchorPolicy()
+        if not isinstance(policy, AnchorPolicy):
+            raise ValueError(f"the anchor policy is None, True or an AnchorPolicy; got {policy!r}")
+        return policy
+
+    def abi(self):
+        """The HOST struct of naruto_odom_anchor_update: min_trace = 1 + 2 cos(max_rot), as ``OdometryGate.abi``."""
+        return _lib.NarutoOdomAnchor(slots=int(self.slots), refail=int(self.refail), min_overlap=float(self.min_overlap), max_trans=float(self.max_trans),
+                                     min_trace=1.0 + 2.0 * math.cos(math.radians(self.max_rot_deg)))
 
 
 class DepthOdometryHIP:
@@ -340,8 +414,147 @@ class DepthOdometryHIP:
         self.verdict(gate, state, record)
         return state
 
-    def _frame(self, frame) -> torch.Tensor:
-        return self.frame_maps(*frame) if isinstance(frame, (tuple, list)) else self.frame_maps(frame)
+    # ------------------------------------------------------------------------------------ a reference ring (module docstring)
+    def new_anchor(self, policy=None) -> SimpleNamespace:
+        """The device side of a reference ring: ``.ring`` float32 [slots, a maps block], ``.head`` int32 [12] (all slots empty),
+        ``.cands`` float64 [slots,2,16], ``.sums`` float64 [slots,9], ``.workspace``, ``.record`` float64 [8], and ``.policy``."""
+        policy = AnchorPolicy.of(policy)
+        self._gate_buffers()
+        ws = int(_lib.load().naruto_odom_score_refs_workspace_bytes(C.byref(self.desc), policy.slots))
+        if ws == 0:
+            raise ValueError(f"{type(self).__name__}: " + _lib.load().naruto_last_error().decode("utf-8", "replace"))
+        head = torch.tensor([0, 0, 0, 0] + [-1] * _lib.ODOM_MAX_REFS, dtype=torch.int32).to(self.device)
+        return SimpleNamespace(policy=policy, slots=policy.slots, ring=torch.zeros(policy.slots, self.maps_bytes // 4, dtype=torch.float32, device=self.device),
+                               head=head, cands=torch.zeros(policy.slots, 2, 16, dtype=torch.float64, device=self.device),
+                               sums=torch.zeros(policy.slots, 9, dtype=torch.float64, device=self.device),
+                               workspace=_lib.workspace(ws, self.device, torch.float64),
+                               record=torch.zeros(_lib.ODOM_ANCHOR_WORDS, dtype=torch.float64, device=self.device))
+
+    def anchor_reset(self, anchor: SimpleNamespace, maps: torch.Tensor, frame: int = 0) -> None:
+        """``maps`` (frame ``frame``'s block) into slot 0 and the head from the host: that slot alone holds a frame, nothing is refused."""
+        if maps.numel() * 4 != self.maps_bytes:
+            raise ValueError(f"{type(self).__name__}: maps must be a maps block of new_maps()")
+        anchor.ring[0].copy_(maps.reshape(-1), non_blocking=True)
+        anchor.head.copy_(torch.tensor([0, 0, 0, 0, int(frame)] + [-1] * (_lib.ODOM_MAX_REFS - 1), dtype=torch.int32))
+
+    def anchor_candidates(self, anchor: SimpleNamespace, est: torch.Tensor, i: int) -> torch.Tensor:
+        """Every slot's two starts of frame ``i`` into ``anchor.cands`` [slots,2,16]: one launch."""
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_anchor_candidates(est.data_ptr(), est.shape[0], int(i), anchor.head.data_ptr(), anchor.slots, anchor.cands.data_ptr(),
+                                                            _stream()), "naruto_odom_anchor_candidates")
+        return anchor.cands
+
+    def score_refs(self, anchor: SimpleNamespace, maps_cur: torch.Tensor, level: Optional[int] = None, trunc: Optional[float] = None) -> torch.Tensor:
+        """``score`` at K = 2 of every slot's pair against that slot's block into ``anchor.sums`` [slots,9]: two launches."""
+        level = self.levels - 1 if level is None else int(level)
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_score_refs(C.byref(self.desc), self._photo_ref(), level, anchor.ring.data_ptr(), anchor.head.data_ptr(), anchor.slots,
+                                                     maps_cur.data_ptr(), anchor.cands.data_ptr(), float(OdometryGate.score_trunc if trunc is None else trunc),
+                                                     anchor.sums.data_ptr(), anchor.workspace.data_ptr(), _stream()), "naruto_odom_score_refs")
+        return anchor.sums
+
+    def anchor_choose(self, anchor: SimpleNamespace, trunc: float, state: torch.Tensor, record: torch.Tensor, anchor_record: Optional[torch.Tensor] = None) -> None:
+        """``naruto_odom_anchor_choose`` on ``anchor.sums`` and ``anchor.cands``: the head's chosen slot, its pair into ``self.cands``, the state
+        block, the record's head and the anchor record's: one launch."""
+        self._gate_buffers()
+        anchor_record = anchor.record if anchor_record is None else anchor_record
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_anchor_choose(anchor.slots, anchor.sums.data_ptr(), anchor.cands.data_ptr(), 1 if self._photo_on else 0, float(trunc),
+                                                        float(self.photo.max_diff) if self._photo_on else 0.0, anchor.head.data_ptr(), self.cands.data_ptr(),
+                                                        state.data_ptr(), record.data_ptr(), anchor_record.data_ptr(), _stream()), "naruto_odom_anchor_choose")
+
+    def accumulate_anchored(self, level: int, anchor: SimpleNamespace, maps_cur: torch.Tensor, state: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``accumulate`` with the previous maps = the ring's block ``head[2]``, resolved on the device."""
+        state = self.state if state is None else state
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_accumulate_anchored(C.byref(self.desc), self._photo_ref(), int(level), anchor.ring.data_ptr(), anchor.head.data_ptr(),
+                                                              anchor.slots, maps_cur.data_ptr(), state.data_ptr(), self.sums.data_ptr(), self.workspace.data_ptr(),
+                                                              _stream()), "naruto_odom_accumulate_anchored")
+        return self.sums
+
+    def score_anchored(self, anchor: SimpleNamespace, maps_cur: torch.Tensor, cands: torch.Tensor, level: int = 0, trunc: Optional[float] = None) -> torch.Tensor:
+        """``score`` at K = 1 of ``cands`` (float64 [16] on the device: a state block's head) against the ring's block ``head[2]``."""
+        self._gate_buffers()
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_score_anchored(C.byref(self.desc), self._photo_ref(), int(level), anchor.ring.data_ptr(), anchor.head.data_ptr(),
+                                                         anchor.slots, maps_cur.data_ptr(), cands.data_ptr(), float(self.desc.max_dist if trunc is None else trunc),
+                                                         self.score_sums.data_ptr(), self.score_workspace.data_ptr(), _stream()), "naruto_odom_score_anchored")
+        return self.score_sums[:5]
+
+    def anchor_update(self, anchor: SimpleNamespace, i: int, record: torch.Tensor, anchor_record: Optional[torch.Tensor] = None) -> None:
+        """The promote decision of frame ``i`` from the verdict's ``record`` into the head and the anchor record: one launch."""
+        anchor_record = anchor.record if anchor_record is None else anchor_record
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_anchor_update(C.byref(anchor.policy.abi()), int(i), record.data_ptr(), anchor.head.data_ptr(), anchor_record.data_ptr(),
+                                                        _stream()), "naruto_odom_anchor_update")
+
+    def anchor_promote(self, anchor: SimpleNamespace, maps_cur: torch.Tensor) -> None:
+        """The current maps into the slot the update chose when the decision word is set, else nothing: one launch."""
+        if maps_cur.numel() * 4 != self.maps_bytes:
+            raise ValueError(f"{type(self).__name__}: maps_cur must be a maps block of new_maps()")
+        with _on_device(self.device):
+            check(_lib.load().naruto_odom_anchor_promote(C.byref(self.desc), self._photo_ref(), anchor.slots, anchor.head.data_ptr(), maps_cur.data_ptr(),
+                                                         anchor.ring.data_ptr(), _stream()), "naruto_odom_anchor_promote")
+
+    def estimate_anchored_device(self, anchor: SimpleNamespace, maps_cur: torch.Tensor, est: torch.Tensor, i: int, gate=None,
+                                 record: Optional[torch.Tensor] = None, anchor_record: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The anchored estimate of frame ``i`` (module docstring): launches only.  ``record``: float64 [16], ``anchor_record``: float64 [8], both on
+        the device (defaults ``self.record``, ``anchor.record``).  Returns the state block: T relative to the reference the anchor record names,
+        for ``pose_chain.pose_predict_anchored``."""
+        gate = OdometryGate.of(gate)
+        anchor.policy.within(gate)
+        self._gate_buffers()
+        record = self.record if record is None else record
+        anchor_record = anchor.record if anchor_record is None else anchor_record
+        if not (record.is_cuda and record.dtype == torch.float64 and record.is_contiguous() and record.numel() == _lib.ODOM_GATE_WORDS):
+            raise ValueError(f"{type(self).__name__}: record is float64 [{_lib.ODOM_GATE_WORDS}] on the device")
+        if not (anchor_record.is_cuda and anchor_record.dtype == torch.float64 and anchor_record.is_contiguous() and anchor_record.numel() == _lib.ODOM_ANCHOR_WORDS):
+            raise ValueError(f"{type(self).__name__}: anchor_record is float64 [{_lib.ODOM_ANCHOR_WORDS}] on the device")
+        state = self.state
+        self.anchor_candidates(anchor, est, i)
+        self.score_refs(anchor, maps_cur, self.levels - 1, gate.score_trunc)
+        self.anchor_choose(anchor, gate.score_trunc, state, record, anchor_record)
+        for k, cap in enumerate(self.iters):
+            level = self.levels - 1 - k
+            for _ in range(cap):
+                self.accumulate_anchored(level, anchor, maps_cur, state)
+                self.step(level, state)
+        self.score_anchored(anchor, maps_cur, state, 0)
+        self.verdict(gate, state, record)
+        self.anchor_update(anchor, i, record, anchor_record)
+        self.anchor_promote(anchor, maps_cur)
+        return state
+
+    def chain(self, frames, gate=None, anchor=None, first=None) -> SimpleNamespace:
+        """A prior-only chain over ``frames`` (depth frames; for the RGB-D odometry (depth, colour) pairs): ``est[0]`` = ``first`` ([4,4], default
+        the identity), every later pose from the gated estimate alone.  ``anchor`` None: frame to frame, ``estimate_gated_device`` +
+        ``pose_predict_relative``; True or an ``AnchorPolicy``: the reference ring.  ``.poses`` float32 [n,4,4], ``.prior_log`` float64 [n,16],
+        ``.anchor_log`` float64 [n,8] or None, on the host; the frames' launches never wait, the call synchronises once at its end."""
+        from . import pose_chain
+        gate, n = OdometryGate.of(gate), len(frames)
+        est = torch.zeros(max(n, 2), 4, 4, dtype=torch.float32, device=self.device)
+        est[0] = torch.eye(4) if first is None else torch.as_tensor(np.asarray(first, dtype=np.float32))
+        prior_log = torch.zeros(n, _lib.ODOM_GATE_WORDS, dtype=torch.float64, device=self.device)
+        pose6 = torch.zeros(6, dtype=torch.float32, device=self.device)
+        maps = [self.new_maps(), self.new_maps()]
+        ring, anchor_log = None, None
+        self._frame(frames[0], maps[0])
+        if anchor is not None and anchor is not False:
+            ring = self.new_anchor(AnchorPolicy.of(anchor).within(gate))
+            anchor_log = torch.zeros(n, _lib.ODOM_ANCHOR_WORDS, dtype=torch.float64, device=self.device)
+            self.anchor_reset(ring, maps[0], 0)
+        for i in range(1, n):
+            cur = self._frame(frames[i], maps[i & 1])
+            if ring is None:
+                state = self.estimate_gated_device(maps[(i - 1) & 1], cur, est=est, i=i, gate=gate, record=prior_log[i])
+                pose_chain.pose_predict_relative(est, i, state, pose6)
+            else:
+                state = self.estimate_anchored_device(ring, cur, est, i, gate, prior_log[i], anchor_log[i])
+                pose_chain.pose_predict_anchored(est, i, anchor_log[i], state, pose6)
+        return SimpleNamespace(poses=est[:n].cpu().numpy(), prior_log=prior_log.cpu().numpy(), anchor_log=None if anchor_log is None else anchor_log.cpu().numpy())
+
+    def _frame(self, frame, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self.frame_maps(*frame, out=out) if isinstance(frame, (tuple, list)) else self.frame_maps(frame, out=out)
 
     def estimate_gated(self, prev, cur, candidates=None, gate=None) -> SimpleNamespace:
         """The gated estimate between two frames (a depth frame; for the RGB-D odometry a (depth, colour) pair).  ``.T`` float64 [4,4] (the

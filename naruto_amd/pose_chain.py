@@ -7,6 +7,7 @@ current stream, allocates only the output it returns when none is given, and nev
   * ``pose_log(c2w)``                                   [P,4,4] -> (omega, t) [P,6]: ``tracking.matrices_to_pose6`` on the device
   * ``pose_predict(est, i, const_speed, pose6_out)``    ``predict_current_pose`` into ``est[i]`` and the tracker's ``pose_init``
   * ``pose_predict_relative(est, i, state_T, pose6_out)``   ``est[i] = est[i-1] @ T`` from a depth-odometry state block, and ``pose_init``
+  * ``pose_predict_anchored(est, i, anchor_record, state_T, pose6_out)``   ``est[i] = est[f] @ T``, f the anchored odometry's reference frame
   * ``pose_commit(est, rel, i, keyframe_every, c2w)``   the tracked pose into ``est[i]``; ``rel[i]`` for a frame that is no keyframe
   * ``pose_scatter(est, refined, P, keyframe_every, cur_id, optim_cur)``   ``global_BA``'s write-back (coslam.py:401-407)
   * ``pose_resolve(est, rel, n, keyframe_every)``       ``convert_relative_pose``: [n,4,4], every frame relative to its refined keyframe
@@ -68,6 +69,20 @@ def pose_predict_relative(est: torch.Tensor, i: int, state_T: torch.Tensor, pose
     with _on_device(est.device):
         check(_lib.load().naruto_pose_predict_relative(est.data_ptr(), est.shape[0], int(i), state_T.data_ptr(), pose6_out.data_ptr(), _stream()),
               "naruto_pose_predict_relative")
+
+
+def pose_predict_anchored(est: torch.Tensor, i: int, anchor_record: torch.Tensor, state_T: torch.Tensor, pose6_out: torch.Tensor) -> None:
+    """``est[i]`` <- ``est[f] @ T`` with ``f`` the reference frame the anchored odometry chose, read ON THE DEVICE from
+    ``anchor_record[1]`` (float64 [8], ``odometry.estimate_anchored_device``'s), and ``T`` the head of ``state_T``; ``pose6_out`` as
+    ``pose_predict_relative`` ends."""
+    est = _mats(est, "est")
+    _vec6(pose6_out, "pose6_out", 1)
+    for t, name, n in ((state_T, "state_T", 16), (anchor_record, "anchor_record", _lib.ODOM_ANCHOR_WORDS)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() >= n):
+            raise ValueError(f"pose_chain: {name} must be a contiguous float64 tensor of at least {n} elements on the GPU")
+    with _on_device(est.device):
+        check(_lib.load().naruto_pose_predict_anchored(est.data_ptr(), est.shape[0], int(i), anchor_record.data_ptr(), state_T.data_ptr(),
+                                                       pose6_out.data_ptr(), _stream()), "naruto_pose_predict_anchored")
 
 
 def pose_commit(est: torch.Tensor, rel: torch.Tensor, i: int, keyframe_every: int, c2w: torch.Tensor) -> None:

@@ -22,6 +22,8 @@ rotation negated as the reference's ``load_Replica_pose`` does.  The run's traje
 (``CoSLAMNarutoHIP(track=True)``) and adds ``ate_rmse(cm)`` / ``ate_mean(cm)``: the estimated trajectory against the poses the frames were
 taken at (``evaluation.ate``).  ``--prior_gate`` (with ``--motion_prior depth_icp`` or ``rgbd_icp``) switches on the odometry prior's scored
 starts and verdict (``CoSLAMNarutoHIP(prior_gate=True)``) and adds ``prior_failed_frames``, the frames whose prior was refused.
+``--prior_anchor [--anchor_slots N]`` (with ``--prior_gate``) registers every frame to one of a ring of reference frames kept on the device
+(``CoSLAMNarutoHIP(prior_anchor=...)``) and adds ``prior_anchor_promotions``, the frames that became references.
 ``--model_align`` (with ``--track``) registers every predicted pose to the field's SDF before the tracker takes it
 (``CoSLAMNarutoHIP(model_align=True)``, ``naruto_amd.registration``) and adds ``align_failed_frames``, the frames whose alignment was refused.  ``--eval_views K`` renders every K-th pose of the run from the final map and scores it against the
 simulator: ``psnr``, ``ssim`` and ``depth_l1(cm)`` (``naruto_amd.render``).
@@ -70,7 +72,7 @@ def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optio
     save.  When ``slam`` tracks (``CoSLAMNarutoHIP(track=True)``): also ``est_poses`` [num_iter,4,4] (``slam.resolved_poses()``, on the
     host) and ``ate`` (``evaluation.ate(est_poses, poses)``; None below 3 steps).  The planner keeps receiving the COMMANDED pose, the
     one the frame was rendered at, not the estimate -- as the reference's loop does (main.py:135-137).  With ``prior_gate``: also
-    ``prior_log`` [num_iter,16] float64 on the host, frame i's record of the odometry prior (``naruto_amd.odometry``; row 0 is zeros).  With
+    ``prior_log`` [num_iter,16] float64 on the host, frame i's record of the odometry prior (``naruto_amd.odometry``; row 0 is zeros).  With ``prior_anchor``: also ``anchor_log`` [num_iter,8] float64 on the host, frame i's anchor record.  With
     ``model_align``: also ``align_log`` [num_iter,8] float64 on the host, frame i's record of the model alignment (``naruto_amd.registration``).  ``eval_views`` = K: after the final
     mesh every K-th pose of the run is rendered from the map and scored against the simulator (``render.evaluate_views``): the result
     gains ``render_eval``.  None: no launch is added."""
@@ -121,6 +123,8 @@ def run_exploration(slam, sim, planner, start_c2w, num_iter: int, on_step: Optio
         out["ate"] = ate(out["est_poses"], out["poses"]) if len(poses) >= 3 else None
     if getattr(slam, "align_log", None) is not None:                       # the model alignment's records, one row per frame (row 0: zeros)
         out["align_log"] = slam.align_log[:len(poses)].cpu()
+    if getattr(slam, "anchor_log", None) is not None:                      # the reference ring's records, one row per frame (row 0: zeros)
+        out["anchor_log"] = slam.anchor_log[:len(poses)].cpu()
     if getattr(slam, "prior_log", None) is not None:                       # the gated odometry prior's records, one row per frame (row 0: zeros)
         out["prior_log"] = slam.prior_log[:len(poses)].cpu()
     if eval_views is not None and poses:
@@ -165,6 +169,10 @@ def parse_args(argv=None):
                         help="with --track: register every predicted pose to the field's SDF before the tracker takes it (adds align_failed_frames to results.txt)")
     parser.add_argument("--prior_gate", action="store_true",
                         help="with --motion_prior depth_icp / rgbd_icp: score the prior's two starts and judge its estimate (adds prior_failed_frames to results.txt)")
+    parser.add_argument("--prior_anchor", action="store_true",
+                        help="with --prior_gate: register every frame to one of a ring of reference frames kept on the device instead of the frame before "
+                             "(adds prior_anchor_promotions to results.txt)")
+    parser.add_argument("--anchor_slots", type=int, default=None, metavar="N", help="with --prior_anchor: the ring's size, 1 .. 8 (default 4)")
     parser.add_argument("--dataset", type=str, default="NARUTO", choices=["Replica", "MP3D", "NARUTO"], help="the planner's collision rule")
     parser.add_argument("--eval_views", type=int, default=None, metavar="K", help="after the run, render every K-th pose from the map and score it against the simulator (psnr, ssim, depth_l1(cm) in results.txt)")
     parser.add_argument("--planner", type=str, nargs="*", default=[], metavar="KEY=VALUE", help="planner settings over naruto_amd.planner.DEFAULTS")
@@ -177,10 +185,20 @@ def parse_args(argv=None):
         args.mesh_frame = "mp3d" if args.dataset == "MP3D" and args.mesh.lower().endswith((".glb", ".gltf")) else "gltf"
     if args.eval_views is not None and args.eval_views < 1:
         parser.error("--eval_views must be positive")
+    if args.anchor_slots is not None and not args.prior_anchor:
+        parser.error("--anchor_slots sizes the ring of --prior_anchor")
     if args.traj is not None and args.start is not None:
         parser.error("--start and --traj exclude each other: the trajectory's first pose is the start")
     args.planner = _planner_overrides(args.planner)
     return args
+
+
+def _anchor_policy(args):
+    """``--prior_anchor [--anchor_slots N]`` as ``CoSLAMNarutoHIP``'s ``prior_anchor``."""
+    if not args.prior_anchor:
+        return None
+    from .odometry import AnchorPolicy
+    return AnchorPolicy() if args.anchor_slots is None else AnchorPolicy(slots=args.anchor_slots)
 
 
 def main(argv=None) -> Dict:
@@ -199,7 +217,7 @@ def main(argv=None) -> Dict:
     os.makedirs(args.result_dir, exist_ok=True)
     slam = CoSLAMNarutoHIP(cfg, active_ray=not args.no_active_ray, num_frames=args.num_iter, seed=args.seed, result_dir=args.result_dir, track=args.track,
                            motion_prior=args.motion_prior, prior_gate=True if args.prior_gate else None,
-                           model_align=True if args.model_align else None)
+                           model_align=True if args.model_align else None, prior_anchor=_anchor_policy(args))
     sim = MeshSimHIP(args.mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=slam.device, mesh_frame=args.mesh_frame)
     planner = None
     if traj is None:
@@ -218,6 +236,8 @@ def main(argv=None) -> Dict:
         results["align_failed_frames"] = int((out["align_log"][1:, 0] == 0.0).sum())
     if out.get("prior_log") is not None:
         results["prior_failed_frames"] = int((out["prior_log"][1:, 0] == 0.0).sum())
+    if out.get("anchor_log") is not None:
+        results["prior_anchor_promotions"] = int((out["anchor_log"][1:, 3] == 1.0).sum())
     if out.get("render_eval") is not None:
         from .render import results_rows
         results.update(results_rows(out["render_eval"]))

@@ -67,6 +67,14 @@ coarsest level -- and after the level loop four checks at level 0 give a verdict
 chosen start instead of the lost estimate.  Frame i's record goes into ``prior_log[i]`` ([num_frames,16] float64 on the device: verdict,
 chosen start, costs, overlap, rmse ...); six launches more per frame, still nothing read back.
 
+PRIOR ANCHOR (``prior_anchor=None`` | ``True`` | ``odometry.AnchorPolicy``, with an odometry prior and ``prior_gate``; ``None`` is the step
+above, launch for launch).  The gated prior composes every estimate onto the frame before, so every estimate's bias stays in the pose.
+With ``prior_anchor`` the frame is registered to one of a ring of reference frames kept on the device -- the cheapest of all (slot, start)
+pairs at the coarsest level -- and ``pose_predict_anchored`` writes ``est[i] = est[reference] @ T``; a reference's pose is ``est`` as it stands,
+so the tracker's result and ``global_BA``'s write-back reach it.  A frame becomes a reference when it has moved away from the one it was
+registered to, or after two refusals in a row (``naruto_amd.odometry``).  Frame i's anchor record goes into ``anchor_log[i]`` ([num_frames,8]
+float64 on the device).  Launches only, nothing read back; ``model_align`` reads the current frame's maps as before.
+
 MODEL ALIGNMENT (``model_align=None`` | ``True`` | ``registration.RegistrationGate``, with ``track=True`` and any ``motion_prior``; ``None`` is
 the step above, launch for launch and bit for bit).  Every prior above is frame to frame, so the chain drifts; with ``model_align`` the
 predicted ``est[i]`` is registered to the field's own SDF (``naruto_amd.registration.FieldRegistrationHIP.align_device``: the frame's depth
@@ -94,7 +102,7 @@ from .capture import no_collection
 from .field import _map_lattice, get_map_volumes
 from .keyframe_store import KeyFrameStoreHIP, frame_ingest
 from .mesh import extract_mesh
-from .pose_chain import pose_commit, pose_log, pose_predict, pose_predict_relative, pose_resolve, pose_scatter
+from .pose_chain import pose_commit, pose_log, pose_predict, pose_predict_anchored, pose_predict_relative, pose_resolve, pose_scatter
 from .trainer import MappingTrainer
 
 
@@ -153,7 +161,7 @@ class DevicePoses:
 class CoSLAMNarutoHIP:
     def __init__(self, config: Dict, voxel_size: float = 0.1, active_ray: Optional[bool] = None, act_ray_num_uncert_sample: int = 500,
                  act_ray_oversample_mul: int = 4, num_frames: int = 2000, seed: Optional[int] = 0, result_dir: Optional[str] = None, device="cuda",
-                 track: bool = False, motion_prior: Optional[str] = None, prior_gate=None, model_align=None):
+                 track: bool = False, motion_prior: Optional[str] = None, prior_gate=None, model_align=None, prior_anchor=None):
         """``config``: a Co-SLAM config (``naruto_amd.config.load_config``); it is kept and, as in the reference's ``override_config``,
         ``mapping.active_ray`` is overwritten when ``active_ray`` is given.  ``num_frames``: the length of the run (sizes the keyframe store
         and the pose tensor).  ``seed``: keys the keyframe store's draws and, through ``torch.manual_seed`` (None: left alone), the
@@ -164,7 +172,9 @@ class CoSLAMNarutoHIP:
         ``prior_gate``: None (today's step, launch for launch), True or an ``odometry.OdometryGate``: the odometry prior scores its two starts
         and judges its estimate (module docstring); needs an odometry prior.  ``model_align``: None (today's step, launch for launch), True or a
         ``registration.RegistrationGate``: every tracked frame's predicted pose is registered to the field's SDF before the tracker takes it
-        (module docstring); needs ``track=True``, works with every ``motion_prior``."""
+        (module docstring); needs ``track=True``, works with every ``motion_prior``.  ``prior_anchor``: None (today's step, launch for launch),
+        True or an ``odometry.AnchorPolicy``: the gated odometry prior registers every frame to one of a ring of reference frames kept on the
+        device instead of the frame before (module docstring); needs an odometry prior and ``prior_gate``."""
         tk = config.get("tracking") or {}
         self.track = bool(track)
         if motion_prior is not None and motion_prior not in ("const_speed", "depth_icp", "rgbd_icp"):
@@ -176,6 +186,9 @@ class CoSLAMNarutoHIP:
             raise ValueError("CoSLAMNarutoHIP: model_align refines the tracker's initial pose and needs track=True")
         if prior_gate is not None and prior_gate is not False and self.motion_prior not in ("depth_icp", "rgbd_icp"):
             raise ValueError("CoSLAMNarutoHIP: prior_gate judges the odometry prior and needs motion_prior='depth_icp' or 'rgbd_icp'")
+        if prior_anchor is not None and prior_anchor is not False and (self.motion_prior not in ("depth_icp", "rgbd_icp") or prior_gate is None or prior_gate is False):
+            raise ValueError("CoSLAMNarutoHIP: prior_anchor keeps reference frames for the gated odometry prior and needs motion_prior='depth_icp' or "
+                             "'rgbd_icp' and prior_gate")
         if not self.track and not bool(tk.get("disable", True)):
             raise NotImplementedError("CoSLAMNarutoHIP: tracking.disable: False asks for camera tracking and pose refinement during the run; they are "
                                       "switched on by the keyword track=True (naruto_amd.tracking.TrackerHIP, FusedBA(optimize_poses=True)), not by the config")
@@ -232,6 +245,11 @@ class CoSLAMNarutoHIP:
             from .odometry import OdometryGate
             self.prior_gate = OdometryGate.of(prior_gate)
             self.prior_log = torch.zeros(self.num_frames, 16, dtype=torch.float64, device=self.device)     # frame i's record (odometry.py)
+        self.prior_anchor, self.anchor_log = None, None
+        if prior_anchor is not None and prior_anchor is not False:
+            from .odometry import AnchorPolicy
+            self.prior_anchor = self.odometry.new_anchor(AnchorPolicy.of(prior_anchor).within(self.prior_gate))
+            self.anchor_log = torch.zeros(self.num_frames, 8, dtype=torch.float64, device=self.device)     # frame i's anchor record (odometry.py)
         self.aligner, self.align_log = None, None
         if model_align is not None and model_align is not False:
             from .registration import FieldRegistrationHIP, RegistrationGate
@@ -300,12 +318,16 @@ class CoSLAMNarutoHIP:
         if self.odometry is not None:
             od, cur = self.odometry, self._odom_maps[i & 1]
             self._odom_frame_maps(color, depth, cur)
-            if self.prior_gate is not None:
+            if self.prior_anchor is not None:
+                state = od.estimate_anchored_device(self.prior_anchor, cur, est.tensor, i, self.prior_gate, self.prior_log[i], self.anchor_log[i])
+                pose_predict_anchored(est.tensor, i, self.anchor_log[i], state, self.tracker.pose_init)
+            elif self.prior_gate is not None:
                 state = od.estimate_gated_device(self._odom_maps[(i - 1) & 1], cur, est=est.tensor, i=i, gate=self.prior_gate, record=self.prior_log[i])
             else:
                 state = od.init_state(est=est.tensor, i=i, const_speed=bool(self.tracking["const_speed"]))
                 od.run_levels(self._odom_maps[(i - 1) & 1], cur, state)
-            pose_predict_relative(est.tensor, i, state, self.tracker.pose_init)
+            if self.prior_anchor is None:
+                pose_predict_relative(est.tensor, i, state, self.tracker.pose_init)
         else:
             pose_predict(est.tensor, i, bool(self.tracking["const_speed"]), self.tracker.pose_init)
         if self.aligner is not None:
@@ -354,6 +376,8 @@ class CoSLAMNarutoHIP:
                     self._capture_tracker(color, depth)
                 if self.odometry is not None:
                     self._odom_frame_maps(color, depth, self._odom_maps[0])
+                    if self.prior_anchor is not None:
+                        self.odometry.anchor_reset(self.prior_anchor, self._odom_maps[0], 0)
             else:
                 every = int(mp["keyframe_every"])
                 if self.track:

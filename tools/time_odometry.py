@@ -12,13 +12,17 @@ Recorded:
     python tools/time_odometry.py [--out profiles/time_odometry.json] [--n-lat 632]
     python tools/time_odometry.py --rgbd [--out profiles/time_odometry_rgbd.json]
     python tools/time_odometry.py --gate [--out profiles/time_odometry_gate.json]
+    python tools/time_odometry.py --anchor [--out profiles/time_odometry_anchor.json]
 
 With --rgbd only this is recorded: the frame maps and a whole estimate of the depth odometry and of the RGB-D odometry
 (naruto_amd.odometry.RGBDOdometryHIP) on the same two frames of the mesh coloured by a smooth function of position, the four calls
 alternating in one loop.  With --gate only this: the gated estimate (scored starts and a verdict, ``estimate_gated_device`` from a pose
 tensor) and the ungated one (``init_state`` + the level loop, today's path) alternating in one loop, for both odometry classes, and
 ``score`` alone at K = 1, 2 and 4 at the coarsest level and at level 0; medians with their spread (min, max), the ratio gated / ungated
-and whether the difference exceeds twice the ungated call's own spread.
+and whether the difference exceeds twice the ungated call's own spread.  With --anchor only this: the anchored estimate
+(``estimate_anchored_device``) on a reference ring of 1 and of 4 slots, every slot holding a frame, and the gated estimate (the baseline)
+alternating in one loop for both classes; the candidates and the score over the references alone; the promote launch with the decision
+word set (the copy of one maps block) and clear; the same figures and the same rule for claiming a cost.
 
 Host wall clock ending in a device synchronise, every shape warmed up first, the MEDIAN of --repeat.  Nothing is asserted."""
 import argparse
@@ -167,6 +171,93 @@ def gate(args, dev, cam):
     return res
 
 
+def anchor(args, dev, cam):
+    """--anchor: the anchored estimate (a reference ring of 1 and of 4 slots, every slot holding a frame) and the gated one alternating in
+    one loop, for both odometry classes; the score over the references alone and the promote copy (module docstring)."""
+    from naruto_amd.odometry import AnchorPolicy
+    from time_tracked_run import smooth_colours
+    v, f = syn.room_sphere_mesh(n_lat=args.n_lat, n_lon=2 * args.n_lat)[:2]
+    sim = MeshSimHIP((v, f, smooth_colours(v)), cam, device=dev)
+    base = np.eye(4)
+    pos, at = np.array([2.0, 4.0, 1.2]), np.array([3.0, 2.5, 1.4])
+    base[:3, :3], base[:3, 3] = compute_camera_pose(pos, at), pos
+    step = motion((0, 1, 0), 2.0, 0.03)
+    chain = [base]
+    for _ in range(4):                                                      # frames 0 .. 4 of a steady motion; frame 4 is the current one
+        chain.append(chain[-1] @ step)
+    poses = np.stack(chain).astype(np.float32)
+    frames = [sim.simulate(p, no_print=True) for p in poses]
+    color, depth = [c.to(dev) for c, _ in frames], [d.to(dev) for _, d in frames]
+    est = torch.from_numpy(np.concatenate([poses, poses[-1:]])).to(dev)
+    rel = np.linalg.inv(poses[3].astype(np.float64)) @ poses[4].astype(np.float64)
+    ods = {"depth": DepthOdometryHIP(cam, device=dev), "rgbd": RGBDOdometryHIP(cam, device=dev)}
+    calls, checks = {}, {}
+    for name, od in ods.items():
+        maps = [od.frame_maps(depth[k], color[k]) if name == "rgbd" else od.frame_maps(depth[k]) for k in range(5)]
+        rings = {}
+        for slots in (1, 4):
+            ring = od.new_anchor(AnchorPolicy(slots=slots))
+            for s in range(slots):                                          # slot s holds frame 3 - s: the frame before, then older ones
+                ring.ring[s].copy_(maps[3 - s])
+            words = [0, 0, 0, 0] + [3 - s for s in range(slots)] + [-1] * (8 - slots)
+            rings[slots] = (ring, torch.tensor(words, dtype=torch.int32, device=dev))
+        record, arec = torch.zeros(16, dtype=torch.float64, device=dev), torch.zeros(8, dtype=torch.float64, device=dev)
+        calls[name + "_gated_ms"] = lambda od=od, maps=maps: od.estimate_gated_device(maps[3], maps[4], est=est, i=4)
+
+        def anchored(od=od, maps=maps, record=record, arec=arec, ring=None, head=None):
+            ring.head.copy_(head)                                           # the same ring every time: a promotion of the last call is undone
+            od.estimate_anchored_device(ring, maps[4], est, 4, None, record, arec)
+        for slots, (ring, head) in rings.items():
+            calls[f"{name}_anchored_slots{slots}_ms"] = lambda fn=anchored, ring=ring, head=head: fn(ring=ring, head=head)
+
+            def refs(od=od, maps=maps, ring=ring, head=head):
+                ring.head.copy_(head)
+                od.anchor_candidates(ring, est, 4)
+                od.score_refs(ring, maps[4])
+            calls[f"{name}_score_refs_slots{slots}_ms"] = refs
+        # the promote launch alone, on a ring of its own (the copy overwrites a slot): the decision word set, and clear
+        spare = od.new_anchor(AnchorPolicy(slots=4))
+        taken = torch.tensor([1, 0, 0, 1, 3, 2] + [-1] * 6, dtype=torch.int32, device=dev)
+        clear = torch.tensor([1, 0, 0, 0, 3, 2] + [-1] * 6, dtype=torch.int32, device=dev)
+
+        def promote(od=od, maps=maps, spare=spare, words=None):
+            spare.head.copy_(words)
+            od.anchor_promote(spare, maps[4])
+        calls[name + "_promote_copy_ms"] = lambda fn=promote, words=taken: fn(words=words)
+        calls[name + "_promote_not_taken_ms"] = lambda fn=promote, words=clear: fn(words=words)
+        checks[name] = (od, maps, rings)
+    times = {k: [] for k in calls}
+    for fn in calls.values():
+        fn()
+    for _ in range(args.repeat):
+        for k, fn in calls.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t)
+    res = {"image": [cam["W"], cam["H"]], "focal": cam["fx"], "faces": len(f), "repeat": args.repeat}
+    for k, vals in times.items():
+        res[k] = {"median": statistics.median(vals) * 1e3, "min": min(vals) * 1e3, "max": max(vals) * 1e3}
+    for name, (od, maps, rings) in checks.items():
+        ga = res[name + "_gated_ms"]
+        spread = ga["max"] - ga["min"]
+        res[name + "_maps_block_MB"] = od.maps_bytes / 1e6
+        for slots, (ring, head) in rings.items():
+            an = res[f"{name}_anchored_slots{slots}_ms"]
+            res[f"{name}_anchored_slots{slots}_over_gated"] = {"ratio": an["median"] / ga["median"], "difference_ms": an["median"] - ga["median"], "gated_spread_ms": spread,
+                                                               "exceeds_twice_the_gated_spread": bool(an["median"] - ga["median"] > 2.0 * spread)}
+            ring.head.copy_(head)
+            state = od.estimate_anchored_device(ring, maps[4], est, 4)
+            a, rec = ring.record.cpu().numpy(), od.record.cpu().numpy()
+            ref = int(a[1])
+            want = np.linalg.inv(poses[ref].astype(np.float64)) @ poses[4].astype(np.float64)
+            dm, dd = error(state.cpu().numpy()[:16].reshape(4, 4), want)
+            res[f"{name}_anchored_slots{slots}_estimate"] = {"reference_frame": ref, "error_mm": dm * 1e3, "error_deg": dd, "anchor_record": [float(x) for x in a],
+                                                             "record": [float(x) for x in rec]}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -174,11 +265,26 @@ def main():
     ap.add_argument("--n-lat", type=int, default=632)
     ap.add_argument("--rgbd", action="store_true", help="depth-only and RGB-D odometry alternating in one run (write to profiles/time_odometry_rgbd.json)")
     ap.add_argument("--gate", action="store_true", help="gated and ungated estimates alternating in one run, and the score kernel alone (write to profiles/time_odometry_gate.json)")
+    ap.add_argument("--anchor", action="store_true", help="anchored and gated estimates alternating in one run, the score over the references and the promote "
+                                                          "copy alone (write to profiles/time_odometry_anchor.json)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/time_odometry.py measures on the GPU; there is none here")
     dev = torch.device("cuda:0")
     cam = {"H": 680, "W": 1200, "fx": 600.0, "fy": 600.0, "cx": 599.5, "cy": 339.5}
+    if args.anchor:
+        res = anchor(args, dev, cam)
+        print(json.dumps(res, indent=1))
+        if args.out:
+            doc = {"device": torch.cuda.get_device_name(0),
+                   "what": "tools/time_odometry.py --anchor: host wall clock ending in a device synchronise, warmed up, all calls alternating in one loop, "
+                           "median (min, max) of --repeat; milliseconds.  The baseline is estimate_gated_device; every anchored and score_refs call "
+                           "includes a 48-byte device copy that puts the ring's head back", "office_0_size": res}
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(doc, fh, indent=1)
+                fh.write("\n")
+        return
     if args.gate:
         res = gate(args, dev, cam)
         print(json.dumps(res, indent=1))

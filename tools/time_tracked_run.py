@@ -11,11 +11,11 @@ the mapping schedule of tools/time_run.py, tracking with replica_coslam.yaml's s
     the others, the trajectory error of the estimate and the motion per step the planner commands (against what one tracking call
     can cover: iter x lr).
 
-    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632] [--motion-prior depth_icp | rgbd_icp [--prior-gate] [--model-align]]
+    python tools/time_tracked_run.py [--out profiles/time_tracked_run.json] [--steps 200] [--n-lat 632] [--motion-prior depth_icp | rgbd_icp [--prior-gate [--prior-anchor]] [--model-align]]
 
 With --motion-prior only the run is made, with CoSLAMNarutoHIP(motion_prior=...), and it is MERGED into the output file as
 office_0_size.run_motion_prior_<name>, beside the run of the default prior (--no-const-speed: tracking.const_speed off, key suffix
-_const_speed_off; --prior-gate: _gated; --model-align: the model alignment of naruto_amd.registration on, _aligned, with its per-frame
+_const_speed_off; --prior-gate: _gated; --prior-anchor: the reference ring of naruto_amd.odometry on, _anchored, with its per-frame records; --model-align: the model alignment of naruto_amd.registration on, _aligned, with its per-frame
 records).  rgbd_icp needs an image: the tool's mesh has no colours, so its vertices are then coloured by a smooth function of position.
 
 Host timers (time.perf_counter), medians over --repeat.  Nothing is asserted.  There is NO reference number: the reference's loop needs
@@ -161,7 +161,8 @@ def whole_run(args, dev, mesh):
     cfg = config(not args.no_const_speed)
     np.random.seed(args.seed)
     slam = CoSLAMNarutoHIP(cfg, active_ray=True, num_frames=args.steps, seed=args.seed, device=dev, track=True, motion_prior=args.motion_prior,
-                           prior_gate=True if args.prior_gate else None, model_align=True if args.model_align else None)
+                           prior_gate=True if args.prior_gate else None, model_align=True if args.model_align else None,
+                           prior_anchor=True if args.prior_anchor else None)
     sim = MeshSimHIP(mesh, {k: getattr(slam, k) for k in ("H", "W", "fx", "fy", "cx", "cy")}, device=dev)
     planner = NarutoPlannerHIP(dataset="NARUTO", device=dev)
     planner.update_sim(sim)
@@ -182,7 +183,11 @@ def whole_run(args, dev, mesh):
 
     def on_step(i, c2w, vols, state):
         """--prior-gate: the pose the prior handed the tracker (est[i-1] @ T, as both stand at the end of the step) and the tracked pose."""
-        if i > 0:
+        if i > 0 and args.prior_anchor:                                     # T is relative to the reference the anchor record names
+            ref = torch.index_select(slam.est_c2w_data.tensor, 0, slam.anchor_log[i, 1:2].long())[0]
+            prior_poses.append(ref.double() @ slam.odometry.state[:16].view(4, 4))
+            tracked_poses.append(slam.est_c2w_data.tensor[i].double().clone())
+        elif i > 0:
             prior_poses.append(slam.est_c2w_data.tensor[i - 1].double() @ slam.odometry.state[:16].view(4, 4))
             tracked_poses.append(slam.est_c2w_data.tensor[i].double().clone())
     out = run_exploration(slam, sim, planner, TR.start_pose(), args.steps, on_step=on_step if args.prior_gate else None)
@@ -213,12 +218,19 @@ def whole_run(args, dev, mesh):
         gated = {"prior_failed_frames": failed, "first_frame_prior_over_10cm": first(pe[0]), "first_frame_tracked_over_10cm": first(te[0]),
                  "per_frame_from_1": {"prior_error_cm": pe[0], "prior_error_deg": pe[1], "tracked_error_cm": te[0], "tracked_error_deg": te[1],
                                       "record": log[1:].tolist()}}
+    if args.prior_anchor:                                                   # the ring's records, frame 1 on; the prior's 16-double records stay with the gated runs
+        alog = out["anchor_log"]
+        refs = alog[1:, 1].long()
+        gated["prior_anchor_promotions"] = int((alog[1:, 3] == 1.0).sum())
+        gated["frames_registered_to_an_older_reference"] = [int(i) + 1 for i in torch.nonzero(refs < torch.arange(len(refs))).flatten()]
+        gated["per_frame_from_1"] = {k: sig(v) for k, v in gated["per_frame_from_1"].items() if k != "record"}
+        gated["anchor_per_frame_from_1"] = {"record": sig(alog[1:].tolist())}
     if args.model_align:                                                    # the alignment's records, frame 1 on, and every frame's tracked error
         log = out["align_log"]
         g = gt[:, :3, 3]
         gated["align_failed_frames"] = [int(i) for i in torch.nonzero(log[1:, 0] == 0.0).flatten() + 1]
         gated["align_per_frame_from_1"] = {"record": sig(log[1:].tolist()), "tracked_error_cm": sig(((out["est_poses"][1:, :3, 3].double() - g[1:]).norm(dim=1) * 100.0).tolist())}
-        if "per_frame_from_1" in gated:                                     # the prior's 16-double records stay with the runs without alignment
+        if "per_frame_from_1" in gated and "record" in gated["per_frame_from_1"]:   # the prior's 16-double records stay with the runs without alignment
             gated["per_frame_from_1"] = {k: sig(v) for k, v in gated["per_frame_from_1"].items() if k != "record"}
     return {**gated, "steps": args.steps, "wall_s_with_final_mesh_and_checkpoint": wall, "loop_s": loop, "steps_per_second": args.steps / loop,
             "phases_total_s": {k: v["total_s"] for k, v in out["timing"].items()},
@@ -243,6 +255,8 @@ def main():
     ap.add_argument("--no-const-speed", action="store_true", help="with --motion-prior: tracking.const_speed off (depth_icp then starts from the identity)")
     ap.add_argument("--prior-gate", action="store_true", help="with --motion-prior depth_icp / rgbd_icp: the prior's scored starts and verdict on; key suffix _gated; "
                     "per-frame errors of the prior and of the tracked pose against the commanded pose, and the records")
+    ap.add_argument("--prior-anchor", action="store_true", help="with --prior-gate: the prior registers every frame to a reference ring kept on the device "
+                    "(CoSLAMNarutoHIP(prior_anchor=True)); key suffix _anchored; the ring's per-frame records")
     ap.add_argument("--model-align", action="store_true", help="with --motion-prior: every predicted pose registered to the field's SDF before the tracker "
                     "takes it (CoSLAMNarutoHIP(model_align=True)); key suffix _aligned; the per-frame records and tracked errors")
     ap.add_argument("--small-test", default=None, help="JSON object merged into the document (figures of tests/test_gpu_tracked_run.py)")
@@ -260,7 +274,7 @@ def main():
             with open(args.out) as fh:
                 doc = json.load(fh)
             doc["office_0_size"]["run_motion_prior_" + args.motion_prior + ("_const_speed_off" if args.no_const_speed else "") + ("_gated" if args.prior_gate else "") +
-                                ("_aligned" if args.model_align else "")] = run
+                                ("_anchored" if args.prior_anchor else "") + ("_aligned" if args.model_align else "")] = run
             with open(args.out, "w") as fh:
                 dump_doc(doc, fh)
         return
